@@ -13,6 +13,14 @@ generated on the device and resident in HBM before the timed region.
 Prints ONE JSON line (rank 0).  `roofline.achieved` is algorithmic bytes
 (8*N + 16 per series) / the fused kernel's average launch duration,
 measured with HIP events on the stream the kernel runs on.
+
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps
+and prints the line, nothing else.  Everything beside the headline -- the CPU
+baseline, the untimed clock-probe repeat behind `roofline.co_bounds`, the extra
+objects (filter-and-refine Run, float32-storage group, many references, two-sided
+xCorr, in_process_shards, long series, config-5 lengths, the reference's own
+benchmark shapes) -- runs only with `--full`.  `--dump-outputs DIR` writes the
+top-N records of the last timed step as DIR/<name>.npy (float64).
 """
 import argparse
 import importlib
@@ -196,6 +204,21 @@ def workload_name(M, N, n_gpus, max_lag, top_n):
     tag = "configs[3]" if (M * n_gpus, N, n_gpus) == (8_000_000, 4096, 8) else "configs[3]-shaped"
     return "%s: 1 ref x %d series, Group sharded by rows over %d GPUs (%d rows each, weak scaling), RCCL all_gather of per-shard top-N records, %s" % (
         tag, M * n_gpus, n_gpus, M, tail)
+
+
+def dump_outputs(d, out):
+    """--dump-outputs: what a caller of the timed Run receives from its last step -- the top-N records (global series index,
+    lag, score) and the mean |score| -- as float64 .npy files (indices below 2^53 are exact).  The directory gets a `*`
+    .gitignore of its own, so that a dump inside a checkout leaves `git status` clean."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    gi = os.path.join(d, ".gitignore")
+    if not os.path.exists(gi):
+        with open(gi, "w") as f:
+            f.write("*\n")
+    series, lag, score, mean_abs = out
+    for name, a in (("top_series", series), ("top_lag", lag), ("top_score", score), ("mean_abs_score", [mean_abs])):
+        np.save(os.path.join(d, name + ".npy"), np.asarray(a, dtype=np.float64))
 
 
 # BASELINE configs[4]: "N in {512 ... 65536} zero-padded to next pow2" -- SURVEY 8d's six lengths plus 20000 (-> 32768, the one FFT
@@ -458,10 +481,15 @@ def main():
     ap.add_argument("--length", type=int, default=4096)
     ap.add_argument("--top-n", type=int, default=20)
     ap.add_argument("--max-lag", type=int, default=15)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline (CPU baseline, clock probe, extra objects, config-5 "
+                         "lengths); off: the run times the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the top-N records of the last one as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--clock-probe", action="store_true",
-                    help="keep the one-wave shader-clock probe resident INSIDE the timed region (default: the clock that prices "
-                         "roofline.co_bounds is measured in a separate, untimed pass of the same steps behind it)")
+                    help="keep the one-wave shader-clock probe resident INSIDE the timed region (otherwise --full measures the "
+                         "clock that prices roofline.co_bounds in a separate, untimed pass of the same steps behind it)")
     ap.add_argument("--in-process-devices", default="auto",
                     help="devices of the in_process_shards extra object (one process, one context + host thread per device, "
                          "SURVEY 8e / INTEGRATION.md): 'all' = every visible GPU, a number k = the first k, 'auto' = all when "
@@ -490,6 +518,9 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    extras_on = args.full and not args.no_extras
     if args.in_process_child:
         in_process_child_main(args)
         return
@@ -629,8 +660,10 @@ def main():
     if use_dist:
         per_rank = [None] * n_gpus
         dist.all_gather_object(per_rank, mine)
-    # the clock that prices the co-bounds (rank 0): by default from an UNTIMED repeat of the same steps behind the timed region
-    if rank == 0 and not args.clock_probe and not args.no_extras:
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, out)
+    # the clock that prices the co-bounds (rank 0): with --full from an UNTIMED repeat of the same steps behind the timed region
+    if rank == 0 and not args.clock_probe and extras_on:
         reps = max(3, min(args.steps, 10))
         sclk, sclk_note, _ = probed(lambda: [db.run(None, 0, args.max_lag, args.top_n, 0.0, 0, True) for _ in range(reps)], est_ms * (reps + 2))
         eng.synchronize()
@@ -639,7 +672,7 @@ def main():
     assert not screened, "the headline Run must not take the fp32 filter-and-refine path"
     # BASELINE configs[4] (mixed lengths, label-grouped, one shared Results): every rank takes part, rank 0 reports
     c5 = None
-    if (not args.no_extras or args.with_config5) and "config5" not in args.skip_extra:
+    if (extras_on or args.with_config5) and "config5" not in args.skip_extra:
         c5 = config5_leg(pkg, eng, args, rank, n_gpus, use_dist, tdev, M, N, Counters())
     if rank == 0:
         total_pairs = float(M) * n_gpus * args.steps
@@ -686,7 +719,8 @@ def main():
         co = {"hbm_measured_copy": {"peak": HBM_COPY_GBPS, "unit": "GB/s", "frac": achieved / HBM_COPY_GBPS},
               "sclk_in_kernel": sclk,
               "sclk_measured_in": "the timed region (--clock-probe)" if args.clock_probe else
-                                  "an untimed repeat of the same Runs on rank 0 behind the timed region (the probe wave is not resident while `value` is timed)"}
+                                  "an untimed repeat of the same Runs on rank 0 behind the timed region (the probe wave is not resident while `value` is timed)"
+                                  if extras_on else "not measured (a plain run; --full measures it)"}
         if sclk_note:
             co["sclk_note"] = sclk_note
         if krec and sclk and k_avg_s > 0:
@@ -704,7 +738,7 @@ def main():
         elif not krec:
             co["note"] = "fp64-VALU / LDS ceilings need the kernel's counters: " + str(rl["traffic_source"].get("note"))
         rl["co_bounds"] = co
-        extras = n_gpus == 1 and not use_dist and not args.no_extras
+        extras = n_gpus == 1 and not use_dist and extras_on
         if extras and db.n >= 512:
             # opt-in filter-and-refine Run (muse_ctx_set_screening(ctx, 1)): fp32 screening pass over every row + fp64
             # re-evaluation of the rows that can reach the top-N; same records.  An extra object, never `value`.
@@ -879,14 +913,14 @@ def main():
                 line["reference_bench_shapes"] = reference_bench_shapes(pkg)
             except Exception as e:
                 line["reference_bench_shapes"] = {"error": str(e)}
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             # (at every N, on rank 0's host cores over a sample of rank 0's shard: the other ranks wait at the closing barrier)
             line["cpu_baseline"] = cpu_baseline(dg, ref, N)
     if use_dist:
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
-        if n_gpus > 1 and (args.with_in_process_child or (not args.no_extras and not args.rehearse_on_one_gpu
+        if n_gpus > 1 and (args.with_in_process_child or (extras_on and not args.rehearse_on_one_gpu
                                                           and "in_process_shards" not in args.skip_extra and pkg.device_count() >= n_gpus)):
             # the design a Go / C++ caller of the C ABI uses (one process, one context + host thread per device, host merge) on
             # the SAME node, after the ranks are done: the ranks have passed the closing barrier and left the process group (they

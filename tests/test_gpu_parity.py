@@ -1847,7 +1847,7 @@ def test_bench_two_ranks_rehearsal_on_one_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
     env["MASTER_PORT"] = "29641"
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--rows", "20001", "--steps", "2", "--warmup", "1",
-                        "--no-extras", "--with-config5", "--config5-rows", "3001", "--rehearse-on-one-gpu",
+                        "--full", "--no-extras", "--with-config5", "--config5-rows", "3001", "--rehearse-on-one-gpu",
                         "--with-in-process-child", "--in-process-rows", "6000"],
                        capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -1888,6 +1888,38 @@ def test_bench_two_ranks_rehearsal_on_one_gpu():
         assert e["rows_total"] == 2 * e["rows"] and e["label_groups"] == e["rows_total"] // 50
         assert abs(e["kernel_ms_avg"] - e["kernel_ms_per_rank"]["max"]) < 1e-9 and e["kernel_ms_avg"] > 0 and e["run_ms"] > 0
         assert e["exchange"].startswith("all_gather")
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_records(eng, muse, tmp_path):
+    """`python bench.py` without --full: the headline fields only, exactly --steps timed Runs, and --dump-outputs writes the
+    records of the last one -- the same records a Run over the same seeded synthetic rows returns in this process"""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
+    M, N, d = 20001, 4096, tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--rows", str(M), "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert r.stdout.count("\n") == 1 and r.stdout.startswith("{"), r.stdout[-2000:]
+    line = json.loads(r.stdout)
+    assert line["steps"] == 3 and line["ranks"][0]["launches_timed"] == 3 and line["ms_per_step"] > 0
+    assert line["dtype"] == "f64" and line["unit"] == "series-pairs/s" and line["higher_is_better"] is True and line["value"] > 0
+    for extra in ("cpu_baseline", "filter_and_refine_run", "f32_storage_group", "many_references", "two_sided_xcorr",
+                  "in_process_shards", "long_series", "config5_mixed_run", "reference_bench_shapes"):
+        assert extra not in line, extra
+    got = {k: np.load(d / (k + ".npy")) for k in ("top_series", "top_lag", "top_score", "mean_abs_score")}
+    assert all(a.dtype == np.float64 for a in got.values())
+    dg, ref = muse.DeviceGroup.synthetic(eng, M, N, seed=0x6D757365)
+    db = muse.DeviceBatch(eng, dg, ref)
+    series, lag, score, mean_abs = db.run(None, 0, 15, 20, 0.0, 0, True)
+    db.close()
+    dg.close()
+    assert len(series) == 20 and np.array_equal(got["top_series"], series) and np.array_equal(got["top_lag"], lag)
+    assert np.array_equal(got["top_score"], score) and got["mean_abs_score"].shape == (1,)
+    assert abs(got["mean_abs_score"][0] - mean_abs) <= 1e-12 * abs(mean_abs)
+    assert line["top_score"] == score[0] and abs(score[0] - 1.0) < 1e-9    # (the planted copy of the reference)
 
 
 def test_reference_bench_shapes_harness(muse):
