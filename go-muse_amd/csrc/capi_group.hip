@@ -160,6 +160,7 @@ static int group_flush(muse_group *g)
 // enqueued so far: call before anything on that stream reads the rows
 int group_ready(muse_group *g, hipStream_t stream)
 {
+    std::lock_guard<std::mutex> lock(g->ready_mu);
     if (g->win_rows)
         return fail(MUSE_ERR_INVALID, "the group has an open staging window (muse_group_stage without its commits)");
     int rc = group_flush(g);
@@ -169,6 +170,20 @@ int group_ready(muse_group *g, hipStream_t stream)
         HIP_TRY(hipStreamWaitEvent(stream ? stream : g->ctx->stream, g->uploaded, 0));
         g->upload_pending = false;
     }
+    return MUSE_OK;
+}
+
+// the same for a stream of the caller's own, from any number of host threads at once (muse_batch_run_group_rows): upload_pending
+// belongs to the compute stream and is left alone, this stream waits for `uploaded` unconditionally
+int group_ready_shared(muse_group *g, hipStream_t stream)
+{
+    std::lock_guard<std::mutex> lock(g->ready_mu);
+    if (g->win_rows)
+        return fail(MUSE_ERR_INVALID, "the group has an open staging window (muse_group_stage without its commits)");
+    int rc = group_flush(g);
+    if (rc)
+        return rc;
+    HIP_TRY(hipStreamWaitEvent(stream, g->uploaded, 0));
     return MUSE_OK;
 }
 
@@ -329,6 +344,93 @@ extern "C" int muse_group_upload(muse_ctx *ctx, const double *rows, int64_t M, i
     return rc;
 }
 
+// ---- rows that are already resident (muse_group_append_from, muse_batch_run_group_rows)
+int check_row_list(const muse_group *src, const int64_t *rows, int64_t count)
+{
+    const int64_t M = src->M;
+    for (int64_t i = 0; i < count; i++)
+        if (rows[i] < 0 || rows[i] >= M)
+            return fail(MUSE_ERR_INVALID, "row %lld of the list is %lld: outside the group's rows [0, %lld)", (long long)i,
+                        (long long)rows[i], (long long)M);
+    return MUSE_OK;
+}
+
+// Ordered on the copy stream like every other write into a group: behind src's packed rows (flushed here) and every upload or
+// growth of either group, in front of dst's later uploads; `uploaded` puts every kernel that reads dst behind the gather.
+int group_gather(muse_group *dst, muse_group *src, const int64_t *rows, int64_t count)
+{
+    if (count <= 0)
+        return MUSE_OK;
+    muse_ctx *ctx = dst->ctx;
+    int rc;
+    {
+        std::lock_guard<std::mutex> lock(src->ready_mu);
+        rc = group_flush(src);
+    }
+    if (!rc)
+        rc = group_flush(dst); // (dst's own packed rows go first: its row order is append order)
+    if (!rc)
+        rc = group_reserve(dst, dst->M + count);
+    if (rc)
+        return rc;
+    if (!dst->gather_done)
+        HIP_TRY(hipEventCreateWithFlags(&dst->gather_done, hipEventDisableTiming));
+    else
+        HIP_TRY(hipEventSynchronize(dst->gather_done)); // the previous gather has read its index list
+    if (count > dst->gidx_cap) {
+        hfree(ctx, dst->gidx_host);
+        dfree(ctx, dst->gidx_dev);
+        dst->gidx_host = dst->gidx_dev = nullptr;
+        dst->gidx_cap = 0;
+        const int64_t cap = std::max<int64_t>(count, 1024);
+        HIP_TRY(hmalloc(ctx, &dst->gidx_host, (size_t)cap * sizeof(long long)));
+        HIP_TRY(dmalloc(ctx, &dst->gidx_dev, (size_t)cap * sizeof(long long)));
+        dst->gidx_cap = cap;
+    }
+    memcpy(dst->gidx_host, rows, (size_t)count * sizeof(long long));
+    HIP_TRY(hipMemcpyAsync(dst->gidx_dev, dst->gidx_host, (size_t)count * sizeof(long long), hipMemcpyHostToDevice,
+                           ctx->copy_stream));
+    HIP_TRY(launch_row_gather(src->base(), src->f32, (char *)dst->base() + (size_t)(dst->M * dst->stride) * dst->elem(), dst->f32,
+                              dst->gidx_dev, count, dst->N, ctx->num_cus, ctx->gather_nt.load(std::memory_order_relaxed),
+                              ctx->copy_stream));
+    HIP_TRY(hipEventRecord(dst->gather_done, ctx->copy_stream));
+    HIP_TRY(hipEventRecord(dst->uploaded, ctx->copy_stream));
+    dst->upload_pending = true;
+    dst->M += count;
+    return MUSE_OK;
+}
+
+extern "C" int muse_group_append_from(muse_group *dst, muse_group *src, const int64_t *rows, int64_t count)
+{
+    if (!dst || !src || count < 0 || (count > 0 && !rows))
+        return fail(MUSE_ERR_INVALID, "bad append_from arguments");
+    if (dst->ctx != src->ctx)
+        return fail(MUSE_ERR_INVALID, "the two groups belong to different contexts");
+    if (dst == src)
+        return fail(MUSE_ERR_INVALID, "a group cannot append its own rows");
+    if (dst->f32 != src->f32)
+        return fail(MUSE_ERR_INVALID, "the two groups store different sample types (float32 / float64)");
+    if (dst->win_rows || src->win_rows)
+        return fail(MUSE_ERR_INVALID, "a group has an open staging window");
+    if (dst->N != src->N) // group.go:45-51: one length per group
+        return fail(MUSE_ERR_LENGTH, "Timeseries has length %d, but current group has length %d", src->N, dst->N);
+    int rc = check_row_list(src, rows, count);
+    if (rc || count == 0)
+        return rc;
+    rc = use_device(dst->ctx);
+    if (rc)
+        return rc;
+    return group_gather(dst, src, rows, count);
+}
+
+extern "C" int muse_test_gather_nontemporal(muse_ctx *ctx, int32_t on)
+{
+    if (!ctx)
+        return fail(MUSE_ERR_INVALID, "NULL context");
+    ctx->gather_nt.store(on != 0);
+    return MUSE_OK;
+}
+
 extern "C" int muse_group_fill_synthetic(muse_group *g, int64_t first, int64_t count, int64_t global_first,
                                          uint64_t seed, uint32_t flags, double *ref_out)
 {
@@ -421,6 +523,10 @@ void group_release(muse_group *g)
     for (void *old : g->retired)
         dfree(g->ctx, old);
     dfree(g->ctx, g->hstats);
+    hfree(g->ctx, g->gidx_host);
+    dfree(g->ctx, g->gidx_dev);
+    if (g->gather_done)
+        (void)hipEventDestroy(g->gather_done);
     for (int i = 0; i < 2; i++) {
         if (g->stage[i]) { // back to the context's pool (the stream is idle: no upload reads it any more)
             std::lock_guard<std::mutex> lock(g->ctx->stage_mu);

@@ -127,6 +127,7 @@ struct muse_ctx {
     std::atomic<bool> rows_always_copy{false}; // test hook (muse_test_rows_always_copy): never let a kernel read the pinned staging buffer
     std::vector<void *> rows_slots;
     std::mutex rows_mu;
+    std::atomic<bool> gather_nt{false}; // measurement hook (muse_test_gather_nontemporal): the row gather's stores bypass the caches
     // Handles may be released in any order (Go finalizers, Python GC): the
     // context lives until it is destroyed AND its last group/batch is freed.
     std::atomic<int> refs{1};
@@ -170,6 +171,14 @@ struct muse_group {
     // waits for it (hipStreamWaitEvent) before a kernel reads the rows: an append of NEW rows overlaps a running score pass
     hipEvent_t uploaded = nullptr;
     bool upload_pending = false;
+    // the flush of the packed rows, upload_pending and the wait for `uploaded` (group_ready, and every caller that reads the
+    // rows on a stream of its own: muse_batch_run_group_rows from any number of host threads)
+    std::mutex ready_mu;
+    // muse_group_append_from: the index list of the last gather into this group (pinned image and device copy), reused by the
+    // next one once `gather_done` has passed
+    long long *gidx_host = nullptr, *gidx_dev = nullptr;
+    int64_t gidx_cap = 0;
+    hipEvent_t gather_done = nullptr;
 };
 
 // The reference spectrum and the tables derived from it: shared (reference-counted) by the batches
@@ -324,6 +333,12 @@ inline void hfree(muse_ctx *ctx, void *p) { pool_free(ctx, true, p); }
 void fill_twiddle(std::vector<double2> &v, size_t i, long long num, long long den);
 void ctx_release(muse_ctx *ctx);                       // capi_context.hip: drops one reference, frees the context with the last
 int group_ready(muse_group *g, hipStream_t stream = nullptr); // capi_group.hip: staged rows uploaded, the compute stream behind the copies
+int group_ready_shared(muse_group *g, hipStream_t stream); // capi_group.hip: the same for a caller's own stream, any number of callers
+// capi_group.hip: rows src[rows[i]] become rows [M, M + count) of dst, gathered on the copy stream (arguments checked by the
+// caller; a float32 src into a float64 dst is widened)
+int group_gather(muse_group *dst, muse_group *src, const int64_t *rows, int64_t count);
+// capi_group.hip: the index-list checks both resident-row entry points share (MUSE_ERR_INVALID outside [0, src->M))
+int check_row_list(const muse_group *src, const int64_t *rows, int64_t count);
 void group_release(muse_group *g);
 void rows_slots_free(muse_ctx *ctx);                   // capi_rows.hip: the idle slots of muse_batch_run_rows (streams idle)
 int ilog2(int64_t n);                                  // capi_batch.hip

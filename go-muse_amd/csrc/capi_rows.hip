@@ -166,6 +166,99 @@ static void slot_return(muse_ctx *ctx, RowsSlot *s)
     slot_destroy(s); // (the slot's work has completed: its event was waited for)
 }
 
+// a slot shaped for M rows of the template's length against the template's reference (rows: s->g.rows, set by the caller)
+static int slot_take(muse_batch *tmpl, int64_t M, size_t elems, RowsSlot **out)
+{
+    muse_ctx *ctx = tmpl->ctx;
+    const int32_t N = tmpl->N;
+    RowsSlot *s = nullptr;
+    int rc = slot_acquire(ctx, elems, &s);
+    if (rc)
+        return rc;
+    // the slot's group and batch take this call's shape and the template's reference
+    s->g.N = N;
+    s->g.stride = N;
+    s->g.M = M;
+    s->g.cap = M;
+    s->g.hstats_rows = 0; // (other rows than the slot's last call: no kept statistics)
+    s->b.N = tmpl->N;
+    s->b.n = tmpl->n;
+    s->b.logn = tmpl->logn;
+    s->b.sp = tmpl->sp;
+    adopt_spectrum(&s->b);
+    s->b.handoff_M = -1; // (no kernel-selection memory across unrelated groups)
+    // kernels that work in the context's shared scratch buffer are serialised on the context's stream
+    s->b.own_stream = tmpl->n >= GENERIC_LDS_MAX_N ? nullptr : s->stream;
+    if (M > s->b.score_cap) { // (grown in steps that small groups never reach twice)
+        dfree(ctx, s->b.mv);
+        dfree(ctx, s->b.lag);
+        s->b.mv = nullptr;
+        s->b.lag = nullptr;
+        s->b.score_cap = 0;
+        const int64_t cap = std::max<int64_t>(M, 4096);
+        hipError_t ea = dmalloc(ctx, &s->b.mv, (size_t)cap * sizeof(double));
+        if (ea == hipSuccess)
+            ea = dmalloc(ctx, &s->b.lag, (size_t)cap * sizeof(int));
+        if (ea != hipSuccess) {
+            slot_destroy(s);
+            return fail(MUSE_ERR_NOMEM, "hipMalloc failed: %s", hipGetErrorString(ea));
+        }
+        s->b.score_cap = cap;
+    }
+    *out = s;
+    return MUSE_OK;
+}
+
+// the slot's rows in place (or their copy enqueued: e its status): the fused kernel, the reduction into the pinned record, the
+// wait for it; the slot goes back to the context
+static int slot_finish(muse_ctx *ctx, RowsSlot *s, int64_t M, int32_t abs_scores, hipError_t e, muse_record *out_winner,
+                       uint8_t *out_state)
+{
+    const hipStream_t st = s->b.stream();
+    int rc = MUSE_OK;
+    if (e == hipSuccess) {
+        rc = muse_batch_score(&s->b); // the fused kernel automatic selection takes for this length (and its redo launch, if any)
+        if (!rc)
+            e = launch_single_group(s->b.mv, s->b.lag, M, abs_scores ? 1 : 0, 0, s->out, st);
+    }
+    if (e != hipSuccess || rc) {
+        (void)hipStreamSynchronize(st); // nothing of this call may still be using the slot
+        slot_return(ctx, s);
+        return rc ? rc : fail(MUSE_ERR_HIP, "muse_batch_run_rows: %s", hipGetErrorString(e));
+    }
+    // The reduction kernel's last act is the record (rec, a system-scope fence, then state) in coherent pinned memory: the
+    // caller polls the state word instead of recording and waiting for an event -- one command-processor packet and one
+    // runtime wait fewer per Muse.Run.  A kernel that never delivers (a device fault) is found by the stream synchronisation
+    // the poll falls back to.
+    {
+        volatile unsigned long long *flag = (volatile unsigned long long *)&s->out->state;
+        struct timespec t0, t1;
+        clock_gettime(CLOCK_MONOTONIC, &t0);
+        for (unsigned spin = 1; *flag == ~0ull; spin++) {
+            __builtin_ia32_pause();
+            if ((spin & 1023u) == 0) {
+                clock_gettime(CLOCK_MONOTONIC, &t1);
+                if ((t1.tv_sec - t0.tv_sec) * 1000000000ll + (t1.tv_nsec - t0.tv_nsec) > 200000000ll) // 0.2 s: hand over to the runtime
+                    break;
+            }
+        }
+        if (*flag == ~0ull) {
+            e = hipStreamSynchronize(st);
+            if (e != hipSuccess) {
+                slot_destroy(s);
+                return fail(MUSE_ERR_HIP, "muse_batch_run_rows: %s", hipGetErrorString(e));
+            }
+        }
+    }
+    const unsigned long long stt = *(volatile unsigned long long *)&s->out->state;
+    *out_winner = s->out->rec;
+    slot_return(ctx, s);
+    if (stt > 2ull)
+        return fail(MUSE_ERR_HIP, "muse_batch_run_rows: the result record did not arrive");
+    *out_state = (uint8_t)stt;
+    return MUSE_OK;
+}
+
 // the general path for groups too large for a slot: what the host mirrors did per Muse.Run before this entry point existed
 static int run_rows_general(muse_batch *tmpl, const double *rows, const double *const *row_ptrs, int64_t M, int64_t row_stride,
                             int32_t abs_scores, muse_record *out_winner, uint8_t *out_state)
@@ -220,40 +313,10 @@ static int run_rows(muse_batch *tmpl, const double *rows, const double *const *r
     if (elems > ROWS_SLOT_MAX_ELEMS)
         return run_rows_general(tmpl, rows, row_ptrs, M, row_stride, abs_scores, out_winner, out_state);
     RowsSlot *s = nullptr;
-    rc = slot_acquire(ctx, elems, &s);
+    rc = slot_take(tmpl, M, elems, &s);
     if (rc)
         return rc;
-    // the slot's group and batch take this call's shape and the template's reference
-    s->g.N = N;
-    s->g.stride = N;
-    s->g.M = M;
-    s->g.cap = M;
-    s->g.hstats_rows = 0; // (other rows than the slot's last call: no kept statistics)
-    s->b.N = tmpl->N;
-    s->b.n = tmpl->n;
-    s->b.logn = tmpl->logn;
-    s->b.sp = tmpl->sp;
-    adopt_spectrum(&s->b);
-    s->b.handoff_M = -1; // (no kernel-selection memory across unrelated groups)
-    // kernels that work in the context's shared scratch buffer are serialised on the context's stream
-    s->b.own_stream = tmpl->n >= GENERIC_LDS_MAX_N ? nullptr : s->stream;
     const hipStream_t st = s->b.stream();
-    if (M > s->b.score_cap) { // (grown in steps that small groups never reach twice)
-        dfree(ctx, s->b.mv);
-        dfree(ctx, s->b.lag);
-        s->b.mv = nullptr;
-        s->b.lag = nullptr;
-        s->b.score_cap = 0;
-        const int64_t cap = std::max<int64_t>(M, 4096);
-        hipError_t ea = dmalloc(ctx, &s->b.mv, (size_t)cap * sizeof(double));
-        if (ea == hipSuccess)
-            ea = dmalloc(ctx, &s->b.lag, (size_t)cap * sizeof(int));
-        if (ea != hipSuccess) {
-            slot_destroy(s);
-            return fail(MUSE_ERR_NOMEM, "hipMalloc failed: %s", hipGetErrorString(ea));
-        }
-        s->b.score_cap = cap;
-    }
     if (rows && row_stride == N) {
         memcpy(s->host, rows, elems * sizeof(double));
     } else {
@@ -270,47 +333,7 @@ static int run_rows(muse_batch *tmpl, const double *rows, const double *const *r
         s->g.rows = s->dev + ROWS_GUARD;
         e = hipMemcpyAsync(s->g.rows, s->host, elems * sizeof(double), hipMemcpyHostToDevice, st);
     }
-    if (e == hipSuccess) {
-        rc = muse_batch_score(&s->b); // the fused kernel automatic selection takes for this length (and its redo launch, if any)
-        if (!rc)
-            e = launch_single_group(s->b.mv, s->b.lag, M, abs_scores ? 1 : 0, 0, s->out, st);
-    }
-    if (e != hipSuccess || rc) {
-        (void)hipStreamSynchronize(st); // nothing of this call may still be using the slot
-        slot_return(ctx, s);
-        return rc ? rc : fail(MUSE_ERR_HIP, "muse_batch_run_rows: %s", hipGetErrorString(e));
-    }
-    // The reduction kernel's last act is the record (rec, a system-scope fence, then state) in coherent pinned memory: the
-    // caller polls the state word instead of recording and waiting for an event -- one command-processor packet and one
-    // runtime wait fewer per Muse.Run.  A kernel that never delivers (a device fault) is found by the stream synchronisation
-    // the poll falls back to.
-    {
-        volatile unsigned long long *flag = (volatile unsigned long long *)&s->out->state;
-        struct timespec t0, t1;
-        clock_gettime(CLOCK_MONOTONIC, &t0);
-        for (unsigned spin = 1; *flag == ~0ull; spin++) {
-            __builtin_ia32_pause();
-            if ((spin & 1023u) == 0) {
-                clock_gettime(CLOCK_MONOTONIC, &t1);
-                if ((t1.tv_sec - t0.tv_sec) * 1000000000ll + (t1.tv_nsec - t0.tv_nsec) > 200000000ll) // 0.2 s: hand over to the runtime
-                    break;
-            }
-        }
-        if (*flag == ~0ull) {
-            e = hipStreamSynchronize(st);
-            if (e != hipSuccess) {
-                slot_destroy(s);
-                return fail(MUSE_ERR_HIP, "muse_batch_run_rows: %s", hipGetErrorString(e));
-            }
-        }
-    }
-    const unsigned long long stt = *(volatile unsigned long long *)&s->out->state;
-    *out_winner = s->out->rec;
-    slot_return(ctx, s);
-    if (stt > 2ull)
-        return fail(MUSE_ERR_HIP, "muse_batch_run_rows: the result record did not arrive");
-    *out_state = (uint8_t)stt;
-    return MUSE_OK;
+    return slot_finish(ctx, s, M, abs_scores, e, out_winner, out_state);
 }
 
 extern "C" int muse_batch_run_rows(muse_batch *tmpl, const double *rows, int64_t M, int64_t row_stride, int32_t abs_scores,
@@ -329,6 +352,91 @@ extern "C" int muse_batch_run_row_ptrs(muse_batch *tmpl, const double *const *ro
     if (M > 0 && !rows)
         return fail(MUSE_ERR_INVALID, "bad arguments");
     return run_rows(tmpl, nullptr, rows, M, 0, abs_scores, out_winner, out_state);
+}
+
+// ---- Muse.Run over rows that are already resident in a group: no host copy and no PCIe transfer of samples
+// the general path for groups too large for a slot: the rows gathered into a group of their own, then the existing Run
+static int run_group_rows_general(muse_batch *tmpl, muse_group *src, const int64_t *rows, int64_t M, int32_t abs_scores,
+                                  muse_record *out_winner, uint8_t *out_state)
+{
+    muse_group *g = nullptr;
+    muse_batch *b = nullptr;
+    int rc = muse_group_create(tmpl->ctx, M, tmpl->N, &g);
+    if (!rc)
+        rc = group_gather(g, src, rows, M); // (a float32 src is widened into the float64 group)
+    if (!rc)
+        rc = muse_batch_create_like(tmpl, g, &b);
+    if (!rc) {
+        std::vector<int32_t> gid((size_t)M, 0);
+        rc = muse_batch_run_groups(b, gid.data(), 1, 0, abs_scores, out_winner, out_state);
+    }
+    muse_batch_free(b);
+    muse_group_free(g);
+    return rc;
+}
+
+extern "C" int muse_batch_run_group_rows(muse_batch *tmpl, muse_group *src, const int64_t *rows, int64_t M, int32_t abs_scores,
+                                         muse_record *out_winner, uint8_t *out_state)
+{
+    if (!tmpl || !src || !out_winner || !out_state || M < 0 || (M > 0 && !rows))
+        return fail(MUSE_ERR_INVALID, "bad arguments");
+    *out_winner = muse_record{-1, 0.0, 0, 0};
+    *out_state = 0;
+    if (src->ctx != tmpl->ctx)
+        return fail(MUSE_ERR_INVALID, "the group and the template belong to different contexts");
+    if (src->win_rows)
+        return fail(MUSE_ERR_INVALID, "the group has an open staging window");
+    const int32_t N = tmpl->N;
+    if (src->N != N) // muse.go:68-70
+        return fail(MUSE_ERR_LENGTH, "Encountered a comparison graph with differing length than the reference (%d vs %d)", src->N, N);
+    int rc = check_row_list(src, rows, M);
+    if (rc || M == 0) // muse.go:47-50: nothing to compare
+        return rc;
+    muse_ctx *ctx = tmpl->ctx;
+    rc = use_device(ctx);
+    if (rc)
+        return rc;
+    const size_t elems = (size_t)M * (size_t)N;
+    if (elems > ROWS_SLOT_MAX_ELEMS)
+        return run_group_rows_general(tmpl, src, rows, M, abs_scores, out_winner, out_state);
+    // one ascending run of a float64 group is scored where it lies (a padded length reads up to n - N samples in front of the
+    // first row and masks them: the row in front of it, or the group's guard in front of row 0)
+    bool contiguous = !src->f32;
+    for (int64_t i = 1; i < M && contiguous; i++)
+        contiguous = rows[i] == rows[0] + i;
+    // the index list rides at the end of the slot's device buffer (behind the M x N gathered rows)
+    RowsSlot *s = nullptr;
+    rc = slot_take(tmpl, M, contiguous ? elems : elems + (size_t)M, &s);
+    if (rc)
+        return rc;
+    const hipStream_t st = s->b.stream();
+    s->out->state = ~0ull;
+    hipError_t e = hipSuccess;
+    // src's packed rows enqueued and this call's stream behind every write into src
+    rc = group_ready_shared(src, st);
+    if (!rc) {
+        if (contiguous) {
+            s->g.rows = src->rows + rows[0] * src->stride;
+        } else {
+            s->g.rows = s->dev + ROWS_GUARD;
+            memcpy(s->host, rows, (size_t)M * sizeof(long long));
+            // (a short list is read by the gather straight from the pinned buffer, as the smallest groups' rows are by run_rows)
+            const long long *idx = (const long long *)s->host_dev;
+            if (!idx || elems * sizeof(double) > ROWS_ZERO_COPY_BYTES || ctx->rows_always_copy.load(std::memory_order_relaxed)) {
+                idx = (const long long *)(s->g.rows + elems);
+                e = hipMemcpyAsync((void *)idx, s->host, (size_t)M * sizeof(long long), hipMemcpyHostToDevice, st);
+            }
+            if (e == hipSuccess)
+                e = launch_row_gather(src->base(), src->f32, s->g.rows, false, idx, M, N, ctx->num_cus,
+                                      ctx->gather_nt.load(std::memory_order_relaxed), st);
+        }
+    }
+    if (rc) {
+        (void)hipStreamSynchronize(st);
+        slot_return(ctx, s);
+        return rc;
+    }
+    return slot_finish(ctx, s, M, abs_scores, e, out_winner, out_state);
 }
 
 extern "C" int muse_test_rows_always_copy(muse_ctx *ctx, int32_t always_copy)

@@ -145,6 +145,10 @@ hipError_t launch_synth(double *rows, long long stride, long long first, long lo
 hipError_t launch_synth_f32(float *rows, long long stride, long long first, long long count, long long global_first,
                             int N, unsigned long long seed, unsigned flags, hipStream_t stream);
 hipError_t launch_synth_ref(double *ref, int N, unsigned long long seed, hipStream_t stream);
+// row_gather.hip: dst row i = src row idx[i] (i < count; rows N elements apart, idx in memory the device reads), float64 or
+// float32 rows, float32 -> float64 widened exactly; nontemporal: the stores bypass the caches
+hipError_t launch_row_gather(const void *src, bool src_f32, void *dst, bool dst_f32, const long long *idx, long long count,
+                             int N, int num_cus, bool nontemporal, hipStream_t stream);
 
 // measurement hook (diag_kernels.hip): one wave sampling delta s_memtime / delta s_memrealtime in windows of window_ms for total_ms
 hipError_t launch_clock_probe(unsigned long long *out, int *count, int max_windows, double window_ms, double total_ms,

@@ -32,6 +32,7 @@
 #include <memory_resource>
 #include <mutex>
 #include <random>
+#include <shared_mutex>
 #include <stdexcept>
 #include <string>
 #include <string_view>
@@ -106,6 +107,24 @@ using LabelsPtr = std::shared_ptr<const Labels>;
 inline LabelsPtr NewLabels(LabelMap m) { return std::make_shared<Labels>(std::move(m)); }
 
 // ------------------------------------------------------------- series.go
+namespace detail {
+// A Group's device rows as a HOME of the Series uploaded into it (Group::ReuseResidentRows): a later Group or Muse::Run on the same
+// context takes such a row from here (HBM -> HBM) instead of uploading it again.  Shared lock: a gather out of `dev`;
+// exclusive: a background upload into it, and its release (alive = false).
+struct DeviceHome {
+    muse_group *dev = nullptr;
+    muse_ctx *ctx = nullptr;
+    int N = 0;
+    bool alive = true;
+    std::shared_mutex mu;
+};
+inline std::mutex &home_mu()
+{
+    static std::mutex mu;
+    return mu;
+}
+} // namespace detail
+
 class Series {
 public:
     Series(std::vector<double> y, LabelsPtr labels) : y_(std::move(y)), labels_(std::move(labels))
@@ -122,11 +141,39 @@ public:
     const std::vector<double> &Values() const { return y_; }
     const LabelsPtr &Labels() const { return labels_; }
     const std::string &UID() const { return uid_; } // series.go:40-42
+    // the first device group that received this row, and the row there (set once; the values are immutable, so any later copy
+    // of the row is the same bytes)
+    void set_home(const std::shared_ptr<detail::DeviceHome> &h, int64_t row) const
+    {
+        if (home_set_.load(std::memory_order_acquire))
+            return;
+        std::lock_guard<std::mutex> lock(detail::home_mu());
+        if (!home_set_.load(std::memory_order_relaxed)) {
+            home_ = h;
+            home_row_ = row;
+            home_set_.store(true, std::memory_order_release);
+        }
+    }
+    // that home if it still holds the row (a live group on ctx, of length N), else null
+    std::shared_ptr<detail::DeviceHome> home(muse_ctx *ctx, int N, int64_t *row) const
+    {
+        if (!home_set_.load(std::memory_order_acquire))
+            return nullptr;
+        std::shared_ptr<detail::DeviceHome> h = home_.lock();
+        if (!h || h->ctx != ctx || h->N != N)
+            return nullptr;
+        *row = home_row_;
+        return h;
+    }
+    bool has_home() const { return home_set_.load(std::memory_order_acquire) && !home_.expired(); }
 
 private:
     std::vector<double> y_;
     LabelsPtr labels_;
     std::string uid_;
+    mutable std::weak_ptr<detail::DeviceHome> home_;
+    mutable int64_t home_row_ = 0;
+    mutable std::atomic<bool> home_set_{false};
 };
 using SeriesPtr = std::shared_ptr<Series>;
 inline SeriesPtr NewSeries(std::vector<double> y, LabelsPtr labels = nullptr)
@@ -404,8 +451,7 @@ public:
     ~Group()
     {
         drain_stream(false);
-        if (dev_)
-            muse_group_free(dev_);
+        drop_dev();
         free_shards();
     }
     // Rows are streamed towards the default engine's HBM as they are added ("Group.Add stages series into a
@@ -417,6 +463,10 @@ public:
     static constexpr size_t STREAM_BYTES = (size_t)4 << 20;
     // the first hand-over of a Group could leave earlier; measured, 1 MB is worse than 4 (cold BenchmarkMuseBatchRunLarge 740 -> 791 us)
     static inline size_t StreamFirstBytes = (size_t)4 << 20;
+    // Series whose row already lives in another Group's device rows on the same engine are copied from there, HBM -> HBM
+    // (muse_group_append_from), and Muse::Run scores such series where they lie (muse_batch_run_group_rows); such series are
+    // not streamed on Add.  Relies on Series values being immutable.  Off: Group::ReuseResidentRows = false (A/B, tests).
+    static inline bool ReuseResidentRows = true;
     std::string Name;
     int Length() const { return n_; }
     // group.go:31-56; errors come back as muse::Error(MUSE_ERR_INVALID / MUSE_ERR_LENGTH)
@@ -442,7 +492,9 @@ public:
                 throw Error(MUSE_ERR_INVALID,
                             "Series with label:values, " + uid + ", already exists within group, " + Name);
             order_.push_back(s);
-            if (StreamOnAdd && (order_.size() - uploaded_) * (size_t)n_ * sizeof(double) >= (uploaded_ ? STREAM_BYTES : StreamFirstBytes))
+            if (ReuseResidentRows && s->has_home())
+                pending_homed_++;
+            if (StreamOnAdd && pending_homed_ == 0 && (order_.size() - uploaded_) * (size_t)n_ * sizeof(double) >= (uploaded_ ? STREAM_BYTES : StreamFirstBytes))
                 maybe_stream();
         }
     }
@@ -575,19 +627,80 @@ public:
         }
         drain_stream(true); // (rows handed to the background uploader are committed; its errors surface here)
         if (!dev_ || eng_ != eng) {
-            if (dev_)
-                muse_group_free(dev_);
-            dev_ = nullptr;
+            drop_dev();
             eng_ = eng;
             uploaded_ = 0;
-            check(muse_group_create(eng->handle(), (int64_t)order_.size(), n_ > 0 ? n_ : 1, &dev_));
+            make_dev((int64_t)order_.size());
         }
-        append_rows(dev_, uploaded_, order_.size(), side);
+        append_resident_or_host(uploaded_, order_.size(), side);
         uploaded_ = order_.size();
+        pending_homed_ = 0;
+        for (; homed_ < order_.size(); homed_++) // (the rows streamed on Add included)
+            order_[homed_]->set_home(home_, (int64_t)homed_);
         return dev_;
     }
 
 private:
+    void make_dev(int64_t capacity)
+    {
+        check(muse_group_create(eng_->handle(), capacity, n_ > 0 ? n_ : 1, &dev_));
+        home_ = std::make_shared<detail::DeviceHome>();
+        home_->dev = dev_;
+        home_->ctx = eng_->handle();
+        home_->N = n_ > 0 ? n_ : 1;
+        homed_ = 0;
+    }
+    void drop_dev()
+    {
+        if (home_) { // (no gather out of these rows is in flight, and none starts: the Series fall back to the host)
+            std::unique_lock<std::shared_mutex> lock(home_->mu);
+            home_->alive = false;
+        }
+        home_.reset();
+        if (dev_)
+            muse_group_free(dev_);
+        dev_ = nullptr;
+    }
+    // series [first, last) to dev_: maximal runs of series that live in ONE other live home on this engine are gathered from
+    // there, everything else goes up from the host (append_rows), in order
+    void append_resident_or_host(size_t first, size_t last, const std::function<void()> *side)
+    {
+        if (!ReuseResidentRows || first >= last) {
+            append_rows(dev_, first, last, side);
+            return;
+        }
+        std::vector<std::shared_ptr<detail::DeviceHome>> homes(last - first);
+        std::vector<int64_t> at(last - first, 0);
+        bool any = false;
+        for (size_t i = first; i < last; i++) {
+            auto h = order_[i]->home(home_->ctx, home_->N, &at[i - first]);
+            if (h && h != home_)
+                homes[i - first] = std::move(h), any = true;
+        }
+        if (!any) {
+            append_rows(dev_, first, last, side);
+            return;
+        }
+        if (side)
+            (*side)();
+        for (size_t lo = first; lo < last;) {
+            const auto &h = homes[lo - first];
+            size_t hi = lo + 1;
+            while (hi < last && homes[hi - first] == h)
+                hi++;
+            bool done = false;
+            if (h) {
+                std::shared_lock<std::shared_mutex> lock(h->mu);
+                if (h->alive) {
+                    check(muse_group_append_from(dev_, h->dev, at.data() + (lo - first), (int64_t)(hi - lo)));
+                    done = true;
+                }
+            }
+            if (!done)
+                append_rows(dev_, lo, hi);
+            lo = hi;
+        }
+    }
     // series [first, last) to a device group through the library's pinned windows (muse_group_stage / _commit): every Series is
     // copied ONCE, straight into pinned memory, by a few threads in pieces of ~256 KB; a piece that completes the packed
     // prefix of the window hands that prefix -- its own rows and every finished piece behind them, as ONE copy -- to the
@@ -686,7 +799,7 @@ private:
             eng_ = stream_eng_;
             uploaded_ = 0;
             // (capacity for four hand-overs; growth beyond is asynchronous in the library: muse_group_append's reserve)
-            check(muse_group_create(eng_->handle(), (int64_t)(4 * (order_.size() - uploaded_)), n_, &dev_));
+            make_dev((int64_t)(4 * (order_.size() - uploaded_)));
         }
         submit_rest();
     }
@@ -697,9 +810,13 @@ private:
         uploaded_ = order_.size();
         muse_group *const dev = dev_;
         const int n = n_;
+        std::shared_ptr<detail::DeviceHome> home = home_;
         if (stream_job_.valid())
             stream_older_.push_back(std::move(stream_job_));
-        stream_job_ = detail::Uploader::get().submit([part, dev, n] { append_window_loop(dev, part->data(), 0, part->size(), n, nullptr); });
+        stream_job_ = detail::Uploader::get().submit([part, dev, n, home] {
+            std::unique_lock<std::shared_mutex> lock(home->mu); // (no gather out of dev while a window is open)
+            append_window_loop(dev, part->data(), 0, part->size(), n, nullptr);
+        });
     }
     void drain_stream(bool rethrow)
     {
@@ -743,6 +860,9 @@ private:
     std::vector<LabelsPtr> index_distinct_;
     std::shared_ptr<Engine> eng_;
     muse_group *dev_ = nullptr;
+    std::shared_ptr<detail::DeviceHome> home_; // dev_ as the home of the series uploaded into it
+    size_t homed_ = 0;                    // series [0, homed_) have been offered dev_ as their home
+    size_t pending_homed_ = 0;            // series added since the last hand-over that have a home (Add then streams nothing)
     size_t uploaded_ = 0;                 // series resident in dev_ or handed to the background uploader
     std::vector<Shard> shards_;
     std::shared_ptr<Engine> stream_eng_;  // the engine Add streams towards (the default engine, if the process had one at the first hand-over)
@@ -1225,12 +1345,32 @@ public:
         }
         muse_record win{};
         uint8_t state = 0;
-        check(muse_batch_run_row_ptrs(template_, rows, (int64_t)compGraphs.size(), 0, &win, &state));
+        if (!run_resident(compGraphs, &win, &state))
+            check(muse_batch_run_row_ptrs(template_, rows, (int64_t)compGraphs.size(), 0, &win, &state));
         if (state == 1 && win.series >= 0)
             Results_->Update(Score{compGraphs[(size_t)win.series]->Labels(), win.lag, win.score});
     }
 
 private:
+    // every series lives in ONE live home on this engine: scored where it lies (muse_batch_run_group_rows), nothing crosses PCIe
+    bool run_resident(const std::vector<SeriesPtr> &compGraphs, muse_record *win, uint8_t *state)
+    {
+        if (!Group::ReuseResidentRows)
+            return false;
+        std::shared_ptr<detail::DeviceHome> src;
+        std::vector<int64_t> at(compGraphs.size());
+        for (size_t i = 0; i < compGraphs.size(); i++) {
+            auto h = compGraphs[i]->home(eng_->handle(), refN_, &at[i]);
+            if (!h || (src && h != src))
+                return false;
+            src = std::move(h);
+        }
+        std::shared_lock<std::shared_mutex> lock(src->mu);
+        if (!src->alive)
+            return false;
+        check(muse_batch_run_group_rows(template_, src->dev, at.data(), (int64_t)at.size(), 0, win, state));
+        return true;
+    }
     std::shared_ptr<Engine> eng_;
     std::vector<double> ref_;
     int refN_ = 0;

@@ -18,6 +18,7 @@ import math
 import sys
 import threading
 import uuid
+import weakref
 
 import numpy as np
 
@@ -39,6 +40,19 @@ class Engine:
         self._h = ctypes.c_void_p()
         B.check(B.load().muse_ctx_create(int(device), ctypes.byref(self._h)))
         self.device = int(device)
+        self._reuse = True
+
+    def reuse_resident_rows(self, on=None):
+        """Group / Muse.Run mirrors on this engine take a Series' row from the DeviceGroup that already holds it (HBM -> HBM,
+        muse_group_append_from / muse_batch_run_group_rows) instead of uploading it again.  On by default; pass False for
+        the host path (A/B runs, tests).  Returns the setting."""
+        if on is not None:
+            self._reuse = bool(on)
+        return self._reuse
+
+    def gather_nontemporal(self, on):
+        """measurement hook: the row gather stores with non-temporal stores (muse_test_gather_nontemporal)"""
+        B.check(B.load().muse_test_gather_nontemporal(self._h, 1 if on else 0))
 
     def close(self):
         if self._h:
@@ -223,6 +237,7 @@ class DeviceGroup:
         B.check(create(engine._h, int(capacity), int(N), ctypes.byref(self._h)))
         self.N = int(N)
         self.f32 = bool(f32)
+        self.alive = True     # False once closed: Series whose home this group is go back to the host path
 
     @classmethod
     def from_rows(cls, engine, rows, f32=False):
@@ -257,6 +272,12 @@ class DeviceGroup:
                             % (rows.shape[1], self.N))
         stride = rows.strides[0] // 8 if rows.shape[0] > 1 else self.N
         B.check(B.load().muse_group_append(self._h, rows.ctypes.data_as(B._dp), rows.shape[0], stride))
+
+    def append_from(self, src, rows):
+        """muse_group_append_from: rows src[rows[i]] of another DeviceGroup on the same engine become this group's next rows,
+        in list order, copied HBM -> HBM (asynchronous; src may be closed right after the call)"""
+        idx = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        B.check(B.load().muse_group_append_from(self._h, src._h, B.i64ptr(idx), idx.shape[0]))
 
     def stage(self, count):
         """muse_group_stage: a window of pinned host memory for up to `count` more rows -> a (granted, N) float64 array VIEW of
@@ -298,6 +319,7 @@ class DeviceGroup:
         return out
 
     def close(self):
+        self.alive = False
         if self._h:
             B.load().muse_group_free(self._h)
             self._h = ctypes.c_void_p()
@@ -434,6 +456,16 @@ class DeviceBatch:
         rec = np.zeros(1, dtype=B.RECORD_DTYPE)
         state = ctypes.c_uint8(0)
         B.check(B.load().muse_batch_run_row_ptrs(self._h, ptrs, len(arrs), 1 if abs_scores else 0, B.recptr(rec), ctypes.byref(state)))
+        return rec[0], int(state.value)
+
+    def run_group_rows(self, src, rows, abs_scores=False):
+        """muse_batch_run_group_rows: run_rows over rows that already live in the DeviceGroup `src` (row i of the label group =
+        src row rows[i]); -> (winner record, state), the winner's series being its position in `rows`"""
+        idx = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        rec = np.zeros(1, dtype=B.RECORD_DTYPE)
+        state = ctypes.c_uint8(0)
+        B.check(B.load().muse_batch_run_group_rows(self._h, src._h, B.i64ptr(idx), idx.shape[0], 1 if abs_scores else 0,
+                                                   B.recptr(rec), ctypes.byref(state)))
         return rec[0], int(state.value)
 
     def run_groups(self, group_id, G, series_offset=0, abs_scores=True):
@@ -604,6 +636,7 @@ class Series:
             labels = NewLabels({DefaultLabel: str(uuid.uuid4())})
         self.y = np.asarray(y, dtype=np.float64)
         self.labels = labels
+        self._home = None     # (weakref to the first DeviceGroup that received this row, its row there): set_home / live_home
 
     def Length(self):
         return int(self.y.shape[0])
@@ -620,6 +653,49 @@ class Series:
 
 def NewSeries(y, labels=None):
     return Series(y, labels)
+
+
+# ------------------------------------------------------ resident rows (reuse)
+# A Series' values are taken as immutable once it is added (as everywhere in this mirror): the first DeviceGroup that receives its
+# row becomes its HOME, and a later Group or Muse.Run on the same engine takes the row from there (HBM -> HBM) instead of
+# sending it across PCIe again.  A closed DeviceGroup is no home any more.
+def set_home(series, dgroup, row):
+    if getattr(series, "_home", None) is None:
+        series._home = (weakref.ref(dgroup), int(row))
+
+
+def live_home(series, engine, N, f32=None):
+    """(DeviceGroup, row) of the Series' home if it is alive, on `engine`, of length N and (f32 not None) of that storage type"""
+    h = getattr(series, "_home", None)
+    if h is None:
+        return None
+    dg = h[0]()
+    if dg is None or not getattr(dg, "alive", False) or dg.engine is not engine or dg.N != N or \
+            (f32 is not None and bool(dg.f32) != bool(f32)):
+        return None
+    return dg, h[1]
+
+
+def plan_rows(series, engine, N, f32=False, dst=None):
+    """Pure planning step of a Group upload: the series list cut into maximal runs, in order, each either
+    ("host", lo, hi) -- uploaded from host memory -- or ("device", lo, hi, src, rows) -- series [lo, hi) all live in the
+    DeviceGroup `src` (same engine, N and storage; not `dst` itself) at rows `rows`, gathered HBM -> HBM."""
+    runs = []
+    for i, s in enumerate(series):
+        h = live_home(s, engine, N, f32)
+        if h is not None and h[0] is dst:
+            h = None
+        if h is None:
+            if runs and runs[-1][0] == "host":
+                runs[-1] = ("host", runs[-1][1], i + 1)
+            else:
+                runs.append(("host", i, i + 1))
+        elif runs and runs[-1][0] == "device" and runs[-1][3] is h[0]:
+            runs[-1][4].append(h[1])
+            runs[-1] = ("device", runs[-1][1], i + 1, h[0], runs[-1][4])
+        else:
+            runs.append(("device", i, i + 1, h[0], [h[1]]))
+    return runs
 
 
 # ---------------------------------------------------------------- group.go
@@ -730,7 +806,15 @@ class Group:
             self._dev = [engine, DeviceGroup(engine, self.n, len(ser)), 0, getattr(self.registry, "version", 0) - len(ser)]
         _, dg, done, _ = self._dev
         if done < len(ser):
-            dg.append(np.stack([s.y for s in ser[done:]]))
+            todo = ser[done:]
+            runs = plan_rows(todo, engine, self.n, False, dg) if engine._reuse else [("host", 0, len(todo))]
+            for run in runs:
+                if run[0] == "host":
+                    dg.append(np.stack([s.y for s in todo[run[1]:run[2]]]))
+                else:
+                    dg.append_from(run[3], run[4])
+            for i, s in enumerate(todo):
+                set_home(s, dg, done + i)
         self._dev[2] = len(ser)
         self._dev[3] = getattr(self.registry, "version", 0)
         return dg
@@ -1095,12 +1179,30 @@ class Muse:
             if s.Length() != self.refN:
                 raise MuseError(B.MUSE_ERR_LENGTH, "Encountered a comparison graph with differing length "
                                 "than the reference, %r" % (s.Labels(),))
-        rows = np.stack([s.y for s in compGraphs])
-        win, state = self._template.run_rows(rows, abs_scores=False)      # one ABI call (muse_batch_run_rows)
+        home = self._resident(compGraphs)
+        if home is not None:      # every row already lives in one DeviceGroup on this engine: nothing crosses PCIe
+            win, state = self._template.run_group_rows(home[0], home[1], abs_scores=False)
+        else:
+            rows = np.stack([s.y for s in compGraphs])
+            win, state = self._template.run_rows(rows, abs_scores=False)      # one ABI call (muse_batch_run_rows)
         if state == 1 and win["series"] >= 0:
             # the group's Score through the unchanged Update, which applies passed() as the reference does (results.go:55-72)
             self.Results.Update(Score(compGraphs[int(win["series"])].Labels(), int(win["lag"]), float(win["score"])))
         return None
+
+
+    def _resident(self, compGraphs):
+        """(DeviceGroup, rows) when reuse is on and every series has a live home in ONE DeviceGroup on this engine"""
+        if not self._engine._reuse:
+            return None
+        src, rows = None, []
+        for s in compGraphs:
+            h = live_home(s, self._engine, self.refN)
+            if h is None or (src is not None and h[0] is not src):
+                return None
+            src = h[0]
+            rows.append(h[1])
+        return src, rows
 
 
 def New(ref, results, engine=None):

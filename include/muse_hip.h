@@ -162,6 +162,17 @@ int muse_group_append(muse_group *g, const double *rows, int64_t count,
  * _stage and its last _commit.  float64 groups only (MUSE_ERR_UNSUPPORTED for float32-storage groups). */
 int muse_group_stage(muse_group *g, int64_t count, double **window, int64_t *granted);
 int muse_group_commit(muse_group *g, int64_t first, int64_t count);
+/* Group.Add of series that already live in another group on the same context (go-muse's Group.Add keeps the caller's
+ * slice, group.go:53, and FilterByLabelValues hands back the same *Series, group.go:60-71, so building a sub-group copies
+ * nothing): rows src[rows[i]] become rows [M, M + count) of dst, in list order, copied HBM -> HBM (no host copy, nothing
+ * crosses PCIe but the index list).  Duplicates and any order are allowed.  MUSE_ERR_INVALID for a NULL handle, count < 0,
+ * an index outside [0, src's M), groups on different contexts, src == dst, different storage types (float32 / float64) or an
+ * open staging window on either group; MUSE_ERR_LENGTH when the lengths differ.  Everything is checked before anything is
+ * enqueued: on an error dst is unchanged.  count == 0 does nothing.  Asynchronous like muse_group_append: the gather runs on
+ * the context's copy stream behind both groups' earlier uploads and in front of dst's later ones, and every later kernel
+ * that reads dst waits for it; src may be freed right after the call.  Rows are taken as immutable once added: the
+ * gather copies what src holds when it runs. */
+int muse_group_append_from(muse_group *dst, muse_group *src, const int64_t *rows, int64_t count);
 /* create + append in one call */
 int muse_group_upload(muse_ctx *ctx, const double *rows, int64_t M, int32_t N,
                       int64_t row_stride, muse_group **out);
@@ -222,6 +233,14 @@ int muse_batch_run_rows(muse_batch *tmpl, const double *rows, int64_t M, int64_t
  * INTEGRATION.md keeps the packed form for Go.) */
 int muse_batch_run_row_ptrs(muse_batch *tmpl, const double *const *rows, int64_t M,
                             int32_t abs_scores, muse_record *out_winner, uint8_t *out_state);
+/* Muse.Run (muse.go:46-92) over rows that are already resident in a group on tmpl's context: as muse_batch_run_rows, with
+ * row i of the label group = src row rows[i] (any order, duplicates allowed); out_winner->series is the position in `rows`.
+ * No sample crosses PCIe: the rows are gathered into the call's device buffer (float32-storage groups widened exactly), or,
+ * when `rows` is one ascending contiguous run of a float64 group, scored where they lie.  Validation as
+ * muse_group_append_from (MUSE_ERR_INVALID / MUSE_ERR_LENGTH for a length other than the reference's).  Any number of host
+ * threads may call it at once on one tmpl and one src; appending to src while such calls are in flight is not allowed. */
+int muse_batch_run_group_rows(muse_batch *tmpl, muse_group *src, const int64_t *rows, int64_t M,
+                              int32_t abs_scores, muse_record *out_winner, uint8_t *out_state);
 int muse_batch_fft_len(muse_batch *b, int32_t *n);
 /* The batch's x (muse_batch.go:47): n/2+1 complex128, interleaved re,im. */
 int muse_batch_spectrum(muse_batch *b, double *out);

@@ -64,6 +64,10 @@ int muse_test_xcorr_repeat(muse_ctx *ctx, int32_t repeat);
  * 0 = the built-in 128 MB (half the Infinity Cache).  tools/huge_bench.py, profiles/r06_long_series.txt. */
 int muse_test_huge_batch_mb(muse_ctx *ctx, int32_t megabytes);
 
+/* Measurement hook: the row gather of muse_group_append_from / muse_batch_run_group_rows (row_gather.hip) stores with
+ * non-temporal stores (on = 1) or plain ones (0, the default): tools/resident_bench.py measures both. */
+int muse_test_gather_nontemporal(muse_ctx *ctx, int32_t on);
+
 #ifdef __cplusplus
 }
 #endif
