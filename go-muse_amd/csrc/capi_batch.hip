@@ -50,20 +50,8 @@ hipError_t ensure_gscratch(muse_ctx *ctx, int64_t n, int slices_per_cu)
 {
     if (n < GENERIC_LDS_MAX_N) // generic kernel above 8192: one slice per workgroup; Stockham from 8192: up to two
         return hipSuccess;
-    const size_t need = (size_t)ctx->num_cus * (size_t)slices_per_cu * (size_t)n;
     std::lock_guard<std::mutex> lock(ctx->stage_mu); // launches that use the buffer hold the same lock (muse_batch_score)
-    if (need <= ctx->gscratch_elems)
-        return hipSuccess;
-    hipError_t e = hipStreamSynchronize(ctx->stream); // nothing may still be using the old buffer
-    if (e != hipSuccess)
-        return e;
-    (void)hipFree(ctx->gscratch);
-    ctx->gscratch = nullptr;
-    ctx->gscratch_elems = 0;
-    e = hipMalloc(&ctx->gscratch, need * sizeof(double2));
-    if (e == hipSuccess)
-        ctx->gscratch_elems = need;
-    return e;
+    return ctx->gscratch.ensure(ctx, (int64_t)ctx->num_cus * slices_per_cu * n, ctx->stream);
 }
 
 // the base table of the long-series sweeps' twiddles, [4096] W_n^(m2) (n = 16384, 32768, 65536): built on first use per length
@@ -294,16 +282,8 @@ extern "C" int muse_batch_spectrum(muse_batch *b, double *out)
 int ensure_scores(muse_batch *b)
 {
     const int64_t M = b->g->M;
-    if (M <= b->score_cap)
-        return MUSE_OK;
-    dfree(b->ctx, b->mv);
-    dfree(b->ctx, b->lag);
-    b->mv = nullptr;
-    b->lag = nullptr;
-    b->score_cap = 0;
-    HIP_TRY(dmalloc(b->ctx, &b->mv, (size_t)M * sizeof(double)));
-    HIP_TRY(dmalloc(b->ctx, &b->lag, (size_t)M * sizeof(int)));
-    b->score_cap = M;
+    HIP_TRY(b->mv.ensure(b->ctx, M, b->stream()));
+    HIP_TRY(b->lag.ensure(b->ctx, M, b->stream()));
     return MUSE_OK;
 }
 
@@ -326,10 +306,10 @@ FusedParams base_params(muse_batch *b)
     p.tw1 = ctx->tw1;
     p.tw2 = ctx->tw2;
     p.twm = ctx->twm;
-    p.gscratch = ctx->gscratch;
-    p.gscratch_slices = b->n > 0 ? (long long)(ctx->gscratch_elems / (size_t)b->n) : 0;
-    p.mv = b->mv;
-    p.lag = b->lag;
+    p.gscratch = ctx->gscratch.p;
+    p.gscratch_slices = b->n > 0 ? (long long)(ctx->gscratch.cap / b->n) : 0;
+    p.mv = b->mv.p;
+    p.lag = b->lag.p;
     p.cc_out = nullptr;
     p.nil_out = nullptr;
     p.g2 = ctx->g2;
@@ -461,22 +441,16 @@ extern "C" int muse_batch_score(muse_batch *b)
         // pairs with a NaN/Inf series or with sigmas too far apart for one shared transform are listed by the kernel
         // (once per such series: 2 entries per pair) and redone by the rescaling kernel right behind it (no host round
         // trip: the count stays on the device and bounds the second launch's loop)
-        if (2 * p.npairs > b->ovf_cap) {
-            dfree(ctx, b->ovf_list);
-            b->ovf_list = nullptr;
-            b->ovf_cap = 0;
-            HIP_TRY(dmalloc(ctx, &b->ovf_list, (size_t)(2 * p.npairs) * sizeof(long long)));
-            b->ovf_cap = 2 * p.npairs;
-        }
+        HIP_TRY(b->ovf_list.ensure(ctx, 2 * p.npairs, st));
         p.ovf_count = b->ovf_count;
         p.work_counter = b->ovf_count + 1;
-        p.ovf_list = b->ovf_list;
+        p.ovf_list = b->ovf_list.p;
         HIP_TRY(hipMemsetAsync(b->ovf_count, 0, 2 * sizeof(int), st));
         HIP_TRY(timer.begin());
         HIP_TRY(launch_fused(p, variant, ctx->num_cus, st));
         HIP_TRY(timer.end());
         FusedParams q = p;
-        q.pair_list = b->ovf_list;
+        q.pair_list = b->ovf_list.p;
         q.pair_count = b->ovf_count;
         // a dense list (the same threshold as the hand-off rule above) makes the redo kernel redo EVERY pair: the results of a
         // mixed-unit group then come from kernel 7 in this pass exactly as in the later ones that go there directly
@@ -500,21 +474,15 @@ extern "C" int muse_batch_score(muse_batch *b)
     } else if (variant == KERNEL_LONG) {
         // as above: NaN / Inf and sigma-spread pairs are listed (one entry per pair) and redone by the four-step kernel that
         // isolates and rescales the series first
-        if (2 * p.npairs > b->ovf_cap) {
-            dfree(ctx, b->ovf_list);
-            b->ovf_list = nullptr;
-            b->ovf_cap = 0;
-            HIP_TRY(dmalloc(ctx, &b->ovf_list, (size_t)(2 * p.npairs) * sizeof(long long)));
-            b->ovf_cap = 2 * p.npairs;
-        }
+        HIP_TRY(b->ovf_list.ensure(ctx, 2 * p.npairs, st));
         p.ovf_count = b->ovf_count;
-        p.ovf_list = b->ovf_list;
+        p.ovf_list = b->ovf_list.p;
         HIP_TRY(hipMemsetAsync(b->ovf_count, 0, 2 * sizeof(int), st));
         HIP_TRY(timer.begin());
         HIP_TRY(launch_fused(p, variant, ctx->num_cus, st));
         HIP_TRY(timer.end());
         FusedParams q = p;
-        q.pair_list = b->ovf_list;
+        q.pair_list = b->ovf_list.p;
         q.pair_count = b->ovf_count;
         q.npairs = std::min<long long>(p.npairs, (long long)ctx->num_cus * STOCKHAM_GLOBAL_WGS_PER_CU);
         HIP_TRY(redo_timer.begin());
@@ -538,8 +506,8 @@ extern "C" int muse_batch_scores(muse_batch *b, int32_t *lag, double *mv)
         return MUSE_OK;
     if (!lag || !mv)
         return fail(MUSE_ERR_INVALID, "NULL output");
-    HIP_TRY(hipMemcpyAsync(lag, b->lag, (size_t)M * sizeof(int), hipMemcpyDeviceToHost, b->stream()));
-    HIP_TRY(hipMemcpyAsync(mv, b->mv, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, b->stream()));
+    HIP_TRY(hipMemcpyAsync(lag, b->lag.p, (size_t)M * sizeof(int), hipMemcpyDeviceToHost, b->stream()));
+    HIP_TRY(hipMemcpyAsync(mv, b->mv.p, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, b->stream()));
     HIP_TRY(hipStreamSynchronize(b->stream()));
     return MUSE_OK;
 }
@@ -595,40 +563,33 @@ extern "C" int muse_batch_free(muse_batch *b)
         c->small_free.emplace_back(b->small_out, b->small_cap);
     }
     dfree(c, b->ovf_count);
-    if (b->handoff_host)
-        hfree(c, b->handoff_host);
-    dfree(c, b->ovf_list);
-    dfree(c, b->mv);
-    dfree(c, b->lag);
-    dfree(c, b->gid_dev);
-    dfree(c, b->gw.key);
-    dfree(c, b->gw.first);
-    dfree(c, b->gw.win);
-    dfree(c, b->rec);
-    dfree(c, b->selkey);
-    dfree(c, b->cand);
-    if (b->cand_host)
-        hfree(c, b->cand_host);
-    if (b->cnt_host)
-        hfree(c, b->cnt_host);
-    if (b->rec_host)
-        hfree(c, b->rec_host);
-    if (b->key_host)
-        hfree(c, b->key_host);
-    dfree(c, b->cnt);
-    dfree(c, b->scr_flags);
-    dfree(c, b->scr_var);
-    dfree(c, b->include);
-    dfree(c, b->scr_keys);
-    dfree(c, b->scr_gmay);
-    dfree(c, b->scr_gkplus);
-    dfree(c, b->scr_gcert);
-    if (b->refine_host)
-        hfree(c, b->refine_host);
-    if (b->err_host)
-        hfree(c, b->err_host);
+    hfree(c, b->handoff_host);
+    hfree(c, b->refine_host);
+    hfree(c, b->err_host);
     dfree(c, b->err_dev);
-    dfree(c, b->est_save);
+    b->ovf_list.release(c);
+    b->mv.release(c);
+    b->lag.release(c);
+    b->gid_dev.release(c);
+    b->gkey.release(c);
+    b->gfirst.release(c);
+    b->gwin.release(c);
+    b->rec.release(c);
+    b->selkey.release(c);
+    b->cand.release(c);
+    b->cnt.release(c);
+    b->cand_host.release(c);
+    b->cnt_host.release(c);
+    b->rec_host.release(c);
+    b->key_host.release(c);
+    b->scr_flags.release(c);
+    b->scr_var.release(c);
+    b->include.release(c);
+    b->scr_keys.release(c);
+    b->scr_gmay.release(c);
+    b->scr_gkplus.release(c);
+    b->scr_gcert.release(c);
+    b->est_save.release(c);
     muse_group *g = b->g;
     muse_ctx *ctx = b->ctx;
     delete b;

@@ -333,6 +333,9 @@ void ctx_release(muse_ctx *ctx)
     (void)hipFree(ctx->dbg_stamps);
     rows_slots_free(ctx);
     huge_free(ctx);
+    ctx->gscratch.release(ctx);
+    ctx->zscratch.release(ctx);
+    ctx->many_tab.release(ctx);
     for (auto &p : ctx->small_free)
         (void)hipHostFree(p.first);
     ctx->small_free.clear();
@@ -355,11 +358,8 @@ void ctx_release(muse_ctx *ctx)
     (void)hipFree(ctx->wsplit);
     for (int k = 0; k < 3; k++)
         (void)hipFree(ctx->twl[k]);
-    (void)hipFree(ctx->zscratch);
-    (void)hipFree(ctx->gscratch);
     for (double *b : ctx->stage_pool)
         (void)hipHostFree(b);
-    (void)hipFree(ctx->many_tab);
     (void)hipFree(ctx->tw2f);
     if (ctx->probe_stream) {
         if (ctx->probe_buf) // (a probe still running ends within microseconds of its stop flag)

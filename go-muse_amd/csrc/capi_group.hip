@@ -377,21 +377,14 @@ int group_gather(muse_group *dst, muse_group *src, const int64_t *rows, int64_t 
         HIP_TRY(hipEventCreateWithFlags(&dst->gather_done, hipEventDisableTiming));
     else
         HIP_TRY(hipEventSynchronize(dst->gather_done)); // the previous gather has read its index list
-    if (count > dst->gidx_cap) {
-        hfree(ctx, dst->gidx_host);
-        dfree(ctx, dst->gidx_dev);
-        dst->gidx_host = dst->gidx_dev = nullptr;
-        dst->gidx_cap = 0;
-        const int64_t cap = std::max<int64_t>(count, 1024);
-        HIP_TRY(hmalloc(ctx, &dst->gidx_host, (size_t)cap * sizeof(long long)));
-        HIP_TRY(dmalloc(ctx, &dst->gidx_dev, (size_t)cap * sizeof(long long)));
-        dst->gidx_cap = cap;
-    }
-    memcpy(dst->gidx_host, rows, (size_t)count * sizeof(long long));
-    HIP_TRY(hipMemcpyAsync(dst->gidx_dev, dst->gidx_host, (size_t)count * sizeof(long long), hipMemcpyHostToDevice,
+    const int64_t cap = std::max<int64_t>(count, 1024);
+    HIP_TRY(dst->gidx_host.ensure(ctx, cap, ctx->copy_stream));
+    HIP_TRY(dst->gidx_dev.ensure(ctx, cap, ctx->copy_stream));
+    memcpy(dst->gidx_host.p, rows, (size_t)count * sizeof(long long));
+    HIP_TRY(hipMemcpyAsync(dst->gidx_dev.p, dst->gidx_host.p, (size_t)count * sizeof(long long), hipMemcpyHostToDevice,
                            ctx->copy_stream));
     HIP_TRY(launch_row_gather(src->base(), src->f32, (char *)dst->base() + (size_t)(dst->M * dst->stride) * dst->elem(), dst->f32,
-                              dst->gidx_dev, count, dst->N, ctx->num_cus, ctx->gather_nt.load(std::memory_order_relaxed),
+                              dst->gidx_dev.p, count, dst->N, ctx->num_cus, ctx->gather_nt.load(std::memory_order_relaxed),
                               ctx->copy_stream));
     HIP_TRY(hipEventRecord(dst->gather_done, ctx->copy_stream));
     HIP_TRY(hipEventRecord(dst->uploaded, ctx->copy_stream));
@@ -522,9 +515,9 @@ void group_release(muse_group *g)
         dfree(g->ctx, (char *)g->base() - GROUP_GUARD * g->elem());
     for (void *old : g->retired)
         dfree(g->ctx, old);
-    dfree(g->ctx, g->hstats);
-    hfree(g->ctx, g->gidx_host);
-    dfree(g->ctx, g->gidx_dev);
+    g->hstats.release(g->ctx);
+    g->gidx_host.release(g->ctx);
+    g->gidx_dev.release(g->ctx);
     if (g->gather_done)
         (void)hipEventDestroy(g->gather_done);
     for (int i = 0; i < 2; i++) {

@@ -40,34 +40,20 @@ int huge_ensure(muse_ctx *ctx, int logn, int64_t pairs, bool tables)
         w.thi[li] = dhi;
         w.tlo[li] = dlo;
     }
-    const auto grow = [&](void **ptr, size_t &have, size_t need) -> hipError_t {
-        if (need <= have)
-            return hipSuccess;
-        hipError_t e = hipStreamSynchronize(ctx->stream); // nothing may still be using the old buffer
-        if (e != hipSuccess)
-            return e;
-        (void)hipFree(*ptr);
-        *ptr = nullptr;
-        have = 0;
-        e = hipMalloc(ptr, need);
-        if (e == hipSuccess)
-            have = need;
-        return e;
-    };
     const int64_t R1 = n / 4096;
-    hipError_t e = grow((void **)&w.Y, w.Y_bytes, (size_t)pairs * (size_t)n * sizeof(double2));
+    hipError_t e = w.Y.ensure(ctx, pairs * n, ctx->stream);
     if (e == hipSuccess && tables)
-        e = grow((void **)&w.T, w.T_bytes, (size_t)pairs * (size_t)n * sizeof(double2));
+        e = w.T.ensure(ctx, pairs * n, ctx->stream);
     if (e == hipSuccess)
-        e = grow((void **)&w.part, w.part_bytes, (size_t)(2 * pairs) * (size_t)R1 * 2 * sizeof(double));
+        e = w.part.ensure(ctx, 2 * pairs * R1 * 2, ctx->stream);
     if (e == hipSuccess)
-        e = grow((void **)&w.snorm, w.snorm_bytes, (size_t)(2 * pairs) * 4 * sizeof(double));
+        e = w.snorm.ensure(ctx, 2 * pairs * 4, ctx->stream);
     if (e == hipSuccess)
-        e = grow((void **)&w.sfin, w.sfin_bytes, (size_t)(2 * pairs) * sizeof(double));
+        e = w.sfin.ensure(ctx, 2 * pairs, ctx->stream);
     if (e == hipSuccess)
-        e = grow((void **)&w.sfin_x, w.sfin_x_bytes, (size_t)(2 * pairs) * sizeof(double));
+        e = w.sfin_x.ensure(ctx, 2 * pairs, ctx->stream);
     if (e == hipSuccess)
-        e = grow((void **)&w.amax, w.amax_bytes, (size_t)pairs * (size_t)R1 * 8 * sizeof(double));
+        e = w.amax.ensure(ctx, pairs * R1 * 8, ctx->stream);
     if (e != hipSuccess)
         return fail(MUSE_ERR_NOMEM, "long-series work buffers: %s", hipGetErrorString(e));
     return MUSE_OK;
@@ -84,11 +70,11 @@ HugeParams huge_base(muse_ctx *ctx, int logn)
     p.g2 = ctx->g2;
     p.g3a = ctx->g3a;
     p.g3b = ctx->g3b;
-    p.Y = ctx->huge.Y;
-    p.part = ctx->huge.part;
-    p.snorm = ctx->huge.snorm;
-    p.sfin = ctx->huge.sfin;
-    p.amax = ctx->huge.amax;
+    p.Y = ctx->huge.Y.p;
+    p.part = ctx->huge.part.p;
+    p.snorm = ctx->huge.snorm.p;
+    p.sfin = ctx->huge.sfin.p;
+    p.amax = ctx->huge.amax.p;
     p.pre_scale = 1.0;
 #ifdef MUSE_HUGE_ABL
     p.abl = getenv("MUSE_HUGE_ABL") ? atoi(getenv("MUSE_HUGE_ABL")) : 0;
@@ -112,19 +98,19 @@ void huge_free(muse_ctx *ctx)
         (void)hipFree(w.thi[i]);
         (void)hipFree(w.tlo[i]);
     }
-    (void)hipFree(w.Y);
-    (void)hipFree(w.T);
-    (void)hipFree(w.part);
-    (void)hipFree(w.snorm);
-    (void)hipFree(w.sfin);
-    (void)hipFree(w.sfin_x);
-    (void)hipFree(w.amax);
-    (void)hipFree(w.Y2);
-    (void)hipFree(w.amax2);
     if (w.stream2) {
         (void)hipStreamSynchronize(w.stream2);
         (void)hipStreamDestroy(w.stream2);
     }
+    w.Y.release(ctx);
+    w.T.release(ctx);
+    w.part.release(ctx);
+    w.snorm.release(ctx);
+    w.sfin.release(ctx);
+    w.sfin_x.release(ctx);
+    w.amax.release(ctx);
+    w.Y2.release(ctx);
+    w.amax2.release(ctx);
     if (w.fork)
         (void)hipEventDestroy(w.fork);
     if (w.join)
@@ -182,13 +168,9 @@ int huge_score(muse_batch *b)
     int rc = huge_ensure(ctx, b->logn, ppb, false);
     if (rc)
         return rc;
-    if (g->hstats_cap < M) { // (grown with the group; what was computed is recomputed: rare)
-        dfree(ctx, g->hstats);
-        g->hstats = nullptr;
-        g->hstats_cap = g->hstats_rows = 0;
-        const int64_t cap = std::max<int64_t>(M, g->cap);
-        HIP_TRY(dmalloc(ctx, &g->hstats, (size_t)cap * 4 * sizeof(double)));
-        g->hstats_cap = cap;
+    if (g->hstats.cap < 4 * M) { // (grown with the group; what was computed is recomputed: rare)
+        g->hstats_rows = 0;
+        HIP_TRY(g->hstats.ensure(ctx, 4 * std::max<int64_t>(M, g->cap), b->stream()));
     }
     // two streams: the batches alternate between the batch's stream and a second one, each with its own work buffer (half the
     // batch size each: the same footprint in the Infinity Cache), so the ragged end of one batch's kernels runs under the next
@@ -198,21 +180,9 @@ int huge_score(muse_batch *b)
     HugeWork &w = ctx->huge;
     if (dual) {
         const int64_t R1 = n / 4096, pairs2 = (spb + 1) / 2;
-        const auto grow2 = [&](void **ptr, size_t &have, size_t need) -> hipError_t {
-            if (need <= have)
-                return hipSuccess;
-            if (w.stream2)
-                (void)hipStreamSynchronize(w.stream2);
-            (void)hipFree(*ptr);
-            *ptr = nullptr;
-            have = 0;
-            const hipError_t e = hipMalloc(ptr, need);
-            if (e == hipSuccess)
-                have = need;
-            return e;
-        };
-        HIP_TRY(grow2((void **)&w.Y2, w.Y2_bytes, (size_t)pairs2 * (size_t)n * sizeof(double2)));
-        HIP_TRY(grow2((void **)&w.amax2, w.amax2_bytes, (size_t)pairs2 * (size_t)R1 * 8 * sizeof(double)));
+        // (only the second stream's batches use these two)
+        HIP_TRY(w.Y2.ensure(ctx, pairs2 * n, w.stream2));
+        HIP_TRY(w.amax2.ensure(ctx, pairs2 * R1 * 8, w.stream2));
         if (!w.stream2)
             HIP_TRY(hipStreamCreateWithFlags(&w.stream2, hipStreamNonBlocking));
         if (!w.fork)
@@ -230,7 +200,7 @@ int huge_score(muse_batch *b)
         p.count = (int)std::min<int64_t>(2 * ppb, M - first);
         p.N = b->N;
         p.normalize = 1;
-        p.snorm = g->hstats + first * 4;
+        p.snorm = g->hstats.p + first * 4;
         HIP_TRY(launch_huge(p, HUGE_STAGE_STATS_ONLY, b->stream()));
     }
     g->hstats_rows = M;
@@ -248,15 +218,15 @@ int huge_score(muse_batch *b)
         p.N = b->N;
         p.solo = 0;
         p.normalize = 1;
-        p.snorm = g->hstats + first * 4;
+        p.snorm = g->hstats.p + first * 4;
         p.table = b->xcp;
         p.table_stride = 0;
-        p.mv = b->mv;
-        p.lag = b->lag;
+        p.mv = b->mv.p;
+        p.lag = b->lag.p;
         const bool second = dual && which;
         if (second) {
-            p.Y = w.Y2;
-            p.amax = w.amax2;
+            p.Y = w.Y2.p;
+            p.amax = w.amax2.p;
         }
         HIP_TRY(launch_huge(p, HUGE_STAGE_SWEEP1 | HUGE_STAGE_ROWS | HUGE_STAGE_SWEEP2 | HUGE_STAGE_FINAL, second ? w.stream2 : b->stream()));
     }
@@ -291,8 +261,8 @@ int huge_pairs(muse_ctx *ctx, const double *xrows, int64_t xstride, int Nx, int 
         px.solo = 1;
         px.normalize = normalize_x;
         px.pre_scale = x_scale;
-        px.sfin = ctx->huge.sfin_x;
-        px.table_out = ctx->huge.T;
+        px.sfin = ctx->huge.sfin_x.p;
+        px.table_out = ctx->huge.T.p;
         px.table_scale = cc_scale;
         HIP_TRY(launch_huge(px, HUGE_STAGE_STATS | HUGE_STAGE_SWEEP1 | HUGE_STAGE_ROWS_FORWARD, ctx->stream));
         HugeParams py = huge_base(ctx, logn);
@@ -303,9 +273,9 @@ int huge_pairs(muse_ctx *ctx, const double *xrows, int64_t xstride, int Nx, int 
         py.N = Ny;
         py.solo = 1;
         py.normalize = normalize_y;
-        py.table = ctx->huge.T;
+        py.table = ctx->huge.T.p;
         py.table_stride = n;
-        py.sfin_x = normalize_x ? ctx->huge.sfin_x : nullptr;
+        py.sfin_x = normalize_x ? ctx->huge.sfin_x.p : nullptr;
         py.mv = mv;
         py.lag = lag;
         py.nil = nil;

@@ -41,8 +41,9 @@ int fail(int status, const char *fmt, ...);
 // Per-context cache of device and pinned-host allocations (capi_context.hip: dmalloc / dfree / hmalloc / hfree).  hipMalloc,
 // hipFree (a device-wide synchronisation each) and hipHostMalloc (hundreds of microseconds) were most of a cold
 // NewGroup -> Add -> NewBatch -> Run -> free cycle (profiles/r06_cold_path.txt); a freed block is kept by size class and handed to
-// the next request of that class.  A block handed back must no longer be in use by the device (the handles synchronise
-// their streams before they free, as they did in front of hipFree).
+// the next request of that class.  A block handed back must no longer be in use by the device: work buffers that grow keep
+// that rule through PoolBuf below; a bare dfree / hfree is left only right behind a synchronisation of the streams that used
+// the block (handle teardown, one-shot temporaries).
 struct MemPool {
     std::mutex mu;
     std::unordered_map<void *, size_t> size_of;            // every block this pool allocated (in use or cached): its class size
@@ -51,18 +52,48 @@ struct MemPool {
     size_t idle_cap = 0;                                    // cached bytes kept at most
     size_t block_cap = 0;                                   // larger blocks are never cached
 };
+hipError_t pool_alloc(muse_ctx *ctx, bool host, void **out, size_t bytes); // capi_context.hip
+void pool_free(muse_ctx *ctx, bool host, void *p);
+// A work buffer that grows on demand: `cap` elements of T from the context's device pool (Host: its pinned host pool).
+template <class T, bool Host = false> struct PoolBuf {
+    T *p = nullptr;
+    int64_t cap = 0;
+    // at least `count` elements (any rounding is the caller's); before a held block goes back to the pool, `busy` -- the stream
+    // its users were enqueued on -- is waited for.  On failure p == nullptr and cap == 0.
+    hipError_t ensure(muse_ctx *ctx, int64_t count, hipStream_t busy)
+    {
+        if (count <= cap)
+            return hipSuccess;
+        if (p) {
+            const hipError_t e = hipStreamSynchronize(busy);
+            if (e != hipSuccess)
+                return e;
+        }
+        release(ctx);
+        const hipError_t e = pool_alloc(ctx, Host, (void **)&p, (size_t)count * sizeof(T));
+        if (e == hipSuccess)
+            cap = count;
+        return e;
+    }
+    // without a wait: teardown, behind a synchronisation of the streams that used the block
+    void release(muse_ctx *ctx)
+    {
+        pool_free(ctx, Host, p);
+        p = nullptr;
+        cap = 0;
+    }
+};
+template <class T> using HostBuf = PoolBuf<T, true>;
 // FFT lengths 2^17 ... 2^20 (xcorr_huge.hip, capi_huge.hip): twiddle tables per length, the work buffer of one batch of pairs,
 // per-pair multiplier tables (two-sided xCorr), chunk sums / flags / tile maxima; grown on demand under muse_ctx::huge_mu
 struct HugeWork {
     double2 *thi[4] = {nullptr, nullptr, nullptr, nullptr}, *tlo[4] = {nullptr, nullptr, nullptr, nullptr};
-    double2 *Y = nullptr, *T = nullptr;
-    double *part = nullptr, *snorm = nullptr, *sfin = nullptr, *sfin_x = nullptr, *amax = nullptr;
-    size_t Y_bytes = 0, T_bytes = 0, part_bytes = 0, snorm_bytes = 0, sfin_bytes = 0, sfin_x_bytes = 0, amax_bytes = 0;
+    PoolBuf<double2> Y, T;
+    PoolBuf<double> part, snorm, sfin, sfin_x, amax;
     // the all-scores pass runs its batches on TWO streams alternately (the tail of one batch's kernels under the head of the
     // next one's): a second work buffer and tile-maximum buffer, the second stream, and the events that fork / join it
-    double2 *Y2 = nullptr;
-    double *amax2 = nullptr;
-    size_t Y2_bytes = 0, amax2_bytes = 0;
+    PoolBuf<double2> Y2;
+    PoolBuf<double> amax2;
     hipStream_t stream2 = nullptr;
     hipEvent_t fork = nullptr, join = nullptr;
 };
@@ -85,15 +116,12 @@ struct muse_ctx {
     // (hipHostMalloc of 32 MB costs milliseconds) and returned when the group is released
     // work buffers of the generic / Stockham kernels for n >= 8192: one allocation per context, grown on demand
     // (every kernel that uses it runs on the context's single stream)
-    double2 *gscratch = nullptr;
-    size_t gscratch_elems = 0;
+    PoolBuf<double2> gscratch;
     std::vector<double *> stage_pool;
     std::mutex stage_mu;
-    double2 *zscratch = nullptr;
-    int zslots = 0;
-    void *many_tab = nullptr; // R x {xcp, mv, lag} pointers
+    PoolBuf<double2> zscratch; // [slots][4096] (upload_many_tab)
+    PoolBuf<void *> many_tab;  // columns of R pointers ({xcp, mv, lag, ...}: upload_many_tab)
     std::vector<void *> many_host; // host image of many_tab (outlives the asynchronous copy)
-    int many_cap = 0;
     double screen_delta = 1e-4;
     // filter-and-refine Run (run_select), OPT-IN (muse_ctx_set_screening): 1 = Runs over large groups screen in fp32 and
     // re-evaluate in fp64 only the rows that can reach the top-N; 0 (default) = every Run scores all rows in fp64, the
@@ -145,8 +173,8 @@ struct muse_group {
     // FFT lengths above 65 536 (capi_huge.hip): the rows never change, so neither do a series' zNormalize statistics -- first sample,
     // mean of the shifted samples, 1 / sigma, flag per row, computed by the first pass that needs them and kept for every later Run
     // and every other reference (rows appended later are added; a re-allocation starts over)
-    double *hstats = nullptr;
-    int64_t hstats_cap = 0, hstats_rows = 0;
+    PoolBuf<double> hstats; // [cap][4]
+    int64_t hstats_rows = 0;
     uint64_t rewrites = 0;          // how often rows already in the group were rewritten (muse_group_fill_synthetic: rows are otherwise immutable)
     // allocations the group has outgrown: kept until the group goes (kernels enqueued before the growth may still read them),
     // so that growing never waits for the device (group_reserve)
@@ -176,8 +204,8 @@ struct muse_group {
     std::mutex ready_mu;
     // muse_group_append_from: the index list of the last gather into this group (pinned image and device copy), reused by the
     // next one once `gather_done` has passed
-    long long *gidx_host = nullptr, *gidx_dev = nullptr;
-    int64_t gidx_cap = 0;
+    HostBuf<long long> gidx_host;
+    PoolBuf<long long> gidx_dev;
     hipEvent_t gather_done = nullptr;
 };
 
@@ -214,47 +242,39 @@ struct muse_batch {
     int *handoff_host = nullptr;
     int64_t handoff_M = -1;         // the rows the count was taken over: M of them, after handoff_rewrites rewrites of the group
     uint64_t handoff_rewrites = 0;
-    long long *ovf_list = nullptr;
-    int64_t ovf_cap = 0;
-    double *mv = nullptr;
-    int *lag = nullptr;
-    int64_t score_cap = 0;
+    PoolBuf<long long> ovf_list;
+    PoolBuf<double> mv;
+    PoolBuf<int> lag;
     // small Runs (launch_small_groups): small_cap slots of coherent pinned memory, handed back to the context on free
     unsigned char *small_out = nullptr;
     int small_cap = 0;
     // selection workspace
-    int *gid_dev = nullptr;
-    int64_t gid_cap = 0;
+    PoolBuf<int> gid_dev;
     std::vector<int32_t> gid_host;
     bool gid_valid = false;
-    GroupWork gw{nullptr, nullptr, nullptr};
-    muse_record *rec = nullptr;
-    unsigned long long *selkey = nullptr;
-    int64_t grp_cap = 0;
-    muse_record *cand = nullptr;
-    int *cnt = nullptr;
-    int64_t cand_cap = 0, cnt_cap = 0;
+    PoolBuf<unsigned long long> gkey; // the GroupWork of the label-group reduction (gw())
+    PoolBuf<long long> gfirst, gwin;
+    GroupWork gw() const { return GroupWork{gkey.p, gfirst.p, gwin.p}; }
+    PoolBuf<muse_record> rec;
+    PoolBuf<unsigned long long> selkey;
+    PoolBuf<muse_record> cand;
+    PoolBuf<int> cnt;
     // pinned host images of cand / cnt: the device top-N pre-selection comes back in two truly asynchronous
     // copies and one synchronisation
-    muse_record *cand_host = nullptr;
-    int *cnt_host = nullptr;
-    int64_t cand_host_cap = 0, cnt_host_cap = 0;
+    HostBuf<muse_record> cand_host;
+    HostBuf<int> cnt_host;
     // pinned host images of rec / selkey: a Run over up to EXACT_FEED_MAX_GROUPS groups feeds the heap one Score per group
-    muse_record *rec_host = nullptr;
-    unsigned long long *key_host = nullptr;
-    int64_t rec_host_cap = 0;
+    HostBuf<muse_record> rec_host;
+    HostBuf<unsigned long long> key_host;
     // filter-and-refine Run
-    unsigned *scr_flags = nullptr;      // [M] SCR_* bits of the screening pass
-    double *scr_var = nullptr;          // [M] sample variances from the screening pass
-    unsigned char *include = nullptr;   // [M] rows re-evaluated in fp64 (the only ones the selection may take)
-    unsigned long long *scr_keys = nullptr;
-    unsigned long long *scr_gmay = nullptr, *scr_gkplus = nullptr; // label groups: per-group bounds
-    int *scr_gcert = nullptr;
-    int64_t scr_gcap = 0;
-    int64_t scr_cap = 0, scr_keys_cap = 0;
+    PoolBuf<unsigned> scr_flags;        // [M] SCR_* bits of the screening pass
+    PoolBuf<double> scr_var;            // [M] sample variances from the screening pass
+    PoolBuf<unsigned char> include;     // [M] rows re-evaluated in fp64 (the only ones the selection may take)
+    PoolBuf<unsigned long long> scr_keys;
+    PoolBuf<unsigned long long> scr_gmay, scr_gkplus; // label groups: per-group bounds
+    PoolBuf<int> scr_gcert;
     int *refine_host = nullptr;         // pinned: pairs re-evaluated by the last screened Run
-    double *est_save = nullptr;         // estimates of the listed rows (2 per pair), for the guard of the bound
-    int64_t est_cap = 0;
+    PoolBuf<double> est_save;           // estimates of the listed rows (2 per pair), for the guard of the bound
     unsigned long long *err_dev = nullptr, *err_host = nullptr; // largest | |estimate| - |fp64 score| | of the last screened Run
     double last_E = 0.0;                // the bound that Run assumed
     // a screened Run with these filters over this many rows re-evaluated too many of them: the same Run is not
@@ -323,8 +343,6 @@ struct LaunchTimer {
 };
 
 // ---- helpers shared by the parts
-hipError_t pool_alloc(muse_ctx *ctx, bool host, void **out, size_t bytes); // capi_context.hip
-void pool_free(muse_ctx *ctx, bool host, void *p);
 void pool_drain(muse_ctx *ctx);                                            // frees every cached block (context teardown, tests)
 template <class T> inline hipError_t dmalloc(muse_ctx *ctx, T **out, size_t bytes) { return pool_alloc(ctx, false, (void **)out, bytes); }
 template <class T> inline hipError_t hmalloc(muse_ctx *ctx, T **out, size_t bytes) { return pool_alloc(ctx, true, (void **)out, bytes); }
@@ -370,5 +388,6 @@ int run_select(muse_batch *b, const int32_t *group_id, int32_t G_in, int64_t ser
                       std::vector<muse_record> &out, bool already_scored = false, bool prescreened = false);
 void emit(const std::vector<muse_record> &sel, int64_t *out_series, int32_t *out_lag, double *out_score,
                  int32_t *out_count, double *out_mean_abs);
+int upload_many_tab(muse_ctx *ctx, std::vector<void *> &tab, bool zscratch); // capi_many.hip
 int screen_many(muse_batch *const *bs, int32_t R, const int32_t *group_id, int32_t G_in, int32_t max_lag,
                        int32_t top_n, double threshold, int32_t sign_filter, int32_t abs_scores, bool &done);

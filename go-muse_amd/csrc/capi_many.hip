@@ -8,6 +8,21 @@ using namespace muse;
 
 
 // -------------------------------------------------------- many references
+// The device pointer table of a many-reference pass (muse_batch_score_many, screen_many): the caller's columns of R pointers
+// each in `tab`, which becomes the host image the asynchronous copy reads (kept by the context until the next pass has waited
+// for the stream).  With `zscratch`, the one-pass kernels' scratch slices too (allocated on first use).
+int upload_many_tab(muse_ctx *ctx, std::vector<void *> &tab, bool zscratch)
+{
+    if (zscratch) // one 64 KB slice per resident workgroup
+        HIP_TRY(ctx->zscratch.ensure(ctx, (int64_t)ctx->num_cus * 4 * 4096, ctx->stream));
+    HIP_TRY(ctx->many_tab.ensure(ctx, (int64_t)tab.size(), ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream)); // the previous pass may still be reading the host image
+    ctx->many_host.swap(tab);
+    HIP_TRY(hipMemcpyAsync(ctx->many_tab.p, ctx->many_host.data(), ctx->many_host.size() * sizeof(void *),
+                           hipMemcpyHostToDevice, ctx->stream));
+    return MUSE_OK;
+}
+
 extern "C" int muse_batch_read_scores(muse_batch *b, int32_t *lag, double *mv)
 {
     if (!b)
@@ -20,15 +35,15 @@ extern "C" int muse_batch_read_scores(muse_batch *b, int32_t *lag, double *mv)
         return MUSE_OK;
     if (!lag || !mv)
         return fail(MUSE_ERR_INVALID, "NULL output");
-    if (M > b->score_cap)
+    if (M > b->mv.cap || M > b->lag.cap)
         return fail(MUSE_ERR_INVALID, "the batch has not been scored since the group grew");
     if (!b->scores_exact) { // the last Run screened in fp32 and re-evaluated only the rows it needed
         rc = muse_batch_score(b);
         if (rc)
             return rc;
     }
-    HIP_TRY(hipMemcpyAsync(lag, b->lag, (size_t)M * sizeof(int), hipMemcpyDeviceToHost, b->ctx->stream));
-    HIP_TRY(hipMemcpyAsync(mv, b->mv, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, b->ctx->stream));
+    HIP_TRY(hipMemcpyAsync(lag, b->lag.p, (size_t)M * sizeof(int), hipMemcpyDeviceToHost, b->ctx->stream));
+    HIP_TRY(hipMemcpyAsync(mv, b->mv.p, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, b->ctx->stream));
     HIP_TRY(hipStreamSynchronize(b->ctx->stream));
     return MUSE_OK;
 }
@@ -91,52 +106,35 @@ extern "C" int muse_batch_score_many(muse_batch *const *bs, int32_t R)
         HIP_TRY(ensure_gscratch(ctx, b0->n, 2 * LONG_WGS_PER_CU));
     if (real_n) // (half an n-element slice per workgroup: the batches' own creation sized the buffer for far more)
         HIP_TRY(ensure_gscratch(ctx, b0->n));
-    if (b0->n == 16384 && !ctx->zscratch) { // (every other length keeps the spectra in registers: no scratch)
-        const int slots = ctx->num_cus * 4; // one 64 KB slice per resident workgroup
-        HIP_TRY(hipMalloc(&ctx->zscratch, (size_t)slots * 4096 * sizeof(double2)));
-        ctx->zslots = slots;
-    }
-    if (R > ctx->many_cap) {
-        (void)hipFree(ctx->many_tab);
-        ctx->many_tab = nullptr;
-        ctx->many_cap = 0;
-        HIP_TRY(hipMalloc(&ctx->many_tab, (size_t)R * 5 * sizeof(void *)));
-        ctx->many_cap = R;
-    }
-    HIP_TRY(hipStreamSynchronize(ctx->stream)); // the previous pass may still be reading the host image
-    std::vector<void *> &tab = ctx->many_host;
-    tab.assign((size_t)R * 4, nullptr);
+    std::vector<void *> tab((size_t)R * 4);
     for (int r = 0; r < R; r++) {
         tab[(size_t)r] = small_n ? bs[r]->xc : real_n ? bs[r]->xcw : bs[r]->xcp;
-        tab[(size_t)R + r] = bs[r]->mv;
-        tab[(size_t)2 * R + r] = bs[r]->lag;
+        tab[(size_t)R + r] = bs[r]->mv.p;
+        tab[(size_t)2 * R + r] = bs[r]->lag.p;
         tab[(size_t)3 * R + r] = bs[r]->c1;
     }
-    HIP_TRY(hipMemcpyAsync(ctx->many_tab, tab.data(), tab.size() * sizeof(void *), hipMemcpyHostToDevice, ctx->stream));
+    rc = upload_many_tab(ctx, tab, b0->n == 16384); // (every other length keeps the spectra in registers: no scratch)
+    if (rc)
+        return rc;
+    void **const t = ctx->many_tab.p;
     FusedParams p = base_params(b0);
     p.R = R;
-    p.xcp_many = (const double2 *const *)ctx->many_tab;
-    p.mv_many = (double *const *)((void **)ctx->many_tab + R);
-    p.lag_many = (int *const *)((void **)ctx->many_tab + 2 * R);
-    p.c1_many = (const double *const *)((void **)ctx->many_tab + 3 * R);
-    p.zscratch = ctx->zscratch;
-    p.zslots = ctx->zslots;
-    if (2 * p.npairs > b0->ovf_cap) {
-        dfree(b0->ctx, b0->ovf_list);
-        b0->ovf_list = nullptr;
-        b0->ovf_cap = 0;
-        HIP_TRY(dmalloc(b0->ctx, &b0->ovf_list, (size_t)(2 * p.npairs) * sizeof(long long)));
-        b0->ovf_cap = 2 * p.npairs;
-    }
+    p.xcp_many = (const double2 *const *)t;
+    p.mv_many = (double *const *)(t + R);
+    p.lag_many = (int *const *)(t + 2 * R);
+    p.c1_many = (const double *const *)(t + 3 * R);
+    p.zscratch = ctx->zscratch.p;
+    p.zslots = (int)(ctx->zscratch.cap / 4096);
+    HIP_TRY(b0->ovf_list.ensure(ctx, 2 * p.npairs, b0->stream()));
     p.ovf_count = b0->ovf_count;
     p.work_counter = b0->ovf_count + 1;
-    p.ovf_list = b0->ovf_list;
+    p.ovf_list = b0->ovf_list.p;
     // (the long-series kernel works in the context's scratch buffer: its pointer must not be swapped between reading it and the launch)
     std::unique_lock<std::mutex> scratch_lock(ctx->stage_mu, std::defer_lock);
     if (long_n || real_n) {
         scratch_lock.lock();
-        p.gscratch = ctx->gscratch;
-        p.gscratch_slices = (long long)(ctx->gscratch_elems / (size_t)b0->n);
+        p.gscratch = ctx->gscratch.p;
+        p.gscratch_slices = (long long)(ctx->gscratch.cap / b0->n);
     }
     LaunchTimer timer(ctx);
     HIP_TRY(hipMemsetAsync(b0->ovf_count, 0, 2 * sizeof(int), ctx->stream));
@@ -162,7 +160,7 @@ extern "C" int muse_batch_score_many(muse_batch *const *bs, int32_t R)
         HIP_TRY(redo_timer.begin());
     for (int r = 0; r < R && !small_n && !real_n; r++) {
         FusedParams q = base_params(bs[r]);
-        q.pair_list = b0->ovf_list;
+        q.pair_list = b0->ovf_list.p;
         q.pair_count = b0->ovf_count;
         if (long_n) { // (the four-step kernel that isolates and rescales first, as behind a single long-series pass)
             q.npairs = std::min<long long>(q.npairs, (long long)ctx->num_cus * STOCKHAM_GLOBAL_WGS_PER_CU);

@@ -55,13 +55,12 @@ static void slot_destroy(RowsSlot *s)
         (void)hipHostFree(s->out);
     if (s->done)
         (void)hipEventDestroy(s->done);
-    dfree(ctx, s->g.hstats);
-    dfree(ctx, s->b.mv);
-    dfree(ctx, s->b.lag);
+    s->g.hstats.release(ctx);
+    s->b.mv.release(ctx);
+    s->b.lag.release(ctx);
+    s->b.ovf_list.release(ctx);
     dfree(ctx, s->b.ovf_count);
-    dfree(ctx, s->b.ovf_list);
-    if (s->b.handoff_host)
-        hfree(ctx, s->b.handoff_host);
+    hfree(ctx, s->b.handoff_host);
     if (s->stream)
         (void)hipStreamDestroy(s->stream);
     delete s;
@@ -189,21 +188,13 @@ static int slot_take(muse_batch *tmpl, int64_t M, size_t elems, RowsSlot **out)
     s->b.handoff_M = -1; // (no kernel-selection memory across unrelated groups)
     // kernels that work in the context's shared scratch buffer are serialised on the context's stream
     s->b.own_stream = tmpl->n >= GENERIC_LDS_MAX_N ? nullptr : s->stream;
-    if (M > s->b.score_cap) { // (grown in steps that small groups never reach twice)
-        dfree(ctx, s->b.mv);
-        dfree(ctx, s->b.lag);
-        s->b.mv = nullptr;
-        s->b.lag = nullptr;
-        s->b.score_cap = 0;
-        const int64_t cap = std::max<int64_t>(M, 4096);
-        hipError_t ea = dmalloc(ctx, &s->b.mv, (size_t)cap * sizeof(double));
-        if (ea == hipSuccess)
-            ea = dmalloc(ctx, &s->b.lag, (size_t)cap * sizeof(int));
-        if (ea != hipSuccess) {
-            slot_destroy(s);
-            return fail(MUSE_ERR_NOMEM, "hipMalloc failed: %s", hipGetErrorString(ea));
-        }
-        s->b.score_cap = cap;
+    const int64_t cap = std::max<int64_t>(M, 4096); // (grown in steps that small groups never reach twice)
+    hipError_t ea = s->b.mv.ensure(ctx, cap, s->stream);
+    if (ea == hipSuccess)
+        ea = s->b.lag.ensure(ctx, cap, s->stream);
+    if (ea != hipSuccess) {
+        slot_destroy(s);
+        return fail(MUSE_ERR_NOMEM, "hipMalloc failed: %s", hipGetErrorString(ea));
     }
     *out = s;
     return MUSE_OK;
@@ -219,7 +210,7 @@ static int slot_finish(muse_ctx *ctx, RowsSlot *s, int64_t M, int32_t abs_scores
     if (e == hipSuccess) {
         rc = muse_batch_score(&s->b); // the fused kernel automatic selection takes for this length (and its redo launch, if any)
         if (!rc)
-            e = launch_single_group(s->b.mv, s->b.lag, M, abs_scores ? 1 : 0, 0, s->out, st);
+            e = launch_single_group(s->b.mv.p, s->b.lag.p, M, abs_scores ? 1 : 0, 0, s->out, st);
     }
     if (e != hipSuccess || rc) {
         (void)hipStreamSynchronize(st); // nothing of this call may still be using the slot

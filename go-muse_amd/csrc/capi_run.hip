@@ -87,74 +87,28 @@ std::vector<muse_record> heap_select(std::vector<muse_record> cands, int64_t top
 
 int ensure_select_ws(muse_batch *b, int64_t M, int64_t G, bool with_gid, int K, bool on_device)
 {
-    if (with_gid && M > b->gid_cap) {
-        dfree(b->ctx, b->gid_dev);
-        b->gid_dev = nullptr;
-        b->gid_cap = 0;
+    muse_ctx *ctx = b->ctx;
+    const hipStream_t st = b->stream();
+    if (with_gid && M > b->gid_dev.cap) {
         b->gid_valid = false;
-        HIP_TRY(dmalloc(b->ctx, &b->gid_dev, (size_t)M * sizeof(int)));
-        b->gid_cap = M;
+        HIP_TRY(b->gid_dev.ensure(ctx, M, st));
     }
-    if (G > b->grp_cap) {
-        dfree(b->ctx, b->gw.key);
-        dfree(b->ctx, b->gw.first);
-        dfree(b->ctx, b->gw.win);
-        dfree(b->ctx, b->rec);
-        dfree(b->ctx, b->selkey);
-        b->gw = GroupWork{nullptr, nullptr, nullptr};
-        b->rec = nullptr;
-        b->selkey = nullptr;
-        b->grp_cap = 0;
-        HIP_TRY(dmalloc(b->ctx, &b->gw.key, (size_t)G * sizeof(unsigned long long)));
-        HIP_TRY(dmalloc(b->ctx, &b->gw.first, (size_t)G * sizeof(long long)));
-        HIP_TRY(dmalloc(b->ctx, &b->gw.win, (size_t)G * sizeof(long long)));
-        HIP_TRY(dmalloc(b->ctx, &b->rec, (size_t)G * sizeof(muse_record)));
-        HIP_TRY(dmalloc(b->ctx, &b->selkey, (size_t)G * sizeof(unsigned long long)));
-        b->grp_cap = G;
-    }
+    HIP_TRY(b->gkey.ensure(ctx, G, st));
+    HIP_TRY(b->gfirst.ensure(ctx, G, st));
+    HIP_TRY(b->gwin.ensure(ctx, G, st));
+    HIP_TRY(b->rec.ensure(ctx, G, st));
+    HIP_TRY(b->selkey.ensure(ctx, G, st));
     const int64_t nb = (G + TOPN_CHUNK - 1) / TOPN_CHUNK;
-    if (nb > b->cnt_cap) {
-        dfree(b->ctx, b->cnt);
-        b->cnt = nullptr;
-        b->cnt_cap = 0;
-        HIP_TRY(dmalloc(b->ctx, &b->cnt, (size_t)nb * sizeof(int)));
-        b->cnt_cap = nb;
-    }
-    if (nb * K > b->cand_cap) {
-        dfree(b->ctx, b->cand);
-        b->cand = nullptr;
-        b->cand_cap = 0;
-        HIP_TRY(dmalloc(b->ctx, &b->cand, (size_t)(nb * K) * sizeof(muse_record)));
-        b->cand_cap = nb * K;
-    }
-    if (!on_device && G > b->rec_host_cap) { // the exact feed: every group's record and selection key through pinned memory
-        if (b->rec_host)
-            hfree(b->ctx, b->rec_host);
-        if (b->key_host)
-            hfree(b->ctx, b->key_host);
-        b->rec_host = nullptr;
-        b->key_host = nullptr;
-        b->rec_host_cap = 0;
+    HIP_TRY(b->cnt.ensure(ctx, nb, st));
+    HIP_TRY(b->cand.ensure(ctx, nb * K, st));
+    if (!on_device && G > 0) { // the exact feed: every group's record and selection key through pinned memory
         const int64_t cap = std::max<int64_t>(G, 64);
-        HIP_TRY(hmalloc(b->ctx, &b->rec_host, (size_t)cap * sizeof(muse_record)));
-        HIP_TRY(hmalloc(b->ctx, &b->key_host, (size_t)cap * sizeof(unsigned long long)));
-        b->rec_host_cap = cap;
+        HIP_TRY(b->rec_host.ensure(ctx, cap, st));
+        HIP_TRY(b->key_host.ensure(ctx, cap, st));
     }
-    if (on_device && nb > b->cnt_host_cap) {
-        if (b->cnt_host)
-            hfree(b->ctx, b->cnt_host); // (hipHostFree(NULL) leaves a sticky error behind)
-        b->cnt_host = nullptr;
-        b->cnt_host_cap = 0;
-        HIP_TRY(hmalloc(b->ctx, &b->cnt_host, (size_t)nb * sizeof(int)));
-        b->cnt_host_cap = nb;
-    }
-    if (on_device && nb * K > b->cand_host_cap) {
-        if (b->cand_host)
-            hfree(b->ctx, b->cand_host);
-        b->cand_host = nullptr;
-        b->cand_host_cap = 0;
-        HIP_TRY(hmalloc(b->ctx, &b->cand_host, (size_t)(nb * K) * sizeof(muse_record)));
-        b->cand_host_cap = nb * K;
+    if (on_device) {
+        HIP_TRY(b->cnt_host.ensure(ctx, nb, st));
+        HIP_TRY(b->cand_host.ensure(ctx, nb * K, st));
     }
     return MUSE_OK;
 }
@@ -168,7 +122,7 @@ int upload_group_ids(muse_batch *b, const int32_t *group_id, int64_t M)
                       memcmp(b->gid_host.data(), group_id, (size_t)M * sizeof(int32_t)) == 0;
     if (!same) {
         b->gid_host.assign(group_id, group_id + M);
-        HIP_TRY(hipMemcpyAsync(b->gid_dev, b->gid_host.data(), (size_t)M * sizeof(int), hipMemcpyHostToDevice,
+        HIP_TRY(hipMemcpyAsync(b->gid_dev.p, b->gid_host.data(), (size_t)M * sizeof(int), hipMemcpyHostToDevice,
                                b->stream()));
         b->gid_valid = true;
     }
@@ -327,22 +281,22 @@ int run_select(muse_batch *b, const int32_t *group_id, int32_t G_in, int64_t ser
         return rc;
     b->last_screened = screened;
     if (screened && !prescreened) { // fp32 screening pass, then fp64 for the rows that can reach the top-N (needs the selection workspace)
-        rc = score_screened(b, max_lag, top_n, threshold, sign_filter, abs_scores, group_id ? b->gid_dev : nullptr, G);
+        rc = score_screened(b, max_lag, top_n, threshold, sign_filter, abs_scores, group_id ? b->gid_dev.p : nullptr, G);
         if (rc)
             return rc;
     }
     SelectParams sp{};
-    sp.mv = b->mv;
-    sp.lag = b->lag;
+    sp.mv = b->mv.p;
+    sp.lag = b->lag.p;
     sp.M = M;
-    sp.group_id = group_id ? b->gid_dev : nullptr;
+    sp.group_id = group_id ? b->gid_dev.p : nullptr;
     sp.G = (int)G;
     sp.abs_scores = abs_scores ? 1 : 0;
     sp.max_lag = max_lag;
     sp.threshold = threshold;
     sp.sign_filter = sign_filter;
     sp.series_offset = series_offset;
-    sp.include = screened ? b->include : nullptr;
+    sp.include = screened ? b->include.p : nullptr;
     std::vector<muse_record> cands;
     if (small) {
         const SmallSlot *slot;
@@ -357,13 +311,13 @@ int run_select(muse_batch *b, const int32_t *group_id, int32_t G_in, int64_t ser
         if (rc)
             return rc;
     } else if (on_device) {
-        HIP_TRY(launch_group_reduce(sp, b->gw, b->rec, b->selkey, b->stream()));
+        HIP_TRY(launch_group_reduce(sp, b->gw(), b->rec.p, b->selkey.p, b->stream()));
         const int64_t nb = (G + TOPN_CHUNK - 1) / TOPN_CHUNK;
-        HIP_TRY(launch_topn(b->rec, b->selkey, (int)G, K, b->cand, b->cnt, b->stream()));
-        const int *cnt = b->cnt_host;
-        const muse_record *cand = b->cand_host;
-        HIP_TRY(hipMemcpyAsync(b->cnt_host, b->cnt, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, b->stream()));
-        HIP_TRY(hipMemcpyAsync(b->cand_host, b->cand, (size_t)(nb * K) * sizeof(muse_record), hipMemcpyDeviceToHost,
+        HIP_TRY(launch_topn(b->rec.p, b->selkey.p, (int)G, K, b->cand.p, b->cnt.p, b->stream()));
+        const int *cnt = b->cnt_host.p;
+        const muse_record *cand = b->cand_host.p;
+        HIP_TRY(hipMemcpyAsync(b->cnt_host.p, b->cnt.p, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, b->stream()));
+        HIP_TRY(hipMemcpyAsync(b->cand_host.p, b->cand.p, (size_t)(nb * K) * sizeof(muse_record), hipMemcpyDeviceToHost,
                                b->stream()));
         HIP_TRY(hipStreamSynchronize(b->stream()));
         for (int64_t blk = 0; blk < nb; blk++)
@@ -376,11 +330,11 @@ int run_select(muse_batch *b, const int32_t *group_id, int32_t G_in, int64_t ser
         if (screened && screen_guard_tripped(b)) // an estimate left its bound: this Run is redone entirely in fp64
             return run_select(b, group_id, G_in, series_offset, max_lag, top_n, threshold, sign_filter, abs_scores, out, false);
     } else {
-        HIP_TRY(launch_group_reduce(sp, b->gw, b->rec, b->selkey, b->stream()));
-        const muse_record *rec = b->rec_host;
-        const unsigned long long *key = b->key_host;
-        HIP_TRY(hipMemcpyAsync(b->rec_host, b->rec, (size_t)G * sizeof(muse_record), hipMemcpyDeviceToHost, b->stream()));
-        HIP_TRY(hipMemcpyAsync(b->key_host, b->selkey, (size_t)G * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+        HIP_TRY(launch_group_reduce(sp, b->gw(), b->rec.p, b->selkey.p, b->stream()));
+        const muse_record *rec = b->rec_host.p;
+        const unsigned long long *key = b->key_host.p;
+        HIP_TRY(hipMemcpyAsync(b->rec_host.p, b->rec.p, (size_t)G * sizeof(muse_record), hipMemcpyDeviceToHost, b->stream()));
+        HIP_TRY(hipMemcpyAsync(b->key_host.p, b->selkey.p, (size_t)G * sizeof(unsigned long long), hipMemcpyDeviceToHost,
                                b->stream()));
         HIP_TRY(hipStreamSynchronize(b->stream()));
         for (int64_t g = 0; g < G; g++)
@@ -475,10 +429,10 @@ extern "C" int muse_batch_run_groups(muse_batch *b, const int32_t *group_id, int
     if (rc)
         return rc;
     SelectParams sp{};
-    sp.mv = b->mv;
-    sp.lag = b->lag;
+    sp.mv = b->mv.p;
+    sp.lag = b->lag.p;
     sp.M = M;
-    sp.group_id = b->gid_dev;
+    sp.group_id = b->gid_dev.p;
     sp.G = G;
     sp.abs_scores = abs_scores ? 1 : 0;
     sp.series_offset = series_offset;
@@ -494,10 +448,10 @@ extern "C" int muse_batch_run_groups(muse_batch *b, const int32_t *group_id, int
         }
         return MUSE_OK;
     }
-    HIP_TRY(launch_group_reduce(sp, b->gw, b->rec, b->selkey, b->stream()));
+    HIP_TRY(launch_group_reduce(sp, b->gw(), b->rec.p, b->selkey.p, b->stream()));
     std::vector<unsigned long long> st((size_t)G);
-    HIP_TRY(hipMemcpyAsync(out_records, b->rec, (size_t)G * sizeof(muse_record), hipMemcpyDeviceToHost, b->stream()));
-    HIP_TRY(hipMemcpyAsync(st.data(), b->selkey, (size_t)G * sizeof(unsigned long long), hipMemcpyDeviceToHost, b->stream()));
+    HIP_TRY(hipMemcpyAsync(out_records, b->rec.p, (size_t)G * sizeof(muse_record), hipMemcpyDeviceToHost, b->stream()));
+    HIP_TRY(hipMemcpyAsync(st.data(), b->selkey.p, (size_t)G * sizeof(unsigned long long), hipMemcpyDeviceToHost, b->stream()));
     HIP_TRY(hipStreamSynchronize(b->stream()));
     for (int32_t g = 0; g < G; g++)
         out_state[g] = (uint8_t)st[(size_t)g];

@@ -95,61 +95,28 @@ static int screen_prepare(muse_batch *b, int32_t top_n, const int *gid_dev, int6
     if (rc)
         return rc;
     const int64_t npairs = (M + 1) / 2;
-    if (M > b->scr_cap) {
-        dfree(b->ctx, b->scr_flags);
-        dfree(b->ctx, b->scr_var);
-        dfree(b->ctx, b->include);
-        b->scr_flags = nullptr;
-        b->scr_var = nullptr;
-        b->include = nullptr;
-        b->scr_cap = 0;
-        HIP_TRY(dmalloc(b->ctx, &b->scr_flags, (size_t)M * sizeof(unsigned)));
-        HIP_TRY(dmalloc(b->ctx, &b->scr_var, (size_t)M * sizeof(double)));
-        HIP_TRY(dmalloc(b->ctx, &b->include, (size_t)M));
-        b->scr_cap = M;
-    }
+    const hipStream_t st = b->stream();
+    HIP_TRY(b->scr_flags.ensure(ctx, M, st));
+    HIP_TRY(b->scr_var.ensure(ctx, M, st));
+    HIP_TRY(b->include.ensure(ctx, M, st));
     const int64_t nkeys = screen_select_scratch(gid_dev ? G : M, top_n);
-    if (gid_dev && G > b->scr_gcap) {
-        dfree(b->ctx, b->scr_gmay);
-        dfree(b->ctx, b->scr_gkplus);
-        dfree(b->ctx, b->scr_gcert);
-        b->scr_gmay = b->scr_gkplus = nullptr;
-        b->scr_gcert = nullptr;
-        b->scr_gcap = 0;
-        HIP_TRY(dmalloc(b->ctx, &b->scr_gmay, (size_t)G * sizeof(unsigned long long)));
-        HIP_TRY(dmalloc(b->ctx, &b->scr_gkplus, (size_t)G * sizeof(unsigned long long)));
-        HIP_TRY(dmalloc(b->ctx, &b->scr_gcert, (size_t)G * sizeof(int)));
-        b->scr_gcap = G;
+    if (gid_dev) {
+        HIP_TRY(b->scr_gmay.ensure(ctx, G, st));
+        HIP_TRY(b->scr_gkplus.ensure(ctx, G, st));
+        HIP_TRY(b->scr_gcert.ensure(ctx, G, st));
     }
-    if (nkeys > b->scr_keys_cap) {
-        dfree(b->ctx, b->scr_keys);
-        b->scr_keys = nullptr;
-        b->scr_keys_cap = 0;
-        HIP_TRY(dmalloc(b->ctx, &b->scr_keys, (size_t)nkeys * sizeof(unsigned long long)));
-        b->scr_keys_cap = nkeys;
-    }
+    HIP_TRY(b->scr_keys.ensure(ctx, nkeys, st));
     if (!b->refine_host)
         HIP_TRY(hmalloc(b->ctx, &b->refine_host, sizeof(int)));
     if (!b->err_host)
         HIP_TRY(hmalloc(b->ctx, &b->err_host, sizeof(unsigned long long)));
     if (!b->err_dev)
         HIP_TRY(dmalloc(b->ctx, &b->err_dev, sizeof(unsigned long long)));
-    if (4 * npairs > b->est_cap) { // two estimates per listed pair; the list holds the selection's pairs plus the guard sample
-        dfree(b->ctx, b->est_save);
-        b->est_save = nullptr;
-        b->est_cap = 0;
-        HIP_TRY(dmalloc(b->ctx, &b->est_save, (size_t)(4 * npairs) * sizeof(double)));
-        b->est_cap = 4 * npairs;
-    }
+    // two estimates per listed pair; the list holds the selection's pairs plus the guard sample
+    HIP_TRY(b->est_save.ensure(ctx, 4 * npairs, st));
     // the list takes the selection's pairs (at most npairs) plus the guard sample (about npairs / 1024, not de-duplicated
     // against the selection): 2 npairs entries, the same capacity the fp64 pass's hand-off list has
-    if (2 * npairs > b->ovf_cap) {
-        dfree(b->ctx, b->ovf_list);
-        b->ovf_list = nullptr;
-        b->ovf_cap = 0;
-        HIP_TRY(dmalloc(b->ctx, &b->ovf_list, (size_t)(2 * npairs) * sizeof(long long)));
-        b->ovf_cap = 2 * npairs;
-    }
+    HIP_TRY(b->ovf_list.ensure(ctx, 2 * npairs, st));
     if (b->sp->xmax < 0.0) { // once per reference: max |X[f]| (X holds the non-redundant half of a real signal's spectrum)
         std::vector<double2> X((size_t)(b->n / 2 + 1));
         HIP_TRY(hipMemcpyAsync(X.data(), b->X, X.size() * sizeof(double2), hipMemcpyDeviceToHost, ctx->stream));
@@ -161,8 +128,8 @@ static int screen_prepare(muse_batch *b, int32_t top_n, const int *gid_dev, int6
     }
     plan.Es = screen_error_scaled(b->sp->xmax, b->n) * ctx->screen_e_scale;
     HIP_TRY(hipMemsetAsync(b->err_dev, 0, sizeof(unsigned long long), ctx->stream));
-    HIP_TRY(hipMemsetAsync(b->scr_flags, 0, (size_t)M * sizeof(unsigned), ctx->stream));
-    HIP_TRY(hipMemsetAsync(b->include, 0, (size_t)M, ctx->stream));
+    HIP_TRY(hipMemsetAsync(b->scr_flags.p, 0, (size_t)M * sizeof(unsigned), ctx->stream));
+    HIP_TRY(hipMemsetAsync(b->include.p, 0, (size_t)M, ctx->stream));
     HIP_TRY(hipMemsetAsync(b->ovf_count, 0, 2 * sizeof(int), ctx->stream));
     return MUSE_OK;
 }
@@ -171,8 +138,8 @@ static FusedParams screen_pass_params(muse_batch *b, int32_t max_lag, const Scre
 {
     FusedParams p = base_params(b);
     p.scr_need_sign = need_sign ? 1 : 0;
-    p.scr_flags = b->scr_flags;
-    p.scr_var = b->scr_var;
+    p.scr_flags = b->scr_flags.p;
+    p.scr_var = b->scr_var.p;
     p.scr_max_lag = max_lag;
     p.screen_delta = 2.0 * plan.Es; // every lag whose fp32 |cc| is within 2 E of the fp32 maximum may be the exact argmax
     return p;
@@ -186,9 +153,9 @@ static int screen_finish(muse_batch *b, int32_t top_n, double threshold, int32_t
     const int64_t npairs = (M + 1) / 2;
     const double Es = plan.Es;
     ScreenSelect q{};
-    q.mv = b->mv;
-    q.var = b->scr_var;
-    q.flags = b->scr_flags;
+    q.mv = b->mv.p;
+    q.var = b->scr_var.p;
+    q.flags = b->scr_flags.p;
     q.M = M;
     q.threshold = threshold;
     q.sign_filter = sign_filter;
@@ -197,22 +164,22 @@ static int screen_finish(muse_batch *b, int32_t top_n, double threshold, int32_t
     q.group_id = gid_dev;
     q.G = (int)G;
     // (the group scratch borrows the final reduction's arrays: that reduction re-initialises them afterwards)
-    const ScreenGroupWork sgw{b->gw.first, b->gw.key, b->scr_gmay, b->scr_gkplus, b->scr_gcert};
-    HIP_TRY(launch_screen_select(q, top_n, b->selkey, b->scr_keys, sgw, b->ovf_list, b->ovf_count, b->include,
+    const ScreenGroupWork sgw{b->gfirst.p, b->gkey.p, b->scr_gmay.p, b->scr_gkplus.p, b->scr_gcert.p};
+    HIP_TRY(launch_screen_select(q, top_n, b->selkey.p, b->scr_keys.p, sgw, b->ovf_list.p, b->ovf_count, b->include.p,
                                  ctx->stream));
     // guard sample (one pair in 1024, a different set every Run): re-evaluated like the listed pairs, so the check of the
     // bound below is not confined to rows the selection wanted anyway
     HIP_TRY(launch_screen_sample(npairs, M, 0x6d757365ull + 0x9E3779B97F4A7C15ull * (unsigned long long)(++b->guard_salt),
-                                 b->ovf_list, b->ovf_count, b->include, ctx->stream));
+                                 b->ovf_list.p, b->ovf_count, b->include.p, ctx->stream));
     // the fp64 kernel re-evaluates the listed pairs (count stays on the device and bounds its loop)
     FusedParams r = base_params(b);
-    r.pair_list = b->ovf_list;
+    r.pair_list = b->ovf_list.p;
     r.pair_count = b->ovf_count;
     r.npairs = std::min<long long>(npairs, (long long)ctx->num_cus * 3);
-    HIP_TRY(launch_screen_save(q, b->ovf_list, b->ovf_count, b->est_save, ctx->stream));
+    HIP_TRY(launch_screen_save(q, b->ovf_list.p, b->ovf_count, b->est_save.p, ctx->stream));
     HIP_TRY(launch_fused(r, b->n == 4096 ? KERNEL_R16_OCC3 : (b->n <= 2048 || b->n == 8192 || b->n == 16384) ? KERNEL_SMALL : KERNEL_STOCKHAM, ctx->num_cus, ctx->stream));
     // guard: the re-evaluated rows have an estimate and an fp64 score; the largest difference must respect the bound
-    HIP_TRY(launch_screen_check(b->mv, M, b->ovf_list, b->ovf_count, b->est_save, b->err_dev, ctx->stream));
+    HIP_TRY(launch_screen_check(b->mv.p, M, b->ovf_list.p, b->ovf_count, b->est_save.p, b->err_dev, ctx->stream));
     *b->refine_host = 0;
     *b->err_host = 0ull;
     b->last_E = q.E;
@@ -295,17 +262,17 @@ extern "C" int muse_batch_screen_estimates(muse_batch *b, int32_t max_lag, doubl
     // (score_screened also ran the selection and the fp64 pass over the rows it picked: fetch the estimates of
     // the rows it did NOT re-evaluate, and mark the others)
     std::vector<unsigned char> inc((size_t)M);
-    HIP_TRY(hipMemcpyAsync(inc.data(), b->include, (size_t)M, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(inc.data(), b->include.p, (size_t)M, hipMemcpyDeviceToHost, ctx->stream));
     if (estimate)
-        HIP_TRY(hipMemcpyAsync(estimate, b->mv, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(estimate, b->mv.p, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (flags)
-        HIP_TRY(hipMemcpyAsync(flags, b->scr_flags, (size_t)M * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(flags, b->scr_flags.p, (size_t)M * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     if (estimate) { // rows the fp64 kernel did not touch hold the scaled fp32 value: divide by sigma
         std::vector<double> var((size_t)M);
         std::vector<unsigned> fl((size_t)M);
-        HIP_TRY(hipMemcpy(var.data(), b->scr_var, (size_t)M * sizeof(double), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(fl.data(), b->scr_flags, (size_t)M * sizeof(unsigned), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(var.data(), b->scr_var.p, (size_t)M * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(fl.data(), b->scr_flags.p, (size_t)M * sizeof(unsigned), hipMemcpyDeviceToHost));
         for (int64_t i = 0; i < M; i++)
             if (!inc[(size_t)i] && !(fl[(size_t)i] & (SCR_NAN | SCR_REFINE)))
                 estimate[i] = var[(size_t)i] > 0.0 ? estimate[i] * (1.0 / std::sqrt(var[(size_t)i])) : 0.0;
@@ -377,51 +344,40 @@ int screen_many(muse_batch *const *bs, int32_t R, const int32_t *group_id, int32
         rc = upload_group_ids(bs[r], group_id, M);
         if (rc)
             return rc;
-        rc = screen_prepare(bs[r], top_n, group_id ? bs[r]->gid_dev : nullptr, G, plan[(size_t)r]);
+        rc = screen_prepare(bs[r], top_n, group_id ? bs[r]->gid_dev.p : nullptr, G, plan[(size_t)r]);
         if (rc)
             return rc;
         Es_max = std::max(Es_max, plan[(size_t)r].Es);
     }
-    if (!ctx->zscratch) {
-        const int slots = ctx->num_cus * 4; // one 64 KB slice per resident workgroup of the fp64 one-pass kernel
-        HIP_TRY(hipMalloc(&ctx->zscratch, (size_t)slots * 4096 * sizeof(double2)));
-        ctx->zslots = slots;
-    }
-    if (R > ctx->many_cap) {
-        (void)hipFree(ctx->many_tab);
-        ctx->many_tab = nullptr;
-        ctx->many_cap = 0;
-        HIP_TRY(hipMalloc(&ctx->many_tab, (size_t)R * 5 * sizeof(void *)));
-        ctx->many_cap = R;
-    }
-    HIP_TRY(hipStreamSynchronize(ctx->stream)); // the previous pass may still be reading the host image
-    std::vector<void *> &tab = ctx->many_host;
-    tab.assign((size_t)R * 5, nullptr);
+    std::vector<void *> tab((size_t)R * 5);
     for (int r = 0; r < R; r++) {
         tab[(size_t)r] = bs[r]->xcf;
-        tab[(size_t)R + r] = bs[r]->mv;
-        tab[(size_t)2 * R + r] = bs[r]->lag;
-        tab[(size_t)3 * R + r] = bs[r]->scr_flags;
-        tab[(size_t)4 * R + r] = bs[r]->scr_var;
+        tab[(size_t)R + r] = bs[r]->mv.p;
+        tab[(size_t)2 * R + r] = bs[r]->lag.p;
+        tab[(size_t)3 * R + r] = bs[r]->scr_flags.p;
+        tab[(size_t)4 * R + r] = bs[r]->scr_var.p;
     }
-    HIP_TRY(hipMemcpyAsync(ctx->many_tab, tab.data(), tab.size() * sizeof(void *), hipMemcpyHostToDevice, ctx->stream));
+    rc = upload_many_tab(ctx, tab, true);
+    if (rc)
+        return rc;
+    void **const t = ctx->many_tab.p;
     ScreenPlan widest;
     widest.Es = Es_max; // one window for the pass: the widest of the references' (a wider window only flags more lags)
     FusedParams p = screen_pass_params(b0, max_lag, widest);
     p.R = R;
-    p.xcf_many = (const float2 *const *)ctx->many_tab;
-    p.mv_many = (double *const *)((void **)ctx->many_tab + R);
-    p.lag_many = (int *const *)((void **)ctx->many_tab + 2 * R);
-    p.flags_many = (unsigned *const *)((void **)ctx->many_tab + 3 * R);
-    p.var_many = (double *const *)((void **)ctx->many_tab + 4 * R);
-    p.zscratch = ctx->zscratch;
-    p.zslots = ctx->zslots;
+    p.xcf_many = (const float2 *const *)t;
+    p.mv_many = (double *const *)(t + R);
+    p.lag_many = (int *const *)(t + 2 * R);
+    p.flags_many = (unsigned *const *)(t + 3 * R);
+    p.var_many = (double *const *)(t + 4 * R);
+    p.zscratch = ctx->zscratch.p;
+    p.zslots = (int)(ctx->zscratch.cap / 4096);
     LaunchTimer timer(ctx);
     HIP_TRY(timer.begin());
     HIP_TRY(launch_screen_pass_many(p, ctx->num_cus, ctx->stream));
     HIP_TRY(timer.end());
     for (int r = 0; r < R; r++) {
-        rc = screen_finish(bs[r], top_n, threshold, sign_filter, abs_scores, group_id ? bs[r]->gid_dev : nullptr, G,
+        rc = screen_finish(bs[r], top_n, threshold, sign_filter, abs_scores, group_id ? bs[r]->gid_dev.p : nullptr, G,
                            plan[(size_t)r]);
         if (rc)
             return rc;

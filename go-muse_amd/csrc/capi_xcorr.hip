@@ -436,8 +436,8 @@ static int xcorr_groups_impl(muse_group *gx, muse_group *gy, int32_t n, int32_t 
         p.g3b = ctx->g3b;
         p.gsmall = (p.logn >= 9 && p.logn <= 11) ? ctx->gsmall[p.logn - 9] : (p.logn == 13 || p.logn == 14) ? ctx->gsmall[p.logn - 10]
                    : p.logn == 15 ? ctx->gsmall[4] /* n = 32768 runs on the 16384-point transform's tables (xcorr_real.hip) */ : nullptr;
-        p.gscratch = ctx->gscratch;
-        p.gscratch_slices = (long long)(ctx->gscratch_elems / (size_t)n);
+        p.gscratch = ctx->gscratch.p;
+        p.gscratch_slices = (long long)(ctx->gscratch.cap / n);
         p.twl = (p.logn >= 14 && p.logn <= 16) ? ctx->twl[p.logn - 14] : nullptr;
         p.mv = dmv;
         p.lag = dlag;

@@ -245,3 +245,83 @@ def test_concurrent_run_rows_on_slot_streams_with_timing_on(muse, eng, oracle):
         assert abs(win["score"] - sc[best]) <= SCORE_RTOL * abs(sc[best]) + SCORE_ATOL
         tmpl.close()
         probe.close()
+
+
+def test_live_batch_grows_every_work_buffer(muse, eng, oracle):
+    """One batch walks through the C API's grow-on-demand work buffers, each growth while a pass of the batch may still be
+    queued (a bare score() without read-back goes in front of every step): the score buffers and the hand-off list, the
+    group grown past its capacity, the selection workspace (more label groups), the screening buffers (screened Runs over
+    more rows and more label groups), the many-reference pointer table (a larger R, fp64 and screened).  Every step is
+    checked against the oracle: scores row by row, Run records against the oracle's Results over the fp64 scores."""
+    rng = np.random.default_rng(6500)
+    N, M0, M1, M2 = 4096, 1000, 2600, 4200
+    refs = [rng.standard_normal(N) for _ in range(4)]
+    rows = rng.standard_normal((M2, N))
+    for i in rng.integers(0, M2, size=300):
+        rows[i] += rng.uniform(-3, 3) * np.roll(refs[int(rng.integers(0, 4))], int(rng.integers(-50, 50)))
+    rows[7, 11] = np.nan                                              # a pair the n = 4096 kernel lists and redoes
+    rows[9] = 5.0                                                     # sigma == 0
+    dg = muse.DeviceGroup(eng, N, M0)
+    dg.append(rows[:M0])
+    db = muse.DeviceBatch(eng, dg, refs[0])
+    others = []
+
+    def exact(b, ref):
+        M = dg.M
+        lag, mv = b.read_scores()
+        olag, omv, gap = oracle.batch_scores(ref, rows[:M], nthreads=8)
+        _check(lag, mv, olag, omv, gap)
+        return lag, mv
+
+    def check_run(b, scores, gid, G, screened, top_n=10, got=None):
+        lag, mv = scores
+        if got is None:
+            got = b.run(gid, G, max_lag=15, top_n=top_n)
+        exp = oracle.results(lag, mv, gid, G, True, 15, top_n, 0.0, 0)
+        assert got[0].tolist() == exp[0].tolist() and got[1].tolist() == exp[1].tolist(), (G, screened)
+        np.testing.assert_allclose(got[2], exp[2], rtol=1e-12, atol=0)
+        assert b.last_run_info()[0] is screened, G
+
+    try:
+        db.score()                                                    # 1. first score buffers, no read-back
+        s = exact(db, refs[0])
+        db.score()
+        dg.append(rows[M0:M1])                                        # 2. past the group's capacity ...
+        db.score()                                                    # ... and larger score buffers
+        s = exact(db, refs[0])
+        for G in (2100, 2500):                                        # 3. more label groups than before (beyond the
+            db.score()                                                #    small-Run kernel's: the selection workspace)
+            gid = rng.permutation(np.arange(M1) % G).astype(np.int32)
+            check_run(db, s, gid, G, False)
+        eng.set_screening(True, min_rows=M0)                          # 4. screened Runs ...
+        db.score()
+        check_run(db, s, None, 0, True)
+        dg.append(rows[M1:M2])
+        db.score()
+        s = exact(db, refs[0])
+        db.score()
+        check_run(db, s, None, 0, True)                               # ... over more rows, then more label groups
+        for G in (40, 900):
+            db.score()
+            gid = rng.permutation(np.arange(M2) % G).astype(np.int32)
+            check_run(db, s, gid, G, True)
+        eng.set_screening(False)
+        others = [muse.DeviceBatch(eng, dg, r) for r in refs[1:]]
+        batches = [db] + others
+        db.score()
+        muse.score_many(batches[:2])                                  # 5. the pointer table for R = 2 ...
+        got = muse.scores_many(batches)                               # ... grown for R = 4
+        scores = []
+        for b, r, (lag, mv) in zip(batches, refs, got):
+            olag, omv, gap = oracle.batch_scores(r, rows, nthreads=8)
+            _check(lag, mv, olag, omv, gap)
+            scores.append((lag, mv))
+        eng.set_screening(True, min_rows=M0)                          # ... and for R = 4 screened (five columns)
+        muse.score_many(batches)
+        for b, sc, g in zip(batches, scores, muse.run_many(batches, None, 0, max_lag=15, top_n=10)):
+            check_run(b, sc, None, 0, True, got=g)
+    finally:
+        eng.set_screening(False)
+        for b in others + [db]:
+            b.close()
+        dg.close()
