@@ -28,6 +28,7 @@ MUSE_ERR_HIP = -5
 MUSE_ERR_UNSUPPORTED = -6
 MUSE_ERR_NOMEM = -7
 MUSE_ERR_EMPTY = -8
+MUSE_LAG_WINDOW_MAX = 63
 
 
 class MuseRecord(ctypes.Structure):
@@ -75,6 +76,8 @@ SIGNATURES = {
     "muse_batch_spectrum": (ctypes.c_int, [_vp, _dp]),
     "muse_batch_score": (ctypes.c_int, [_vp]),
     "muse_batch_scores": (ctypes.c_int, [_vp, _i32p, _dp]),
+    "muse_batch_set_lag_window": (ctypes.c_int, [_vp, _i32]),
+    "muse_batch_lag_window": (ctypes.c_int, [_vp, _i32p]),
     "muse_batch_run": (ctypes.c_int, [_vp, _i32p, _i32, _i32, _i32, _f64, _i32, _i32,
                                       _i64p, _i32p, _dp, _i32p, _dp]),
     "muse_batch_run_shard": (ctypes.c_int, [_vp, _i32p, _i32, _i64, _i32, _i32, _f64, _i32, _i32,

@@ -412,6 +412,10 @@ extern "C" int muse_batch_score(muse_batch *b)
     rc = ensure_scores(b);
     if (rc)
         return rc;
+    if (b->windowed()) { // the best match inside +-MaxLag, directly (xcorr_window.hip): no transform, never screened
+        b->scores_exact = true;
+        return score_windowed(b);
+    }
     if (b->n > GENERIC_MAX_N) { // series longer than 65 536 samples: a sequence of chip-wide kernels per batch of pairs (xcorr_huge.hip)
         if (b->g->f32)
             return fail(MUSE_ERR_UNSUPPORTED, "float32-storage groups run on the default kernels only (FFT lengths 512 ... 16384)");
@@ -522,7 +526,11 @@ extern "C" int muse_batch_kernel_name(muse_batch *b, char *name, int32_t cap)
     // (the names rocprofv3 prints for the instantiations: profiles/r*_counters.json is keyed by them)
     char k[96] = "xcorr_fused_generic";
     const char *padded = b->N < b->n ? "true" : "false", *f32 = b->g->f32 ? "true" : "false";
-    if (b->n > GENERIC_MAX_N) { // (the pass is a sequence of kernels: the one that moves the most bytes)
+    if (b->windowed()) {
+        const int L = std::min(b->lag_window, b->n / 2);
+        snprintf(k, sizeof(k), "xcorr_window_mfma<%d, %s>", (2 * L + 1 + 15) / 16,
+                 window_wide(b->g->rows, b->g->stride) ? "true" : "false");
+    } else if (b->n > GENERIC_MAX_N) { // (the pass is a sequence of kernels: the one that moves the most bytes)
         snprintf(k, sizeof(k), "huge_rows<false>");
     } else {
         const KernelChoice kc = choose_kernel(b, (b->g->M + 1) / 2);
@@ -590,6 +598,8 @@ extern "C" int muse_batch_free(muse_batch *b)
     b->scr_gkplus.release(c);
     b->scr_gcert.release(c);
     b->est_save.release(c);
+    b->win_e.release(c);
+    b->win_pw.release(c);
     muse_group *g = b->g;
     muse_ctx *ctx = b->ctx;
     delete b;

@@ -296,6 +296,13 @@ struct muse_batch {
     bool last_screened = false;         // the last Run took the filter-and-refine path
     int64_t guard_trips = 0;            // Runs redone in fp64 because an estimate left its bound
     uint64_t guard_salt = 0;            // varies the guard's row sample from Run to Run
+    // lag window (muse_batch_set_lag_window, capi_window.hip): < 0 = off; otherwise every scoring pass takes xcorr_window.hip
+    // with L = min(lag_window, n / 2).  win_e / win_pw: the shifted-reference image and its window sums for win_L (built by
+    // the first windowed pass; -1: none yet)
+    int32_t lag_window = -1;
+    int32_t win_L = -1;
+    PoolBuf<double> win_e, win_pw;
+    bool windowed() const { return lag_window >= 0; }
 };
 
 int use_device(muse_ctx *ctx);
@@ -372,6 +379,7 @@ int build_spectrum(muse_ctx *ctx, const double *ref_host, int N, int n, int norm
 hipError_t ensure_gscratch(muse_ctx *ctx, int64_t n, int slices_per_cu = muse::GSCRATCH_SLICES_PER_CU);
 hipError_t ensure_twl(muse_ctx *ctx, int64_t n);
 int ensure_scores(muse_batch *b);
+int score_windowed(muse_batch *b);                     // capi_window.hip: the all-scores pass of a batch with a lag window (scores allocated)
 muse::FusedParams base_params(muse_batch *b);
 int ensure_select_ws(muse_batch *b, int64_t M, int64_t G, bool with_gid, int K, bool on_device);
 // the selection of a Run happens on the device (each chunk's best top_n) only beyond EXACT_FEED_MAX_GROUPS groups: capi_run.hip, run_select

@@ -61,6 +61,9 @@ extern "C" int muse_batch_score_many(muse_batch *const *bs, int32_t R)
             if (bs[q] == bs[r])
                 return fail(MUSE_ERR_INVALID, "the same batch appears twice in the list");
     }
+    for (int r = 0; r < R; r++)
+        if (bs[r]->windowed())
+            return fail(MUSE_ERR_UNSUPPORTED, "a batch with a lag window cannot take part in a many-references pass");
     muse_batch *b0 = bs[0];
     muse_ctx *ctx = b0->ctx;
     // the one-pass kernel is built for N == n == 4096 (and is only taken under automatic kernel
@@ -180,6 +183,9 @@ extern "C" int muse_batch_run_many(muse_batch *const *bs, int32_t R, const int32
                                    int32_t abs_scores, int64_t *out_series, int32_t *out_lag, double *out_score,
                                    int32_t *out_count, double *out_mean_abs)
 {
+    for (int r = 0; bs && r < R; r++)
+        if (bs[r] && bs[r]->windowed())
+            return fail(MUSE_ERR_UNSUPPORTED, "a batch with a lag window cannot take part in a many-references pass");
     bool prescreened = false;
     int rc = screen_many(bs, R, group_id, G, max_lag, top_n, threshold, sign_filter, abs_scores, prescreened);
     if (rc)

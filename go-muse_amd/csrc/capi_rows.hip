@@ -286,6 +286,8 @@ static int run_rows(muse_batch *tmpl, const double *rows, const double *const *r
         return fail(MUSE_ERR_INVALID, "bad arguments");
     *out_winner = muse_record{-1, 0.0, 0, 0};
     *out_state = 0;
+    if (tmpl->windowed())
+        return fail(MUSE_ERR_UNSUPPORTED, "a batch with a lag window cannot be the template of a Muse.Run");
     if (M == 0) // muse.go:47-50: nothing to compare
         return MUSE_OK;
     const int32_t N = tmpl->N;
@@ -373,6 +375,8 @@ extern "C" int muse_batch_run_group_rows(muse_batch *tmpl, muse_group *src, cons
         return fail(MUSE_ERR_INVALID, "bad arguments");
     *out_winner = muse_record{-1, 0.0, 0, 0};
     *out_state = 0;
+    if (tmpl->windowed())
+        return fail(MUSE_ERR_UNSUPPORTED, "a batch with a lag window cannot be the template of a Muse.Run");
     if (src->ctx != tmpl->ctx)
         return fail(MUSE_ERR_INVALID, "the group and the template belong to different contexts");
     if (src->win_rows)

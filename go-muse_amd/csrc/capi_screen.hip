@@ -30,7 +30,7 @@ int32_t screen_path(const muse_batch *b, const muse_batch::RunKey &key, bool alr
     const muse_ctx *ctx = b->ctx;
     const int64_t M = b->g->M;
     const bool length_ok = b->n >= 512 && b->n <= 65536; // every FFT length with a tuned kernel (N > n/2 by construction)
-    const bool eligible = !already_scored && ctx->screening && ctx->variant == 0 && length_ok && b->xcf && !b->g->f32 && key.top_n >= 1 &&
+    const bool eligible = !already_scored && !b->windowed() && ctx->screening && ctx->variant == 0 && length_ok && b->xcf && !b->g->f32 && key.top_n >= 1 &&
                           key.top_n <= TOPN_DEVICE_MAX && M / 2 < 0x7fffffffLL &&
                           (ctx->screen_min_rows > 0 ? M >= ctx->screen_min_rows : M * (int64_t)b->n >= (int64_t)32768 * 4096);
     if (!eligible)

@@ -130,6 +130,25 @@ constexpr int GSCRATCH_SLICES_PER_CU = 4;
 static_assert(LONG_WGS_PER_CU <= GSCRATCH_SLICES_PER_CU && GENERIC_GLOBAL_WGS_PER_CU <= GSCRATCH_SLICES_PER_CU &&
                   2 * STOCKHAM_GLOBAL_WGS_PER_CU <= GSCRATCH_SLICES_PER_CU,
               "the scratch buffer is sized for GSCRATCH_SLICES_PER_CU slices per CU");
+// ---- the lag-window pass (xcorr_window.hip): the best match inside +-L lags from a direct matrix product, no transform
+constexpr int WIN_KC = 1024;    // samples per chunk of the reference image a workgroup stages in LDS
+constexpr int WIN_E_TAIL = 128; // >= 2 * MUSE_LAG_WINDOW_MAX + 2: what a chunk's image holds behind its WIN_KC samples
+static_assert(2 * MUSE_LAG_WINDOW_MAX + 2 <= WIN_E_TAIL, "the staged image covers every lag of the widest window");
+struct WindowParams {
+    const double *rows; // M x N row-major float64, row stride `stride` elements
+    long long M, stride;
+    int N;
+    int L, Lneg;        // lags -Lneg .. L (Lneg = L, or L - 1 when L == n / 2: index n / 2 is lag +n/2 only)
+    const double *e;    // [window_e_len(N)] e[v] = xs[(n - N + v - L) mod n], zero from N + 2 L on
+    const double *pw;   // [2 L + 1] pw[v] = sum_t e[t + v]
+    double invN, invNm1;
+    double *mv;         // out: M signed values
+    int *lag;           // out: M lags
+};
+inline bool window_wide(const double *rows, long long stride) { return stride % 2 == 0 && ((uintptr_t)rows & 15) == 0; } // every row 16-byte aligned
+inline long long window_e_len(int N) { return (long long)((N + WIN_KC - 1) / WIN_KC) * WIN_KC + WIN_E_TAIL; }
+hipError_t launch_window_tables(const double *xs, int N, int n, int L, double *e, long long e_len, double *pw, hipStream_t stream);
+hipError_t launch_window(const WindowParams &p, hipStream_t stream);
 hipError_t launch_direct(const double *x, int lenx, const double *y, int leny, int n, int normalize_x,
                          int normalize_y, double x_scale, double cc_scale, double *cc, int *lag, double *mv,
                          int *status, hipStream_t stream);

@@ -1,0 +1,261 @@
+// xcorr_window.hip -- the lag-window pass (muse_batch_set_lag_window): the best match INSIDE +-L lags, computed directly.
+//
+// For a window of L lags no transform is needed: with e[v] = xp[(pad + v - L) mod n] (xp = the batch's padded time-domain
+// reference, FusedParams::xs; pad = n - N) the correlation slice of xCorrWithX (xcorr.go:160-187) at lag v - L is
+//     cc[v] = (S[v] - mean(d) P[v]) / sigma(d),   S[v] = sum_t d[t] e[t + v],   P[v] = sum_t e[t + v],   t = 0 .. N-1,
+// d = y - y[0] (the shift every kernel here uses against cancellation).  S is a (2L+1 x N) by (N x M) matrix product between
+// shifted copies of the reference and the rows as they lie in HBM: one pass over the rows, any N, on the fp64 matrix pipe
+// (v_mfma_f64_16x16x4_f64: lags on the 16 A rows, 16 series on the B columns); mean and sigma come out of the same pass on
+// the vector unit.
+//
+// One 256-thread workgroup scores 16 series.  The samples are cut into chunks of WIN_KC; per chunk the workgroup stages
+// e[T0 .. T0 + WIN_KC + 2 L_max) in LDS and its four waves take the chunk's 64-sample pieces in turn (K split across the
+// waves).  In a piece, lane (r = lane & 15, q = lane >> 4) loads sample T + 4 m + q of row r for m = 0 .. 15 (B[k = q][col r] of
+// k-step m: per load instruction 16 rows x 32 contiguous bytes, four consecutive instructions use a 128-byte line up) and reads
+// A[row r][k = q] = e[T + 4 m + q + 16 tile + r] from the LDS image (consecutive doubles: no bank conflict).  Rows that are
+// 16-byte aligned (even stride) take the WIDE build: the k order inside a piece is free as long as A follows it, so a lane
+// loads two consecutive samples at once (16 rows x 64 contiguous bytes per instruction, half the load instructions).  The four waves'
+// accumulator tiles are summed through LDS in wave order (deterministic), then 16 threads per series scan the window in the
+// order of the definition -- lags 0, 1 .. L, then -L .. -1, strict '>', first index wins (xcorr.go:39-50) -- and are merged
+// in that order.
+#include "xcorr_kernels.h"
+
+namespace muse {
+
+typedef double v4d __attribute__((ext_vector_type(4)));
+
+constexpr int WIN_THREADS = 256;
+static_assert(2 * MUSE_LAG_WINDOW_MAX + 1 <= 8 * 16, "at most eight accumulator tiles of 16 lags");
+constexpr int WIN_ELDS = WIN_KC + WIN_E_TAIL; // doubles of e staged per chunk
+
+// e[v], v < len: the reference at padded index (pad + v - L) mod n for v < N + 2L, zero behind (the last chunk reads on)
+__global__ __launch_bounds__(256) void window_table_e(const double *__restrict__ xs, int N, int n, int L, long long len,
+                                                      double *__restrict__ e)
+{
+    const long long v = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (v >= len)
+        return;
+    double x = 0.0;
+    if (v < (long long)N + 2 * L) {
+        long long idx = ((long long)(n - N) + v - L) % n;
+        if (idx < 0)
+            idx += n;
+        x = xs[idx];
+    }
+    e[v] = x;
+}
+
+// pw[v] = sum_t e[t + v], t < N: one workgroup per v, fixed summation order
+__global__ __launch_bounds__(256) void window_table_p(const double *__restrict__ e, int N, double *__restrict__ pw)
+{
+    __shared__ double part[256];
+    const int v = blockIdx.x, t = threadIdx.x;
+    double s = 0.0;
+    for (int i = t; i < N; i += 256)
+        s += e[i + v];
+    part[t] = s;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if (t < h)
+            part[t] += part[t + h];
+        __syncthreads();
+    }
+    if (t == 0)
+        pw[v] = part[0];
+}
+
+hipError_t launch_window_tables(const double *xs, int N, int n, int L, double *e, long long e_len, double *pw, hipStream_t stream)
+{
+    window_table_e<<<dim3((unsigned)((e_len + 255) / 256)), dim3(256), 0, stream>>>(xs, N, n, L, e_len, e);
+    window_table_p<<<dim3((unsigned)(2 * L + 1)), dim3(256), 0, stream>>>(e, N, pw);
+    return hipGetLastError();
+}
+
+template <int TILES, bool WIDE>
+__global__ __launch_bounds__(WIN_THREADS) void xcorr_window_mfma(const WindowParams p)
+{
+    constexpr int RED = TILES * 256;                  // the summed accumulator tiles: [tile][lag row][series]
+    constexpr int BUF = WIN_ELDS > RED ? WIN_ELDS : RED; // (the e image is dead when the tiles are summed: one region)
+    constexpr int STAT = BUF;                         // [4 waves][16 series][2]
+    constexpr int CAND = STAT + 128;                  // [16 parts][16 series][3]
+    __shared__ double lds[CAND + 16 * 16 * 3];
+
+    const int t = threadIdx.x;
+    const int lane = t & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int r = lane & 15, q = lane >> 4;
+    const int N = p.N;
+    const long long row0 = (long long)blockIdx.x * 16;
+    long long row = row0 + r;
+    if (row >= p.M) // masked tail rows read the last row (valid memory); nothing of them is written
+        row = p.M - 1;
+    const double *__restrict__ y = p.rows + row * p.stride;
+    const double y0 = y[0];
+
+    v4d acc[TILES];
+#pragma unroll
+    for (int i = 0; i < TILES; i++)
+        acc[i] = v4d{0.0, 0.0, 0.0, 0.0};
+    double s1 = 0.0, s2 = 0.0;
+
+    for (int T0 = 0; T0 < N; T0 += WIN_KC) {
+        if (T0 > 0)
+            __syncthreads();
+        for (int v = t; v < WIN_ELDS; v += WIN_THREADS) // (the table is padded with zeros to whole chunks)
+            lds[v] = p.e[T0 + v];
+        __syncthreads();
+        for (int s = wave; s < WIN_KC / 64; s += 4) {
+            const int T = T0 + 64 * s;
+            if (T >= N)
+                break;
+            // WIDE: k-step m = 2 mp + h <-> sample T + 8 mp + 2 q + h (one 16-byte load per two k-steps: 16 rows x 64 contiguous
+            // bytes per instruction); else k-step m <-> sample T + 4 m + q (8-byte loads: rows of any alignment)
+            double d[16];
+            if (WIDE && T + 64 <= N) {
+#pragma unroll
+                for (int mp = 0; mp < 8; mp++) {
+                    const double2 v = *reinterpret_cast<const double2 *>(y + T + 8 * mp + 2 * q);
+                    d[2 * mp] = v.x - y0;
+                    d[2 * mp + 1] = v.y - y0;
+                }
+            } else if (T + 64 <= N) {
+#pragma unroll
+                for (int m = 0; m < 16; m++)
+                    d[m] = y[T + 4 * m + q] - y0;
+            } else {
+#pragma unroll
+                for (int m = 0; m < 16; m++) {
+                    const int tt = T + (WIDE ? 8 * (m >> 1) + 2 * q + (m & 1) : 4 * m + q);
+                    d[m] = tt < N ? y[tt] - y0 : 0.0;
+                }
+            }
+            const double *a = lds + 64 * s + (WIDE ? 2 * q : q) + r;
+#pragma unroll
+            for (int m = 0; m < 16; m++) {
+                s1 += d[m];
+                s2 = fma(d[m], d[m], s2);
+#pragma unroll
+                for (int i = 0; i < TILES; i++)
+                    acc[i] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[(WIDE ? 8 * (m >> 1) + (m & 1) : 4 * m) + 16 * i], d[m], acc[i], 0, 0, 0);
+            }
+        }
+    }
+    // statistics: the four k-lanes of a series, then (below) the four waves
+    s1 += __shfl_xor(s1, 16);
+    s2 += __shfl_xor(s2, 16);
+    s1 += __shfl_xor(s1, 32);
+    s2 += __shfl_xor(s2, 32);
+    if (q == 0) {
+        lds[STAT + wave * 32 + 2 * r] = s1;
+        lds[STAT + wave * 32 + 2 * r + 1] = s2;
+    }
+    __syncthreads(); // every wave is done with the e image
+    // C/D of v_mfma_f64_16x16x4_f64: register j of lane (r, q) = [row q + 4 j][column r]
+    for (int w = 0; w < 4; w++) {
+        if (wave == w) {
+#pragma unroll
+            for (int i = 0; i < TILES; i++)
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    const int at = i * 256 + (q + 4 * j) * 16 + r;
+                    lds[at] = w == 0 ? acc[i][j] : lds[at] + acc[i][j];
+                }
+        }
+        __syncthreads();
+    }
+
+    // the windowed maxAbsIndex: scan position pos = 0 .. W-1 <-> lag 0 .. L, -Lneg .. -1
+    const int c = t & 15, part = t >> 4;
+    const int L = p.L, Lneg = p.Lneg, W = L + 1 + Lneg;
+    double t1 = 0.0, t2 = 0.0;
+#pragma unroll
+    for (int w = 0; w < 4; w++) {
+        t1 += lds[STAT + w * 32 + 2 * c];
+        t2 += lds[STAT + w * 32 + 2 * c + 1];
+    }
+    const double var = (t2 - t1 * t1 * p.invN) * p.invNm1;
+    const bool nan = !__builtin_isfinite(var);
+    const bool zero = !nan && !(var > 0.0);
+    const double mean = t1 * p.invN;
+    const double inv_sigma = 1.0 / sqrt(var);
+    double best_abs = 0.0, best_val = 0.0, best_pos = -1.0;
+#pragma unroll
+    for (int k = 0; k < TILES; k++) {
+        const int pos = part * TILES + k;
+        if (pos < W) {
+            const int v = pos <= L ? pos + L : pos - 1 - Lneg; // lag + L
+            const double S = lds[(v >> 4) * 256 + (v & 15) * 16 + c];
+            const double val = (S - mean * p.pw[v]) * inv_sigma;
+            if (fabs(val) > best_abs) {
+                best_abs = fabs(val);
+                best_val = val;
+                best_pos = (double)pos;
+            }
+        }
+    }
+    lds[CAND + (part * 16 + c) * 3] = best_abs;
+    lds[CAND + (part * 16 + c) * 3 + 1] = best_val;
+    lds[CAND + (part * 16 + c) * 3 + 2] = best_pos;
+    __syncthreads();
+    if (t < 16 && row0 + t < p.M) {
+        double ba = 0.0, bv = 0.0;
+        int bp = -1;
+        for (int k = 0; k < 16; k++) {
+            const double a = lds[CAND + (k * 16 + c) * 3];
+            if (a > ba) {
+                ba = a;
+                bv = lds[CAND + (k * 16 + c) * 3 + 1];
+                bp = (int)lds[CAND + (k * 16 + c) * 3 + 2];
+            }
+        }
+        int lag = 0;
+        double mv;
+        if (nan) {
+            mv = __builtin_nan("");
+        } else if (zero) {
+            mv = 0.0; // sigma == 0: (nil, 0, 0), xcorr.go:165-168
+        } else if (bp < 0) { // only zeros or NaN in the window: index 0 stands
+            mv = (lds[(L >> 4) * 256 + (L & 15) * 16 + c] - mean * p.pw[L]) * inv_sigma;
+        } else {
+            mv = bv;
+            lag = bp <= L ? bp : bp - 1 - Lneg - L;
+        }
+        p.mv[row0 + t] = mv;
+        p.lag[row0 + t] = lag;
+    }
+}
+
+hipError_t launch_window(const WindowParams &p, hipStream_t stream)
+{
+    if (p.M <= 0)
+        return hipSuccess;
+    if (p.L < 0 || p.L > MUSE_LAG_WINDOW_MAX || p.Lneg < 0 || p.Lneg > p.L || p.N < 2)
+        return hipErrorInvalidValue;
+    const long long blocks = (p.M + 15) / 16;
+    if (blocks > 0x7fffffffLL)
+        return hipErrorInvalidValue;
+    const dim3 grid((unsigned)blocks), block(WIN_THREADS);
+    const int W = 2 * p.L + 1; // lag + L runs up to 2 L whichever side the window drops
+    const bool wide = window_wide(p.rows, p.stride);
+#define MUSE_WINDOW_LAUNCH(T)                                                    \
+    do {                                                                         \
+        if (wide)                                                                \
+            xcorr_window_mfma<T, true><<<grid, block, 0, stream>>>(p);           \
+        else                                                                     \
+            xcorr_window_mfma<T, false><<<grid, block, 0, stream>>>(p);          \
+    } while (0)
+    switch ((W + 15) / 16) { // accumulator tiles of 16 lags
+    case 1: MUSE_WINDOW_LAUNCH(1); break;
+    case 2: MUSE_WINDOW_LAUNCH(2); break;
+    case 3: MUSE_WINDOW_LAUNCH(3); break;
+    case 4: MUSE_WINDOW_LAUNCH(4); break;
+    case 5: MUSE_WINDOW_LAUNCH(5); break;
+    case 6: MUSE_WINDOW_LAUNCH(6); break;
+    case 7: MUSE_WINDOW_LAUNCH(7); break;
+    default: MUSE_WINDOW_LAUNCH(8); break;
+    }
+#undef MUSE_WINDOW_LAUNCH
+    return hipGetLastError();
+}
+
+} // namespace muse

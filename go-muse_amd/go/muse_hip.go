@@ -359,6 +359,7 @@ type Batch struct {
 	batchGroup  *C.muse_group
 	shardBatch  []*C.muse_batch // sharded Runs (SetDevices): one device batch per shard
 	shardGroup  []*C.muse_group
+	window      int // RunWindowed: the lag window of the Run in progress (-1: none)
 }
 
 // NewBatch replaces muse_batch.go:23-52: same length check, same
@@ -376,7 +377,7 @@ func NewBatch(ref *Series, comp *Group, results *Results, cc int) (*Batch, error
 	if err != nil {
 		return nil, err
 	}
-	b := &Batch{ref: append([]float64(nil), ref.Values()...), Comparison: comp, Results: results, Concurrency: cc}
+	b := &Batch{ref: append([]float64(nil), ref.Values()...), Comparison: comp, Results: results, Concurrency: cc, window: -1}
 	// validate the reference now (sigma == 0 -> error), as the reference does
 	runtime.LockOSThread()
 	defer runtime.UnlockOSThread()
@@ -458,6 +459,9 @@ func (b *Batch) Run(groupByLabels []string) error {
 		}
 		b.batchGroup = dg
 	}
+	if err := hipError(C.muse_batch_set_lag_window(b.batch, C.int32_t(b.window))); err != nil {
+		return err
+	}
 	if exact {
 		recs := (*C.muse_record)(C.calloc(C.size_t(G), C.size_t(unsafe.Sizeof(C.muse_record{}))))
 		defer C.free(unsafe.Pointer(recs))
@@ -493,6 +497,18 @@ func (b *Batch) Run(groupByLabels []string) error {
 		b.Results.Update(Score{Labels: b.Comparison.order[idx[k]].Labels(), Lag: int(lag[k]), PercentScore: float64(score[k])})
 	}
 	return nil
+}
+
+// RunWindowed is Run with Results.MaxLag as a LAG WINDOW (muse_batch_set_lag_window): every series contributes its best
+// match inside +-MaxLag, where Run drops a series whose best match over all lags lies outside.  Same feeds and devices as Run;
+// the window is taken off again behind the Run, so Run itself never changes.
+func (b *Batch) RunWindowed(groupByLabels []string) error {
+	if b.Results.MaxLag < 0 || b.Results.MaxLag > C.MUSE_LAG_WINDOW_MAX {
+		return fmt.Errorf("RunWindowed: MaxLag outside 0 .. %d", int(C.MUSE_LAG_WINDOW_MAX))
+	}
+	b.window = b.Results.MaxLag
+	defer func() { b.window = -1 }()
+	return b.Run(groupByLabels)
 }
 
 const exactFeedMaxGroups = 65536
@@ -555,6 +571,10 @@ func (b *Batch) runSharded(es []*engine, gid []C.int32_t, G int, exact bool) err
 					return err
 				}
 				b.shardGroup[r] = sh.g
+			}
+			if err := hipError(C.muse_batch_set_lag_window(b.shardBatch[r], C.int32_t(b.window))); err != nil {
+				runtime.UnlockOSThread()
+				return err
 			}
 		}
 		runtime.UnlockOSThread()

@@ -1072,6 +1072,21 @@ public:
             Results_->Update(Score{Comparison->series()[idx[k]]->Labels(), lag[k], score[k]});
     }
 
+    // Run with Results.MaxLag as a LAG WINDOW (muse_batch_set_lag_window): every series contributes its best match inside
+    // +-MaxLag, where Run drops a series whose best match over all lags lies outside.  Same feeds and engines as Run; the
+    // window is taken off again behind the Run, so Run itself never changes.
+    void RunWindowed(const std::vector<std::string> &groupByLabels)
+    {
+        if (Results_->MaxLag < 0 || Results_->MaxLag > MUSE_LAG_WINDOW_MAX)
+            throw Error(MUSE_ERR_UNSUPPORTED, "RunWindowed: MaxLag outside 0 .. MUSE_LAG_WINDOW_MAX");
+        struct Reset {
+            int32_t &w;
+            ~Reset() { w = -1; }
+        } reset{window_};
+        window_ = (int32_t)Results_->MaxLag; // (ensure / ensure_shard_batches hand it to the batches the Run scores)
+        Run(groupByLabels);
+    }
+
     // The README use case (README.md:10-13) runs many references against one Group: the same as
     // calling Run on every batch, but the resident rows are read and transformed once for all of
     // them (muse_batch_run_many).  The batches must share the Comparison group and the Results settings
@@ -1188,6 +1203,7 @@ private:
                 check(muse_batch_create(shards[r].eng->handle(), shards[r].dev, ref_.data(), (int32_t)ref_.size(), &sb.batch));
                 sb.group = shards[r].dev;
             }
+            check(muse_batch_set_lag_window(sb.batch, window_));
         }
     }
     // The sharded Run over very many label groups.  Label groups that live on ONE shard each (always the case when every series is its own group):
@@ -1278,7 +1294,9 @@ private:
             check(muse_batch_create_like(template_, dg, &batch_));
             batch_group_ = dg;
         }
+        check(muse_batch_set_lag_window(batch_, window_));
     }
+    int32_t window_ = -1; // RunWindowed: the lag window of the Run in progress (-1: none)
     std::shared_ptr<Engine> eng_;
     std::vector<double> ref_;
     muse_batch *batch_ = nullptr;

@@ -368,6 +368,16 @@ class DeviceBatch:
         B.check(B.load().muse_batch_scores(self._h, B.i32ptr(lag), B.dptr(mv)))
         return lag, mv
 
+    def set_lag_window(self, max_lag):
+        """every scoring pass of this batch returns the best match inside +-max_lag (muse_batch_set_lag_window; < 0: off)"""
+        B.check(B.load().muse_batch_set_lag_window(self._h, int(max_lag)))
+
+    def lag_window(self):
+        """the batch's lag window, -1 = off (muse_batch_lag_window)"""
+        w = ctypes.c_int32(0)
+        B.check(B.load().muse_batch_lag_window(self._h, ctypes.byref(w)))
+        return int(w.value)
+
     def read_scores(self):
         """(lag, mv) of the last scoring pass without re-scoring (muse_batch_read_scores)"""
         M = self.dgroup.M
@@ -1038,6 +1048,25 @@ class Batch:
         for k in order:
             r.Update(Score(series[int(idx[k])].Labels(), int(lag[k]), float(score[k])))
         return None
+
+    def RunWindowed(self, groupByLabels):
+        """Run with Results.MaxLag as a LAG WINDOW (muse_batch_set_lag_window): every series contributes its best match inside
+        +-MaxLag, where Run drops a series whose best match over all lags lies outside.  Same feeds, same engines as Run; the
+        window is taken off again behind the Run, so Run itself never changes."""
+        if not self.Comparison.indexLabelValues(groupByLabels):
+            return None
+        if self._engines:
+            self._shard_batches()
+            dbs = list(self._shard_db)
+        else:
+            dbs = [self._batch()]
+        try:
+            for db in dbs:
+                db.set_lag_window(self.Results.MaxLag)
+            return self.Run(groupByLabels)
+        finally:
+            for db in dbs:
+                db.set_lag_window(-1)
 
     def _shard_batches(self):
         shards = self.Comparison._device_shards(self._engines)

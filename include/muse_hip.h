@@ -250,6 +250,26 @@ int muse_batch_spectrum(muse_batch *b, double *out);
  * slice: lag and signed max value; sigma==0 series give (0, 0.0).  Results
  * stay on the device (asynchronous; see muse_ctx_synchronize). */
 int muse_batch_score(muse_batch *b);
+/* Lag window, OPT-IN (off for every new batch; muse_batch_create_like does not inherit it).  Today's Run applies
+ * Results.MaxLag the way the reference does (results.go:46-52): a series whose best lag over ALL n lags lies outside
+ * +-MaxLag is dropped.  With a window set, every scoring pass of this batch (muse_batch_score, _scores, _run,
+ * _run_shard, _run_groups) instead returns per series the best match INSIDE the window: with cc[0 .. n-1] the slice
+ * xCorrWithX computes (xcorr.go:160-187) and lag(i) = i if i <= n/2 else i - n, maxAbsIndex (xcorr.go:39-50) runs over
+ * the indices with |lag(i)| <= L only, in ascending index order (0 .. L, then n-L .. n-1), same start values, same
+ * strict '>': the first index wins ties, a window of zeros / NaN gives (0, cc[0]), a NaN / Inf series (0, NaN),
+ * sigma == 0 (0, 0.0).  L = min(max_lag, n/2); with L = n/2 the result is the unwindowed one, and whenever the
+ * unwindowed winner lies inside the window the windowed result is that same (lag, value).  The pass is a direct
+ * matrix product on the fp64 matrix pipe (xcorr_window.hip), one read of the rows, no transform; it is never screened
+ * (muse_batch_last_run_path: MUSE_RUN_PATH_FP64).
+ *   max_lag < 0                      : off -- the transform kernels, bit for bit as if never set
+ *   0 <= max_lag <= MUSE_LAG_WINDOW_MAX : on
+ * MUSE_ERR_UNSUPPORTED, the batch unchanged: max_lag > MUSE_LAG_WINDOW_MAX (beyond a few dozen lags the direct product
+ * costs more than the transform); a float32-storage group; series longer than 65536 samples.  A batch with a window is
+ * refused (MUSE_ERR_UNSUPPORTED) by muse_batch_score_many / _run_many and as the template of muse_batch_run_rows /
+ * _run_row_ptrs / _run_group_rows.  muse_batch_lag_window reads the setting back (-1 = off). */
+#define MUSE_LAG_WINDOW_MAX 63
+int muse_batch_set_lag_window(muse_batch *b, int32_t max_lag);
+int muse_batch_lag_window(muse_batch *b, int32_t *max_lag);
 /* muse_batch_score + D2H of the per-series results (lag[M], mv[M]). */
 int muse_batch_scores(muse_batch *b, int32_t *lag, double *mv);
 /* Batch.Run + Results.Update + Results.Fetch (muse_batch.go:99-130,
