@@ -394,7 +394,201 @@ static KernelChoice choose_kernel(muse_batch *b, long long npairs)
     return kc;
 }
 
+// ------------------------------------------------------------------- spectrum cache
+int spectrum_cache_policy(int64_t rows, int32_t N, bool f32, int mode, int64_t min_rows, int64_t free_bytes, int64_t budget,
+                          int64_t *rows_cached, int64_t *bytes)
+{
+    *rows_cached = 0;
+    *bytes = 0;
+    // float64 rows at FFT length 4096 (2048 < N <= 4096), automatic mode, a group large enough to be worth its footprint
+    if (mode != 1 || f32 || N <= 2048 || N > 4096 || rows < std::max<int64_t>(min_rows, 2))
+        return ZC_POLICY_NONE;
+    const int64_t pairs = rows / 2; // a trailing single row is never cached
+    *rows_cached = 2 * pairs;
+    *bytes = pairs * ZC_PAIR_BYTES;
+    const int64_t limit = budget >= 0 ? budget : free_bytes / 2; // at most half of what is free
+    return *bytes <= limit ? ZC_POLICY_BUILD : ZC_POLICY_DECLINED;
+}
+
+void group_drop_spectrum_cache(muse_group *g)
+{
+    for (auto &sg : g->zc_segs)
+        dfree(g->ctx, sg.mem);
+    g->zc_segs.clear();
+    g->zc_state = muse_group::ZC_NONE;
+    g->zc_rows = g->zc_bytes = 0;
+    g->zc_passes = 0;
+    g->zc_declined_M = -1;
+}
+
+// does this batch's all-scores pass go through the group's spectrum cache at all (the default n = 4096 kernel under automatic
+// selection on the context's stream, a float64 group that keeps its rows)?  Mode, size and memory: spectrum_cache_policy.
+static bool spectrum_cache_candidate(const muse_batch *b, int variant)
+{
+    return variant == KERNEL_R16_FOLD && b->ctx->variant == 0 && b->n == 4096 && !b->g->f32 && !b->g->transient &&
+           !b->own_stream;
+}
+
+// What this pass launches (ready_mu held): `readers` segments from the cache, then the pairs from tail_pair0 on from the rows, the
+// first tail_zpairs of them into tail_seg.  use == false: the plain kernel over everything.
+struct ZcPlan {
+    bool use = false;
+    std::vector<muse_group::ZcSegment> readers;
+    int64_t tail_pair0 = 0, tail_zpairs = 0;
+    muse_group::ZcSegment tail_seg;
+};
+static int plan_spectrum_cache(muse_batch *b, ZcPlan &plan)
+{
+    muse_ctx *ctx = b->ctx;
+    muse_group *g = b->g;
+    const int64_t M = g->M;
+    if (g->zc_rewrites != g->rewrites) { // rows below M were rewritten: what was cached describes other rows
+        if (!g->zc_segs.empty())
+            HIP_TRY(hipStreamSynchronize(ctx->stream)); // (a pass enqueued earlier may still be reading the blocks)
+        group_drop_spectrum_cache(g);
+        g->zc_rewrites = g->rewrites;
+    }
+    const int mode = ctx->zc_mode.load();
+    const int64_t min_rows = ctx->zc_min_rows.load(), budget = ctx->zc_budget.load();
+    int64_t want_rows = 0, want_bytes = 0;
+    if (spectrum_cache_policy(M, b->N, g->f32, mode, min_rows, 0, 0, &want_rows, &want_bytes) == ZC_POLICY_NONE)
+        return MUSE_OK; // (mode 0 leaves an existing cache alone and unused: muse_group_drop_spectrum_cache gives the HBM back)
+    // a block for the pairs [pair0, pair0 + pairs), if half of the free HBM (or the test hook's budget) holds it
+    const auto grow = [&](int64_t pair0, int64_t pairs, muse_group::ZcSegment &sg) -> bool {
+        size_t free_b = 0, total_b = 0;
+        if (budget < 0 && hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
+            (void)hipGetLastError();
+            return false;
+        }
+        const int64_t bytes = pairs * ZC_PAIR_BYTES;
+        if (bytes > (budget >= 0 ? budget - g->zc_bytes : (int64_t)(free_b / 2)))
+            return false;
+        void *mem = nullptr;
+        if (pool_alloc(ctx, false, &mem, (size_t)bytes, false) != hipSuccess) { // (never at the price of the allocation cache)
+            (void)hipGetLastError();
+            return false;
+        }
+        sg.mem = mem;
+        sg.pair0 = pair0;
+        sg.pairs = pairs;
+        g->zc_segs.push_back(sg);
+        g->zc_bytes += bytes;
+        return true;
+    };
+    if (g->zc_state != muse_group::ZC_VALID) {
+        if (g->zc_state == muse_group::ZC_DECLINED && g->zc_declined_M == M)
+            return MUSE_OK;
+        if (++g->zc_passes < 2) // the first pass over these rows: a group scored once pays nothing
+            return MUSE_OK;
+        if (!grow(0, want_rows / 2, plan.tail_seg)) {
+            g->zc_state = muse_group::ZC_DECLINED;
+            g->zc_declined_M = M;
+            return MUSE_OK;
+        }
+        g->zc_state = muse_group::ZC_VALID;
+        g->zc_rows = want_rows;
+        plan.use = true;
+        plan.tail_pair0 = 0;
+        plan.tail_zpairs = want_rows / 2;
+        return MUSE_OK;
+    }
+    plan.use = true;
+    plan.readers = g->zc_segs;
+    plan.tail_pair0 = g->zc_rows / 2;
+    const int64_t more = M / 2 - g->zc_rows / 2; // pairs of two rows appended behind the cache
+    if (more > 0 && (int)g->zc_segs.size() < ZC_MAX_SEGMENTS && g->zc_declined_M != M) {
+        if (grow(plan.tail_pair0, more, plan.tail_seg)) {
+            plan.tail_zpairs = more;
+            g->zc_rows = 2 * (M / 2);
+        } else {
+            g->zc_declined_M = M; // (the cached rows stay; the tail is asked for again once M changes)
+        }
+    }
+    return MUSE_OK;
+}
+
+extern "C" int muse_ctx_set_spectrum_cache(muse_ctx *ctx, int32_t mode)
+{
+    if (!ctx || (mode != 0 && mode != 1))
+        return fail(MUSE_ERR_INVALID, "spectrum cache mode is 0 (off) or 1 (automatic)");
+    ctx->zc_mode.store(mode);
+    return MUSE_OK;
+}
+
+extern "C" int muse_group_spectrum_cache(muse_group *g, int64_t *rows_cached, int64_t *bytes)
+{
+    if (!g)
+        return fail(MUSE_ERR_INVALID, "NULL group");
+    std::lock_guard<std::mutex> lock(g->ready_mu);
+    if (rows_cached)
+        *rows_cached = (g->zc_state == muse_group::ZC_VALID && g->zc_rewrites == g->rewrites) ? g->zc_rows : 0;
+    if (bytes)
+        *bytes = g->zc_bytes;
+    return MUSE_OK;
+}
+
+extern "C" int muse_group_drop_spectrum_cache(muse_group *g)
+{
+    if (!g)
+        return fail(MUSE_ERR_INVALID, "NULL group");
+    std::lock_guard<std::mutex> lock(g->ready_mu);
+    if (g->zc_segs.empty() && g->zc_state == muse_group::ZC_NONE)
+        return MUSE_OK;
+    int rc = use_device(g->ctx);
+    if (rc)
+        return rc;
+    HIP_TRY(hipStreamSynchronize(g->ctx->stream)); // a pass enqueued earlier may still be reading the blocks
+    group_drop_spectrum_cache(g);
+    return MUSE_OK;
+}
+
+extern "C" int muse_test_spectrum_cache_limits(muse_ctx *ctx, int64_t min_rows, int64_t budget_bytes)
+{
+    if (!ctx)
+        return fail(MUSE_ERR_INVALID, "NULL context");
+    ctx->zc_min_rows.store(min_rows < 0 ? ZC_MIN_ROWS : min_rows);
+    ctx->zc_budget.store(budget_bytes < 0 ? -1 : budget_bytes);
+    return MUSE_OK;
+}
+
+extern "C" int muse_test_spectrum_cache_policy(int64_t rows, int32_t N, int32_t f32, int32_t mode, int64_t min_rows,
+                                               int64_t free_bytes, int64_t budget_bytes, int32_t *decision,
+                                               int64_t *rows_cached, int64_t *bytes)
+{
+    if (!decision || !rows_cached || !bytes)
+        return fail(MUSE_ERR_INVALID, "NULL output");
+    *decision = spectrum_cache_policy(rows, N, f32 != 0, mode, min_rows < 0 ? ZC_MIN_ROWS : min_rows, free_bytes,
+                                      budget_bytes < 0 ? -1 : budget_bytes, rows_cached, bytes);
+    return MUSE_OK;
+}
+
+// test hook: the pairs the last n = 4096 all-scores pass of this batch listed for the rescaling kernel, in list order
+extern "C" int muse_test_batch_redo_pairs(muse_batch *b, int64_t *pairs, int64_t cap, int64_t *count)
+{
+    if (!b || !count || cap < 0 || (cap > 0 && !pairs))
+        return fail(MUSE_ERR_INVALID, "bad redo-list arguments");
+    *count = 0;
+    int rc = use_device(b->ctx);
+    if (rc)
+        return rc;
+    HIP_TRY(hipStreamSynchronize(b->stream()));
+    if (!b->ovf_count || !b->ovf_list.p)
+        return MUSE_OK;
+    int listed = 0;
+    HIP_TRY(hipMemcpy(&listed, b->ovf_count, sizeof(int), hipMemcpyDeviceToHost));
+    *count = listed;
+    const int64_t k = std::min<int64_t>(std::min<int64_t>(listed, cap), b->ovf_list.cap);
+    if (k > 0)
+        HIP_TRY(hipMemcpy(pairs, b->ovf_list.p, (size_t)k * sizeof(long long), hipMemcpyDeviceToHost));
+    return MUSE_OK;
+}
+
 extern "C" int muse_batch_score(muse_batch *b)
+{
+    return batch_score(b, true);
+}
+
+int batch_score(muse_batch *b, bool allow_spectrum_cache)
 {
     if (!b)
         return fail(MUSE_ERR_INVALID, "NULL batch");
@@ -450,8 +644,44 @@ extern "C" int muse_batch_score(muse_batch *b)
         p.work_counter = b->ovf_count + 1;
         p.ovf_list = b->ovf_list.p;
         HIP_TRY(hipMemsetAsync(b->ovf_count, 0, 2 * sizeof(int), st));
+        // the group's spectrum cache: decided and enqueued under the group's lock, so that of two batches scored from
+        // two host threads one builds and the other one's reader sits behind that writer on the stream
+        ZcPlan plan;
+        std::unique_lock<std::mutex> zc_lock(b->g->ready_mu, std::defer_lock);
+        if (allow_spectrum_cache && spectrum_cache_candidate(b, variant)) {
+            zc_lock.lock();
+            rc = plan_spectrum_cache(b, plan);
+            if (rc)
+                return rc;
+            if (!plan.use)
+                zc_lock.unlock();
+        }
         HIP_TRY(timer.begin());
-        HIP_TRY(launch_fused(p, variant, ctx->num_cus, st));
+        if (plan.use) { // (one bracket around the pass's launches: in steady state the reader alone)
+            bool launched = false;
+            const auto next_launch = [&]() { // every launch hands its pairs out from a counter of zero
+                const hipError_t e = launched ? hipMemsetAsync(b->ovf_count + 1, 0, sizeof(int), st) : hipSuccess;
+                launched = true;
+                return e;
+            };
+            for (const auto &sg : plan.readers) {
+                FusedParams r = p;
+                r.npairs = sg.pairs;
+                HIP_TRY(next_launch());
+                HIP_TRY(launch_cached(r, SpectrumCacheArgs{sg.zc(), sg.zstat(), sg.pair0, sg.pairs}, ctx->num_cus, st));
+            }
+            if (plan.tail_pair0 < p.npairs) {
+                FusedParams w = p;
+                w.npairs = p.npairs - plan.tail_pair0;
+                HIP_TRY(next_launch());
+                HIP_TRY(launch_cache_fill(w, SpectrumCacheArgs{plan.tail_zpairs ? plan.tail_seg.zc() : nullptr,
+                                                               plan.tail_zpairs ? plan.tail_seg.zstat() : nullptr,
+                                                               plan.tail_pair0, plan.tail_zpairs}, ctx->num_cus, st));
+            }
+            zc_lock.unlock();
+        } else {
+            HIP_TRY(launch_fused(p, variant, ctx->num_cus, st));
+        }
         HIP_TRY(timer.end());
         FusedParams q = p;
         q.pair_list = b->ovf_list.p;
@@ -535,7 +765,21 @@ extern "C" int muse_batch_kernel_name(muse_batch *b, char *name, int32_t cap)
     } else {
         const KernelChoice kc = choose_kernel(b, (b->g->M + 1) / 2);
         switch (kc.error ? -1 : kc.variant) {
-        case KERNEL_R16_FOLD: snprintf(k, sizeof(k), "xcorr_fused_n4096_fold<false, %s, %s>", padded, f32); break;
+        case KERNEL_R16_FOLD: {
+            // the reader once the group's spectrum cache is valid for the rows as they are (what the next pass launches first)
+            bool cached = false;
+            if (spectrum_cache_candidate(b, kc.variant)) {
+                std::lock_guard<std::mutex> lock(b->g->ready_mu);
+                int64_t rc_ = 0, by_ = 0;
+                cached = b->g->zc_state == muse_group::ZC_VALID && b->g->zc_rewrites == b->g->rewrites && b->g->zc_rows > 0 &&
+                         spectrum_cache_policy(b->g->M, b->N, false, b->ctx->zc_mode.load(), b->ctx->zc_min_rows.load(), 0, 0, &rc_, &by_) != ZC_POLICY_NONE;
+            }
+            if (cached)
+                snprintf(k, sizeof(k), "xcorr_cached_n4096<%s>", padded);
+            else
+                snprintf(k, sizeof(k), "xcorr_fused_n4096_fold<false, %s, %s>", padded, f32);
+            break;
+        }
         case KERNEL_R16_OCC3: snprintf(k, sizeof(k), "xcorr_fused_n4096_occ4"); break;
         case KERNEL_SMALL: snprintf(k, sizeof(k), "xcorr_fused_small<%d, %s, false, %s>", b->logn, padded, f32); break;
         case KERNEL_LONG: snprintf(k, sizeof(k), "xcorr_fused_long<%d, %s, false>", b->logn, padded); break;

@@ -70,7 +70,7 @@ static size_t pool_class(size_t bytes)
     return (bytes + (((size_t)1 << 20) - 1)) & ~(((size_t)1 << 20) - 1);
 }
 
-hipError_t pool_alloc(muse_ctx *ctx, bool host, void **out, size_t bytes)
+hipError_t pool_alloc(muse_ctx *ctx, bool host, void **out, size_t bytes, bool drain_on_failure)
 {
     MemPool &mp = host ? ctx->host_pool : ctx->dev_pool;
     const size_t cls = pool_class(bytes);
@@ -87,7 +87,7 @@ hipError_t pool_alloc(muse_ctx *ctx, bool host, void **out, size_t bytes)
     }
     void *p = nullptr;
     hipError_t e = host ? hipHostMalloc(&p, cls, hipHostMallocDefault) : hipMalloc(&p, cls);
-    if (e != hipSuccess) { // out of memory with blocks cached: give them back and try once more
+    if (e != hipSuccess && drain_on_failure) { // out of memory with blocks cached: give them back and try once more
         (void)hipGetLastError();
         pool_drain(ctx);
         e = host ? hipHostMalloc(&p, cls, hipHostMallocDefault) : hipMalloc(&p, cls);

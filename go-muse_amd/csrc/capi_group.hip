@@ -515,6 +515,7 @@ void group_release(muse_group *g)
         dfree(g->ctx, (char *)g->base() - GROUP_GUARD * g->elem());
     for (void *old : g->retired)
         dfree(g->ctx, old);
+    group_drop_spectrum_cache(g); // (behind the same wait as the rows)
     g->hstats.release(g->ctx);
     g->gidx_host.release(g->ctx);
     g->gidx_dev.release(g->ctx);

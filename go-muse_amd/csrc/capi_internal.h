@@ -52,7 +52,8 @@ struct MemPool {
     size_t idle_cap = 0;                                    // cached bytes kept at most
     size_t block_cap = 0;                                   // larger blocks are never cached
 };
-hipError_t pool_alloc(muse_ctx *ctx, bool host, void **out, size_t bytes); // capi_context.hip
+// (drain_on_failure: out of memory with blocks cached -> give them back and try once more)
+hipError_t pool_alloc(muse_ctx *ctx, bool host, void **out, size_t bytes, bool drain_on_failure = true); // capi_context.hip
 void pool_free(muse_ctx *ctx, bool host, void *p);
 // A work buffer that grows on demand: `cap` elements of T from the context's device pool (Host: its pinned host pool).
 template <class T, bool Host = false> struct PoolBuf {
@@ -97,6 +98,8 @@ struct HugeWork {
     hipStream_t stream2 = nullptr;
     hipEvent_t fork = nullptr, join = nullptr;
 };
+constexpr int64_t ZC_MIN_ROWS = 65536; // smaller groups are never cached: a pass over them is under 0.6 ms (the small-Run regime)
+constexpr int ZC_MAX_SEGMENTS = 64;    // appends extend the cache by one segment each; beyond this many the tail stays on the rows
 constexpr int PROBE_WINDOWS = 4096; // clock probe (muse_test_clock_probe_*): windows its pinned buffer holds; the window count and the stop flag sit behind them
 struct muse_ctx {
     int device = 0;
@@ -155,6 +158,11 @@ struct muse_ctx {
     std::atomic<bool> rows_always_copy{false}; // test hook (muse_test_rows_always_copy): never let a kernel read the pinned staging buffer
     std::vector<void *> rows_slots;
     std::mutex rows_mu;
+    // spectrum cache of resident float64 groups at FFT length 4096 (muse_ctx_set_spectrum_cache; capi_batch.hip):
+    // 0 = off, 1 = automatic.  zc_min_rows / zc_budget: test hooks (muse_test_spectrum_cache_limits; budget < 0 = half of the free HBM)
+    std::atomic<int> zc_mode{1};
+    std::atomic<int64_t> zc_min_rows{ZC_MIN_ROWS};
+    std::atomic<int64_t> zc_budget{-1};
     std::atomic<bool> gather_nt{false}; // measurement hook (muse_test_gather_nontemporal): the row gather's stores bypass the caches
     // Handles may be released in any order (Go finalizers, Python GC): the
     // context lives until it is destroyed AND its last group/batch is freed.
@@ -207,6 +215,25 @@ struct muse_group {
     HostBuf<long long> gidx_host;
     PoolBuf<long long> gidx_dev;
     hipEvent_t gather_done = nullptr;
+    // Spectrum cache (n = 4096, float64 rows; xcorr_r16_cached.hip): per pair of rows what the default kernel's first
+    // half computes from the rows alone, kept for every later pass of every batch over the group.  Rows [0, zc_rows) are covered
+    // (zc_rows even: a trailing single row's pair changes when a row is appended), in segments in pair order -- an append adds a
+    // segment, nothing is rebuilt or moved.  Valid for the rows as they were after `zc_rewrites` rewrites.  All of it under ready_mu;
+    // every kernel that writes or reads it runs on the context's compute stream, in the order it was enqueued under that lock.
+    struct ZcSegment {
+        void *mem = nullptr; // one block: zc[pairs][4096] double2, then zstat[pairs][ZC_STAT] double
+        int64_t pair0 = 0, pairs = 0;
+        double2 *zc() const { return (double2 *)mem; }
+        double *zstat() const { return (double *)((char *)mem + (size_t)pairs * 4096 * sizeof(double2)); }
+    };
+    enum { ZC_NONE = 0, ZC_DECLINED = 1, ZC_VALID = 2 };
+    std::vector<ZcSegment> zc_segs;
+    int zc_state = ZC_NONE;
+    int64_t zc_rows = 0, zc_bytes = 0;
+    uint64_t zc_rewrites = 0;
+    int64_t zc_passes = 0;       // eligible passes over the rows as they are (a group scored once pays nothing: the second one builds)
+    int64_t zc_declined_M = -1;  // ZC_DECLINED: the row count that did not fit (asked again once it changes)
+    bool transient = false;      // the slot groups of muse_batch_run_rows: other rows on every call, never cached
 };
 
 // The reference spectrum and the tables derived from it: shared (reference-counted) by the batches
@@ -379,6 +406,13 @@ int build_spectrum(muse_ctx *ctx, const double *ref_host, int N, int n, int norm
 hipError_t ensure_gscratch(muse_ctx *ctx, int64_t n, int slices_per_cu = muse::GSCRATCH_SLICES_PER_CU);
 hipError_t ensure_twl(muse_ctx *ctx, int64_t n);
 int ensure_scores(muse_batch *b);
+int batch_score(muse_batch *b, bool allow_spectrum_cache); // capi_batch.hip: muse_batch_score (the many-references fallback passes false)
+// the spectrum cache's policy, a pure host function: what a pass over `rows` rows of length N does about a cache
+// that does not exist yet -- nothing, build one of *bytes for *rows_cached rows, or decline for lack of memory
+enum { ZC_POLICY_NONE = 0, ZC_POLICY_BUILD = 1, ZC_POLICY_DECLINED = 2 };
+int spectrum_cache_policy(int64_t rows, int32_t N, bool f32, int mode, int64_t min_rows, int64_t free_bytes, int64_t budget,
+                          int64_t *rows_cached, int64_t *bytes);
+void group_drop_spectrum_cache(muse_group *g);             // capi_batch.hip: frees the segments (ready_mu held, compute stream idle)
 int score_windowed(muse_batch *b);                     // capi_window.hip: the all-scores pass of a batch with a lag window (scores allocated)
 muse::FusedParams base_params(muse_batch *b);
 int ensure_select_ws(muse_batch *b, int64_t M, int64_t G, bool with_gid, int K, bool on_device);

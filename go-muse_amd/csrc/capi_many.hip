@@ -85,7 +85,7 @@ extern "C" int muse_batch_score_many(muse_batch *const *bs, int32_t R)
         one_pass = bs[r]->N == b0->N && (small_n || real_n || b0->N == b0->n || bs[r]->c1 != nullptr) && (!long_n || bs[r]->xcp != nullptr);
     if (!one_pass) {
         for (int r = 0; r < R; r++) {
-            int rc = muse_batch_score(bs[r]);
+            int rc = batch_score(bs[r], false); // (a many-references pass never builds or reads the spectrum cache)
             if (rc)
                 return rc;
         }

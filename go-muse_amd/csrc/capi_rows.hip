@@ -180,6 +180,7 @@ static int slot_take(muse_batch *tmpl, int64_t M, size_t elems, RowsSlot **out)
     s->g.M = M;
     s->g.cap = M;
     s->g.hstats_rows = 0; // (other rows than the slot's last call: no kept statistics)
+    s->g.transient = true; // (nor a spectrum cache)
     s->b.N = tmpl->N;
     s->b.n = tmpl->n;
     s->b.logn = tmpl->logn;

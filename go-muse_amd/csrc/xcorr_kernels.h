@@ -97,6 +97,19 @@ hipError_t launch_screen_pass_stk(const FusedParams &p, int num_cus, hipStream_t
 enum : unsigned { SCR_IN = 1u, SCR_OUT = 2u, SCR_POS = 4u, SCR_NEG = 8u, SCR_REFINE = 16u, SCR_NAN = 32u };
 hipError_t launch_fused_fold(const FusedParams &p, int num_cus, hipStream_t stream); // xcorr_r16_fold.hip (n == 4096, default)
 hipError_t launch_fused_multi(const FusedParams &p, int num_cus, hipStream_t stream); // xcorr_r16_fold.hip (R references)
+// xcorr_r16_cached.hip: a resident float64 group's spectrum cache at n = 4096.  One segment covers the pairs [pair0, pair0 + zpairs)
+// of the group: zc[(pair - pair0)][16][256] double2, zstat[(pair - pair0)][ZC_STAT] double.  Both launchers process the pairs
+// [pair0, pair0 + p.npairs) (p.M, p.mv, p.lag, p.ovf_list: the whole group's), ADD to *p.ovf_count and want *p.work_counter zero.
+constexpr int ZC_STAT = 16;                                       // doubles per pair: 8 sum-of-squares partials, 2 sums, 6 unused
+constexpr long long ZC_PAIR_BYTES = 4096 * 16 + ZC_STAT * 8;      // 64 KB + 128 B
+struct SpectrumCacheArgs {
+    double2 *zc;
+    double *zstat;
+    long long pair0;
+    long long zpairs;
+};
+hipError_t launch_cache_fill(const FusedParams &p, const SpectrumCacheArgs &c, int num_cus, hipStream_t stream); // from the rows; the first c.zpairs pairs into the cache
+hipError_t launch_cached(const FusedParams &p, const SpectrumCacheArgs &c, int num_cus, hipStream_t stream);     // from the cache
 hipError_t launch_fused_small(const FusedParams &p, int num_cus, hipStream_t stream); // xcorr_small.hip (n = 512, 1024, 2048: default)
 hipError_t launch_fused_stockham(const FusedParams &p, int num_cus, hipStream_t stream); // xcorr_stockham.hip (n = 512 .. 2048, 8192 .. 65536)
 hipError_t launch_fused_long(const FusedParams &p, int num_cus, hipStream_t stream); // xcorr_long.hip (n = 65536: default; 16384, 32768)

@@ -172,6 +172,22 @@ func SetScreening(enable bool, minRows int) error {
 	return hipError(C.muse_ctx_set_screening(e.ctx, v))
 }
 
+// SetSpectrumCache switches the spectrum cache of the default engine (include/muse_hip.h: muse_ctx_set_spectrum_cache; ON by
+// default): a float64 group of at least 65 536 series of length 2049 .. 4096 that is scored a second time keeps the forward
+// spectra of its rows in HBM (its footprint doubles, if that fits in half of the free memory) and every later Run reads them
+// instead of the rows: same Scores, about half the arithmetic.
+func SetSpectrumCache(on bool) error {
+	e, err := getEngine()
+	if err != nil {
+		return err
+	}
+	v := C.int32_t(0)
+	if on {
+		v = 1
+	}
+	return hipError(C.muse_ctx_set_spectrum_cache(e.ctx, v))
+}
+
 // appendSeries uploads series (all of length n) to a device group through the library's pinned staging windows
 // (muse_group_stage / muse_group_commit): every Series is copied ONCE, straight out of its Go slice into pinned C memory, by a
 // few goroutines in pieces of ~256 KB; a piece that completes the packed prefix of the window commits that prefix -- runs of

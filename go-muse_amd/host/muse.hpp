@@ -392,6 +392,8 @@ public:
     Engine(const Engine &) = delete;
     Engine &operator=(const Engine &) = delete;
     muse_ctx *handle() const { return ctx_; }
+    // muse_ctx_set_spectrum_cache: on (the default) a large n = 4096 group scored more than once keeps its forward spectra in HBM
+    void SetSpectrumCache(bool on) { check(muse_ctx_set_spectrum_cache(ctx_, on ? 1 : 0)); }
     static std::shared_ptr<Engine> Default()
     {
         static std::shared_ptr<Engine> e = std::make_shared<Engine>(0);

@@ -86,6 +86,14 @@ class Engine:
         """test hook (include/muse_hip_test.h): scales the error bound the filter-and-refine Run assumes"""
         B.check(B.load().muse_test_set_screen_bound_scale(self._h, float(scale)))
 
+    def set_spectrum_cache(self, on):
+        """muse_ctx_set_spectrum_cache: True (the default) = a large n = 4096 group scored more than once keeps its forward spectra in HBM"""
+        B.check(B.load().muse_ctx_set_spectrum_cache(self._h, 1 if on else 0))
+
+    def spectrum_cache_limits(self, min_rows=-1, budget_bytes=-1):
+        """test hook (include/muse_hip_test.h): smallest cached group and a byte budget (0 = always decline); negative = default"""
+        B.check(B.load().muse_test_spectrum_cache_limits(self._h, int(min_rows), int(budget_bytes)))
+
     def trim(self):
         """muse_ctx_trim: hands the context's cached device / pinned blocks back to the system"""
         B.check(B.load().muse_ctx_trim(self._h))
@@ -318,6 +326,15 @@ class DeviceGroup:
         B.check(B.load().muse_group_read(self._h, int(first), int(count), B.dptr(out)))
         return out
 
+    def spectrum_cache(self):
+        """muse_group_spectrum_cache: (rows the next pass reads from the cache, HBM bytes the cache holds)"""
+        r, b = ctypes.c_int64(0), ctypes.c_int64(0)
+        B.check(B.load().muse_group_spectrum_cache(self._h, ctypes.byref(r), ctypes.byref(b)))
+        return int(r.value), int(b.value)
+
+    def drop_spectrum_cache(self):
+        B.check(B.load().muse_group_drop_spectrum_cache(self._h))
+
     def close(self):
         self.alive = False
         if self._h:
@@ -385,6 +402,14 @@ class DeviceBatch:
         mv = np.zeros(M)
         B.check(B.load().muse_batch_read_scores(self._h, B.i32ptr(lag), B.dptr(mv)))
         return lag, mv
+
+    def redo_pairs(self):
+        """test hook: the pairs the last n = 4096 all-scores pass listed for the rescaling kernel (include/muse_hip_test.h)"""
+        cap = self.dgroup.M + 2
+        out = np.zeros(cap, dtype=np.int64)
+        cnt = ctypes.c_int64(0)
+        B.check(B.load().muse_test_batch_redo_pairs(self._h, B.i64ptr(out), cap, ctypes.byref(cnt)))
+        return out[:min(int(cnt.value), cap)].copy()
 
     def last_run_info(self):
         """(screened, refined_pairs) of the last run on this batch (muse_batch_last_run_info)"""

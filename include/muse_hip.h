@@ -106,6 +106,16 @@ int muse_ctx_device_pci_bus_id(muse_ctx *ctx, char *out, int32_t cap);
  * group, the reference's own order among exactly tied scores) -- so with the mirrors screening only ever applies to Runs
  * over more label groups than that (Run(nil) over a large Group). */
 int muse_ctx_set_screening(muse_ctx *ctx, int32_t enable);
+/* Spectrum cache of resident groups: mode 1 (the default) = automatic, 0 = off.  Of what the default
+ * kernel for FFT length 4096 computes per pair of series, the first half -- shift, sum of squares, forward transform --
+ * depends on the group's rows alone.  A float64-storage group of series of length 2049 .. 4096 with at least 65 536 rows
+ * that is scored a SECOND time (by any batch, against any reference) keeps that half in HBM: 64 KB + 128 B per pair of rows,
+ * i.e. the group's footprint doubles, taken only if it fits in half of the device memory that is free at that moment.
+ * Every later all-scores pass over the group reads the kept spectra instead of the rows: the same bytes, about half the
+ * arithmetic, bit-identical scores and lags.  Every pass still scores every series; nothing of a Run's result is cached.
+ * Rows appended later are added to the cache by the next pass; muse_group_fill_synthetic over existing rows drops it.
+ * Mode 0 neither builds nor reads a cache (one that exists stays until muse_group_drop_spectrum_cache or muse_group_free). */
+int muse_ctx_set_spectrum_cache(muse_ctx *ctx, int32_t mode);
 /* Which path the last muse_batch_run / muse_batch_run_shard on this batch took: *screened = 1 for filter-and-refine,
  * *refined_pairs = pairs of series it re-evaluated in fp64.  Any out pointer may be NULL. */
 int muse_batch_last_run_info(muse_batch *b, int32_t *screened, int64_t *refined_pairs);
@@ -193,6 +203,11 @@ int muse_group_shape(muse_group *g, int64_t *M, int32_t *N);
 /* D2H copy of rows [first, first+count) (dense, N doubles per row): lets a
  * checker feed byte-identical inputs to a CPU oracle. */
 int muse_group_read(muse_group *g, int64_t first, int64_t count, double *out);
+/* The group's spectrum cache (muse_ctx_set_spectrum_cache): *rows_cached = the rows [0, *rows_cached) the next pass reads
+ * from it (0: none), *bytes = the HBM it holds.  Any out pointer may be NULL.  _drop waits for the passes enqueued so far and
+ * gives the HBM back; under mode 1 a later second pass builds it again. */
+int muse_group_spectrum_cache(muse_group *g, int64_t *rows_cached, int64_t *bytes);
+int muse_group_drop_spectrum_cache(muse_group *g);
 int muse_group_free(muse_group *g);
 
 /* -------------------------------------------------------------- batch */

@@ -68,6 +68,20 @@ int muse_test_huge_batch_mb(muse_ctx *ctx, int32_t megabytes);
  * non-temporal stores (on = 1) or plain ones (0, the default): tools/resident_bench.py measures both. */
 int muse_test_gather_nontemporal(muse_ctx *ctx, int32_t on);
 
+/* Spectrum cache (muse_ctx_set_spectrum_cache): the smallest group that is cached (default 65 536 rows; negative = default) and
+ * a byte budget for a group's cache in place of half the free device memory (0 = always decline; negative = no override). */
+int muse_test_spectrum_cache_limits(muse_ctx *ctx, int64_t min_rows, int64_t budget_bytes);
+/* The cache's policy, a pure host function (no device needed): what the second pass over `rows` rows of length N decides with
+ * free_bytes of device memory free -- *decision = 0 no cache, 1 build one of *bytes for rows [0, *rows_cached), 2 declined for
+ * lack of memory.  min_rows / budget_bytes as in muse_test_spectrum_cache_limits. */
+int muse_test_spectrum_cache_policy(int64_t rows, int32_t N, int32_t f32_storage, int32_t mode, int64_t min_rows,
+                                    int64_t free_bytes, int64_t budget_bytes, int32_t *decision, int64_t *rows_cached,
+                                    int64_t *bytes);
+/* The pairs of series (row >> 1) the last all-scores pass of this batch at FFT length 4096 listed for the rescaling kernel (a NaN /
+ * Inf series -- once per such series -- or sigmas too far apart), in list order: *count of them, the first min(*count, cap) in
+ * pairs[].  Waits for the batch's stream. */
+int muse_test_batch_redo_pairs(muse_batch *b, int64_t *pairs, int64_t cap, int64_t *count);
+
 #ifdef __cplusplus
 }
 #endif
