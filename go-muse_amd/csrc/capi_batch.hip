@@ -606,6 +606,7 @@ int batch_score(muse_batch *b, bool allow_spectrum_cache)
     rc = ensure_scores(b);
     if (rc)
         return rc;
+    b->many_tiles = 0;
     if (b->windowed()) { // the best match inside +-MaxLag, directly (xcorr_window.hip): no transform, never screened
         b->scores_exact = true;
         return score_windowed(b);
@@ -756,7 +757,9 @@ extern "C" int muse_batch_kernel_name(muse_batch *b, char *name, int32_t cap)
     // (the names rocprofv3 prints for the instantiations: profiles/r*_counters.json is keyed by them)
     char k[96] = "xcorr_fused_generic";
     const char *padded = b->N < b->n ? "true" : "false", *f32 = b->g->f32 ? "true" : "false";
-    if (b->windowed()) {
+    if (b->many_tiles > 0) { // (the packed pass that filled mv / lag: it is an argument of a call, not a setting the next pass takes)
+        snprintf(k, sizeof(k), "xcorr_window_many_mfma<%d, %s>", b->many_tiles, window_wide(b->g->rows, b->g->stride) ? "true" : "false");
+    } else if (b->windowed()) {
         const int L = std::min(b->lag_window, b->n / 2);
         snprintf(k, sizeof(k), "xcorr_window_mfma<%d, %s>", (2 * L + 1 + 15) / 16,
                  window_wide(b->g->rows, b->g->stride) ? "true" : "false");

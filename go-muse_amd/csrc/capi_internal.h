@@ -330,6 +330,9 @@ struct muse_batch {
     int32_t win_L = -1;
     PoolBuf<double> win_e, win_pw;
     bool windowed() const { return lag_window >= 0; }
+    // > 0: the batch's scores come from a packed launch of muse_batch_score_many_windowed (capi_window_many.hip) of this many
+    // accumulator tiles (muse_batch_kernel_name names it); any other scoring pass of the batch clears it
+    int32_t many_tiles = 0;
 };
 
 int use_device(muse_ctx *ctx);

@@ -91,6 +91,8 @@ extern "C" int muse_batch_score_many(muse_batch *const *bs, int32_t R)
         }
         return MUSE_OK;
     }
+    for (int r = 0; r < R; r++)
+        bs[r]->many_tiles = 0;
     int rc = use_device(ctx);
     if (rc)
         return rc;

@@ -1,0 +1,206 @@
+// capi_window_many.hip -- many references inside a lag window in one pass (muse_batch_score_many_windowed / _run_many_windowed)
+// Part of the implementation of the C ABI declared in include/muse_hip.h (capi_internal.h: the handles and the helpers the
+// parts share).  Host-side orchestration only; there is no CPU compute fallback anywhere: without a gfx950 device every
+// compute entry point returns MUSE_ERR_NO_DEVICE.
+#include "capi_internal.h"
+
+using namespace muse;
+
+// test hook: the planner alone (xcorr_window_many.hip), no device
+extern "C" int muse_test_window_many_plan(int32_t R, int32_t L, int32_t *launches, int32_t *launch_of, int32_t *tiles_of,
+                                          int32_t *max_refs, int32_t *img_of, int32_t *kc_of)
+{
+    if (R < 1 || L < 0 || L > MUSE_LAG_WINDOW_MAX || !launches)
+        return fail(MUSE_ERR_INVALID, "window plan: R >= 1, 0 <= L <= %d", MUSE_LAG_WINDOW_MAX);
+    std::vector<int> of((size_t)R), tiles((size_t)R);
+    const int n = window_many_plan(R, L, of.data(), tiles.data());
+    *launches = n;
+    if (max_refs)
+        *max_refs = window_many_max_refs(L);
+    std::vector<int> refs((size_t)n, 0);
+    for (int r = 0; r < R; r++) {
+        refs[(size_t)of[(size_t)r]]++;
+        if (launch_of)
+            launch_of[r] = of[(size_t)r];
+    }
+    for (int l = 0; l < n; l++) {
+        const int kc = refs[(size_t)l] > 1 ? window_many_kc(L, refs[(size_t)l]) : WIN_KC; // (one reference: xcorr_window_mfma's chunk)
+        if (tiles_of)
+            tiles_of[l] = tiles[(size_t)l];
+        if (kc_of)
+            kc_of[l] = kc;
+        if (img_of)
+            img_of[l] = refs[(size_t)l] > 1 ? window_many_img(L, kc) : WIN_KC + WIN_E_TAIL;
+    }
+    return MUSE_OK;
+}
+
+// the list checks of muse_batch_score_many, then the window's: nothing is changed before the last of them has passed
+static int check_many_windowed(muse_batch *const *bs, int32_t R, int32_t max_lag)
+{
+    if (!bs || R < 1)
+        return fail(MUSE_ERR_INVALID, "bad batch list");
+    for (int r = 0; r < R; r++) {
+        if (!bs[r])
+            return fail(MUSE_ERR_INVALID, "NULL batch in list");
+        if (bs[r]->ctx != bs[0]->ctx || bs[r]->g != bs[0]->g)
+            return fail(MUSE_ERR_INVALID, "batches of one pass must share the context and the comparison group");
+        for (int q = 0; q < r; q++)
+            if (bs[q] == bs[r])
+                return fail(MUSE_ERR_INVALID, "the same batch appears twice in the list");
+    }
+    if (max_lag < 0)
+        return fail(MUSE_ERR_INVALID, "a windowed many-references pass needs a lag window >= 0");
+    if (max_lag > MUSE_LAG_WINDOW_MAX)
+        return fail(MUSE_ERR_UNSUPPORTED, "lag window %d > MUSE_LAG_WINDOW_MAX (%d): beyond it the direct product costs more than the transform",
+                    max_lag, MUSE_LAG_WINDOW_MAX);
+    if (bs[0]->g->f32)
+        return fail(MUSE_ERR_UNSUPPORTED, "the lag-window pass reads float64 groups only");
+    for (int r = 0; r < R; r++) {
+        if (bs[r]->n > GENERIC_MAX_N || !bs[r]->xs)
+            return fail(MUSE_ERR_UNSUPPORTED, "the lag-window pass is built for series of up to %d samples", GENERIC_MAX_N);
+        if (bs[r]->windowed() && bs[r]->lag_window != max_lag)
+            return fail(MUSE_ERR_INVALID, "batch %d has a lag window of %d of its own: it must be off or equal to the pass's (%d)", r,
+                        bs[r]->lag_window, max_lag);
+    }
+    return MUSE_OK;
+}
+
+extern "C" int muse_batch_score_many_windowed(muse_batch *const *bs, int32_t R, int32_t max_lag)
+{
+    int rc = check_many_windowed(bs, R, max_lag);
+    if (rc)
+        return rc;
+    muse_batch *b0 = bs[0];
+    muse_ctx *ctx = b0->ctx;
+    rc = use_device(ctx);
+    if (rc)
+        return rc;
+    rc = group_ready(b0->g);
+    if (rc)
+        return rc;
+    const int64_t M = b0->g->M;
+    if (M == 0)
+        return MUSE_OK;
+    const hipStream_t st = ctx->stream;
+    for (int r = 0; r < R; r++) {
+        rc = ensure_scores(bs[r]);
+        if (rc)
+            return rc;
+    }
+    // one window for the pass: batches of one group share N, and with it (muse_batch_create) the FFT length; a list that does
+    // not is scored reference by reference
+    bool same = true;
+    for (int r = 1; r < R; r++)
+        same = same && bs[r]->N == b0->N && bs[r]->n == b0->n;
+    const int L = std::min(max_lag, b0->n / 2);
+    std::vector<int> launch_of((size_t)R), tiles_of((size_t)R);
+    int launches = R;
+    if (same) {
+        launches = window_many_plan(R, L, launch_of.data(), tiles_of.data());
+    } else {
+        for (int r = 0; r < R; r++)
+            launch_of[(size_t)r] = r;
+    }
+    // each batch's tables, cached under win_L exactly as score_windowed caches them: the same buffers serve both forms
+    for (int r = 0; r < R; r++) {
+        muse_batch *b = bs[r];
+        const int Lb = std::min(max_lag, b->n / 2);
+        if (b->win_L != Lb) {
+            b->win_L = -1;
+            const long long e_len = window_e_len(b->N);
+            HIP_TRY(b->win_e.ensure(ctx, e_len, st));
+            HIP_TRY(b->win_pw.ensure(ctx, 2 * MUSE_LAG_WINDOW_MAX + 1, st));
+            HIP_TRY(launch_window_tables(b->xs, b->N, b->n, Lb, b->win_e.p, e_len, b->win_pw.p, st));
+            b->win_L = Lb;
+        }
+    }
+    bool packed = false;
+    for (int r = 0; r + 1 < R; r++)
+        packed = packed || launch_of[(size_t)r] == launch_of[(size_t)r + 1];
+    void **tab_dev = nullptr;
+    if (packed) { // columns of R pointers: e, pw, mv, lag (a launch takes its slice of each)
+        std::vector<void *> tab((size_t)R * 4);
+        for (int r = 0; r < R; r++) {
+            tab[(size_t)r] = bs[r]->win_e.p;
+            tab[(size_t)R + r] = bs[r]->win_pw.p;
+            tab[(size_t)2 * R + r] = bs[r]->mv.p;
+            tab[(size_t)3 * R + r] = bs[r]->lag.p;
+        }
+        rc = upload_many_tab(ctx, tab, false);
+        if (rc)
+            return rc;
+        tab_dev = ctx->many_tab.p;
+    }
+    LaunchTimer timer(ctx, false, st); // one bracket around all launches of the pass
+    HIP_TRY(timer.begin());
+    for (int r0 = 0; r0 < R;) {
+        int r1 = r0 + 1;
+        while (r1 < R && launch_of[(size_t)r1] == launch_of[(size_t)r0])
+            r1++;
+        muse_batch *b = bs[r0];
+        const int Lb = std::min(max_lag, b->n / 2);
+        if (r1 - r0 == 1) { // a reference that fills its launch alone: the single-reference kernel
+            WindowParams p{};
+            p.rows = b->g->rows;
+            p.M = M;
+            p.stride = b->g->stride;
+            p.N = b->N;
+            p.L = Lb;
+            p.Lneg = 2 * Lb == b->n ? Lb - 1 : Lb; // index n / 2 is lag +n/2 (xcorr.go:192-194): it is scanned once
+            p.e = b->win_e.p;
+            p.pw = b->win_pw.p;
+            p.invN = 1.0 / (double)b->N;
+            p.invNm1 = 1.0 / (double)(b->N - 1);
+            p.mv = b->mv.p;
+            p.lag = b->lag.p;
+            HIP_TRY(launch_window(p, st));
+        } else {
+            WindowManyParams p{};
+            p.rows = b->g->rows;
+            p.M = M;
+            p.stride = b->g->stride;
+            p.N = b->N;
+            p.L = Lb;
+            p.Lneg = 2 * Lb == b->n ? Lb - 1 : Lb;
+            p.R = r1 - r0;
+            p.e = (const double *const *)(tab_dev + r0);
+            p.pw = (const double *const *)(tab_dev + R + r0);
+            p.mv = (double *const *)(tab_dev + 2 * R + r0);
+            p.lag = (int *const *)(tab_dev + 3 * R + r0);
+            p.invN = 1.0 / (double)b->N;
+            p.invNm1 = 1.0 / (double)(b->N - 1);
+            HIP_TRY(launch_window_many(p, st));
+        }
+        for (int r = r0; r < r1; r++) {
+            bs[r]->scores_exact = true;
+            bs[r]->last_path = MUSE_RUN_PATH_FP64;
+            bs[r]->last_screened = false;
+            bs[r]->many_tiles = r1 - r0 > 1 ? tiles_of[(size_t)launch_of[(size_t)r0]] : 0;
+        }
+        r0 = r1;
+    }
+    HIP_TRY(timer.end());
+    return MUSE_OK;
+}
+
+extern "C" int muse_batch_run_many_windowed(muse_batch *const *bs, int32_t R, const int32_t *group_id, int32_t G,
+                                            int32_t max_lag, int32_t top_n, double threshold, int32_t sign_filter,
+                                            int32_t abs_scores, int64_t *out_series, int32_t *out_lag, double *out_score,
+                                            int32_t *out_count, double *out_mean_abs)
+{
+    int rc = muse_batch_score_many_windowed(bs, R, max_lag);
+    if (rc)
+        return rc;
+    const size_t cap = (size_t)std::max(top_n, 0);
+    for (int r = 0; r < R; r++) {
+        std::vector<muse_record> sel;
+        rc = run_select(bs[r], group_id, G, 0, max_lag, top_n, threshold, sign_filter, abs_scores, sel, true, false);
+        if (rc)
+            return rc;
+        emit(sel, out_series ? out_series + cap * r : nullptr, out_lag ? out_lag + cap * r : nullptr,
+             out_score ? out_score + cap * r : nullptr, out_count ? out_count + r : nullptr,
+             out_mean_abs ? out_mean_abs + r : nullptr);
+    }
+    return MUSE_OK;
+}

@@ -162,6 +162,31 @@ inline bool window_wide(const double *rows, long long stride) { return stride % 
 inline long long window_e_len(int N) { return (long long)((N + WIN_KC - 1) / WIN_KC) * WIN_KC + WIN_E_TAIL; }
 hipError_t launch_window_tables(const double *xs, int N, int n, int L, double *e, long long e_len, double *pw, hipStream_t stream);
 hipError_t launch_window(const WindowParams &p, hipStream_t stream);
+// ---- the same for many references in one pass (xcorr_window_many.hip): the references' windows packed into the tiles of one product
+constexpr int WINM_MAX_TILES = 8;       // accumulator tiles of a launch: 128 packed (reference, lag) rows
+constexpr int WINM_PACK_MAX_ROWS = 48;   // wider windows (four tiles per reference) are not packed: one launch per reference
+constexpr int WINM_IMG_DOUBLES = 4608;  // LDS budget of a launch's staged reference images (36 KB: four workgroups per CU)
+struct WindowManyParams {
+    const double *rows; // as WindowParams
+    long long M, stride;
+    int N;
+    int L, Lneg;
+    int R;                    // references of this launch: R (2 L + 1) <= 16 WINM_MAX_TILES
+    const double *const *e;   // [R] each reference's WindowParams::e   (the four tables: device memory)
+    const double *const *pw;  // [R] each reference's WindowParams::pw
+    double *const *mv;        // [R] out: each reference's M signed values
+    int *const *lag;          // [R] out: each reference's M lags
+    double invN, invNm1;
+    int kc, img, buf, parts;  // filled in by launch_window_many: chunk length, image stride, doubles of the image / tile region, scan parts per reference
+};
+// the planner (pure host functions): image stride for window L and chunk length kc; the most references one launch takes; the chunk
+// length of a launch of `refs` references; the cut of R references into consecutive launches (returns their number; launch_of[R],
+// tiles_of[launches <= R])
+int window_many_img(int L, int kc);
+int window_many_max_refs(int L);
+int window_many_kc(int L, int refs);
+int window_many_plan(int R, int L, int *launch_of, int *tiles_of);
+hipError_t launch_window_many(WindowManyParams p, hipStream_t stream);
 hipError_t launch_direct(const double *x, int lenx, const double *y, int leny, int n, int normalize_x,
                          int normalize_y, double x_scale, double cc_scale, double *cc, int *lag, double *mv,
                          int *status, hipStream_t stream);

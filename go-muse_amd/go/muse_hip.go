@@ -711,6 +711,19 @@ func (b *Batch) runSharded(es []*engine, gid []C.int32_t, G int, exact bool) err
 // references (muse_batch_run_many).  Not part of the reference's API; batches
 // that do not qualify are simply run one after the other.
 func RunMany(batches []*Batch, groupByLabels []string) error {
+	return runMany(batches, groupByLabels, false)
+}
+
+// RunManyWindowed is RunMany with the shared Results.MaxLag as a LAG WINDOW
+// (muse_batch_run_many_windowed): every batch receives what its own
+// RunWindowed gives, from one pass over the rows whose matrix product holds
+// the windows of all references.  Batches that do not qualify for RunMany are
+// RunWindowed one after the other.
+func RunManyWindowed(batches []*Batch, groupByLabels []string) error {
+	return runMany(batches, groupByLabels, true)
+}
+
+func runMany(batches []*Batch, groupByLabels []string, windowed bool) error {
 	if len(batches) == 0 {
 		return nil
 	}
@@ -723,11 +736,18 @@ func RunMany(batches []*Batch, groupByLabels []string) error {
 	}
 	if !same {
 		for _, b := range batches {
-			if err := b.Run(groupByLabels); err != nil {
+			run := b.Run
+			if windowed {
+				run = b.RunWindowed
+			}
+			if err := run(groupByLabels); err != nil {
 				return err
 			}
 		}
 		return nil
+	}
+	if windowed && (b0.Results.MaxLag < 0 || b0.Results.MaxLag > int(C.MUSE_LAG_WINDOW_MAX)) {
+		return fmt.Errorf("RunManyWindowed: MaxLag outside 0 .. %d", int(C.MUSE_LAG_WINDOW_MAX))
 	}
 	labelValuesSet := b0.Comparison.indexLabelValues(groupByLabels)
 	if len(labelValuesSet) == 0 {
@@ -771,6 +791,10 @@ func RunMany(batches []*Batch, groupByLabels []string) error {
 			}
 			b.batchGroup = dg
 		}
+		// (as Run does: a window an earlier RunWindowed left on the handle goes; the windowed pass takes its own as an argument)
+		if err := hipError(C.muse_batch_set_lag_window(b.batch, C.int32_t(b.window))); err != nil {
+			return err
+		}
 		hv[i] = b.batch
 	}
 	r := b0.Results
@@ -783,8 +807,14 @@ func RunMany(batches []*Batch, groupByLabels []string) error {
 	score := make([]C.double, R*top)
 	cnt := make([]C.int32_t, R)
 	mean := make([]C.double, R)
-	st := C.muse_batch_run_many(hs, C.int32_t(R), &gid[0], C.int32_t(len(labelValuesSet)), C.int32_t(r.MaxLag),
-		C.int32_t(r.TopN), C.double(r.Threshold), C.int32_t(r.SignFilter), 1, &idx[0], &lag[0], &score[0], &cnt[0], &mean[0])
+	var st C.int
+	if windowed {
+		st = C.muse_batch_run_many_windowed(hs, C.int32_t(R), &gid[0], C.int32_t(len(labelValuesSet)), C.int32_t(r.MaxLag),
+			C.int32_t(r.TopN), C.double(r.Threshold), C.int32_t(r.SignFilter), 1, &idx[0], &lag[0], &score[0], &cnt[0], &mean[0])
+	} else {
+		st = C.muse_batch_run_many(hs, C.int32_t(R), &gid[0], C.int32_t(len(labelValuesSet)), C.int32_t(r.MaxLag),
+			C.int32_t(r.TopN), C.double(r.Threshold), C.int32_t(r.SignFilter), 1, &idx[0], &lag[0], &score[0], &cnt[0], &mean[0])
+	}
 	if err := hipError(st); err != nil {
 		return err
 	}

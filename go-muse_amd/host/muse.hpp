@@ -1096,6 +1096,24 @@ public:
     // they all agree; otherwise the batches are run one by one).
     static void RunMany(const std::vector<std::shared_ptr<Batch>> &batches, const std::vector<std::string> &groupByLabels)
     {
+        run_many(batches, groupByLabels, false);
+    }
+
+    // RunMany with the shared Results.MaxLag as a LAG WINDOW (muse_batch_run_many_windowed): every batch receives what its own
+    // RunWindowed gives, from one pass over the rows whose matrix product holds the windows of all references.  Batches that do
+    // not qualify for RunMany are RunWindowed one by one.
+    static void RunManyWindowed(const std::vector<std::shared_ptr<Batch>> &batches, const std::vector<std::string> &groupByLabels)
+    {
+        run_many(batches, groupByLabels, true);
+    }
+
+    // Batch.Run feeds Results one Score per label group (the reference's feed) up to this many groups
+    // (settable: the tests also drive the pre-selecting path, which is otherwise only taken above this many groups)
+    static inline int64_t EXACT_FEED_MAX_GROUPS = 65536;
+
+private:
+    static void run_many(const std::vector<std::shared_ptr<Batch>> &batches, const std::vector<std::string> &groupByLabels, bool windowed)
+    {
         if (batches.empty())
             return;
         bool same = true;
@@ -1106,10 +1124,12 @@ public:
         }
         if (!same) {
             for (auto &b : batches)
-                b->Run(groupByLabels);
+                windowed ? b->RunWindowed(groupByLabels) : b->Run(groupByLabels);
             return;
         }
         Batch &b0 = *batches[0];
+        if (windowed && (b0.Results_->MaxLag < 0 || b0.Results_->MaxLag > MUSE_LAG_WINDOW_MAX))
+            throw Error(MUSE_ERR_UNSUPPORTED, "RunManyWindowed: MaxLag outside 0 .. MUSE_LAG_WINDOW_MAX");
         std::vector<int32_t> gid;
         auto lvs = b0.Comparison->indexLabelValues(groupByLabels, &gid);
         if (lvs.empty())
@@ -1124,9 +1144,14 @@ public:
         std::vector<int64_t> idx((size_t)R * cap);
         std::vector<int32_t> lag((size_t)R * cap), cnt((size_t)R);
         std::vector<double> score((size_t)R * cap), mean((size_t)R);
-        check(muse_batch_run_many(hs.data(), R, gid.data(), (int32_t)lvs.size(), b0.Results_->MaxLag, top,
-                                  b0.Results_->Threshold, (int32_t)b0.Results_->Filter, 1, idx.data(), lag.data(),
-                                  score.data(), cnt.data(), mean.data()));
+        if (windowed)
+            check(muse_batch_run_many_windowed(hs.data(), R, gid.data(), (int32_t)lvs.size(), b0.Results_->MaxLag, top,
+                                               b0.Results_->Threshold, (int32_t)b0.Results_->Filter, 1, idx.data(), lag.data(),
+                                               score.data(), cnt.data(), mean.data()));
+        else
+            check(muse_batch_run_many(hs.data(), R, gid.data(), (int32_t)lvs.size(), b0.Results_->MaxLag, top,
+                                      b0.Results_->Threshold, (int32_t)b0.Results_->Filter, 1, idx.data(), lag.data(),
+                                      score.data(), cnt.data(), mean.data()));
         for (int r = 0; r < R; r++) {
             const size_t o = (size_t)r * std::max(top, 0);
             std::vector<int> order(cnt[r]);
@@ -1138,11 +1163,6 @@ public:
         }
     }
 
-    // Batch.Run feeds Results one Score per label group (the reference's feed) up to this many groups
-    // (settable: the tests also drive the pre-selecting path, which is otherwise only taken above this many groups)
-    static inline int64_t EXACT_FEED_MAX_GROUPS = 65536;
-
-private:
     // The reference's own feed (muse_batch.go:124-128): ONE Score per label group, in group order, through Results.Update --
     // the heap's history, and with it the order Fetch returns exactly tied scores in and which of them survives at the TopN
     // boundary, is the reference's (for insertion-ordered groups), also when the Results already holds the Scores of earlier

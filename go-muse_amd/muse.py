@@ -583,6 +583,70 @@ def run_many(batches, group_id=None, G=0, max_lag=10, top_n=20, threshold=0.0, s
     return res
 
 
+def score_many_windowed(batches, max_lag):
+    """muse_batch_score_many_windowed: R references against one resident group, each series' best match INSIDE +-max_lag, the
+    references' windows packed into one matrix product per launch (asynchronous; results land in each DeviceBatch's own
+    buffers, bit-identical to set_lag_window(max_lag) + score() per batch; no batch's own window setting changes)."""
+    batches, arr = _batch_handles(batches)
+    B.check(B.load().muse_batch_score_many_windowed(arr, len(batches), int(max_lag)))
+
+
+def scores_many_windowed(batches, max_lag):
+    """score_many_windowed + copy back: list of (lag, mv), one per batch"""
+    batches, arr = _batch_handles(batches)
+    lib = B.load()
+    B.check(lib.muse_batch_score_many_windowed(arr, len(batches), int(max_lag)))
+    out = []
+    for b in batches:
+        M = b.dgroup.M
+        lag = np.zeros(M, dtype=np.int32)
+        mv = np.zeros(M)
+        if M:
+            B.check(lib.muse_batch_read_scores(b._h, B.i32ptr(lag), B.dptr(mv)))
+        out.append((lag, mv))
+    return out
+
+
+def run_many_windowed(batches, group_id=None, G=0, max_lag=10, top_n=20, threshold=0.0, sign_filter=0, abs_scores=True):
+    """muse_batch_run_many_windowed: Batch.RunWindowed for every reference (max_lag is the window and the Results.MaxLag);
+    returns a list of (series, lag, score, mean_abs), one per batch"""
+    batches, arr = _batch_handles(batches)
+    R = len(batches)
+    cap = max(int(top_n), 1)
+    o_s = np.zeros(R * cap, dtype=np.int64)
+    o_l = np.zeros(R * cap, dtype=np.int32)
+    o_v = np.zeros(R * cap)
+    cnt = np.zeros(R, dtype=np.int32)
+    mean = np.zeros(R)
+    gid = None
+    if group_id is not None:
+        gid = np.ascontiguousarray(group_id, dtype=np.int32)
+    B.check(B.load().muse_batch_run_many_windowed(
+        arr, R, B.i32ptr(gid) if gid is not None else None, int(G), int(max_lag), int(top_n),
+        float(threshold), int(sign_filter), 1 if abs_scores else 0,
+        B.i64ptr(o_s), B.i32ptr(o_l), B.dptr(o_v), B.i32ptr(cnt), B.dptr(mean)))
+    tn = max(int(top_n), 0)
+    res = []
+    for r in range(R):
+        c = int(cnt[r])
+        res.append((o_s[r * tn:r * tn + c].copy(), o_l[r * tn:r * tn + c].copy(), o_v[r * tn:r * tn + c].copy(),
+                    float(mean[r])))
+    return res
+
+
+def window_many_plan(R, L):
+    """muse_test_window_many_plan (no device): how score_many_windowed cuts R references with window L into launches --
+    dict(launches, launch_of[R], tiles_of[launches], max_refs, img_of[launches], kc_of[launches])"""
+    R = int(R)
+    n, mx = ctypes.c_int32(0), ctypes.c_int32(0)
+    of, tiles, img, kc = (np.zeros(max(R, 1), dtype=np.int32) for _ in range(4))
+    B.check(B.load().muse_test_window_many_plan(R, int(L), ctypes.byref(n), B.i32ptr(of), B.i32ptr(tiles), ctypes.byref(mx),
+                                                B.i32ptr(img), B.i32ptr(kc)))
+    k = int(n.value)
+    return dict(launches=k, launch_of=of[:R].copy(), tiles_of=tiles[:k].copy(), max_refs=int(mx.value), img_of=img[:k].copy(),
+                kc_of=kc[:k].copy())
+
+
 def device_count():
     n = ctypes.c_int32(0)
     B.check(B.load().muse_device_count(ctypes.byref(n)))
@@ -1200,6 +1264,37 @@ def RunMany(batches, groupByLabels):
     gid = comp._group_ids()
     res = run_many([b._batch() for b in batches], gid, len(labelValuesSet), r0.MaxLag, r0.TopN, r0.Threshold,
                    r0.SignFilter, abs_scores=True)
+    for b, (idx, lag, score, _) in zip(batches, res):
+        order = np.argsort(gid[idx], kind="stable")
+        for k in order:
+            b.Results.Update(Score(series[int(idx[k])].Labels(), int(lag[k]), float(score[k])))
+    return None
+
+
+def RunManyWindowed(batches, groupByLabels):
+    """RunMany with the shared Results.MaxLag as a LAG WINDOW (muse_batch_run_many_windowed): every batch receives what its own
+    RunWindowed(groupByLabels) gives, from one pass over the rows whose matrix product holds the windows of all references.
+    Batches that do not qualify for RunMany are RunWindowed one after the other."""
+    batches = list(batches)
+    if not batches:
+        return None
+    b0 = batches[0]
+    r0 = b0.Results
+    same = all(b.Comparison is b0.Comparison and b._engine is b0._engine and
+               (b.Results.MaxLag, b.Results.TopN, b.Results.Threshold, b.Results.SignFilter) ==
+               (r0.MaxLag, r0.TopN, r0.Threshold, r0.SignFilter) for b in batches)
+    if not same:
+        for b in batches:
+            b.RunWindowed(groupByLabels)
+        return None
+    comp = b0.Comparison
+    labelValuesSet = comp.indexLabelValues(groupByLabels)
+    if not labelValuesSet:
+        return None
+    series = comp._series_list()
+    gid = comp._group_ids()
+    res = run_many_windowed([b._batch() for b in batches], gid, len(labelValuesSet), r0.MaxLag, r0.TopN, r0.Threshold,
+                            r0.SignFilter, abs_scores=True)
     for b, (idx, lag, score, _) in zip(batches, res):
         order = np.argsort(gid[idx], kind="stable")
         for k in order:

@@ -280,7 +280,7 @@ int muse_batch_score(muse_batch *b);
  *   0 <= max_lag <= MUSE_LAG_WINDOW_MAX : on
  * MUSE_ERR_UNSUPPORTED, the batch unchanged: max_lag > MUSE_LAG_WINDOW_MAX (beyond a few dozen lags the direct product
  * costs more than the transform); a float32-storage group; series longer than 65536 samples.  A batch with a window is
- * refused (MUSE_ERR_UNSUPPORTED) by muse_batch_score_many / _run_many and as the template of muse_batch_run_rows /
+ * refused (MUSE_ERR_UNSUPPORTED) by muse_batch_score_many / _run_many (muse_batch_score_many_windowed is their windowed form) and as the template of muse_batch_run_rows /
  * _run_row_ptrs / _run_group_rows.  muse_batch_lag_window reads the setting back (-1 = off). */
 #define MUSE_LAG_WINDOW_MAX 63
 int muse_batch_set_lag_window(muse_batch *b, int32_t max_lag);
@@ -374,6 +374,27 @@ int muse_batch_run_many(muse_batch *const *batches, int32_t R,
                         int32_t abs_scores, int64_t *out_series,
                         int32_t *out_lag, double *out_score,
                         int32_t *out_count, double *out_mean_abs);
+/* Many references INSIDE A LAG WINDOW in one pass over the rows: per batch and series the best match inside +-L,
+ * L = min(max_lag, n/2), exactly as defined at muse_batch_set_lag_window -- but the window is an argument of the call, applied
+ * to this pass only: no batch's own lag_window setting is changed, and every later pass of a batch is what it was before.  The
+ * windows of the references are packed, reference after reference, into the A rows of one fp64 matrix product
+ * (xcorr_window_many.hip: up to 128 (reference, lag) rows and a fixed budget of staged reference images per launch), so that
+ * narrow windows share the accumulator tiles a single reference leaves empty and the rows are read once per launch; references
+ * that do not fit one launch go to consecutive launches, and from 2 max_lag + 1 > 48 on (a window that fills four tiles by itself
+ * is bound by the matrix pipe: packing two measured no faster) every reference has a launch of its own, the single-reference kernel's.  For every batch, mv and lag are BIT-IDENTICAL to muse_batch_set_lag_window(b, max_lag) +
+ * muse_batch_score(b) on that batch alone, so a caller may switch between the two forms freely.  The pass is never screened
+ * (muse_batch_last_run_path: MUSE_RUN_PATH_FP64) and never touches the spectrum cache.
+ *   The list is checked as muse_batch_score_many checks it (one context, one group, no duplicate, no NULL: MUSE_ERR_INVALID);
+ *   max_lag < 0, or a batch whose own window is on and differs from max_lag: MUSE_ERR_INVALID;
+ *   max_lag > MUSE_LAG_WINDOW_MAX, a float32-storage group, series longer than 65536 samples: MUSE_ERR_UNSUPPORTED.
+ * Every refusal leaves the handles as they were.  (muse_batch_score_many / _run_many go on refusing a batch with a window.) */
+int muse_batch_score_many_windowed(muse_batch *const *batches, int32_t R, int32_t max_lag);
+/* muse_batch_score_many_windowed followed by Batch.Run's selection for every batch, outputs as muse_batch_run_many;
+ * max_lag is both the window and the Results.MaxLag of passed() (which every windowed score passes). */
+int muse_batch_run_many_windowed(muse_batch *const *batches, int32_t R, const int32_t *group_id, int32_t G,
+                                 int32_t max_lag, int32_t top_n, double threshold, int32_t sign_filter,
+                                 int32_t abs_scores, int64_t *out_series, int32_t *out_lag, double *out_score,
+                                 int32_t *out_count, double *out_mean_abs);
 int muse_batch_free(muse_batch *b);
 
 /* ------------------------------------------- single-pair entry points */

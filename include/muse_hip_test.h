@@ -81,6 +81,14 @@ int muse_test_spectrum_cache_policy(int64_t rows, int32_t N, int32_t f32_storage
  * Inf series -- once per such series -- or sigmas too far apart), in list order: *count of them, the first min(*count, cap) in
  * pairs[].  Waits for the batch's stream. */
 int muse_test_batch_redo_pairs(muse_batch *b, int64_t *pairs, int64_t cap, int64_t *count);
+/* The planner of muse_batch_score_many_windowed, a pure host function (no device needed): R >= 1 references with window
+ * 0 <= L <= MUSE_LAG_WINDOW_MAX are cut into *launches consecutive launches; launch_of[r] (R entries) = the launch of reference r,
+ * tiles_of[l] (room for R entries) = the accumulator tiles of 16 packed rows of launch l.  *max_refs = the most references one
+ * launch takes at this L (128 packed rows and the budget of staged images); img_of[l] / kc_of[l] (room for R entries each) = the
+ * distance in doubles between the staged images of launch l and its chunk length in samples.  A launch of one reference is the
+ * single-reference kernel's (xcorr_window_mfma).  Any out pointer but launches may be NULL. */
+int muse_test_window_many_plan(int32_t R, int32_t L, int32_t *launches, int32_t *launch_of, int32_t *tiles_of, int32_t *max_refs,
+                               int32_t *img_of, int32_t *kc_of);
 
 #ifdef __cplusplus
 }
