@@ -76,6 +76,12 @@ SIGNATURES = {
     "muse_batch_spectrum": (ctypes.c_int, [_vp, _dp]),
     "muse_batch_score": (ctypes.c_int, [_vp]),
     "muse_batch_scores": (ctypes.c_int, [_vp, _i32p, _dp]),
+    "muse_batch_run_rows_windowed": (ctypes.c_int, [_vp, _dp, _i64, _i64, _i32, _i32, _recp, ctypes.POINTER(ctypes.c_uint8)]),
+    "muse_batch_run_row_ptrs_windowed": (ctypes.c_int, [_vp, ctypes.POINTER(_dp), _i64, _i32, _i32, _recp, ctypes.POINTER(ctypes.c_uint8)]),
+    "muse_batch_run_group_rows_windowed": (ctypes.c_int, [_vp, _vp, _i64p, _i64, _i32, _i32, _recp, ctypes.POINTER(ctypes.c_uint8)]),
+    "muse_test_window_rows_plan": (ctypes.c_int, [_i64, _i32, _i32, _i32p, _i32p]),
+    "muse_test_window_rows_slices": (ctypes.c_int, [_vp, _i32]),
+    "muse_test_run_rows_windowed_scores": (ctypes.c_int, [_vp, _dp, _i64, _i64, _i32, _i32p, _dp]),
     "muse_batch_set_lag_window": (ctypes.c_int, [_vp, _i32]),
     "muse_batch_lag_window": (ctypes.c_int, [_vp, _i32p]),
     "muse_batch_run": (ctypes.c_int, [_vp, _i32p, _i32, _i32, _i32, _f64, _i32, _i32,

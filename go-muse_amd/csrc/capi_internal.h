@@ -163,6 +163,7 @@ struct muse_ctx {
     std::atomic<int> zc_mode{1};
     std::atomic<int64_t> zc_min_rows{ZC_MIN_ROWS};
     std::atomic<int64_t> zc_budget{-1};
+    std::atomic<int> win_rows_slices{0}; // test hook (muse_test_window_rows_slices): 0 = window_rows_plan; S >= 1 forces the slice count of the windowed Muse.Run
     std::atomic<bool> gather_nt{false}; // measurement hook (muse_test_gather_nontemporal): the row gather's stores bypass the caches
     // Handles may be released in any order (Go finalizers, Python GC): the
     // context lives until it is destroyed AND its last group/batch is freed.
@@ -238,8 +239,12 @@ struct muse_group {
 
 // The reference spectrum and the tables derived from it: shared (reference-counted) by the batches
 // created with muse_batch_create_like -- Muse.Run builds one small group per call against ONE reference.
+inline std::atomic<uint64_t> g_spectrum_serial{0}; // one per library: muse_spectrum::serial
 struct muse_spectrum {
     std::atomic<int> refs{1};
+    // never 0 and never handed out twice: what a cache of tables derived from the spectrum is keyed by (a freed spectrum's address
+    // may come back with the next one; its serial does not) -- the window tables of a muse_batch_run_rows_windowed slot (capi_rows.hip)
+    const uint64_t serial = g_spectrum_serial.fetch_add(1, std::memory_order_relaxed) + 1;
     double2 *X = nullptr, *xc = nullptr, *xcp = nullptr;
     double2 *xcw = nullptr; // n == 32768: FusedParams::xcw
     float2 *xcf = nullptr;

@@ -16,6 +16,14 @@
 // since every slot owns a stream the callers' kernels -- a few dozen workgroups each -- run beside each other instead of
 // queueing on one stream (round 5: sixteen callers gained 1.85 x over one; profiles/r06_cold_path.txt for now).  FFT lengths
 // whose kernels work in the context's shared scratch buffer (n >= 8192) stay on the context's stream.
+//
+// The WINDOWED forms (muse_batch_run_rows_windowed / _run_row_ptrs_windowed / _run_group_rows_windowed) are the same calls with the
+// per-row (lag, mv) of the lag window (muse_batch_set_lag_window) in place of the transform kernel's: the window is an argument of
+// the call, no batch's own setting is touched.  The slot keeps its own window tables (the e image and pw of launch_window_tables),
+// keyed by (the template spectrum's serial number, L) and rebuilt on the slot's stream when the key differs -- any number of host
+// threads share one template, so nothing is cached on it.  The window kernels need none of the context's shared scratch: every FFT
+// length runs on the slot's stream.  Few rows of long series take the split-K kernels (xcorr_window_split.hip) when
+// window_rows_plan says so; otherwise launch_window, the kernel of muse_batch_set_lag_window, untouched.
 #include "capi_internal.h"
 
 using namespace muse;
@@ -39,6 +47,17 @@ struct RowsSlot {
     SingleGroupOut *out = nullptr; // pinned: the winner record, written by the device
     hipEvent_t done = nullptr;
     hipStream_t stream = nullptr;  // the slot's own stream
+    // the windowed forms: the tables of launch_window_tables for (win_serial, win_L) (0: none), and the slabs of the split-K kernels
+    PoolBuf<double> win_e, win_pw, win_slabs;
+    uint64_t win_serial = 0;
+    int32_t win_L = -1;
+};
+
+// what a windowed call adds to slot_finish: the window, and (the test hook) where the slot's per-row results go before it is returned
+struct WindowCall {
+    int32_t max_lag;
+    int32_t *lag_out;
+    double *mv_out;
 };
 
 static void slot_destroy(RowsSlot *s)
@@ -58,6 +77,9 @@ static void slot_destroy(RowsSlot *s)
     s->g.hstats.release(ctx);
     s->b.mv.release(ctx);
     s->b.lag.release(ctx);
+    s->win_e.release(ctx);
+    s->win_pw.release(ctx);
+    s->win_slabs.release(ctx);
     s->b.ovf_list.release(ctx);
     dfree(ctx, s->b.ovf_count);
     hfree(ctx, s->b.handoff_host);
@@ -166,7 +188,8 @@ static void slot_return(muse_ctx *ctx, RowsSlot *s)
 }
 
 // a slot shaped for M rows of the template's length against the template's reference (rows: s->g.rows, set by the caller)
-static int slot_take(muse_batch *tmpl, int64_t M, size_t elems, RowsSlot **out)
+// (windowed: the window kernels need none of the context's shared scratch -- every length on the slot's stream)
+static int slot_take(muse_batch *tmpl, int64_t M, size_t elems, RowsSlot **out, bool windowed = false)
 {
     muse_ctx *ctx = tmpl->ctx;
     const int32_t N = tmpl->N;
@@ -188,7 +211,7 @@ static int slot_take(muse_batch *tmpl, int64_t M, size_t elems, RowsSlot **out)
     adopt_spectrum(&s->b);
     s->b.handoff_M = -1; // (no kernel-selection memory across unrelated groups)
     // kernels that work in the context's shared scratch buffer are serialised on the context's stream
-    s->b.own_stream = tmpl->n >= GENERIC_LDS_MAX_N ? nullptr : s->stream;
+    s->b.own_stream = tmpl->n >= GENERIC_LDS_MAX_N && !windowed ? nullptr : s->stream;
     const int64_t cap = std::max<int64_t>(M, 4096); // (grown in steps that small groups never reach twice)
     hipError_t ea = s->b.mv.ensure(ctx, cap, s->stream);
     if (ea == hipSuccess)
@@ -201,15 +224,60 @@ static int slot_take(muse_batch *tmpl, int64_t M, size_t elems, RowsSlot **out)
     return MUSE_OK;
 }
 
+// the windowed per-row pass of a slot (rows in place or their copy enqueued, mv / lag allocated): the slot's tables for
+// (spectrum, L), then launch_window or -- few rows of long series -- the split-K kernels, all on the slot's stream
+static int slot_score_windowed(muse_ctx *ctx, RowsSlot *s, int32_t max_lag)
+{
+    muse_batch *b = &s->b;
+    const hipStream_t st = b->stream();
+    const int L = std::min(max_lag, b->n / 2);
+    if (s->win_serial != b->sp->serial || s->win_L != L) {
+        s->win_serial = 0;
+        const long long e_len = window_e_len(b->N);
+        HIP_TRY(s->win_e.ensure(ctx, e_len, st));
+        HIP_TRY(s->win_pw.ensure(ctx, 2 * MUSE_LAG_WINDOW_MAX + 1, st));
+        HIP_TRY(launch_window_tables(b->xs, b->N, b->n, L, s->win_e.p, e_len, s->win_pw.p, st));
+        s->win_serial = b->sp->serial;
+        s->win_L = L;
+    }
+    WindowParams p{};
+    p.rows = s->g.rows;
+    p.M = s->g.M;
+    p.stride = s->g.stride;
+    p.N = b->N;
+    p.L = L;
+    p.Lneg = 2 * L == b->n ? L - 1 : L; // index n / 2 is lag +n/2 (xcorr.go:192-194): it is scanned once
+    p.e = s->win_e.p;
+    p.pw = s->win_pw.p;
+    p.invN = 1.0 / (double)b->N;
+    p.invNm1 = 1.0 / (double)(b->N - 1);
+    p.mv = b->mv.p;
+    p.lag = b->lag.p;
+    const int chunks = (b->N + WIN_KC - 1) / WIN_KC;
+    const int forced = ctx->win_rows_slices.load(std::memory_order_relaxed);
+    const int S = forced >= 1 ? std::min(forced, chunks) : window_rows_plan(p.M, p.N, ctx->num_cus, nullptr);
+    if (S > 1)
+        HIP_TRY(s->win_slabs.ensure(ctx, (p.M + 15) / 16 * S * window_split_slab_doubles(L), st));
+    LaunchTimer timer(ctx, false, st);
+    HIP_TRY(timer.begin());
+    if (S > 1)
+        HIP_TRY(launch_window_split(p, S, s->win_slabs.p, st));
+    else
+        HIP_TRY(launch_window(p, st));
+    HIP_TRY(timer.end());
+    return MUSE_OK;
+}
+
 // the slot's rows in place (or their copy enqueued: e its status): the fused kernel, the reduction into the pinned record, the
 // wait for it; the slot goes back to the context
 static int slot_finish(muse_ctx *ctx, RowsSlot *s, int64_t M, int32_t abs_scores, hipError_t e, muse_record *out_winner,
-                       uint8_t *out_state)
+                       uint8_t *out_state, const WindowCall *wc = nullptr)
 {
     const hipStream_t st = s->b.stream();
     int rc = MUSE_OK;
     if (e == hipSuccess) {
-        rc = muse_batch_score(&s->b); // the fused kernel automatic selection takes for this length (and its redo launch, if any)
+        // the fused kernel automatic selection takes for this length (and its redo launch, if any), or the window kernels
+        rc = wc ? slot_score_windowed(ctx, s, wc->max_lag) : muse_batch_score(&s->b);
         if (!rc)
             e = launch_single_group(s->b.mv.p, s->b.lag.p, M, abs_scores ? 1 : 0, 0, s->out, st);
     }
@@ -244,6 +312,20 @@ static int slot_finish(muse_ctx *ctx, RowsSlot *s, int64_t M, int32_t abs_scores
     }
     const unsigned long long stt = *(volatile unsigned long long *)&s->out->state;
     *out_winner = s->out->rec;
+    // TEST HOOK ONLY (muse_test_run_rows_windowed_scores; the product's calls leave lag_out / mv_out NULL and skip this): the slot's
+    // per-row pairs, copied back here because the slot is about to be returned (the record arrived: the scores are behind it on the
+    // same stream)
+    if (wc && wc->lag_out && wc->mv_out) {
+        e = hipMemcpyAsync(wc->lag_out, s->b.lag.p, (size_t)M * sizeof(int), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(wc->mv_out, s->b.mv.p, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess)
+            e = hipStreamSynchronize(st);
+        if (e != hipSuccess) {
+            slot_destroy(s);
+            return fail(MUSE_ERR_HIP, "muse_test_run_rows_windowed_scores: %s", hipGetErrorString(e));
+        }
+    }
     slot_return(ctx, s);
     if (stt > 2ull)
         return fail(MUSE_ERR_HIP, "muse_batch_run_rows: the result record did not arrive");
@@ -251,12 +333,45 @@ static int slot_finish(muse_ctx *ctx, RowsSlot *s, int64_t M, int32_t abs_scores
     return MUSE_OK;
 }
 
+// the refusals of the windowed forms (nothing is changed before the last of them has passed)
+static int check_window_call(const muse_batch *tmpl, int32_t max_lag)
+{
+    if (max_lag < 0)
+        return fail(MUSE_ERR_INVALID, "a windowed Muse.Run needs a lag window >= 0");
+    if (tmpl->windowed() && tmpl->lag_window != max_lag)
+        return fail(MUSE_ERR_INVALID, "the template has a lag window of %d of its own: it must be off or equal to the call's (%d)",
+                    tmpl->lag_window, max_lag);
+    if (max_lag > MUSE_LAG_WINDOW_MAX)
+        return fail(MUSE_ERR_UNSUPPORTED, "lag window %d > MUSE_LAG_WINDOW_MAX (%d): beyond it the direct product costs more than the transform",
+                    max_lag, MUSE_LAG_WINDOW_MAX);
+    if (tmpl->n > GENERIC_MAX_N || !tmpl->xs)
+        return fail(MUSE_ERR_UNSUPPORTED, "the lag-window pass is built for series of up to %d samples", GENERIC_MAX_N);
+    return MUSE_OK;
+}
+
+// the private batch of a general path: like tmpl over g, with the call's window (if any); Run with G = 1; the test hook's scores
+static int run_general_batch(muse_batch *tmpl, muse_group *g, int64_t M, int32_t abs_scores, muse_record *out_winner,
+                             uint8_t *out_state, const WindowCall *wc)
+{
+    muse_batch *b = nullptr;
+    int rc = muse_batch_create_like(tmpl, g, &b);
+    if (!rc && wc)
+        rc = muse_batch_set_lag_window(b, wc->max_lag);
+    if (!rc) {
+        std::vector<int32_t> gid((size_t)M, 0);
+        rc = muse_batch_run_groups(b, gid.data(), 1, 0, abs_scores, out_winner, out_state);
+    }
+    if (!rc && wc && wc->lag_out && wc->mv_out)
+        rc = muse_batch_read_scores(b, wc->lag_out, wc->mv_out);
+    muse_batch_free(b);
+    return rc;
+}
+
 // the general path for groups too large for a slot: what the host mirrors did per Muse.Run before this entry point existed
 static int run_rows_general(muse_batch *tmpl, const double *rows, const double *const *row_ptrs, int64_t M, int64_t row_stride,
-                            int32_t abs_scores, muse_record *out_winner, uint8_t *out_state)
+                            int32_t abs_scores, muse_record *out_winner, uint8_t *out_state, const WindowCall *wc)
 {
     muse_group *g = nullptr;
-    muse_batch *b = nullptr;
     int rc;
     if (rows) {
         rc = muse_group_upload(tmpl->ctx, rows, M, tmpl->N, row_stride, &g);
@@ -269,26 +384,27 @@ static int run_rows_general(muse_batch *tmpl, const double *rows, const double *
         muse_group_free(g);
         return rc;
     }
-    rc = muse_batch_create_like(tmpl, g, &b);
-    if (!rc) {
-        std::vector<int32_t> gid((size_t)M, 0);
-        rc = muse_batch_run_groups(b, gid.data(), 1, 0, abs_scores, out_winner, out_state);
-    }
-    muse_batch_free(b);
+    rc = run_general_batch(tmpl, g, M, abs_scores, out_winner, out_state, wc);
     muse_group_free(g);
     return rc;
 }
 
 // rows: M x N with stride row_stride, or (rows == NULL) row_ptrs[r] -> the N samples of row r
+// wc: the windowed forms (NULL: the transform kernels)
 static int run_rows(muse_batch *tmpl, const double *rows, const double *const *row_ptrs, int64_t M, int64_t row_stride,
-                    int32_t abs_scores, muse_record *out_winner, uint8_t *out_state)
+                    int32_t abs_scores, muse_record *out_winner, uint8_t *out_state, const WindowCall *wc = nullptr)
 {
     if (!tmpl || !out_winner || !out_state || M < 0 || (M > 0 && !rows && !row_ptrs))
         return fail(MUSE_ERR_INVALID, "bad arguments");
     *out_winner = muse_record{-1, 0.0, 0, 0};
     *out_state = 0;
-    if (tmpl->windowed())
+    if (wc) {
+        const int wrc = check_window_call(tmpl, wc->max_lag);
+        if (wrc)
+            return wrc;
+    } else if (tmpl->windowed()) {
         return fail(MUSE_ERR_UNSUPPORTED, "a batch with a lag window cannot be the template of a Muse.Run");
+    }
     if (M == 0) // muse.go:47-50: nothing to compare
         return MUSE_OK;
     const int32_t N = tmpl->N;
@@ -305,9 +421,9 @@ static int run_rows(muse_batch *tmpl, const double *rows, const double *const *r
         return rc;
     const size_t elems = (size_t)M * (size_t)N;
     if (elems > ROWS_SLOT_MAX_ELEMS)
-        return run_rows_general(tmpl, rows, row_ptrs, M, row_stride, abs_scores, out_winner, out_state);
+        return run_rows_general(tmpl, rows, row_ptrs, M, row_stride, abs_scores, out_winner, out_state, wc);
     RowsSlot *s = nullptr;
-    rc = slot_take(tmpl, M, elems, &s);
+    rc = slot_take(tmpl, M, elems, &s, wc != nullptr);
     if (rc)
         return rc;
     const hipStream_t st = s->b.stream();
@@ -327,7 +443,7 @@ static int run_rows(muse_batch *tmpl, const double *rows, const double *const *r
         s->g.rows = s->dev + ROWS_GUARD;
         e = hipMemcpyAsync(s->g.rows, s->host, elems * sizeof(double), hipMemcpyHostToDevice, st);
     }
-    return slot_finish(ctx, s, M, abs_scores, e, out_winner, out_state);
+    return slot_finish(ctx, s, M, abs_scores, e, out_winner, out_state, wc);
 }
 
 extern "C" int muse_batch_run_rows(muse_batch *tmpl, const double *rows, int64_t M, int64_t row_stride, int32_t abs_scores,
@@ -351,33 +467,32 @@ extern "C" int muse_batch_run_row_ptrs(muse_batch *tmpl, const double *const *ro
 // ---- Muse.Run over rows that are already resident in a group: no host copy and no PCIe transfer of samples
 // the general path for groups too large for a slot: the rows gathered into a group of their own, then the existing Run
 static int run_group_rows_general(muse_batch *tmpl, muse_group *src, const int64_t *rows, int64_t M, int32_t abs_scores,
-                                  muse_record *out_winner, uint8_t *out_state)
+                                  muse_record *out_winner, uint8_t *out_state, const WindowCall *wc)
 {
     muse_group *g = nullptr;
-    muse_batch *b = nullptr;
     int rc = muse_group_create(tmpl->ctx, M, tmpl->N, &g);
     if (!rc)
         rc = group_gather(g, src, rows, M); // (a float32 src is widened into the float64 group)
     if (!rc)
-        rc = muse_batch_create_like(tmpl, g, &b);
-    if (!rc) {
-        std::vector<int32_t> gid((size_t)M, 0);
-        rc = muse_batch_run_groups(b, gid.data(), 1, 0, abs_scores, out_winner, out_state);
-    }
-    muse_batch_free(b);
+        rc = run_general_batch(tmpl, g, M, abs_scores, out_winner, out_state, wc);
     muse_group_free(g);
     return rc;
 }
 
-extern "C" int muse_batch_run_group_rows(muse_batch *tmpl, muse_group *src, const int64_t *rows, int64_t M, int32_t abs_scores,
-                                         muse_record *out_winner, uint8_t *out_state)
+static int run_group_rows(muse_batch *tmpl, muse_group *src, const int64_t *rows, int64_t M, int32_t abs_scores,
+                          muse_record *out_winner, uint8_t *out_state, const WindowCall *wc)
 {
     if (!tmpl || !src || !out_winner || !out_state || M < 0 || (M > 0 && !rows))
         return fail(MUSE_ERR_INVALID, "bad arguments");
     *out_winner = muse_record{-1, 0.0, 0, 0};
     *out_state = 0;
-    if (tmpl->windowed())
+    if (wc) {
+        const int wrc = check_window_call(tmpl, wc->max_lag);
+        if (wrc)
+            return wrc;
+    } else if (tmpl->windowed()) {
         return fail(MUSE_ERR_UNSUPPORTED, "a batch with a lag window cannot be the template of a Muse.Run");
+    }
     if (src->ctx != tmpl->ctx)
         return fail(MUSE_ERR_INVALID, "the group and the template belong to different contexts");
     if (src->win_rows)
@@ -394,7 +509,7 @@ extern "C" int muse_batch_run_group_rows(muse_batch *tmpl, muse_group *src, cons
         return rc;
     const size_t elems = (size_t)M * (size_t)N;
     if (elems > ROWS_SLOT_MAX_ELEMS)
-        return run_group_rows_general(tmpl, src, rows, M, abs_scores, out_winner, out_state);
+        return run_group_rows_general(tmpl, src, rows, M, abs_scores, out_winner, out_state, wc);
     // one ascending run of a float64 group is scored where it lies (a padded length reads up to n - N samples in front of the
     // first row and masks them: the row in front of it, or the group's guard in front of row 0)
     bool contiguous = !src->f32;
@@ -402,7 +517,7 @@ extern "C" int muse_batch_run_group_rows(muse_batch *tmpl, muse_group *src, cons
         contiguous = rows[i] == rows[0] + i;
     // the index list rides at the end of the slot's device buffer (behind the M x N gathered rows)
     RowsSlot *s = nullptr;
-    rc = slot_take(tmpl, M, contiguous ? elems : elems + (size_t)M, &s);
+    rc = slot_take(tmpl, M, contiguous ? elems : elems + (size_t)M, &s, wc != nullptr);
     if (rc)
         return rc;
     const hipStream_t st = s->b.stream();
@@ -432,7 +547,70 @@ extern "C" int muse_batch_run_group_rows(muse_batch *tmpl, muse_group *src, cons
         slot_return(ctx, s);
         return rc;
     }
-    return slot_finish(ctx, s, M, abs_scores, e, out_winner, out_state);
+    return slot_finish(ctx, s, M, abs_scores, e, out_winner, out_state, wc);
+}
+
+extern "C" int muse_batch_run_group_rows(muse_batch *tmpl, muse_group *src, const int64_t *rows, int64_t M, int32_t abs_scores,
+                                         muse_record *out_winner, uint8_t *out_state)
+{
+    return run_group_rows(tmpl, src, rows, M, abs_scores, out_winner, out_state, nullptr);
+}
+
+// ---- the windowed forms: the per-row (lag, mv) is the lag window's (muse_batch_set_lag_window), everything behind it unchanged
+extern "C" int muse_batch_run_rows_windowed(muse_batch *tmpl, const double *rows, int64_t M, int64_t row_stride, int32_t max_lag,
+                                            int32_t abs_scores, muse_record *out_winner, uint8_t *out_state)
+{
+    if (M > 0 && !rows)
+        return fail(MUSE_ERR_INVALID, "bad arguments");
+    const WindowCall wc{max_lag, nullptr, nullptr};
+    return run_rows(tmpl, rows, nullptr, M, row_stride, abs_scores, out_winner, out_state, &wc);
+}
+
+extern "C" int muse_batch_run_row_ptrs_windowed(muse_batch *tmpl, const double *const *rows, int64_t M, int32_t max_lag,
+                                                int32_t abs_scores, muse_record *out_winner, uint8_t *out_state)
+{
+    if (M > 0 && !rows)
+        return fail(MUSE_ERR_INVALID, "bad arguments");
+    const WindowCall wc{max_lag, nullptr, nullptr};
+    return run_rows(tmpl, nullptr, rows, M, 0, abs_scores, out_winner, out_state, &wc);
+}
+
+extern "C" int muse_batch_run_group_rows_windowed(muse_batch *tmpl, muse_group *src, const int64_t *rows, int64_t M, int32_t max_lag,
+                                                  int32_t abs_scores, muse_record *out_winner, uint8_t *out_state)
+{
+    const WindowCall wc{max_lag, nullptr, nullptr};
+    return run_group_rows(tmpl, src, rows, M, abs_scores, out_winner, out_state, &wc);
+}
+
+// ---- test hooks of the windowed forms (include/muse_hip_test.h)
+extern "C" int muse_test_window_rows_plan(int64_t M, int32_t N, int32_t num_cus, int32_t *S, int32_t *chunks_per_slice)
+{
+    if (M < 1 || N < 2 || num_cus < 1 || !S)
+        return fail(MUSE_ERR_INVALID, "window rows plan: M >= 1, N >= 2, num_cus >= 1");
+    int cps = 0;
+    *S = window_rows_plan(M, N, num_cus, &cps);
+    if (chunks_per_slice)
+        *chunks_per_slice = cps;
+    return MUSE_OK;
+}
+
+extern "C" int muse_test_window_rows_slices(muse_ctx *ctx, int32_t S)
+{
+    if (!ctx || S < 0)
+        return fail(MUSE_ERR_INVALID, "window rows slices: a context and S >= 0");
+    ctx->win_rows_slices.store(S);
+    return MUSE_OK;
+}
+
+extern "C" int muse_test_run_rows_windowed_scores(muse_batch *tmpl, const double *rows, int64_t M, int64_t row_stride,
+                                                  int32_t max_lag, int32_t *lag_out, double *mv_out)
+{
+    if (M > 0 && (!rows || !lag_out || !mv_out))
+        return fail(MUSE_ERR_INVALID, "bad arguments");
+    muse_record win;
+    uint8_t state = 0;
+    const WindowCall wc{max_lag, lag_out, mv_out};
+    return run_rows(tmpl, rows, nullptr, M, row_stride, 0, &win, &state, &wc);
 }
 
 extern "C" int muse_test_rows_always_copy(muse_ctx *ctx, int32_t always_copy)

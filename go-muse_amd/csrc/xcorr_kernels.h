@@ -162,6 +162,21 @@ inline bool window_wide(const double *rows, long long stride) { return stride % 
 inline long long window_e_len(int N) { return (long long)((N + WIN_KC - 1) / WIN_KC) * WIN_KC + WIN_E_TAIL; }
 hipError_t launch_window_tables(const double *xs, int N, int n, int L, double *e, long long e_len, double *pw, hipStream_t stream);
 hipError_t launch_window(const WindowParams &p, hipStream_t stream);
+// ---- the same for few rows of long series (xcorr_window_split.hip; muse_batch_run_rows_windowed): K split across workgroups.
+// window_rows_plan (pure host function): the slice count S for M rows of N samples on num_cus CUs -- the largest S with blocks x S
+// (blocks = ceil(M / 16)) within the CUs and S <= min(chunks, max(WIN_ROWS_FULL_SPLIT, chunks / WIN_ROWS_MIN_CHUNKS)): one chunk of
+// WIN_KC samples per slice up to WIN_ROWS_FULL_SPLIT slices, at least WIN_ROWS_MIN_CHUNKS chunks per slice beyond (slice s = chunks
+// [s chunks / S, (s + 1) chunks / S)); *chunks_per_slice = the largest slice.  S == 1: launch_window, untouched.
+// Measured (tools/window_rows_bench.py part (b), profiles/window_rows_bench.txt, one box): at every shape with blocks < CUs
+// every S > 1 beat S = 1 by 1.35 x or more; the fastest S was chunks at 4 and 16 chunks, chunks / 2 at 40 and 64 chunks (the
+// finish kernel adds a block's slabs one after the other: 40 / 64 one-chunk slices lost 10 ... 35 % against 20 / 32).
+constexpr int WIN_ROWS_FULL_SPLIT = 16;        // up to this many slices a slice may be a single chunk
+constexpr int WIN_ROWS_MIN_CHUNKS = 2;         // beyond: chunks per slice at least
+constexpr bool WIN_ROWS_SPLIT_ENABLED = true;  // false: the planner returns 1 everywhere
+int window_rows_plan(long long M, int N, int num_cus, int *chunks_per_slice);
+long long window_split_slab_doubles(int L);    // doubles of one (block, slice) slab for window L: tiles x 256 + 32
+// S >= 2 slices (<= chunks) into slabs[blocks x S x window_split_slab_doubles(L)], summed in slice order, scanned into p.mv / p.lag
+hipError_t launch_window_split(const WindowParams &p, int S, double *slabs, hipStream_t stream);
 // ---- the same for many references in one pass (xcorr_window_many.hip): the references' windows packed into the tiles of one product
 constexpr int WINM_MAX_TILES = 8;       // accumulator tiles of a launch: 128 packed (reference, lag) rows
 constexpr int WINM_PACK_MAX_ROWS = 48;   // wider windows (four tiles per reference) are not packed: one launch per reference

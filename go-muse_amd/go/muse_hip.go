@@ -932,6 +932,21 @@ func New(ref *Series, results *Results) (*Muse, error) {
 // goroutines (muse_test.go:203-214): every call owns its group and batch, the
 // spectrum is shared read-only, Results has its mutex.
 func (m *Muse) Run(compGraphs []*Series) error {
+	return m.run(compGraphs, -1)
+}
+
+// RunWindowed is Run with Results.MaxLag as a LAG WINDOW (muse_batch_run_rows_windowed): every series contributes its best
+// match inside +-MaxLag, where Run takes its best match over all lags and Update drops the group when that lies outside.
+// The window is an argument of the call: Run itself never changes, and both may be in flight from many goroutines.
+func (m *Muse) RunWindowed(compGraphs []*Series) error {
+	if m.Results.MaxLag < 0 || m.Results.MaxLag > C.MUSE_LAG_WINDOW_MAX {
+		return fmt.Errorf("RunWindowed: MaxLag outside 0 .. %d", int(C.MUSE_LAG_WINDOW_MAX))
+	}
+	return m.run(compGraphs, m.Results.MaxLag)
+}
+
+// window < 0: Run; otherwise RunWindowed with that window
+func (m *Muse) run(compGraphs []*Series, window int) error {
 	if len(compGraphs) == 0 {
 		return nil
 	}
@@ -952,7 +967,12 @@ func (m *Muse) Run(compGraphs []*Series) error {
 	// copied before the call returns (cgo rule); Results.Update applies passed() as the reference does.
 	var win C.muse_record
 	var state C.uint8_t
-	st := C.muse_batch_run_rows(m.template, (*C.double)(unsafe.Pointer(&rows[0])), C.int64_t(len(compGraphs)), C.int64_t(N), 0, &win, &state)
+	var st C.int
+	if window >= 0 {
+		st = C.muse_batch_run_rows_windowed(m.template, (*C.double)(unsafe.Pointer(&rows[0])), C.int64_t(len(compGraphs)), C.int64_t(N), C.int32_t(window), 0, &win, &state)
+	} else {
+		st = C.muse_batch_run_rows(m.template, (*C.double)(unsafe.Pointer(&rows[0])), C.int64_t(len(compGraphs)), C.int64_t(N), 0, &win, &state)
+	}
 	if err := hipError(st); err != nil {
 		return err
 	}

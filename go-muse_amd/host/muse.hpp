@@ -1364,7 +1364,20 @@ public:
     Muse(const Muse &) = delete;
     Muse &operator=(const Muse &) = delete;
     ResultsPtr Results_;
-    void Run(const std::vector<SeriesPtr> &compGraphs) // muse.go:46-92
+    void Run(const std::vector<SeriesPtr> &compGraphs) { run(compGraphs, -1); } // muse.go:46-92
+    // Run with Results.MaxLag as a LAG WINDOW (muse_batch_run_row_ptrs_windowed / _run_group_rows_windowed): every series
+    // contributes its best match inside +-MaxLag, where Run takes its best match over all lags and Update drops the group when
+    // that lies outside.  Same length check, same resident-row reuse, same Update; Run itself never changes.
+    void RunWindowed(const std::vector<SeriesPtr> &compGraphs)
+    {
+        if (Results_->MaxLag < 0 || Results_->MaxLag > MUSE_LAG_WINDOW_MAX)
+            throw Error(MUSE_ERR_UNSUPPORTED, "RunWindowed: MaxLag outside 0 .. MUSE_LAG_WINDOW_MAX");
+        run(compGraphs, (int32_t)Results_->MaxLag);
+    }
+
+private:
+    // window < 0: Run; otherwise RunWindowed with that window
+    void run(const std::vector<SeriesPtr> &compGraphs, int32_t window)
     {
         if (compGraphs.empty())
             return;
@@ -1385,15 +1398,18 @@ public:
         }
         muse_record win{};
         uint8_t state = 0;
-        if (!run_resident(compGraphs, &win, &state))
-            check(muse_batch_run_row_ptrs(template_, rows, (int64_t)compGraphs.size(), 0, &win, &state));
+        if (!run_resident(compGraphs, window, &win, &state)) {
+            if (window >= 0)
+                check(muse_batch_run_row_ptrs_windowed(template_, rows, (int64_t)compGraphs.size(), window, 0, &win, &state));
+            else
+                check(muse_batch_run_row_ptrs(template_, rows, (int64_t)compGraphs.size(), 0, &win, &state));
+        }
         if (state == 1 && win.series >= 0)
             Results_->Update(Score{compGraphs[(size_t)win.series]->Labels(), win.lag, win.score});
     }
 
-private:
     // every series lives in ONE live home on this engine: scored where it lies (muse_batch_run_group_rows), nothing crosses PCIe
-    bool run_resident(const std::vector<SeriesPtr> &compGraphs, muse_record *win, uint8_t *state)
+    bool run_resident(const std::vector<SeriesPtr> &compGraphs, int32_t window, muse_record *win, uint8_t *state)
     {
         if (!Group::ReuseResidentRows)
             return false;
@@ -1408,7 +1424,10 @@ private:
         std::shared_lock<std::shared_mutex> lock(src->mu);
         if (!src->alive)
             return false;
-        check(muse_batch_run_group_rows(template_, src->dev, at.data(), (int64_t)at.size(), 0, win, state));
+        if (window >= 0)
+            check(muse_batch_run_group_rows_windowed(template_, src->dev, at.data(), (int64_t)at.size(), window, 0, win, state));
+        else
+            check(muse_batch_run_group_rows(template_, src->dev, at.data(), (int64_t)at.size(), 0, win, state));
         return true;
     }
     std::shared_ptr<Engine> eng_;

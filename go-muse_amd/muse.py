@@ -116,6 +116,10 @@ class Engine:
         """test hook: muse_batch_run_rows copies even the smallest groups to HBM instead of letting the kernel read the pinned buffer"""
         B.check(B.load().muse_test_rows_always_copy(self._h, 1 if on else 0))
 
+    def window_rows_slices(self, S):
+        """test hook: the windowed Muse.Run scores in S slices (0 = the planner, 1 = the unsplit kernel; muse_test_window_rows_slices)"""
+        B.check(B.load().muse_test_window_rows_slices(self._h, int(S)))
+
     def wave_argmax(self, cc_a, cc_b):
         """test hook: the n = 4096 kernels' per-wave argmax step on 2 x 4096 given values; (4, 2, 3) array of
         {max |cc|, signed value, index} per wave and series"""
@@ -503,6 +507,56 @@ class DeviceBatch:
                                                    B.recptr(rec), ctypes.byref(state)))
         return rec[0], int(state.value)
 
+    # ---- the same inside a lag window: the window is an argument of the call, this batch's own setting is not touched
+    @staticmethod
+    def _rows2d(rows):
+        rows = np.asarray(rows, dtype=np.float64)
+        if rows.ndim != 2:
+            raise ValueError("rows must be 2-D")
+        if rows.shape[0] and rows.strides[1] != 8:
+            rows = np.ascontiguousarray(rows)
+        return rows, (rows.strides[0] // 8 if rows.shape[0] > 1 else rows.shape[1])
+
+    def run_rows_windowed(self, rows, max_lag, abs_scores=False):
+        """muse_batch_run_rows_windowed: run_rows with every row's best match INSIDE +-max_lag (the lag window of set_lag_window)"""
+        rows, stride = self._rows2d(rows)
+        rec = np.zeros(1, dtype=B.RECORD_DTYPE)
+        state = ctypes.c_uint8(0)
+        B.check(B.load().muse_batch_run_rows_windowed(self._h, rows.ctypes.data_as(B._dp), rows.shape[0], stride, int(max_lag),
+                                                      1 if abs_scores else 0, B.recptr(rec), ctypes.byref(state)))
+        return rec[0], int(state.value)
+
+    def run_row_ptrs_windowed(self, series, max_lag, abs_scores=False):
+        """muse_batch_run_row_ptrs_windowed: run_row_ptrs inside the lag window"""
+        arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in series]
+        for a in arrs:
+            if a.ndim != 1 or a.shape[0] != self.dgroup.N:
+                raise MuseError(B.MUSE_ERR_LENGTH, "Encountered a comparison graph with differing length than the reference")
+        ptrs = (B._dp * max(len(arrs), 1))(*[a.ctypes.data_as(B._dp) for a in arrs])
+        rec = np.zeros(1, dtype=B.RECORD_DTYPE)
+        state = ctypes.c_uint8(0)
+        B.check(B.load().muse_batch_run_row_ptrs_windowed(self._h, ptrs, len(arrs), int(max_lag), 1 if abs_scores else 0,
+                                                          B.recptr(rec), ctypes.byref(state)))
+        return rec[0], int(state.value)
+
+    def run_group_rows_windowed(self, src, rows, max_lag, abs_scores=False):
+        """muse_batch_run_group_rows_windowed: run_group_rows inside the lag window (a float32-storage src is accepted)"""
+        idx = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        rec = np.zeros(1, dtype=B.RECORD_DTYPE)
+        state = ctypes.c_uint8(0)
+        B.check(B.load().muse_batch_run_group_rows_windowed(self._h, src._h, B.i64ptr(idx), idx.shape[0], int(max_lag),
+                                                            1 if abs_scores else 0, B.recptr(rec), ctypes.byref(state)))
+        return rec[0], int(state.value)
+
+    def run_rows_windowed_scores(self, rows, max_lag):
+        """test hook: the per-row (lag, mv) of run_rows_windowed's path (muse_test_run_rows_windowed_scores)"""
+        rows, stride = self._rows2d(rows)
+        lag = np.zeros(rows.shape[0], dtype=np.int32)
+        mv = np.zeros(rows.shape[0])
+        B.check(B.load().muse_test_run_rows_windowed_scores(self._h, rows.ctypes.data_as(B._dp), rows.shape[0], stride, int(max_lag),
+                                                            B.i32ptr(lag), B.dptr(mv)))
+        return lag, mv
+
     def run_groups(self, group_id, G, series_offset=0, abs_scores=True):
         """this shard's winner per label group, unfiltered (muse_batch_run_groups): (records[G], state[G])"""
         rec = np.zeros(max(int(G), 1), dtype=B.RECORD_DTYPE)
@@ -645,6 +699,14 @@ def window_many_plan(R, L):
     k = int(n.value)
     return dict(launches=k, launch_of=of[:R].copy(), tiles_of=tiles[:k].copy(), max_refs=int(mx.value), img_of=img[:k].copy(),
                 kc_of=kc[:k].copy())
+
+
+def window_rows_plan(M, N, num_cus):
+    """muse_test_window_rows_plan (no device): (S, chunks_per_slice) of the windowed Muse.Run for M rows of N samples on num_cus CUs;
+    slice s covers the 1024-sample chunks [s * chunks // S, (s + 1) * chunks // S)"""
+    S, cps = ctypes.c_int32(0), ctypes.c_int32(0)
+    B.check(B.load().muse_test_window_rows_plan(int(M), int(N), int(num_cus), ctypes.byref(S), ctypes.byref(cps)))
+    return int(S.value), int(cps.value)
 
 
 def device_count():
@@ -1339,6 +1401,29 @@ class Muse:
             self.Results.Update(Score(compGraphs[int(win["series"])].Labels(), int(win["lag"]), float(win["score"])))
         return None
 
+
+    def RunWindowed(self, compGraphs):
+        """Run with Results.MaxLag as a LAG WINDOW (muse_batch_run_rows_windowed / _run_group_rows_windowed): every series
+        contributes its best match inside +-MaxLag, where Run takes its best match over all lags and Update then drops the group
+        when that lies outside.  Same length check, same resident-row reuse, same Update as Run; Run itself never changes."""
+        if len(compGraphs) == 0:
+            return None
+        window = int(self.Results.MaxLag)
+        if window < 0 or window > B.MUSE_LAG_WINDOW_MAX:
+            raise MuseError(B.MUSE_ERR_UNSUPPORTED, "RunWindowed needs 0 <= Results.MaxLag <= %d" % B.MUSE_LAG_WINDOW_MAX)
+        for s in compGraphs:                      # muse.go:68-70
+            if s.Length() != self.refN:
+                raise MuseError(B.MUSE_ERR_LENGTH, "Encountered a comparison graph with differing length "
+                                "than the reference, %r" % (s.Labels(),))
+        home = self._resident(compGraphs)
+        if home is not None:
+            win, state = self._template.run_group_rows_windowed(home[0], home[1], window, abs_scores=False)
+        else:
+            rows = np.stack([s.y for s in compGraphs])
+            win, state = self._template.run_rows_windowed(rows, window, abs_scores=False)
+        if state == 1 and win["series"] >= 0:
+            self.Results.Update(Score(compGraphs[int(win["series"])].Labels(), int(win["lag"]), float(win["score"])))
+        return None
 
     def _resident(self, compGraphs):
         """(DeviceGroup, rows) when reuse is on and every series has a live home in ONE DeviceGroup on this engine"""

@@ -281,10 +281,31 @@ int muse_batch_score(muse_batch *b);
  * MUSE_ERR_UNSUPPORTED, the batch unchanged: max_lag > MUSE_LAG_WINDOW_MAX (beyond a few dozen lags the direct product
  * costs more than the transform); a float32-storage group; series longer than 65536 samples.  A batch with a window is
  * refused (MUSE_ERR_UNSUPPORTED) by muse_batch_score_many / _run_many (muse_batch_score_many_windowed is their windowed form) and as the template of muse_batch_run_rows /
- * _run_row_ptrs / _run_group_rows.  muse_batch_lag_window reads the setting back (-1 = off). */
+ * _run_row_ptrs / _run_group_rows (their _windowed forms below take the window as an argument).  muse_batch_lag_window reads the
+ * setting back (-1 = off). */
 #define MUSE_LAG_WINDOW_MAX 63
 int muse_batch_set_lag_window(muse_batch *b, int32_t max_lag);
 int muse_batch_lag_window(muse_batch *b, int32_t *max_lag);
+/* Muse.Run (muse.go:46-92) INSIDE A LAG WINDOW, in one call.  Each behaves as its unwindowed namesake (muse_batch_run_rows,
+ * _run_row_ptrs, _run_group_rows): same validation, same out_winner / out_state rules, same abs_scores, M == 0 gives state 0, the
+ * same pool of slots, any number of host threads on one tmpl.  The only difference is the per-row (lag, mv): the windowed one defined
+ * at muse_batch_set_lag_window, with L = min(max_lag, n/2).  The window is an argument of the call: no batch's own lag_window setting
+ * is touched, and the three unwindowed entry points go on refusing a windowed template.  Everything behind the per-row pair is
+ * unchanged (signed clamp or |.|, the first member attaining the maximum wins, a NaN first member gives state 2).
+ * Refused, every handle left as it was: max_lag < 0, or a template whose own window is on and differs from max_lag
+ * (MUSE_ERR_INVALID); max_lag > MUSE_LAG_WINDOW_MAX, or series longer than 65536 samples (MUSE_ERR_UNSUPPORTED).  A float32-storage
+ * src is accepted by _run_group_rows_windowed (the gather widens exactly).
+ * Numerics: few rows of long series are scored by kernels that split the samples of a row over several workgroups and sum the
+ * partial products in a fixed order (xcorr_window_split.hip; deterministic: two calls give the same bits).  Where that split is
+ * not taken (one slice), a row's (lag, mv) is BIT-IDENTICAL to muse_batch_set_lag_window + muse_batch_score over the same rows;
+ * where it is, the summation tree differs, and the result equals the definition at the project's tolerance (1e-6 relative),
+ * not the unsplit kernel's bit for bit. */
+int muse_batch_run_rows_windowed(muse_batch *tmpl, const double *rows, int64_t M, int64_t row_stride,
+                                 int32_t max_lag, int32_t abs_scores, muse_record *out_winner, uint8_t *out_state);
+int muse_batch_run_row_ptrs_windowed(muse_batch *tmpl, const double *const *rows, int64_t M,
+                                     int32_t max_lag, int32_t abs_scores, muse_record *out_winner, uint8_t *out_state);
+int muse_batch_run_group_rows_windowed(muse_batch *tmpl, muse_group *src, const int64_t *rows, int64_t M,
+                                       int32_t max_lag, int32_t abs_scores, muse_record *out_winner, uint8_t *out_state);
 /* muse_batch_score + D2H of the per-series results (lag[M], mv[M]). */
 int muse_batch_scores(muse_batch *b, int32_t *lag, double *mv);
 /* Batch.Run + Results.Update + Results.Fetch (muse_batch.go:99-130,

@@ -89,6 +89,17 @@ int muse_test_batch_redo_pairs(muse_batch *b, int64_t *pairs, int64_t cap, int64
  * single-reference kernel's (xcorr_window_mfma).  Any out pointer but launches may be NULL. */
 int muse_test_window_many_plan(int32_t R, int32_t L, int32_t *launches, int32_t *launch_of, int32_t *tiles_of, int32_t *max_refs,
                                int32_t *img_of, int32_t *kc_of);
+/* The planner of the windowed Muse.Run (muse_batch_run_rows_windowed; xcorr_window_split.hip), a pure host function (no device
+ * needed): M >= 1 rows of N >= 2 samples on num_cus CUs are scored in *S slices of whole 1024-sample chunks, slice s = chunks
+ * [s chunks / S, (s + 1) chunks / S) of chunks = ceil(N / 1024); *chunks_per_slice = the largest slice.  *S == 1: the unsplit kernel. */
+int muse_test_window_rows_plan(int64_t M, int32_t N, int32_t num_cus, int32_t *S, int32_t *chunks_per_slice);
+/* Forces the slice count of the windowed Muse.Run on this context: 0 = the planner (default); S >= 1 = that many slices, clipped to
+ * the chunks of the length (1 = the unsplit kernel) -- drives the split kernels at small shapes. */
+int muse_test_window_rows_slices(muse_ctx *ctx, int32_t S);
+/* muse_batch_run_rows_windowed's path (same checks, same slot, same kernels), and the slot's per-row (lag_out[M], mv_out[M]) copied
+ * back before the slot is returned: without it only the winner is observable. */
+int muse_test_run_rows_windowed_scores(muse_batch *tmpl, const double *rows, int64_t M, int64_t row_stride, int32_t max_lag,
+                                       int32_t *lag_out, double *mv_out);
 
 #ifdef __cplusplus
 }
