@@ -71,6 +71,8 @@ SIGNATURES = {
     "muse_group_append_from": (ctypes.c_int, [_vp, _vp, _i64p, _i64]),
     "muse_batch_run_group_rows": (ctypes.c_int, [_vp, _vp, _i64p, _i64, _i32, _recp, ctypes.POINTER(ctypes.c_uint8)]),
     "muse_test_gather_nontemporal": (ctypes.c_int, [_vp, _i32]),
+    "muse_group_slide": (ctypes.c_int, [_vp, _i64, _i64, _dp, _i32, _i64]),
+    "muse_test_slide_plan": (ctypes.c_int, [_i32, _i32, _i32, _i32p]),
     "muse_ctx_trim": (ctypes.c_int, [_vp]),
     "muse_batch_fft_len": (ctypes.c_int, [_vp, _i32p]),
     "muse_batch_spectrum": (ctypes.c_int, [_vp, _dp]),

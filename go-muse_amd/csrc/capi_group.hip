@@ -462,6 +462,92 @@ extern "C" int muse_group_fill_synthetic(muse_group *g, int64_t first, int64_t c
     return MUSE_OK;
 }
 
+// ---- rows that follow time (muse_group_slide; row_slide.hip)
+constexpr size_t SLIDE_STAGE_BYTES = 4u << 20; // one pinned half of the tails' staging pair (at least one tail)
+
+extern "C" int muse_group_slide(muse_group *g, int64_t first, int64_t count, const double *tails, int32_t k, int64_t tail_stride)
+{
+    // everything is checked before anything is enqueued: on an error the group is unchanged
+    if (!g)
+        return fail(MUSE_ERR_INVALID, "NULL group");
+    if (first < 0 || count < 0 || first > g->M || count > g->M - first)
+        return fail(MUSE_ERR_INVALID, "slide of rows [%lld, %lld + %lld) outside the group's rows [0, %lld)", (long long)first,
+                    (long long)first, (long long)count, (long long)g->M);
+    if (k < 0 || k > g->N)
+        return fail(MUSE_ERR_INVALID, "slide by %d samples: outside 0 .. N = %d", k, g->N);
+    if (tail_stride < k)
+        return fail(MUSE_ERR_INVALID, "tail_stride %lld is smaller than k = %d", (long long)tail_stride, k);
+    if (!tails && count > 0 && k > 0)
+        return fail(MUSE_ERR_INVALID, "tails is NULL");
+    if (g->win_rows)
+        return fail(MUSE_ERR_INVALID, "the group has an open staging window");
+    if (k == 0 || count == 0) // nothing moves: no cache is dropped, `rewrites` stays
+        return MUSE_OK;
+    muse_ctx *ctx = g->ctx;
+    int rc = use_device(ctx);
+    if (rc)
+        return rc;
+    rc = group_ready(g); // rows packed but not sent yet go first
+    if (rc)
+        return rc;
+    // the tails: packed densely (float32 storage: narrowed, as muse_group_append narrows rows) into two pinned halves in turn and
+    // sent on the copy stream into a device buffer of their own -- count x k samples cross PCIe, in pieces of megabytes, beside
+    // whatever the device is still doing; the group's staging pair and its cur / staged / flushed state are not involved
+    const size_t elem = g->elem(), tail_bytes = (size_t)k * elem;
+    const int64_t half_rows = std::max<int64_t>(1, (int64_t)(SLIDE_STAGE_BYTES / tail_bytes));
+    const size_t half_bytes = (size_t)half_rows * tail_bytes;
+    HIP_TRY(g->slide_dev.ensure(ctx, (int64_t)((size_t)count * tail_bytes), ctx->copy_stream));
+    HIP_TRY(g->slide_host.ensure(ctx, (int64_t)(2 * half_bytes), ctx->copy_stream));
+    for (int i = 0; i < 2; i++)
+        if (!g->slide_copied[i])
+            HIP_TRY(hipEventCreateWithFlags(&g->slide_copied[i], hipEventDisableTiming));
+    int64_t piece = 0;
+    for (int64_t r0 = 0; r0 < count; r0 += half_rows, piece++) {
+        const int h = (int)(piece & 1);
+        if (piece >= 2)
+            HIP_TRY(hipEventSynchronize(g->slide_copied[h])); // the half's previous copy has left it
+        unsigned char *half = g->slide_host.p + (size_t)h * half_bytes;
+        const int64_t rows = std::min(half_rows, count - r0);
+        for (int64_t r = 0; r < rows; r++) {
+            const double *src = tails + (r0 + r) * tail_stride;
+            if (g->f32) {
+                float *dst = (float *)half + r * k;
+                for (int32_t j = 0; j < k; j++)
+                    dst[j] = (float)src[j];
+            } else {
+                memcpy(half + (size_t)r * tail_bytes, src, tail_bytes);
+            }
+        }
+        HIP_TRY(hipMemcpyAsync(g->slide_dev.p + (size_t)r0 * tail_bytes, half, (size_t)rows * tail_bytes, hipMemcpyHostToDevice,
+                               ctx->copy_stream));
+        HIP_TRY(hipEventRecord(g->slide_copied[h], ctx->copy_stream));
+    }
+    // The slide rewrites rows that work enqueued earlier may still be reading -- score passes on the compute stream, gathers on
+    // the copy stream with this group as their source, muse_batch_run_group_rows on the slot streams: every stream of the device
+    // is waited for (the tails have landed with them), and the call returns once the kernel has finished
+    HIP_TRY(hipDeviceSynchronize());
+    {
+        std::lock_guard<std::mutex> lock(g->ready_mu);
+        g->rewrites++; // the spectrum cache (zc_rewrites) and the batches' kernel selection (handoff_rewrites) describe other rows now
+        g->hstats_rows = std::min(g->hstats_rows, first); // (and so do the kept statistics from row `first` on)
+    }
+    LaunchTimer timer(ctx);
+    HIP_TRY(timer.begin());
+    HIP_TRY(launch_row_slide((char *)g->base() + (size_t)(first * g->stride) * elem, g->f32, count, g->N, k, g->slide_dev.p,
+                             ctx->num_cus, ctx->stream));
+    HIP_TRY(timer.end());
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return MUSE_OK;
+}
+
+extern "C" int muse_test_slide_plan(int32_t N, int32_t k, int32_t f32_storage, int32_t *unit_bytes)
+{
+    if (!unit_bytes || N < 1 || k < 0 || k > N)
+        return fail(MUSE_ERR_INVALID, "bad slide plan arguments");
+    *unit_bytes = slide_unit_bytes(N, k, f32_storage != 0);
+    return MUSE_OK;
+}
+
 extern "C" int muse_group_shape(muse_group *g, int64_t *M, int32_t *N)
 {
     if (!g)
@@ -521,6 +607,11 @@ void group_release(muse_group *g)
     g->gidx_dev.release(g->ctx);
     if (g->gather_done)
         (void)hipEventDestroy(g->gather_done);
+    g->slide_host.release(g->ctx);
+    g->slide_dev.release(g->ctx);
+    for (int i = 0; i < 2; i++)
+        if (g->slide_copied[i])
+            (void)hipEventDestroy(g->slide_copied[i]);
     for (int i = 0; i < 2; i++) {
         if (g->stage[i]) { // back to the context's pool (the stream is idle: no upload reads it any more)
             std::lock_guard<std::mutex> lock(g->ctx->stage_mu);

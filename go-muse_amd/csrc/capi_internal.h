@@ -184,7 +184,7 @@ struct muse_group {
     // and every other reference (rows appended later are added; a re-allocation starts over)
     PoolBuf<double> hstats; // [cap][4]
     int64_t hstats_rows = 0;
-    uint64_t rewrites = 0;          // how often rows already in the group were rewritten (muse_group_fill_synthetic: rows are otherwise immutable)
+    uint64_t rewrites = 0;          // how often rows already in the group were rewritten (muse_group_fill_synthetic, muse_group_slide: rows are otherwise immutable)
     // allocations the group has outgrown: kept until the group goes (kernels enqueued before the growth may still read them),
     // so that growing never waits for the device (group_reserve)
     std::vector<void *> retired;
@@ -216,6 +216,11 @@ struct muse_group {
     HostBuf<long long> gidx_host;
     PoolBuf<long long> gidx_dev;
     hipEvent_t gather_done = nullptr;
+    // muse_group_slide: the tails of the last slide -- two pinned halves the host packs (and narrows) into alternately, each
+    // reused once its copy (`slide_copied`) has left it, and the dense count x k device image the kernel reads; kept for the next slide
+    HostBuf<unsigned char> slide_host;
+    PoolBuf<unsigned char> slide_dev;
+    hipEvent_t slide_copied[2] = {nullptr, nullptr};
     // Spectrum cache (n = 4096, float64 rows; xcorr_r16_cached.hip): per pair of rows what the default kernel's first
     // half computes from the rows alone, kept for every later pass of every batch over the group.  Rows [0, zc_rows) are covered
     // (zc_rows even: a trailing single row's pair changes when a row is appended), in segments in pair order -- an append adds a

@@ -221,6 +221,13 @@ hipError_t launch_synth_ref(double *ref, int N, unsigned long long seed, hipStre
 // float32 rows, float32 -> float64 widened exactly; nontemporal: the stores bypass the caches
 hipError_t launch_row_gather(const void *src, bool src_f32, void *dst, bool dst_f32, const long long *idx, long long count,
                              int N, int num_cus, bool nontemporal, hipStream_t stream);
+// row_slide.hip: rows [0, count) behind `rows` (N elements apart, float64 or float32) move forward by 1 <= k <= N samples in place:
+// row r <- old row r [k .. N) followed by tails[r * k + 0 .. k) (a dense count x k device buffer of the rows' type, 256-byte
+// aligned).  One wave owns a row; nothing outside the count rows is stored to.  slide_unit_bytes (pure host function): the vector
+// unit the kernel moves in -- the widest of 16 / 8 (/ 4 for float32) bytes that divides both N x elem and k x elem
+int slide_unit_bytes(int N, int k, bool f32);
+hipError_t launch_row_slide(void *rows, bool f32, long long count, int N, int k, const void *tails, int num_cus,
+                            hipStream_t stream);
 
 // measurement hook (diag_kernels.hip): one wave sampling delta s_memtime / delta s_memrealtime in windows of window_ms for total_ms
 hipError_t launch_clock_probe(unsigned long long *out, int *count, int max_windows, double window_ms, double total_ms,

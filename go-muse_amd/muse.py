@@ -250,6 +250,7 @@ class DeviceGroup:
         self.N = int(N)
         self.f32 = bool(f32)
         self.alive = True     # False once closed: Series whose home this group is go back to the host path
+        self.slides = 0       # slides that moved rows (slide): a Series' home set before the last one no longer holds its values
 
     @classmethod
     def from_rows(cls, engine, rows, f32=False):
@@ -290,6 +291,20 @@ class DeviceGroup:
         in list order, copied HBM -> HBM (asynchronous; src may be closed right after the call)"""
         idx = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
         B.check(B.load().muse_group_append_from(self._h, src._h, B.i64ptr(idx), idx.shape[0]))
+
+    def slide(self, tails, first=0):
+        """muse_group_slide: rows [first, first + count) move forward by k samples in place in HBM -- row r becomes its old samples
+        [k, N) followed by tails[r - first]; tails: (count, k).  Waits for the device and returns when the rows have moved."""
+        tails = np.asarray(tails, dtype=np.float64)
+        if tails.ndim != 2:
+            raise ValueError("tails must be 2-D (count, k)")
+        count, k = tails.shape
+        if count > 0 and k > 0 and (tails.strides[1] != 8 or (count > 1 and tails.strides[0] < 8 * k)):
+            tails = np.ascontiguousarray(tails)
+        stride = tails.strides[0] // 8 if count > 1 and k > 0 else k
+        B.check(B.load().muse_group_slide(self._h, int(first), count, tails.ctypes.data_as(B._dp), k, stride))
+        if count > 0 and k > 0:
+            self.slides += 1
 
     def stage(self, count):
         """muse_group_stage: a window of pinned host memory for up to `count` more rows -> a (granted, N) float64 array VIEW of
@@ -797,7 +812,7 @@ class Series:
             labels = NewLabels({DefaultLabel: str(uuid.uuid4())})
         self.y = np.asarray(y, dtype=np.float64)
         self.labels = labels
-        self._home = None     # (weakref to the first DeviceGroup that received this row, its row there): set_home / live_home
+        self._home = None     # (weakref to the first DeviceGroup that received this row, its row there, the group's slides then): set_home / live_home
 
     def Length(self):
         return int(self.y.shape[0])
@@ -819,20 +834,28 @@ def NewSeries(y, labels=None):
 # ------------------------------------------------------ resident rows (reuse)
 # A Series' values are taken as immutable once it is added (as everywhere in this mirror): the first DeviceGroup that receives its
 # row becomes its HOME, and a later Group or Muse.Run on the same engine takes the row from there (HBM -> HBM) instead of
-# sending it across PCIe again.  A closed DeviceGroup is no home any more.
+# sending it across PCIe again.  A closed DeviceGroup is no home any more, and neither is one that has slid since
+# (DeviceGroup.slide: the row holds later samples now) -- the home remembers the group's `slides` count; such a home is replaced
+# by the next group that receives the row.
 def set_home(series, dgroup, row):
-    if getattr(series, "_home", None) is None:
-        series._home = (weakref.ref(dgroup), int(row))
+    h = getattr(series, "_home", None)
+    if h is not None:
+        dg = h[0]()
+        if dg is not None and getattr(dg, "slides", 0) != h[2]:
+            h = None
+    if h is None:
+        series._home = (weakref.ref(dgroup), int(row), getattr(dgroup, "slides", 0))
 
 
 def live_home(series, engine, N, f32=None):
-    """(DeviceGroup, row) of the Series' home if it is alive, on `engine`, of length N and (f32 not None) of that storage type"""
+    """(DeviceGroup, row) of the Series' home if it is alive, on `engine`, of length N, (f32 not None) of that storage type and has
+    not slid since the home was set"""
     h = getattr(series, "_home", None)
     if h is None:
         return None
     dg = h[0]()
     if dg is None or not getattr(dg, "alive", False) or dg.engine is not engine or dg.N != N or \
-            (f32 is not None and bool(dg.f32) != bool(f32)):
+            (f32 is not None and bool(dg.f32) != bool(f32)) or getattr(dg, "slides", 0) != h[2]:
         return None
     return dg, h[1]
 

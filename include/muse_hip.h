@@ -113,7 +113,7 @@ int muse_ctx_set_screening(muse_ctx *ctx, int32_t enable);
  * i.e. the group's footprint doubles, taken only if it fits in half of the device memory that is free at that moment.
  * Every later all-scores pass over the group reads the kept spectra instead of the rows: the same bytes, about half the
  * arithmetic, bit-identical scores and lags.  Every pass still scores every series; nothing of a Run's result is cached.
- * Rows appended later are added to the cache by the next pass; muse_group_fill_synthetic over existing rows drops it.
+ * Rows appended later are added to the cache by the next pass; muse_group_slide and muse_group_fill_synthetic over existing rows drop it.
  * Mode 0 neither builds nor reads a cache (one that exists stays until muse_group_drop_spectrum_cache or muse_group_free). */
 int muse_ctx_set_spectrum_cache(muse_ctx *ctx, int32_t mode);
 /* Which path the last muse_batch_run / muse_batch_run_shard on this batch took: *screened = 1 for filter-and-refine,
@@ -183,6 +183,26 @@ int muse_group_commit(muse_group *g, int64_t first, int64_t count);
  * that reads dst waits for it; src may be freed right after the call.  Rows are taken as immutable once added: the
  * gather copies what src holds when it runs. */
 int muse_group_append_from(muse_group *dst, muse_group *src, const int64_t *rows, int64_t count);
+/* The rows follow time: rows [first, first + count) of g move forward by k samples -- row r becomes
+ *   old row r [k .. N)  followed by  tails[(r - first) * tail_stride + 0 .. k)
+ * in place in HBM (row_slide.hip); only count x k samples cross PCIe.  Both storage types and every N a group allows; a
+ * float32-storage group narrows the tails with (float)x, exactly as muse_group_append narrows rows.  k == N replaces the rows
+ * outright.  MUSE_ERR_INVALID -- everything is checked before anything is enqueued, the group is unchanged -- for a NULL group,
+ * first < 0, count < 0, first + count > M, k < 0, k > N, tail_stride < k, NULL tails with count > 0 and k > 0, or an open
+ * staging window.  k == 0 or count == 0 returns MUSE_OK and changes nothing (no cache is dropped).
+ * `tails` is not retained after the call (as with muse_group_append).
+ * Ordering: rows packed by earlier small appends are sent first.  The slide REWRITES rows that earlier work may still be
+ * reading, so the call waits until the context's device is idle -- every stream: score passes, gathers that read this group,
+ * muse_batch_run_group_rows calls in flight -- before its kernel is enqueued, and returns after the kernel has finished (as
+ * muse_group_fill_synthetic does).  Calling it while other host threads are inside calls that read the same group is the
+ * caller's error, as it is for muse_group_free.  The guard in front of row 0, the rows outside the range and the memory behind
+ * row M are never written.
+ * What describes the old rows goes with them: the group's spectrum cache is dropped by the next pass (muse_group_spectrum_cache
+ * reports 0 rows right after the slide) and built again by the second pass over the new rows -- a group that slides between
+ * every two passes never builds one --, the kept statistics of long series are recomputed from row `first` on, and automatic
+ * kernel selection forgets what it learned from the old rows.  Scores a batch computed before the slide are those of the old
+ * rows until its next scoring pass. */
+int muse_group_slide(muse_group *g, int64_t first, int64_t count, const double *tails, int32_t k, int64_t tail_stride);
 /* create + append in one call */
 int muse_group_upload(muse_ctx *ctx, const double *rows, int64_t M, int32_t N,
                       int64_t row_stride, muse_group **out);

@@ -67,6 +67,10 @@ int muse_test_huge_batch_mb(muse_ctx *ctx, int32_t megabytes);
 /* Measurement hook: the row gather of muse_group_append_from / muse_batch_run_group_rows (row_gather.hip) stores with
  * non-temporal stores (on = 1) or plain ones (0, the default): tools/resident_bench.py measures both. */
 int muse_test_gather_nontemporal(muse_ctx *ctx, int32_t on);
+/* The vector unit of muse_group_slide's kernel (row_slide.hip), a pure host function (no device needed): *unit_bytes = the widest
+ * of 16 / 8 (/ 4 for float32 storage) bytes that divides both N x elem and k x elem -- float64 rows with odd k or odd N move in
+ * 8-byte units.  MUSE_ERR_INVALID for N < 1 or k outside 0 .. N. */
+int muse_test_slide_plan(int32_t N, int32_t k, int32_t f32_storage, int32_t *unit_bytes);
 
 /* Spectrum cache (muse_ctx_set_spectrum_cache): the smallest group that is cached (default 65 536 rows; negative = default) and
  * a byte budget for a group's cache in place of half the free device memory (0 = always decline; negative = no override). */
