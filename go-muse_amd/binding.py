@@ -73,6 +73,10 @@ SIGNATURES = {
     "muse_test_gather_nontemporal": (ctypes.c_int, [_vp, _i32]),
     "muse_group_slide": (ctypes.c_int, [_vp, _i64, _i64, _dp, _i32, _i64]),
     "muse_test_slide_plan": (ctypes.c_int, [_i32, _i32, _i32, _i32p]),
+    "muse_batch_slide_score_windowed": (ctypes.c_int, [_vp, _dp, _i32, _i64, _i32]),
+    "muse_batch_slide_run_windowed": (ctypes.c_int, [_vp, _dp, _i32, _i64, _i32p, _i32, _i32, _i32, _f64, _i32, _i32,
+                                                     _i64p, _i32p, _dp, _i32p, _dp]),
+    "muse_test_slide_score_plan": (ctypes.c_int, [_i32, _i32, _i32, _i32p, _i32p]),
     "muse_ctx_trim": (ctypes.c_int, [_vp]),
     "muse_batch_fft_len": (ctypes.c_int, [_vp, _i32p]),
     "muse_batch_spectrum": (ctypes.c_int, [_vp, _dp]),

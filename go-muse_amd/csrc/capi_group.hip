@@ -465,34 +465,13 @@ extern "C" int muse_group_fill_synthetic(muse_group *g, int64_t first, int64_t c
 // ---- rows that follow time (muse_group_slide; row_slide.hip)
 constexpr size_t SLIDE_STAGE_BYTES = 4u << 20; // one pinned half of the tails' staging pair (at least one tail)
 
-extern "C" int muse_group_slide(muse_group *g, int64_t first, int64_t count, const double *tails, int32_t k, int64_t tail_stride)
+// the tails of a slide of `count` rows by k >= 1 samples: packed densely (float32 storage: narrowed, as muse_group_append narrows
+// rows) into two pinned halves in turn and sent on the copy stream into a device buffer of their own (g->slide_dev) -- count x k
+// samples cross PCIe, in pieces of megabytes, beside whatever the device is still doing; the group's staging pair and its cur /
+// staged / flushed state are not involved.  The copies are enqueued, not waited for.
+int slide_upload_tails(muse_group *g, int64_t count, const double *tails, int32_t k, int64_t tail_stride)
 {
-    // everything is checked before anything is enqueued: on an error the group is unchanged
-    if (!g)
-        return fail(MUSE_ERR_INVALID, "NULL group");
-    if (first < 0 || count < 0 || first > g->M || count > g->M - first)
-        return fail(MUSE_ERR_INVALID, "slide of rows [%lld, %lld + %lld) outside the group's rows [0, %lld)", (long long)first,
-                    (long long)first, (long long)count, (long long)g->M);
-    if (k < 0 || k > g->N)
-        return fail(MUSE_ERR_INVALID, "slide by %d samples: outside 0 .. N = %d", k, g->N);
-    if (tail_stride < k)
-        return fail(MUSE_ERR_INVALID, "tail_stride %lld is smaller than k = %d", (long long)tail_stride, k);
-    if (!tails && count > 0 && k > 0)
-        return fail(MUSE_ERR_INVALID, "tails is NULL");
-    if (g->win_rows)
-        return fail(MUSE_ERR_INVALID, "the group has an open staging window");
-    if (k == 0 || count == 0) // nothing moves: no cache is dropped, `rewrites` stays
-        return MUSE_OK;
     muse_ctx *ctx = g->ctx;
-    int rc = use_device(ctx);
-    if (rc)
-        return rc;
-    rc = group_ready(g); // rows packed but not sent yet go first
-    if (rc)
-        return rc;
-    // the tails: packed densely (float32 storage: narrowed, as muse_group_append narrows rows) into two pinned halves in turn and
-    // sent on the copy stream into a device buffer of their own -- count x k samples cross PCIe, in pieces of megabytes, beside
-    // whatever the device is still doing; the group's staging pair and its cur / staged / flushed state are not involved
     const size_t elem = g->elem(), tail_bytes = (size_t)k * elem;
     const int64_t half_rows = std::max<int64_t>(1, (int64_t)(SLIDE_STAGE_BYTES / tail_bytes));
     const size_t half_bytes = (size_t)half_rows * tail_bytes;
@@ -522,15 +501,51 @@ extern "C" int muse_group_slide(muse_group *g, int64_t first, int64_t count, con
                                ctx->copy_stream));
         HIP_TRY(hipEventRecord(g->slide_copied[h], ctx->copy_stream));
     }
+    return MUSE_OK;
+}
+
+// rows from `first` on are about to be rewritten: what describes the old rows goes with them
+void slide_invalidate(muse_group *g, int64_t first)
+{
+    std::lock_guard<std::mutex> lock(g->ready_mu);
+    g->rewrites++; // the spectrum cache (zc_rewrites) and the batches' kernel selection (handoff_rewrites) describe other rows now
+    g->hstats_rows = std::min(g->hstats_rows, first); // (and so do the kept statistics from row `first` on)
+}
+
+extern "C" int muse_group_slide(muse_group *g, int64_t first, int64_t count, const double *tails, int32_t k, int64_t tail_stride)
+{
+    // everything is checked before anything is enqueued: on an error the group is unchanged
+    if (!g)
+        return fail(MUSE_ERR_INVALID, "NULL group");
+    if (first < 0 || count < 0 || first > g->M || count > g->M - first)
+        return fail(MUSE_ERR_INVALID, "slide of rows [%lld, %lld + %lld) outside the group's rows [0, %lld)", (long long)first,
+                    (long long)first, (long long)count, (long long)g->M);
+    if (k < 0 || k > g->N)
+        return fail(MUSE_ERR_INVALID, "slide by %d samples: outside 0 .. N = %d", k, g->N);
+    if (tail_stride < k)
+        return fail(MUSE_ERR_INVALID, "tail_stride %lld is smaller than k = %d", (long long)tail_stride, k);
+    if (!tails && count > 0 && k > 0)
+        return fail(MUSE_ERR_INVALID, "tails is NULL");
+    if (g->win_rows)
+        return fail(MUSE_ERR_INVALID, "the group has an open staging window");
+    if (k == 0 || count == 0) // nothing moves: no cache is dropped, `rewrites` stays
+        return MUSE_OK;
+    muse_ctx *ctx = g->ctx;
+    int rc = use_device(ctx);
+    if (rc)
+        return rc;
+    rc = group_ready(g); // rows packed but not sent yet go first
+    if (rc)
+        return rc;
+    rc = slide_upload_tails(g, count, tails, k, tail_stride);
+    if (rc)
+        return rc;
     // The slide rewrites rows that work enqueued earlier may still be reading -- score passes on the compute stream, gathers on
     // the copy stream with this group as their source, muse_batch_run_group_rows on the slot streams: every stream of the device
     // is waited for (the tails have landed with them), and the call returns once the kernel has finished
     HIP_TRY(hipDeviceSynchronize());
-    {
-        std::lock_guard<std::mutex> lock(g->ready_mu);
-        g->rewrites++; // the spectrum cache (zc_rewrites) and the batches' kernel selection (handoff_rewrites) describe other rows now
-        g->hstats_rows = std::min(g->hstats_rows, first); // (and so do the kept statistics from row `first` on)
-    }
+    slide_invalidate(g, first);
+    const size_t elem = g->elem();
     LaunchTimer timer(ctx);
     HIP_TRY(timer.begin());
     HIP_TRY(launch_row_slide((char *)g->base() + (size_t)(first * g->stride) * elem, g->f32, count, g->N, k, g->slide_dev.p,

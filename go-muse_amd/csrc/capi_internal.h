@@ -405,6 +405,11 @@ int group_gather(muse_group *dst, muse_group *src, const int64_t *rows, int64_t 
 // capi_group.hip: the index-list checks both resident-row entry points share (MUSE_ERR_INVALID outside [0, src->M))
 int check_row_list(const muse_group *src, const int64_t *rows, int64_t count);
 void group_release(muse_group *g);
+// capi_group.hip, the host side of a slide (muse_group_slide, muse_batch_slide_score_windowed): `count` rows' tails (k >= 1 samples
+// each, arguments checked by the caller) packed and enqueued on the copy stream into g->slide_dev; and the invalidation of what
+// described the rows from `first` on (rewrites++, hstats_rows)
+int slide_upload_tails(muse_group *g, int64_t count, const double *tails, int32_t k, int64_t tail_stride);
+void slide_invalidate(muse_group *g, int64_t first);
 void rows_slots_free(muse_ctx *ctx);                   // capi_rows.hip: the idle slots of muse_batch_run_rows (streams idle)
 int ilog2(int64_t n);                                  // capi_batch.hip
 // capi_huge.hip: FFT lengths above GENERIC_MAX_N up to HUGE_MAX_N (xcorr_huge.h)

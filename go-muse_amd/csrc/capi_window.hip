@@ -1,4 +1,5 @@
-// capi_window.hip -- the lag window of a batch (muse_batch_set_lag_window): the setting, its tables and the windowed all-scores pass
+// capi_window.hip -- the lag window of a batch (muse_batch_set_lag_window): the setting, its tables, the windowed all-scores pass, and
+// that pass fused with the slide of the group's rows (muse_batch_slide_score_windowed / _slide_run_windowed)
 // Part of the implementation of the C ABI declared in include/muse_hip.h (capi_internal.h: the handles and the helpers the
 // parts share).  Host-side orchestration only; there is no CPU compute fallback anywhere: without a gfx950 device every
 // compute entry point returns MUSE_ERR_NO_DEVICE.
@@ -33,20 +34,24 @@ extern "C" int muse_batch_lag_window(muse_batch *b, int32_t *max_lag)
     return MUSE_OK;
 }
 
-// muse_batch_score of a batch with a window (device selected, rows uploaded, M > 0, mv / lag allocated)
-int score_windowed(muse_batch *b)
+// the shifted-reference image and its window sums for window L, once per window (cached under win_L)
+static int window_tables(muse_batch *b, int L)
 {
+    if (b->win_L == L)
+        return MUSE_OK;
     muse_ctx *ctx = b->ctx;
     const hipStream_t st = b->stream();
-    const int L = std::min(b->lag_window, b->n / 2);
-    if (b->win_L != L) { // the shifted-reference image and its window sums, once per window
-        b->win_L = -1;
-        const long long e_len = window_e_len(b->N);
-        HIP_TRY(b->win_e.ensure(ctx, e_len, st));
-        HIP_TRY(b->win_pw.ensure(ctx, 2 * MUSE_LAG_WINDOW_MAX + 1, st));
-        HIP_TRY(launch_window_tables(b->xs, b->N, b->n, L, b->win_e.p, e_len, b->win_pw.p, st));
-        b->win_L = L;
-    }
+    b->win_L = -1;
+    const long long e_len = window_e_len(b->N);
+    HIP_TRY(b->win_e.ensure(ctx, e_len, st));
+    HIP_TRY(b->win_pw.ensure(ctx, 2 * MUSE_LAG_WINDOW_MAX + 1, st));
+    HIP_TRY(launch_window_tables(b->xs, b->N, b->n, L, b->win_e.p, e_len, b->win_pw.p, st));
+    b->win_L = L;
+    return MUSE_OK;
+}
+
+static WindowParams window_params(muse_batch *b, int L)
+{
     WindowParams p{};
     p.rows = b->g->rows;
     p.M = b->g->M;
@@ -60,9 +65,125 @@ int score_windowed(muse_batch *b)
     p.invNm1 = 1.0 / (double)(b->N - 1);
     p.mv = b->mv.p;
     p.lag = b->lag.p;
+    return p;
+}
+
+// muse_batch_score of a batch with a window (device selected, rows uploaded, M > 0, mv / lag allocated)
+int score_windowed(muse_batch *b)
+{
+    muse_ctx *ctx = b->ctx;
+    const hipStream_t st = b->stream();
+    const int L = std::min(b->lag_window, b->n / 2);
+    int rc = window_tables(b, L);
+    if (rc)
+        return rc;
+    const WindowParams p = window_params(b, L);
     LaunchTimer timer(ctx, false, st);
     HIP_TRY(timer.begin());
     HIP_TRY(launch_window(p, st));
     HIP_TRY(timer.end());
+    return MUSE_OK;
+}
+
+// ---- the slide and the windowed pass in one kernel (xcorr_window_slide.hip)
+extern "C" int muse_batch_slide_score_windowed(muse_batch *b, const double *tails, int32_t k, int64_t tail_stride, int32_t max_lag)
+{
+    // everything is checked before anything is enqueued: on an error the batch and the group are unchanged
+    if (!b)
+        return fail(MUSE_ERR_INVALID, "NULL batch");
+    muse_group *g = b->g;
+    const int64_t M = g->M;
+    if (k < 0 || k > g->N)
+        return fail(MUSE_ERR_INVALID, "slide by %d samples: outside 0 .. N = %d", k, g->N);
+    if (tail_stride < k)
+        return fail(MUSE_ERR_INVALID, "tail_stride %lld is smaller than k = %d", (long long)tail_stride, k);
+    if (!tails && M > 0 && k > 0)
+        return fail(MUSE_ERR_INVALID, "tails is NULL");
+    if (g->win_rows)
+        return fail(MUSE_ERR_INVALID, "the group has an open staging window");
+    if (max_lag < 0)
+        return fail(MUSE_ERR_INVALID, "a windowed pass needs a lag window >= 0");
+    if (max_lag > MUSE_LAG_WINDOW_MAX)
+        return fail(MUSE_ERR_UNSUPPORTED, "lag window %d > MUSE_LAG_WINDOW_MAX (%d): beyond it the direct product costs more than the transform",
+                    max_lag, MUSE_LAG_WINDOW_MAX);
+    if (g->f32)
+        return fail(MUSE_ERR_UNSUPPORTED, "the lag-window pass reads float64 groups only");
+    if (b->n > GENERIC_MAX_N || !b->xs)
+        return fail(MUSE_ERR_UNSUPPORTED, "the lag-window pass is built for series of up to %d samples", GENERIC_MAX_N);
+    if (b->windowed() && b->lag_window != max_lag)
+        return fail(MUSE_ERR_INVALID, "the batch has a lag window of %d of its own: it must be off or equal to the call's (%d)",
+                    b->lag_window, max_lag);
+    if (M == 0) // nothing to move, nothing to score
+        return MUSE_OK;
+    muse_ctx *ctx = b->ctx;
+    int rc = use_device(ctx);
+    if (rc)
+        return rc;
+    const hipStream_t st = b->stream();
+    rc = group_ready(g, st); // rows packed but not sent yet go first
+    if (rc)
+        return rc;
+    rc = ensure_scores(b);
+    if (rc)
+        return rc;
+    b->many_tiles = 0;
+    b->scores_exact = true;
+    const int L = std::min(max_lag, b->n / 2);
+    rc = window_tables(b, L);
+    if (rc)
+        return rc;
+    const WindowParams p = window_params(b, L);
+    if (k == 0) { // nothing moves and nothing is invalidated: the windowed pass alone
+        LaunchTimer timer(ctx, false, st);
+        HIP_TRY(timer.begin());
+        HIP_TRY(launch_window(p, st));
+        HIP_TRY(timer.end());
+        return MUSE_OK;
+    }
+    rc = slide_upload_tails(g, M, tails, k, tail_stride);
+    if (rc)
+        return rc;
+    // as muse_group_slide: the kernel rewrites rows that work enqueued earlier on any stream of the device may still be reading
+    // (the tails and the tables have landed with it), and the call returns once the kernel has finished
+    HIP_TRY(hipDeviceSynchronize());
+    slide_invalidate(g, 0);
+    LaunchTimer timer(ctx, false, st);
+    HIP_TRY(timer.begin());
+    HIP_TRY(launch_window_slide(p, (const double *)g->slide_dev.p, k, st));
+    HIP_TRY(timer.end());
+    HIP_TRY(hipStreamSynchronize(st));
+    return MUSE_OK;
+}
+
+extern "C" int muse_batch_slide_run_windowed(muse_batch *b, const double *tails, int32_t k, int64_t tail_stride,
+                                             const int32_t *group_id, int32_t G, int32_t max_lag, int32_t top_n, double threshold,
+                                             int32_t sign_filter, int32_t abs_scores, int64_t *out_series, int32_t *out_lag,
+                                             double *out_score, int32_t *out_count, double *out_mean_abs)
+{
+    // (the selection's own argument checks come first: a refusal leaves the rows where they were)
+    if (sign_filter < -1 || sign_filter > 1)
+        return fail(MUSE_ERR_INVALID, "sign_filter must be -1, 0 or 1");
+    if (group_id && G < 0)
+        return fail(MUSE_ERR_INVALID, "negative group count");
+    int rc = muse_batch_slide_score_windowed(b, tails, k, tail_stride, max_lag);
+    if (rc)
+        return rc;
+    std::vector<muse_record> sel;
+    rc = run_select(b, group_id, G, 0, max_lag, top_n, threshold, sign_filter, abs_scores, sel, true, false);
+    if (rc)
+        return rc;
+    emit(sel, out_series, out_lag, out_score, out_count, out_mean_abs);
+    return MUSE_OK;
+}
+
+// test hook: the planner alone (xcorr_window_slide.hip), no device
+extern "C" int muse_test_slide_score_plan(int32_t N, int32_t k, int32_t wide, int32_t *load_bytes, int32_t *store_bytes)
+{
+    if (!load_bytes || !store_bytes || N < 2 || k < 0 || k > N || (wide != 0 && N % 2 != 0))
+        return fail(MUSE_ERR_INVALID, "bad slide-score plan arguments (N >= 2, 0 <= k <= N, wide rows have an even N)");
+    int lb = 0, sb = 0;
+    slide_score_plan(N, k, wide != 0, &lb, &sb);
+    *load_bytes = lb;
+    *store_bytes = sb;
     return MUSE_OK;
 }

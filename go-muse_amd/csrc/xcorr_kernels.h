@@ -162,6 +162,13 @@ inline bool window_wide(const double *rows, long long stride) { return stride % 
 inline long long window_e_len(int N) { return (long long)((N + WIN_KC - 1) / WIN_KC) * WIN_KC + WIN_E_TAIL; }
 hipError_t launch_window_tables(const double *xs, int N, int n, int L, double *e, long long e_len, double *pw, hipStream_t stream);
 hipError_t launch_window(const WindowParams &p, hipStream_t stream);
+// ---- the same while the rows slide (xcorr_window_slide.hip; muse_batch_slide_score_windowed): xcorr_window_mfma over the NEW rows
+// -- old row[k .. N) followed by tails[r * k + 0 .. k), a dense M x k device buffer, 16-byte aligned -- which are stored in place on
+// the way: one read and one write of the rows instead of launch_row_slide's pair plus launch_window's read, the same bits as the two.
+// Dense rows (stride == N), 1 <= k <= N.  slide_score_plan (pure host function): the widths the kernel moves in -- 16-byte loads
+// iff the rows are wide (window_wide) and k is even, 16-byte stores iff they are wide, 8 bytes otherwise
+void slide_score_plan(int N, int k, bool wide, int *load_bytes, int *store_bytes);
+hipError_t launch_window_slide(const WindowParams &p, const double *tails, int k, hipStream_t stream);
 // ---- the same for few rows of long series (xcorr_window_split.hip; muse_batch_run_rows_windowed): K split across workgroups.
 // window_rows_plan (pure host function): the slice count S for M rows of N samples on num_cus CUs -- the largest S with blocks x S
 // (blocks = ceil(M / 16)) within the CUs and S <= min(chunks, max(WIN_ROWS_FULL_SPLIT, chunks / WIN_ROWS_MIN_CHUNKS)): one chunk of

@@ -572,6 +572,50 @@ class DeviceBatch:
                                                             B.i32ptr(lag), B.dptr(mv)))
         return lag, mv
 
+    # ---- the slide of the group's rows and the windowed pass over the new rows in one kernel
+    def _tails2d(self, tails):
+        """tails (M, k) as DeviceGroup.slide prepares them -> (array, k, stride, moved)"""
+        tails = np.asarray(tails, dtype=np.float64)
+        if tails.ndim != 2:
+            raise ValueError("tails must be 2-D (M, k)")
+        count, k = tails.shape
+        if count != self.dgroup.M:
+            raise ValueError("tails has %d rows, the group has %d: the whole group slides" % (count, self.dgroup.M))
+        if count > 0 and k > 0 and (tails.strides[1] != 8 or (count > 1 and tails.strides[0] < 8 * k)):
+            tails = np.ascontiguousarray(tails)
+        stride = tails.strides[0] // 8 if count > 1 and k > 0 else k
+        return tails, k, stride, count > 0 and k > 0
+
+    def slide_score_windowed(self, tails, max_lag):
+        """muse_batch_slide_score_windowed: DeviceGroup.slide(tails) over the WHOLE group and set_lag_window(max_lag) + score() over
+        the new rows in one pass over HBM -- the same rows and the same scores (read_scores), bit for bit; tails: (M, k).  This
+        batch's own lag window is not touched.  Waits for the device and returns when the kernel has finished."""
+        tails, k, stride, moved = self._tails2d(tails)
+        B.check(B.load().muse_batch_slide_score_windowed(self._h, tails.ctypes.data_as(B._dp), k, stride, int(max_lag)))
+        if moved:
+            self.dgroup.slides += 1
+
+    def slide_run_windowed(self, tails, max_lag, group_id=None, G=0, top_n=20, threshold=0.0, sign_filter=0, abs_scores=True):
+        """muse_batch_slide_run_windowed: slide_score_windowed followed by Batch.Run's selection (max_lag is the window and the
+        Results.MaxLag); -> (series, lag, score, mean_abs) as run()"""
+        tails, k, stride, moved = self._tails2d(tails)
+        cap = max(int(top_n), 1)
+        o_s = np.zeros(cap, dtype=np.int64)
+        o_l = np.zeros(cap, dtype=np.int32)
+        o_v = np.zeros(cap)
+        cnt, mean = ctypes.c_int32(0), ctypes.c_double(0)
+        gid = None
+        if group_id is not None:
+            gid = np.ascontiguousarray(group_id, dtype=np.int32)
+        B.check(B.load().muse_batch_slide_run_windowed(
+            self._h, tails.ctypes.data_as(B._dp), k, stride, B.i32ptr(gid) if gid is not None else None, int(G), int(max_lag),
+            int(top_n), float(threshold), int(sign_filter), 1 if abs_scores else 0,
+            B.i64ptr(o_s), B.i32ptr(o_l), B.dptr(o_v), ctypes.byref(cnt), ctypes.byref(mean)))
+        if moved:
+            self.dgroup.slides += 1
+        c = cnt.value
+        return o_s[:c].copy(), o_l[:c].copy(), o_v[:c].copy(), float(mean.value)
+
     def run_groups(self, group_id, G, series_offset=0, abs_scores=True):
         """this shard's winner per label group, unfiltered (muse_batch_run_groups): (records[G], state[G])"""
         rec = np.zeros(max(int(G), 1), dtype=B.RECORD_DTYPE)

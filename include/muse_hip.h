@@ -326,6 +326,28 @@ int muse_batch_run_row_ptrs_windowed(muse_batch *tmpl, const double *const *rows
                                      int32_t max_lag, int32_t abs_scores, muse_record *out_winner, uint8_t *out_state);
 int muse_batch_run_group_rows_windowed(muse_batch *tmpl, muse_group *src, const int64_t *rows, int64_t M,
                                        int32_t max_lag, int32_t abs_scores, muse_record *out_winner, uint8_t *out_state);
+/* THE SLIDE AND THE WINDOWED PASS IN ONE KERNEL (xcorr_window_slide.hip): one read and one write of the rows where the two calls
+ * below move them three times.  muse_batch_slide_score_windowed is equivalent to
+ *   muse_group_slide(the batch's group, 0, M, tails, k, tail_stride)  followed by  a windowed all-scores pass with window max_lag:
+ * afterwards the group holds the slid rows -- BIT FOR BIT those of muse_group_slide -- and muse_batch_read_scores returns, BIT FOR
+ * BIT, what muse_batch_set_lag_window(max_lag) + muse_batch_score give over them.  The whole group always slides (a row range would
+ * leave scores of mixed age); everything muse_group_slide says about ordering (the call waits until the device is idle and returns
+ * after its kernel has finished), about `tails` and about what goes with the old rows (the spectrum cache, kept statistics, kernel
+ * selection) holds here.  The window is an argument of the call, as with the other _windowed entry points: the batch's own
+ * lag_window must be off or equal to max_lag and is not touched; the window's tables are kept for the next call.
+ * k == 0 or M == 0 is not an error: nothing moves and nothing is invalidated (with M > 0 the call is the windowed pass alone).
+ * Refused, every handle left as it was (everything is checked before anything is enqueued): a NULL batch, k < 0, k > N,
+ * tail_stride < k, NULL tails with M > 0 and k > 0, an open staging window, max_lag < 0, or a batch whose own window is on and
+ * differs from max_lag (MUSE_ERR_INVALID); max_lag > MUSE_LAG_WINDOW_MAX, a float32-storage group, or series longer than 65536
+ * samples (MUSE_ERR_UNSUPPORTED).
+ * muse_batch_slide_run_windowed is that call followed by Batch.Run's selection over the scores, outputs as muse_batch_run; max_lag
+ * is both the window and the Results.MaxLag of the selection (as in muse_batch_run_many_windowed).  A sign_filter outside -1 .. 1
+ * or a negative G with group_id is refused before anything moves. */
+int muse_batch_slide_score_windowed(muse_batch *b, const double *tails, int32_t k, int64_t tail_stride, int32_t max_lag);
+int muse_batch_slide_run_windowed(muse_batch *b, const double *tails, int32_t k, int64_t tail_stride,
+                                  const int32_t *group_id, int32_t G, int32_t max_lag, int32_t top_n, double threshold,
+                                  int32_t sign_filter, int32_t abs_scores, int64_t *out_series, int32_t *out_lag,
+                                  double *out_score, int32_t *out_count, double *out_mean_abs);
 /* muse_batch_score + D2H of the per-series results (lag[M], mv[M]). */
 int muse_batch_scores(muse_batch *b, int32_t *lag, double *mv);
 /* Batch.Run + Results.Update + Results.Fetch (muse_batch.go:99-130,

@@ -104,6 +104,11 @@ int muse_test_window_rows_slices(muse_ctx *ctx, int32_t S);
  * back before the slot is returned: without it only the winner is observable. */
 int muse_test_run_rows_windowed_scores(muse_batch *tmpl, const double *rows, int64_t M, int64_t row_stride, int32_t max_lag,
                                        int32_t *lag_out, double *mv_out);
+/* The load / store widths of muse_batch_slide_score_windowed's kernel (xcorr_window_slide.hip), a pure host function (no device
+ * needed): for rows of N samples slid by k, `wide` = the rows are 16-byte aligned (even N: the kernel's WIDE mapping) -- *load_bytes
+ * = 16 iff wide and k is even (8 otherwise: the same samples from two loads), *store_bytes = 16 iff wide.  MUSE_ERR_INVALID for
+ * N < 2, k outside 0 .. N, wide with an odd N, or a NULL out pointer. */
+int muse_test_slide_score_plan(int32_t N, int32_t k, int32_t wide, int32_t *load_bytes, int32_t *store_bytes);
 
 #ifdef __cplusplus
 }
