@@ -142,7 +142,10 @@ def test_sign_filter_tie_is_exact(golden, oracle):
 
 @pytest.mark.parametrize("N", [5, 8, 12, 16, 100, 480, 512, 1000])
 def test_oracle_exactness_vs_long_double_direct(oracle, N):
-    """The oracle's own error: FFT path vs direct long-double correlation."""
+    """The oracle's own error: FFT path vs direct long-double correlation.
+
+    The direct correlation is O(n^2), so this stops at N = 1000.  Above that -- up to n = 2^20 -- the oracle is held to
+    K_ORACLE * log2(n) * 2^-53 of an O(N) long-double sum at planted winning indices: tests/test_lag_sweep_cpu.py."""
     rng = np.random.default_rng(N)
     ref = rng.standard_normal(N)
     y = rng.standard_normal(N) + 0.5 * np.roll(ref, 3)
