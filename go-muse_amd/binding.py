@@ -29,6 +29,7 @@ MUSE_ERR_UNSUPPORTED = -6
 MUSE_ERR_NOMEM = -7
 MUSE_ERR_EMPTY = -8
 MUSE_LAG_WINDOW_MAX = 63
+MUSE_IN_WINDOW_UNSUPPORTED, MUSE_IN_WINDOW_PLAIN, MUSE_IN_WINDOW_MFMA, MUSE_IN_WINDOW_MASKED = 0, 1, 2, 3   # muse_hip_test.h
 
 
 class MuseRecord(ctypes.Structure):
@@ -88,6 +89,12 @@ SIGNATURES = {
     "muse_test_window_rows_plan": (ctypes.c_int, [_i64, _i32, _i32, _i32p, _i32p]),
     "muse_test_window_rows_slices": (ctypes.c_int, [_vp, _i32]),
     "muse_test_run_rows_windowed_scores": (ctypes.c_int, [_vp, _dp, _i64, _i64, _i32, _i32p, _dp]),
+    "muse_batch_score_in_window": (ctypes.c_int, [_vp, _i32]),
+    "muse_batch_run_in_window": (ctypes.c_int, [_vp, _i32p, _i32, _i32, _i32, _f64, _i32, _i32,
+                                                _i64p, _i32p, _dp, _i32p, _dp]),
+    "muse_test_in_window_plan": (ctypes.c_int, [_i32, _i32, _i32, _i32p]),
+    "muse_test_in_window_force_transform": (ctypes.c_int, [_vp, _i32]),
+    "muse_test_last_in_window_path": (ctypes.c_int, [_vp, _i32p]),
     "muse_batch_set_lag_window": (ctypes.c_int, [_vp, _i32]),
     "muse_batch_lag_window": (ctypes.c_int, [_vp, _i32p]),
     "muse_batch_run": (ctypes.c_int, [_vp, _i32p, _i32, _i32, _i32, _f64, _i32, _i32,

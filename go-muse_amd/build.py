@@ -182,3 +182,20 @@ def build_rows_window_test(force=False):
                            "-I" + os.path.join(PKG, "host"), src, "-o", ROWS_WINDOW_TEST,
                            "-L" + LIBDIR, "-lmuse_hip", "-pthread", "-Wl,-rpath," + LIBDIR])
     return ROWS_WINDOW_TEST
+
+
+IN_WINDOW_TEST = os.path.join(LIBDIR, "muse_in_window_test")
+
+
+def build_in_window_test(force=False):
+    """g++ build of the C++ host mirror's wide-window program (host/muse_in_window_test.cpp; tests/test_gpu_in_window.py)."""
+    src = os.path.join(PKG, "host", "muse_in_window_test.cpp")
+    hdr = os.path.join(PKG, "host", "muse.hpp")
+    build()
+    if (not force and os.path.exists(IN_WINDOW_TEST)
+            and os.path.getmtime(IN_WINDOW_TEST) >= max(os.path.getmtime(src), os.path.getmtime(hdr), os.path.getmtime(LIB))):
+        return IN_WINDOW_TEST
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-I" + os.path.join(ROOT, "include"),
+                           "-I" + os.path.join(PKG, "host"), src, "-o", IN_WINDOW_TEST,
+                           "-L" + LIBDIR, "-lmuse_hip", "-pthread", "-Wl,-rpath," + LIBDIR])
+    return IN_WINDOW_TEST

@@ -588,7 +588,7 @@ extern "C" int muse_batch_score(muse_batch *b)
     return batch_score(b, true);
 }
 
-int batch_score(muse_batch *b, bool allow_spectrum_cache)
+int batch_score(muse_batch *b, bool allow_spectrum_cache, int win_L)
 {
     if (!b)
         return fail(MUSE_ERR_INVALID, "NULL batch");
@@ -607,7 +607,8 @@ int batch_score(muse_batch *b, bool allow_spectrum_cache)
     if (rc)
         return rc;
     b->many_tiles = 0;
-    if (b->windowed()) { // the best match inside +-MaxLag, directly (xcorr_window.hip): no transform, never screened
+    b->in_window_path = 0;
+    if (win_L < 0 && b->windowed()) { // the best match inside +-MaxLag, directly (xcorr_window.hip): no transform, never screened
         b->scores_exact = true;
         return score_windowed(b);
     }
@@ -632,6 +633,14 @@ int batch_score(muse_batch *b, bool allow_spectrum_cache)
     const int variant = kc.variant;
     if (kc.gsmall)
         p.gsmall = kc.gsmall;
+    if (win_L >= 0) { // the masked argmax: built into the default kernels of n = 512 ... 4096 and the rescaling kernel behind the n = 4096 one
+        if (!(variant == KERNEL_R16_FOLD || variant == KERNEL_R16_OCC3 || (variant == KERNEL_SMALL && b->logn <= 11)) || 2 * win_L > b->n)
+            return fail(MUSE_ERR_UNSUPPORTED, "the masked transform pass runs on the default kernels of FFT lengths 512 ... 4096");
+        b->in_window_variant = variant;
+        p.win = 1;
+        p.win_lpos = win_L;
+        p.win_lneg = 2 * win_L == b->n ? win_L - 1 : win_L; // index n / 2 is lag +n/2 (xcorr.go:192-194), as in window_params
+    }
     if (variant == KERNEL_GENERIC && b->n <= GENERIC_LDS_MAX_N)
         p.gscratch = nullptr; // the generic kernel takes a non-NULL scratch pointer as "work in global memory"
     LaunchTimer timer(ctx, false, st); // (brackets the fused launch alone: not the counter reset in front of it, not the redo launch behind it)
@@ -649,7 +658,7 @@ int batch_score(muse_batch *b, bool allow_spectrum_cache)
         // two host threads one builds and the other one's reader sits behind that writer on the stream
         ZcPlan plan;
         std::unique_lock<std::mutex> zc_lock(b->g->ready_mu, std::defer_lock);
-        if (allow_spectrum_cache && spectrum_cache_candidate(b, variant)) {
+        if (allow_spectrum_cache && win_L < 0 && spectrum_cache_candidate(b, variant)) { // (a masked pass always reads the rows)
             zc_lock.lock();
             rc = plan_spectrum_cache(b, plan);
             if (rc)
@@ -757,7 +766,17 @@ extern "C" int muse_batch_kernel_name(muse_batch *b, char *name, int32_t cap)
     // (the names rocprofv3 prints for the instantiations: profiles/r*_counters.json is keyed by them)
     char k[96] = "xcorr_fused_generic";
     const char *padded = b->N < b->n ? "true" : "false", *f32 = b->g->f32 ? "true" : "false";
-    if (b->many_tiles > 0) { // (the packed pass that filled mv / lag: it is an argument of a call, not a setting the next pass takes)
+    if (b->in_window_path == MUSE_IN_WINDOW_MASKED) { // (as many_tiles below: the pass that filled mv / lag, an argument of a call)
+        if (b->n == 4096 && b->in_window_variant == KERNEL_R16_OCC3) // (the learned hand-off, or no correction table)
+            snprintf(k, sizeof(k), "xcorr_fused_n4096_occ4<%s, 3, false, %s, true>", padded, f32);
+        else if (b->n == 4096)
+            snprintf(k, sizeof(k), "xcorr_fused_n4096_fold<false, %s, %s, true>", padded, f32);
+        else
+            snprintf(k, sizeof(k), "xcorr_fused_small<%d, %s, false, %s, true>", b->logn, padded, f32);
+    } else if (b->in_window_path == MUSE_IN_WINDOW_MFMA) { // (the direct product with the call's window, whatever the batch's own setting)
+        snprintf(k, sizeof(k), "xcorr_window_mfma<%d, %s>", (2 * b->in_window_L + 1 + 15) / 16,
+                 window_wide(b->g->rows, b->g->stride) ? "true" : "false");
+    } else if (b->many_tiles > 0) { // (the packed pass that filled mv / lag: it is an argument of a call, not a setting the next pass takes)
         snprintf(k, sizeof(k), "xcorr_window_many_mfma<%d, %s>", b->many_tiles, window_wide(b->g->rows, b->g->stride) ? "true" : "false");
     } else if (b->windowed()) {
         const int L = std::min(b->lag_window, b->n / 2);

@@ -164,6 +164,7 @@ struct muse_ctx {
     std::atomic<int64_t> zc_min_rows{ZC_MIN_ROWS};
     std::atomic<int64_t> zc_budget{-1};
     std::atomic<int> win_rows_slices{0}; // test hook (muse_test_window_rows_slices): 0 = window_rows_plan; S >= 1 forces the slice count of the windowed Muse.Run
+    std::atomic<bool> in_window_force{false}; // test hook (muse_test_in_window_force_transform): float64 windows <= MUSE_LAG_WINDOW_MAX of muse_batch_score_in_window take the masked transform kernels
     std::atomic<bool> gather_nt{false}; // measurement hook (muse_test_gather_nontemporal): the row gather's stores bypass the caches
     // Handles may be released in any order (Go finalizers, Python GC): the
     // context lives until it is destroyed AND its last group/batch is freed.
@@ -343,6 +344,9 @@ struct muse_batch {
     // > 0: the batch's scores come from a packed launch of muse_batch_score_many_windowed (capi_window_many.hip) of this many
     // accumulator tiles (muse_batch_kernel_name names it); any other scoring pass of the batch clears it
     int32_t many_tiles = 0;
+    // the path the batch's scores came by when the last scoring pass was muse_batch_score_in_window (MUSE_IN_WINDOW_*,
+    // muse_hip_test.h; MASKED: in_window_L = the window, muse_batch_kernel_name names the masked instantiation); any other scoring pass clears it
+    int32_t in_window_path = 0, in_window_L = -1, in_window_variant = 0; // (_variant: the KERNEL_* the masked pass launched first)
 };
 
 int use_device(muse_ctx *ctx);
@@ -424,7 +428,10 @@ int build_spectrum(muse_ctx *ctx, const double *ref_host, int N, int n, int norm
 hipError_t ensure_gscratch(muse_ctx *ctx, int64_t n, int slices_per_cu = muse::GSCRATCH_SLICES_PER_CU);
 hipError_t ensure_twl(muse_ctx *ctx, int64_t n);
 int ensure_scores(muse_batch *b);
-int batch_score(muse_batch *b, bool allow_spectrum_cache); // capi_batch.hip: muse_batch_score (the many-references fallback passes false)
+// capi_batch.hip: muse_batch_score (the many-references fallback passes false).  win_L >= 0: the MASKED pass of muse_batch_score_in_window --
+// the same launch sequence with the argmax of the transform kernels restricted to +-win_L (n = 512 ... 4096; the batch's own window and
+// the group's spectrum cache are neither read nor touched)
+int batch_score(muse_batch *b, bool allow_spectrum_cache, int win_L = -1);
 // the spectrum cache's policy, a pure host function: what a pass over `rows` rows of length N does about a cache
 // that does not exist yet -- nothing, build one of *bytes for *rows_cached rows, or decline for lack of memory
 enum { ZC_POLICY_NONE = 0, ZC_POLICY_BUILD = 1, ZC_POLICY_DECLINED = 2 };

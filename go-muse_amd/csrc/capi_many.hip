@@ -91,8 +91,10 @@ extern "C" int muse_batch_score_many(muse_batch *const *bs, int32_t R)
         }
         return MUSE_OK;
     }
-    for (int r = 0; r < R; r++)
+    for (int r = 0; r < R; r++) {
         bs[r]->many_tiles = 0;
+        bs[r]->in_window_path = 0;
+    }
     int rc = use_device(ctx);
     if (rc)
         return rc;

@@ -187,6 +187,7 @@ static int screen_finish(muse_batch *b, int32_t top_n, double threshold, int32_t
     HIP_TRY(hipMemcpyAsync(b->err_host, b->err_dev, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
     b->scores_exact = false;
     b->many_tiles = 0;
+    b->in_window_path = 0;
     return MUSE_OK;
 }
 

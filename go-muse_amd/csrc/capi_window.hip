@@ -1,5 +1,6 @@
-// capi_window.hip -- the lag window of a batch (muse_batch_set_lag_window): the setting, its tables, the windowed all-scores pass, and
-// that pass fused with the slide of the group's rows (muse_batch_slide_score_windowed / _slide_run_windowed)
+// capi_window.hip -- the lag window of a batch (muse_batch_set_lag_window): the setting, its tables, the windowed all-scores pass,
+// that pass fused with the slide of the group's rows (muse_batch_slide_score_windowed / _slide_run_windowed), and the window of any
+// width as an argument (muse_batch_score_in_window / _run_in_window: the direct product or the masked transform kernels)
 // Part of the implementation of the C ABI declared in include/muse_hip.h (capi_internal.h: the handles and the helpers the
 // parts share).  Host-side orchestration only; there is no CPU compute fallback anywhere: without a gfx950 device every
 // compute entry point returns MUSE_ERR_NO_DEVICE.
@@ -127,6 +128,7 @@ extern "C" int muse_batch_slide_score_windowed(muse_batch *b, const double *tail
     if (rc)
         return rc;
     b->many_tiles = 0;
+    b->in_window_path = 0;
     b->scores_exact = true;
     const int L = std::min(max_lag, b->n / 2);
     rc = window_tables(b, L);
@@ -172,6 +174,108 @@ extern "C" int muse_batch_slide_run_windowed(muse_batch *b, const double *tails,
     rc = run_select(b, group_id, G, 0, max_lag, top_n, threshold, sign_filter, abs_scores, sel, true, false);
     if (rc)
         return rc;
+    emit(sel, out_series, out_lag, out_score, out_count, out_mean_abs);
+    return MUSE_OK;
+}
+
+// ---- the window as an argument, any width (muse_batch_score_in_window)
+// The dispatch, a pure host function: which pass scores series of N samples (float32 storage or not) inside +-max_lag.
+//   L == n / 2                                        : the window is every lag -- the plain pass of batch_score, any length, any storage
+//   float64, L <= MUSE_LAG_WINDOW_MAX, n <= 65536      : the direct product (score_windowed), unless `force_transform` and the length has masked kernels
+//   n in {512, 1024, 2048, 4096}, L > 63 or float32    : the transform kernels with a masked argmax (the WIN builds)
+//   anything else                                      : not built
+static int in_window_plan(int32_t N, bool f32, int32_t max_lag, bool force_transform)
+{
+    const int64_t n = muse_next_pow2((double)N);
+    const int64_t L = std::min<int64_t>(max_lag, n / 2);
+    if (2 * L == n)
+        return MUSE_IN_WINDOW_PLAIN;
+    const bool masked_len = n == 512 || n == 1024 || n == 2048 || n == 4096;
+    if (!f32 && L <= MUSE_LAG_WINDOW_MAX && n <= GENERIC_MAX_N && !(force_transform && masked_len))
+        return MUSE_IN_WINDOW_MFMA;
+    return masked_len ? MUSE_IN_WINDOW_MASKED : MUSE_IN_WINDOW_UNSUPPORTED;
+}
+
+extern "C" int muse_test_in_window_plan(int32_t N, int32_t f32, int32_t max_lag, int32_t *path)
+{
+    if (!path || N < 2 || max_lag < 0)
+        return fail(MUSE_ERR_INVALID, "bad in-window plan arguments (N >= 2, max_lag >= 0)");
+    *path = in_window_plan(N, f32 != 0, max_lag, false);
+    return MUSE_OK;
+}
+
+extern "C" int muse_test_in_window_force_transform(muse_ctx *ctx, int32_t on)
+{
+    if (!ctx)
+        return fail(MUSE_ERR_INVALID, "NULL context");
+    ctx->in_window_force.store(on != 0);
+    return MUSE_OK;
+}
+
+extern "C" int muse_test_last_in_window_path(muse_batch *b, int32_t *path)
+{
+    if (!b || !path)
+        return fail(MUSE_ERR_INVALID, "NULL argument");
+    *path = b->in_window_path;
+    return MUSE_OK;
+}
+
+extern "C" int muse_batch_score_in_window(muse_batch *b, int32_t max_lag)
+{
+    // everything is checked before anything is enqueued: on a refusal the batch is unchanged
+    if (!b)
+        return fail(MUSE_ERR_INVALID, "NULL batch");
+    if (max_lag < 0)
+        return fail(MUSE_ERR_INVALID, "a windowed pass needs a lag window >= 0");
+    if (b->windowed() && b->lag_window != max_lag)
+        return fail(MUSE_ERR_INVALID, "the batch has a lag window of %d of its own: it must be off or equal to the call's (%d)",
+                    b->lag_window, max_lag);
+    const int path = in_window_plan(b->N, b->g->f32, max_lag, b->ctx->in_window_force.load());
+    if (path == MUSE_IN_WINDOW_UNSUPPORTED || (path == MUSE_IN_WINDOW_MFMA && !b->xs))
+        return fail(MUSE_ERR_UNSUPPORTED, "a lag window of %d over series of %d samples%s is not built: wider than MUSE_LAG_WINDOW_MAX (%d) and for "
+                    "float32 storage the window is a masked argmax of the transform kernels of FFT lengths 512 ... 4096",
+                    max_lag, b->N, b->g->f32 ? " in float32 storage" : "", MUSE_LAG_WINDOW_MAX);
+    const int L = std::min(max_lag, b->n / 2);
+    const int32_t own = b->lag_window;
+    int rc;
+    if (path == MUSE_IN_WINDOW_MASKED) {
+        rc = batch_score(b, false, L);
+    } else { // the pass a batch with (MFMA) / without (PLAIN) a window of its own takes; the setting is put back, whatever the outcome
+        b->lag_window = path == MUSE_IN_WINDOW_MFMA ? max_lag : -1;
+        rc = batch_score(b, true);
+        b->lag_window = own;
+    }
+    if (rc)
+        return rc;
+    if (b->g->M == 0)
+        return MUSE_OK;
+    b->scores_exact = true;
+    b->last_path = MUSE_RUN_PATH_FP64;
+    b->last_screened = false;
+    b->in_window_path = path;
+    b->in_window_L = L;
+    return MUSE_OK;
+}
+
+extern "C" int muse_batch_run_in_window(muse_batch *b, const int32_t *group_id, int32_t G, int32_t max_lag, int32_t top_n,
+                                        double threshold, int32_t sign_filter, int32_t abs_scores, int64_t *out_series,
+                                        int32_t *out_lag, double *out_score, int32_t *out_count, double *out_mean_abs)
+{
+    // (the selection's own argument checks come first, as in muse_batch_slide_run_windowed)
+    if (sign_filter < -1 || sign_filter > 1)
+        return fail(MUSE_ERR_INVALID, "sign_filter must be -1, 0 or 1");
+    if (group_id && G < 0)
+        return fail(MUSE_ERR_INVALID, "negative group count");
+    int rc = muse_batch_score_in_window(b, max_lag);
+    if (rc)
+        return rc;
+    const int32_t path = b->in_window_path, L = b->in_window_L;
+    std::vector<muse_record> sel;
+    rc = run_select(b, group_id, G, 0, max_lag, top_n, threshold, sign_filter, abs_scores, sel, true, false);
+    if (rc)
+        return rc;
+    b->in_window_path = path; // (the selection scores nothing: the scores are still this pass's)
+    b->in_window_L = L;
     emit(sel, out_series, out_lag, out_score, out_count, out_mean_abs);
     return MUSE_OK;
 }

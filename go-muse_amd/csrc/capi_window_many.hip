@@ -177,6 +177,7 @@ extern "C" int muse_batch_score_many_windowed(muse_batch *const *bs, int32_t R, 
             bs[r]->last_path = MUSE_RUN_PATH_FP64;
             bs[r]->last_screened = false;
             bs[r]->many_tiles = r1 - r0 > 1 ? tiles_of[(size_t)launch_of[(size_t)r0]] : 0;
+            bs[r]->in_window_path = 0;
         }
         r0 = r1;
     }

@@ -97,6 +97,25 @@ __device__ __forceinline__ double2 ldg2u(gptr<double2> p, unsigned i)
     return make_double2(x.x, x.y);
 }
 
+// Masked argmax (the WIN builds; FusedParams::win_lpos / ::win_lneg, nl = n - win_lneg): a thread holds the value of cc index
+// base + STEP m in v[m] (BITREV: in v[bit-reversed m]); every value whose index lies outside the lag window, lpos < index < nl,
+// becomes +0.0 in front of maxAbsIndex.  A select, not a multiply: a NaN outside the window goes with the rest.  The two bounds
+// are taken relative to the thread's base once (two registers, formed here and not hoisted out of the pair loop), so that each
+// register costs two compares against a literal and four selects, and no scalar register holds a bound per register.
+template <bool BITREV, int STEP>
+__device__ __forceinline__ void mask_window(double2 (&v)[16], const int base, const int lpos, const int nl)
+{
+    int a = lpos - base, b = nl - base;
+    asm volatile("" : "+v"(a), "+v"(b));
+#pragma unroll
+    for (int m = 0; m < 16; m++) {
+        const int k = BITREV ? ((m & 1) << 3) | ((m & 2) << 1) | ((m & 4) >> 1) | ((m & 8) >> 3) : m;
+        const bool in = STEP * m <= a || STEP * m >= b;
+        v[k].x = in ? v[k].x : 0.0;
+        v[k].y = in ? v[k].y : 0.0;
+    }
+}
+
 // One LDS transpose in two half rounds through the 8 x 272 buffer (positions in
 // double2 units).  Layouts (same bank analysis as xcorr_kernels.hip):
 //   A: writer (b = hi, c = lo) output k1 -> 272*(k1&7) + t

@@ -80,6 +80,10 @@ struct FusedParams {
     // registers; formed by the kernel (N is a run-time value in the builds for zero-padded series) they come out of the vector
     // divider, and wave-uniform values in vector registers were what those builds parked in scratch
     double invN, invNm1;
+    // masked argmax (the WIN builds of xcorr_r16_fold.hip, xcorr_r16_occ4.hip and xcorr_small.hip; muse_batch_score_in_window): win != 0 ->
+    // index i of cc takes part in maxAbsIndex iff i <= win_lpos || i >= n - win_lneg (WindowParams::L / ::Lneg); every other value
+    // is replaced by +0.0 in front of the argmax.  Last in the structure: the offsets of everything above are what they were.
+    int win, win_lpos, win_lneg;
 };
 inline FusedParams with_reciprocals(FusedParams p)
 {

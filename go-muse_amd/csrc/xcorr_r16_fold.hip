@@ -31,7 +31,9 @@ namespace muse {
 // PADDED (2048 < N < 4096, leading zero pad): as in xcorr_r16_fast.hip -- the transforms run on d, sum d is read
 // off the DC bin and the 16 values a lane ends with are corrected by -m c1[index] before the argmax.
 // F32: float32-storage group (half the HBM bytes; samples widened exactly on consumption, same float64 arithmetic)
-template <bool TIMING = false, bool PADDED = false, bool F32 = false>
+// WIN: masked argmax (muse_batch_score_in_window): the values outside the lag window p.win_lpos / p.win_lneg are replaced by +0.0
+// right in front of the argmax (behind the PADDED correction); everything else is the kernel as it is
+template <bool TIMING = false, bool PADDED = false, bool F32 = false, bool WIN = false>
 __global__ __launch_bounds__(OCC_THREADS, 4) void xcorr_fused_n4096_fold(const FusedParams p)
 {
     using namespace occ4;
@@ -199,6 +201,8 @@ __global__ __launch_bounds__(OCC_THREADS, 4) void xcorr_fused_n4096_fold(const F
                 }
             }
         }
+        if (WIN) // cc index t + 256 m3 at v[BR16(m3)]
+            mask_window<true, 256>(v, tl(), p.win_lpos, 4096 - p.win_lneg);
         clk.template stamp<11>();
         // float32 rows take 34 registers instead of 66: room to request them BEFORE the argmax, which then runs under
         // the HBM latency (float64 rows: behind it, there is no register left to land them in)
@@ -601,6 +605,21 @@ hipError_t launch_fused_fold(const FusedParams &p_in, int num_cus, hipStream_t s
     if (p.N < 4096 && !p.c1) // leading zero pad: needs the batch's correction table
         return hipErrorInvalidValue;
     const dim3 g((unsigned)grid), b(OCC_THREADS);
+    if (p.win) { // the masked argmax (muse_batch_score_in_window)
+        if (p.win_lpos < 0 || p.win_lneg < 0 || p.win_lpos > 2048 || p.win_lneg > p.win_lpos)
+            return hipErrorInvalidValue;
+        if (p.rows32) {
+            if (p.N < 4096)
+                hipLaunchKernelGGL((xcorr_fused_n4096_fold<false, true, true, true>), g, b, 0, stream, p);
+            else
+                hipLaunchKernelGGL((xcorr_fused_n4096_fold<false, false, true, true>), g, b, 0, stream, p);
+        } else if (p.N < 4096) {
+            hipLaunchKernelGGL((xcorr_fused_n4096_fold<false, true, false, true>), g, b, 0, stream, p);
+        } else {
+            hipLaunchKernelGGL((xcorr_fused_n4096_fold<false, false, false, true>), g, b, 0, stream, p);
+        }
+        return hipGetLastError();
+    }
     if (p.rows32) {
         if (p.N < 4096)
             hipLaunchKernelGGL((xcorr_fused_n4096_fold<false, true, true>), g, b, 0, stream, p);

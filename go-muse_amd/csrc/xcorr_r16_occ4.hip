@@ -138,7 +138,9 @@ __device__ __forceinline__ void finalize(const double *r, const Stat &st, double
 
 } // namespace occ4
 
-template <bool PADDED, int WPS, bool TIMING = false, bool F32 = false>
+// WIN: masked argmax (muse_batch_score_in_window; r16_device.h, mask_window): the pairs the default kernel's WIN build hands over, and
+// whole groups after a dense hand-off, keep their lag window
+template <bool PADDED, int WPS, bool TIMING = false, bool F32 = false, bool WIN = false>
 __global__ __launch_bounds__(OCC_THREADS, WPS) void xcorr_fused_n4096_occ4(const FusedParams p)
 {
     using namespace occ4;
@@ -295,6 +297,8 @@ __global__ __launch_bounds__(OCC_THREADS, WPS) void xcorr_fused_n4096_occ4(const
         // max |cc| is tracked; the wave's first index attaining the wave maximum and
         // its sign come from ballots (scalar unit).  Lowest k first, then lowest lane
         // == lowest index, because t < 256.
+        if (WIN)
+            mask_window<false, 256>(v, t, p.win_lpos, 4096 - p.win_lneg);
         double ma = 0.0, mb = 0.0;
 #pragma unroll
         for (int k = 0; k < 16; k++) {
@@ -374,6 +378,20 @@ hipError_t launch_fused_occ4(const FusedParams &p_in, int num_cus, hipStream_t s
     if (grid > cap)
         grid = cap;
     const dim3 g((unsigned)grid), b(OCC_THREADS);
+    if (p.win) { // the masked argmax (muse_batch_score_in_window)
+        if (p.win_lpos < 0 || p.win_lneg < 0 || p.win_lpos > 2048 || p.win_lneg > p.win_lpos)
+            return hipErrorInvalidValue;
+        if (p.rows32) {
+            if (p.N < 4096)
+                hipLaunchKernelGGL((xcorr_fused_n4096_occ4<true, 3, false, true, true>), g, b, 0, stream, p);
+            else
+                hipLaunchKernelGGL((xcorr_fused_n4096_occ4<false, 3, false, true, true>), g, b, 0, stream, p);
+        } else if (p.N < 4096)
+            hipLaunchKernelGGL((xcorr_fused_n4096_occ4<true, 3, false, false, true>), g, b, 0, stream, p);
+        else
+            hipLaunchKernelGGL((xcorr_fused_n4096_occ4<false, 3, false, false, true>), g, b, 0, stream, p);
+        return hipGetLastError();
+    }
     if (p.rows32) {
         if (p.N < 4096)
             hipLaunchKernelGGL((xcorr_fused_n4096_occ4<true, 3, false, true>), g, b, 0, stream, p);

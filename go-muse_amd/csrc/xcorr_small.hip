@@ -51,7 +51,9 @@ namespace muse {
 // consumed; the arithmetic is the float64 arithmetic of the float64 groups.
 // ZREG (MULTI, n <= 8192): the pair's spectrum stays in REGISTERS over the references (256 VGPRs: half the resident waves)
 // instead of being parked in the workgroup's slice of global scratch (n = 16384: 1024 threads per pair cap a lane at 128).
-template <int LOGN, bool PADDED, bool MULTI, bool F32 = false>
+// WIN (single reference, n <= 2048): masked argmax (muse_batch_score_in_window; r16_device.h, mask_window) -- the values outside the
+// lag window p.win_lpos / p.win_lneg are replaced by +0.0 right in front of the argmax
+template <int LOGN, bool PADDED, bool MULTI, bool F32 = false, bool WIN = false>
 __global__ __launch_bounds__((LOGN >= 11 ? (1 << LOGN) / 16 : 256), ((MULTI && LOGN <= 13) ? 2 : 4)) void xcorr_fused_small(const FusedParams p)
 {
     using namespace occ4;
@@ -62,6 +64,7 @@ __global__ __launch_bounds__((LOGN >= 11 ? (1 << LOGN) / 16 : 256), ((MULTI && L
     constexpr int TPB = LOGN >= 11 ? S : 256;
     constexpr int G = TPB / S;  // pairs per workgroup iteration: 8, 4, 1, 1, 1
     static_assert((LOGN >= 9 && LOGN <= 11) || LOGN == 13 || LOGN == 14, "n = 512, 1024, 2048, 8192, 16384");
+    static_assert(!WIN || (!MULTI && LOGN <= 11), "the masked argmax is built for one reference at n = 512, 1024, 2048");
     __shared__ double red[112]; // multi-wave pair reductions (n >= 2048): sums [4][16], maxima [2][16], indices [2][16] ints
     // pass 2's eight factors per phase m2 / R1: 8 x R1 distinct values for the whole workgroup.  Gathered per lane from the
     // W_65536 table they were the kernel's longest stall (scattered L2 lines in front of the first butterfly of a pass:
@@ -83,7 +86,10 @@ __global__ __launch_bounds__((LOGN >= 11 ? (1 << LOGN) / 16 : 256), ((MULTI && L
         g2l[t] = tw_factor<R1_>(twm, t % R1_, t / R1_);
     __syncthreads();
     // optional indirection (filter-and-refine Run): process pair_list[0 .. *pair_count) instead of every pair
-    const long long total = p.pair_list ? (long long)*p.pair_count : p.npairs;
+    // (WIN: never listed -- the count read through a vector load kept the group count, a wave-uniform value, in vector registers,
+    // which the n = 512 builds park in scratch)
+    const long long *const plist = WIN ? nullptr : p.pair_list;
+    const long long total = plist ? (long long)*p.pair_count : p.npairs;
     const long long ngroups = (total + G - 1) / G;
 
     // The rows of the NEXT iteration are requested behind the per-lane argmax of the current one (the transform registers
@@ -97,7 +103,7 @@ __global__ __launch_bounds__((LOGN >= 11 ? (1 << LOGN) / 16 : 256), ((MULTI && L
             it2 = ngroups - 1; // (nothing left: an L2-hot dummy)
         const long long slot = it2 * G + g;
         const long long sl = slot < total ? slot : total - 1;
-        const long long pair = p.pair_list ? p.pair_list[sl] : sl;
+        const long long pair = plist ? plist[sl] : sl;
         const long long rA = 2 * pair;
         const bool hasB = rA + 1 < p.M;
         int jr = j;
@@ -184,7 +190,7 @@ __global__ __launch_bounds__((LOGN >= 11 ? (1 << LOGN) / 16 : 256), ((MULTI && L
         const long long slot = it * G + g;
         const bool live = slot < total;
         const long long sl = live ? slot : total - 1; // idle sub-groups shadow the last pair
-        const long long pair = p.pair_list ? p.pair_list[sl] : sl;
+        const long long pair = plist ? plist[sl] : sl;
         const long long rA = 2 * pair;
         const bool hasB = rA + 1 < p.M;
         // ---- d = x - K with K the first sample, shifted statistics
@@ -311,6 +317,12 @@ __global__ __launch_bounds__((LOGN >= 11 ? (1 << LOGN) / 16 : 256), ((MULTI && L
                 v[r] = w[r];
         }
         forward<LOGN>(v, b, g2l, gs, j); // cc[j + r S] at v[BR16(r)]
+        if (WIN) {
+            int jw = j;
+            asm volatile("" : "+v"(jw)); // (derived here, not hoisted)
+            jw &= S - 1;
+            mask_window<true, S>(v, jw, p.win_lpos, n - p.win_lneg);
+        }
         // ---- maxAbsIndex (xcorr.go:39-50) per series: ascending r = ascending index for this thread
         double sa = 0.0, sb = 0.0; // signed value of the lane's first maximum of |cc|, and its register index
         int ra_ = 0, rb_ = 0;
@@ -558,6 +570,8 @@ static hipError_t launch_small_n(const FusedParams &p, int num_cus, hipStream_t 
     constexpr int TPB = LOGN >= 11 ? (1 << LOGN) / 16 : 256;
     constexpr int G = TPB / ((1 << LOGN) / 16);
     const long long ngroups = (p.npairs + G - 1) / G;
+    if (p.R > 1 && p.win)
+        return hipErrorInvalidValue; // (the masked argmax is built for one reference)
     if (p.R > 1) { // one pass for R references: exactly the resident workgroups (n = 16384: each with its slice of the spectrum scratch)
         constexpr bool ZREG = LOGN <= 13;
         if (!p.xcp_many || !p.mv_many || !p.lag_many || (!ZREG && !p.zscratch))
@@ -572,6 +586,24 @@ static hipError_t launch_small_n(const FusedParams &p, int num_cus, hipStream_t 
         return hipGetLastError();
     }
     const long long grid = std::min<long long>(ngroups, (long long)num_cus * (1024 / TPB) * 8);
+    if (p.win) { // the masked argmax (muse_batch_score_in_window): n = 512, 1024, 2048
+        if constexpr (LOGN <= 11) {
+            if (p.pair_list || p.win_lpos < 0 || p.win_lneg < 0 || p.win_lpos > (1 << LOGN) / 2 || p.win_lneg > p.win_lpos)
+                return hipErrorInvalidValue;
+            if (p.rows32) {
+                if (p.N < (1 << LOGN))
+                    hipLaunchKernelGGL((xcorr_fused_small<LOGN, true, false, true, true>), dim3((unsigned)grid), dim3(TPB), 0, stream, p);
+                else
+                    hipLaunchKernelGGL((xcorr_fused_small<LOGN, false, false, true, true>), dim3((unsigned)grid), dim3(TPB), 0, stream, p);
+            } else if (p.N < (1 << LOGN))
+                hipLaunchKernelGGL((xcorr_fused_small<LOGN, true, false, false, true>), dim3((unsigned)grid), dim3(TPB), 0, stream, p);
+            else
+                hipLaunchKernelGGL((xcorr_fused_small<LOGN, false, false, false, true>), dim3((unsigned)grid), dim3(TPB), 0, stream, p);
+            return hipGetLastError();
+        } else {
+            return hipErrorInvalidValue;
+        }
+    }
     if (p.rows32) {
         if (p.N < (1 << LOGN))
             hipLaunchKernelGGL((xcorr_fused_small<LOGN, true, false, true>), dim3((unsigned)grid), dim3(TPB), 0, stream, p);

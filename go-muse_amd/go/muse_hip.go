@@ -527,6 +527,90 @@ func (b *Batch) RunWindowed(groupByLabels []string) error {
 	return b.Run(groupByLabels)
 }
 
+// RunInWindow is RunWindowed for ANY Results.MaxLag >= 0 (muse_batch_run_in_window): every series contributes its best match
+// inside +-MaxLag -- beyond MUSE_LAG_WINDOW_MAX, and over float32-storage groups, from the transform kernels with a masked
+// argmax (FFT lengths 512 ... 4096; what the library does not build comes back as its error).  One device.  Results is fed as
+// Run feeds it: up to exactFeedMaxGroups label groups ONE Score per group, in group order, through Results.Update (the device
+// returns every group's winner, nothing filtered but NaN, which never passes); beyond, the device's TopN pre-selection in group
+// order.  The window is an argument of the call: Run and RunWindowed stay what they are.
+func (b *Batch) RunInWindow(groupByLabels []string) error {
+	if b.Results.MaxLag < 0 {
+		return fmt.Errorf("RunInWindow: MaxLag < 0")
+	}
+	if es := shardEngines(); es != nil {
+		return fmt.Errorf("RunInWindow runs on one device")
+	}
+	labelValuesSet := b.Comparison.indexLabelValues(groupByLabels)
+	if len(labelValuesSet) == 0 {
+		return nil
+	}
+	pos := make(map[string]int, len(b.Comparison.order))
+	for i, s := range b.Comparison.order {
+		pos[s.UID()] = i
+	}
+	gid := make([]C.int32_t, len(b.Comparison.order))
+	gi := 0
+	for _, lv := range labelValuesSet {
+		for _, uid := range b.Comparison.index[lv.ID(lv.Keys())] {
+			gid[pos[uid]] = C.int32_t(gi)
+		}
+		gi++
+	}
+	e, err := getEngine()
+	if err != nil {
+		return err
+	}
+	dg, err := b.Comparison.residentRows(e)
+	if err != nil {
+		return err
+	}
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	if b.batch == nil || b.batchGroup != dg {
+		if b.batch != nil {
+			C.muse_batch_free(b.batch)
+		}
+		st := C.muse_batch_create_like(b.template, dg, &b.batch)
+		if err := hipError(st); err != nil {
+			return err
+		}
+		b.batchGroup = dg
+	}
+	// (as Run does: a window an earlier RunWindowed left on the handle goes; this pass takes its own as an argument)
+	if err := hipError(C.muse_batch_set_lag_window(b.batch, C.int32_t(b.window))); err != nil {
+		return err
+	}
+	r := b.Results
+	G := len(labelValuesSet)
+	topN, threshold, sign := r.TopN, r.Threshold, int(r.SignFilter)
+	if G <= exactFeedMaxGroups {
+		topN, threshold, sign = G, 0.0, 0
+	}
+	top := topN
+	if top < 1 {
+		top = 1
+	}
+	idx := make([]C.int64_t, top)
+	lag := make([]C.int32_t, top)
+	score := make([]C.double, top)
+	var cnt C.int32_t
+	var mean C.double
+	st := C.muse_batch_run_in_window(b.batch, &gid[0], C.int32_t(G), C.int32_t(r.MaxLag), C.int32_t(topN),
+		C.double(threshold), C.int32_t(sign), 1, &idx[0], &lag[0], &score[0], &cnt, &mean)
+	if err := hipError(st); err != nil {
+		return err
+	}
+	order := make([]int, int(cnt))
+	for i := range order {
+		order[i] = i
+	}
+	sort.SliceStable(order, func(a, c int) bool { return gid[idx[order[a]]] < gid[idx[order[c]]] })
+	for _, k := range order {
+		b.Results.Update(Score{Labels: b.Comparison.order[idx[k]].Labels(), Lag: int(lag[k]), PercentScore: float64(score[k])})
+	}
+	return nil
+}
+
 const exactFeedMaxGroups = 65536
 
 // feedGroupWinners merges the shards' per-group records (muse_merge_group_winners: the first shard with a member decides the NaN

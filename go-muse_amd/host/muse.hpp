@@ -1089,6 +1089,44 @@ public:
         Run(groupByLabels);
     }
 
+    // RunWindowed for ANY Results.MaxLag >= 0 (muse_batch_run_in_window): every series contributes its best match inside +-MaxLag --
+    // beyond MUSE_LAG_WINDOW_MAX, and over float32-storage groups, from the transform kernels with a masked argmax (FFT lengths
+    // 512 ... 4096; anything else the library does not build is its MUSE_ERR_UNSUPPORTED).  One device.  Results is fed as Run feeds
+    // it: up to EXACT_FEED_MAX_GROUPS label groups ONE Score per group, in group order, through Results.Update (the device returns
+    // every group's winner, nothing filtered but NaN, which never passes); beyond, the device's TopN pre-selection in group order.
+    // The window is an argument of the call: Run and RunWindowed stay what they are.
+    void RunInWindow(const std::vector<std::string> &groupByLabels)
+    {
+        if (Results_->MaxLag < 0)
+            throw Error(MUSE_ERR_INVALID, "RunInWindow: MaxLag < 0");
+        if (!engines_.empty())
+            throw Error(MUSE_ERR_UNSUPPORTED, "RunInWindow runs on one device");
+        std::vector<int32_t> gid;
+        std::vector<LabelsPtr> lvs;
+        const std::function<void()> side = [&] { lvs = Comparison->indexLabelValues(groupByLabels, &gid); };
+        muse_group *dg = Comparison->device(eng_, &side);
+        if (lvs.empty())
+            return;
+        ensure(dg);
+        const bool exact = (int64_t)lvs.size() <= EXACT_FEED_MAX_GROUPS;
+        const int32_t top = exact ? (int32_t)lvs.size() : Results_->TopN;
+        const int cap = std::max(top, 1);
+        std::vector<int64_t> idx(cap);
+        std::vector<int32_t> lag(cap);
+        std::vector<double> score(cap);
+        int32_t cnt = 0;
+        double mean = 0;
+        check(muse_batch_run_in_window(batch_, gid.data(), (int32_t)lvs.size(), (int32_t)Results_->MaxLag, top,
+                                       exact ? 0.0 : Results_->Threshold, exact ? 0 : (int32_t)Results_->Filter, 1, idx.data(),
+                                       lag.data(), score.data(), &cnt, &mean));
+        std::vector<int> order(cnt);
+        for (int i = 0; i < cnt; i++)
+            order[i] = i;
+        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return gid[idx[a]] < gid[idx[b]]; });
+        for (int k : order)
+            Results_->Update(Score{Comparison->series()[idx[k]]->Labels(), lag[k], score[k]});
+    }
+
     // The README use case (README.md:10-13) runs many references against one Group: the same as
     // calling Run on every batch, but the resident rows are read and transformed once for all of
     // them (muse_batch_run_many).  The batches must share the Comparison group and the Results settings

@@ -120,6 +120,11 @@ class Engine:
         """test hook: the windowed Muse.Run scores in S slices (0 = the planner, 1 = the unsplit kernel; muse_test_window_rows_slices)"""
         B.check(B.load().muse_test_window_rows_slices(self._h, int(S)))
 
+    def in_window_force_transform(self, on):
+        """test hook: score_in_window sends float64 windows up to MUSE_LAG_WINDOW_MAX through the masked transform kernels too
+        (muse_test_in_window_force_transform)"""
+        B.check(B.load().muse_test_in_window_force_transform(self._h, 1 if on else 0))
+
     def wave_argmax(self, cc_a, cc_b):
         """test hook: the n = 4096 kernels' per-wave argmax step on 2 x 4096 given values; (4, 2, 3) array of
         {max |cc|, signed value, index} per wave and series"""
@@ -412,6 +417,42 @@ class DeviceBatch:
         """the batch's lag window, -1 = off (muse_batch_lag_window)"""
         w = ctypes.c_int32(0)
         B.check(B.load().muse_batch_lag_window(self._h, ctypes.byref(w)))
+        return int(w.value)
+
+    def score_in_window(self, max_lag):
+        """muse_batch_score_in_window: an all-scores pass with every series' best match inside +-max_lag, for ANY max_lag >= 0 and
+        for float32-storage groups too (FFT lengths 512 ... 4096: the transform kernels with a masked argmax; up to
+        MUSE_LAG_WINDOW_MAX on float64 groups: the direct product, bit for bit set_lag_window + score).  The window is an argument:
+        this batch's own lag window must be off or equal and is not touched.  Results: read_scores()."""
+        B.check(B.load().muse_batch_score_in_window(self._h, int(max_lag)))
+
+    def scores_in_window(self, max_lag):
+        """score_in_window + copy back: (lag, mv)"""
+        self.score_in_window(max_lag)
+        return self.read_scores()
+
+    def run_in_window(self, max_lag, group_id=None, G=0, top_n=20, threshold=0.0, sign_filter=0, abs_scores=True):
+        """muse_batch_run_in_window: score_in_window followed by Batch.Run's selection (max_lag is the window and the
+        Results.MaxLag); -> (series, lag, score, mean_abs) as run()"""
+        cap = max(int(top_n), 1)
+        o_s = np.zeros(cap, dtype=np.int64)
+        o_l = np.zeros(cap, dtype=np.int32)
+        o_v = np.zeros(cap)
+        cnt, mean = ctypes.c_int32(0), ctypes.c_double(0)
+        gid = None
+        if group_id is not None:
+            gid = np.ascontiguousarray(group_id, dtype=np.int32)
+        B.check(B.load().muse_batch_run_in_window(
+            self._h, B.i32ptr(gid) if gid is not None else None, int(G), int(max_lag), int(top_n), float(threshold),
+            int(sign_filter), 1 if abs_scores else 0, B.i64ptr(o_s), B.i32ptr(o_l), B.dptr(o_v), ctypes.byref(cnt),
+            ctypes.byref(mean)))
+        c = cnt.value
+        return o_s[:c].copy(), o_l[:c].copy(), o_v[:c].copy(), float(mean.value)
+
+    def last_in_window_path(self):
+        """test hook: MUSE_IN_WINDOW_* of the last score_in_window / run_in_window, 0 after any other scoring pass"""
+        w = ctypes.c_int32(0)
+        B.check(B.load().muse_test_last_in_window_path(self._h, ctypes.byref(w)))
         return int(w.value)
 
     def read_scores(self):
@@ -766,6 +807,14 @@ def window_rows_plan(M, N, num_cus):
     S, cps = ctypes.c_int32(0), ctypes.c_int32(0)
     B.check(B.load().muse_test_window_rows_plan(int(M), int(N), int(num_cus), ctypes.byref(S), ctypes.byref(cps)))
     return int(S.value), int(cps.value)
+
+
+def in_window_plan(N, f32, max_lag):
+    """muse_test_in_window_plan (no device): MUSE_IN_WINDOW_* -- the pass score_in_window takes for series of N samples
+    (f32: float32 storage) and window max_lag"""
+    path = ctypes.c_int32(-1)
+    B.check(B.load().muse_test_in_window_plan(int(N), 1 if f32 else 0, int(max_lag), ctypes.byref(path)))
+    return int(path.value)
 
 
 def device_count():
@@ -1285,6 +1334,33 @@ class Batch:
         finally:
             for db in dbs:
                 db.set_lag_window(-1)
+
+    def RunInWindow(self, groupByLabels):
+        """RunWindowed for ANY Results.MaxLag >= 0 (muse_batch_run_in_window): every series contributes its best match inside
+        +-MaxLag -- beyond MUSE_LAG_WINDOW_MAX, and over float32-storage groups, from the transform kernels with a masked argmax
+        (FFT lengths 512 ... 4096).  One device.  Results is fed as Run feeds it: up to EXACT_FEED_MAX_GROUPS label groups ONE Score
+        per group, in group order, through Results.Update (the device returns every group's winner, nothing filtered but NaN,
+        which never passes); beyond, the device's TopN pre-selection in group order."""
+        comp = self.Comparison
+        labelValuesSet = comp.indexLabelValues(groupByLabels)
+        if not labelValuesSet:
+            return None
+        if self._engines:
+            raise MuseError(B.MUSE_ERR_UNSUPPORTED, "RunInWindow runs on one device")
+        r = self.Results
+        if r.MaxLag < 0:
+            raise MuseError(B.MUSE_ERR_INVALID, "RunInWindow needs Results.MaxLag >= 0")
+        series = comp._series_list()
+        gid = comp._group_ids()
+        G = len(labelValuesSet)
+        if G <= EXACT_FEED_MAX_GROUPS:
+            idx, lag, score, _ = self._batch().run_in_window(r.MaxLag, gid, G, G, 0.0, SignFilter_ANY, abs_scores=True)
+        else:
+            idx, lag, score, _ = self._batch().run_in_window(r.MaxLag, gid, G, r.TopN, r.Threshold, r.SignFilter, abs_scores=True)
+        order = np.argsort(gid[idx], kind="stable")
+        for k in order:
+            r.Update(Score(series[int(idx[k])].Labels(), int(lag[k]), float(score[k])))
+        return None
 
     def _shard_batches(self):
         shards = self.Comparison._device_shards(self._engines)

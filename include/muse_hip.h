@@ -298,6 +298,8 @@ int muse_batch_score(muse_batch *b);
  * (muse_batch_last_run_path: MUSE_RUN_PATH_FP64).
  *   max_lag < 0                      : off -- the transform kernels, bit for bit as if never set
  *   0 <= max_lag <= MUSE_LAG_WINDOW_MAX : on
+ * MUSE_LAG_WINDOW_MAX is the widest window of the DIRECT PRODUCT, the one mechanism behind this setting and behind the _windowed
+ * entry points below; wider windows, and windows over float32-storage groups, are muse_batch_score_in_window's.
  * MUSE_ERR_UNSUPPORTED, the batch unchanged: max_lag > MUSE_LAG_WINDOW_MAX (beyond a few dozen lags the direct product
  * costs more than the transform); a float32-storage group; series longer than 65536 samples.  A batch with a window is
  * refused (MUSE_ERR_UNSUPPORTED) by muse_batch_score_many / _run_many (muse_batch_score_many_windowed is their windowed form) and as the template of muse_batch_run_rows /
@@ -348,6 +350,31 @@ int muse_batch_slide_run_windowed(muse_batch *b, const double *tails, int32_t k,
                                   const int32_t *group_id, int32_t G, int32_t max_lag, int32_t top_n, double threshold,
                                   int32_t sign_filter, int32_t abs_scores, int64_t *out_series, int32_t *out_lag,
                                   double *out_score, int32_t *out_count, double *out_mean_abs);
+/* THE WINDOW AS AN ARGUMENT, ANY WIDTH.  muse_batch_score_in_window is an all-scores pass whose per-series (lag, mv) is the
+ * windowed one defined at muse_batch_set_lag_window, with L = min(max_lag, n/2) -- for every max_lag >= 0, not only up to
+ * MUSE_LAG_WINDOW_MAX, and for float32-storage groups too.  The window is an argument of the call, as with the other _windowed
+ * entry points: the batch's own lag_window must be off or equal to max_lag and is not touched.  Results land in the batch's score
+ * buffers (muse_batch_read_scores); the pass is exact fp64 and never screened (muse_batch_last_run_path: MUSE_RUN_PATH_FP64).
+ * Which pass runs is decided from the length, the storage and L alone:
+ *   L == n/2 (the window is every lag), any length, any storage     : muse_batch_score's pass with the window off, bit for bit
+ *   float64 group, L <= MUSE_LAG_WINDOW_MAX, up to 65536 samples     : the direct product, bit for bit muse_batch_set_lag_window(L) +
+ *                                                                      muse_batch_score
+ *   FFT length 512, 1024, 2048 or 4096 (256 < N <= 4096) and
+ *   L > MUSE_LAG_WINDOW_MAX or a float32-storage group               : the transform kernels of muse_batch_score with their argmax
+ *                                                                      restricted to the window (every cc[i] outside it is replaced
+ *                                                                      by +0.0 in front of maxAbsIndex): the cost of the unwindowed
+ *                                                                      pass, constant in L.  It always reads the rows: the group's
+ *                                                                      spectrum cache is neither used, built nor counted towards.
+ *   anything else (L > MUSE_LAG_WINDOW_MAX with N <= 256 or N > 4096,
+ *   a float32-storage group outside 256 < N <= 4096)                 : MUSE_ERR_UNSUPPORTED, nothing changed
+ * MUSE_ERR_INVALID, nothing changed: a NULL batch, max_lag < 0, a batch whose own window is on and differs from max_lag.
+ * muse_batch_run_in_window is that pass followed by Batch.Run's selection over the scores, outputs as muse_batch_run; max_lag is
+ * both the window and the Results.MaxLag of the selection (as in muse_batch_slide_run_windowed).  A sign_filter outside -1 .. 1 or
+ * a negative G with group_id is refused before anything is scored. */
+int muse_batch_score_in_window(muse_batch *b, int32_t max_lag);
+int muse_batch_run_in_window(muse_batch *b, const int32_t *group_id, int32_t G, int32_t max_lag, int32_t top_n,
+                             double threshold, int32_t sign_filter, int32_t abs_scores, int64_t *out_series,
+                             int32_t *out_lag, double *out_score, int32_t *out_count, double *out_mean_abs);
 /* muse_batch_score + D2H of the per-series results (lag[M], mv[M]). */
 int muse_batch_scores(muse_batch *b, int32_t *lag, double *mv);
 /* Batch.Run + Results.Update + Results.Fetch (muse_batch.go:99-130,

@@ -110,6 +110,22 @@ int muse_test_run_rows_windowed_scores(muse_batch *tmpl, const double *rows, int
  * N < 2, k outside 0 .. N, wide with an odd N, or a NULL out pointer. */
 int muse_test_slide_score_plan(int32_t N, int32_t k, int32_t wide, int32_t *load_bytes, int32_t *store_bytes);
 
+/* muse_batch_score_in_window's dispatch, a pure host function (no device needed): the pass that scores series of N >= 2 samples
+ * (f32_storage: a float32-storage group) inside +-max_lag >= 0 -- *path = MUSE_IN_WINDOW_PLAIN (L == n/2: the unwindowed pass),
+ * _MFMA (the direct product), _MASKED (the transform kernels with a masked argmax) or _UNSUPPORTED (the call returns
+ * MUSE_ERR_UNSUPPORTED).  MUSE_ERR_INVALID for N < 2, max_lag < 0 or a NULL out pointer. */
+#define MUSE_IN_WINDOW_UNSUPPORTED 0
+#define MUSE_IN_WINDOW_PLAIN 1
+#define MUSE_IN_WINDOW_MFMA 2
+#define MUSE_IN_WINDOW_MASKED 3
+int muse_test_in_window_plan(int32_t N, int32_t f32_storage, int32_t max_lag, int32_t *path);
+/* on = 1: muse_batch_score_in_window sends float64 windows up to MUSE_LAG_WINDOW_MAX through the masked transform kernels too, where
+ * the length has them (FFT lengths 512 ... 4096) -- cross-checks of the two mechanisms and tools/in_window_bench.py; 0 (default): the table. */
+int muse_test_in_window_force_transform(muse_ctx *ctx, int32_t on);
+/* The path (MUSE_IN_WINDOW_*) the batch's scores came by if its last scoring pass was muse_batch_score_in_window / _run_in_window;
+ * 0 after any other scoring pass. */
+int muse_test_last_in_window_path(muse_batch *b, int32_t *path);
+
 #ifdef __cplusplus
 }
 #endif
