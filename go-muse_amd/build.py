@@ -65,137 +65,66 @@ if __name__ == "__main__":
     print(build(force=True, verbose=True, extra_flags=flags))
 
 
+def _build_host_program(name, opt, force):
+    """g++ build of host/<name>.cpp, a program over the C++ host mirror (host/muse.hpp), linked to libmuse_hip.so."""
+    src = os.path.join(PKG, "host", name + ".cpp")
+    hdr = os.path.join(PKG, "host", "muse.hpp")
+    exe = os.path.join(LIBDIR, name)
+    build()
+    if (not force and os.path.exists(exe)
+            and os.path.getmtime(exe) >= max(os.path.getmtime(src), os.path.getmtime(hdr), os.path.getmtime(LIB))):
+        return exe
+    subprocess.check_call(["g++", "-std=c++17", opt, "-Wall", "-I" + os.path.join(ROOT, "include"),
+                           "-I" + os.path.join(PKG, "host"), src, "-o", exe,
+                           "-L" + LIBDIR, "-lmuse_hip", "-pthread", "-Wl,-rpath," + LIBDIR])
+    return exe
+
+
 HOST_TEST = os.path.join(LIBDIR, "muse_host_test")
-
-
-def build_host_test(force=False):
-    """g++ build of the C++ host mirror's test program (links libmuse_hip.so)."""
-    src = os.path.join(PKG, "host", "muse_host_test.cpp")
-    hdr = os.path.join(PKG, "host", "muse.hpp")
-    build()
-    if (not force and os.path.exists(HOST_TEST)
-            and os.path.getmtime(HOST_TEST) >= max(os.path.getmtime(src), os.path.getmtime(hdr), os.path.getmtime(LIB))):
-        return HOST_TEST
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(PKG, "host"), src, "-o", HOST_TEST,
-                           "-L" + LIBDIR, "-lmuse_hip", "-pthread", "-Wl,-rpath," + LIBDIR])
-    return HOST_TEST
-
-
 REF_BENCH = os.path.join(LIBDIR, "muse_ref_bench")
-
-
-def build_ref_bench(force=False):
-    """g++ build of the reference's own benchmark shapes over the C++ host mirror (host/muse_ref_bench.cpp; bench.py runs it)."""
-    src = os.path.join(PKG, "host", "muse_ref_bench.cpp")
-    hdr = os.path.join(PKG, "host", "muse.hpp")
-    build()
-    if (not force and os.path.exists(REF_BENCH)
-            and os.path.getmtime(REF_BENCH) >= max(os.path.getmtime(src), os.path.getmtime(hdr), os.path.getmtime(LIB))):
-        return REF_BENCH
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(PKG, "host"), src, "-o", REF_BENCH,
-                           "-L" + LIBDIR, "-lmuse_hip", "-pthread", "-Wl,-rpath," + LIBDIR])
-    return REF_BENCH
-
-
 COLD_PHASES = os.path.join(LIBDIR, "muse_cold_phases")
-
-
-def build_cold_phases(force=False):
-    """g++ build of the cold-path phase breakdown (host/muse_cold_phases.cpp; profiles/r06_cold_path.txt)."""
-    src = os.path.join(PKG, "host", "muse_cold_phases.cpp")
-    hdr = os.path.join(PKG, "host", "muse.hpp")
-    build()
-    if (not force and os.path.exists(COLD_PHASES)
-            and os.path.getmtime(COLD_PHASES) >= max(os.path.getmtime(src), os.path.getmtime(hdr), os.path.getmtime(LIB))):
-        return COLD_PHASES
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(PKG, "host"), src, "-o", COLD_PHASES,
-                           "-L" + LIBDIR, "-lmuse_hip", "-pthread", "-Wl,-rpath," + LIBDIR])
-    return COLD_PHASES
-
-
 RESIDENT_TEST = os.path.join(LIBDIR, "muse_resident_test")
-
-
-def build_resident_test(force=False):
-    """g++ build of the C++ host mirror's resident-row reuse test (host/muse_resident_test.cpp; tests/test_gpu_resident_rows.py)."""
-    src = os.path.join(PKG, "host", "muse_resident_test.cpp")
-    hdr = os.path.join(PKG, "host", "muse.hpp")
-    build()
-    if (not force and os.path.exists(RESIDENT_TEST)
-            and os.path.getmtime(RESIDENT_TEST) >= max(os.path.getmtime(src), os.path.getmtime(hdr), os.path.getmtime(LIB))):
-        return RESIDENT_TEST
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(PKG, "host"), src, "-o", RESIDENT_TEST,
-                           "-L" + LIBDIR, "-lmuse_hip", "-pthread", "-Wl,-rpath," + LIBDIR])
-    return RESIDENT_TEST
-
-
 WINDOW_TEST = os.path.join(LIBDIR, "muse_window_test")
-
-
-def build_window_test(force=False):
-    """g++ build of the C++ host mirror's lag-window program (host/muse_window_test.cpp; tests/test_gpu_lag_window.py)."""
-    src = os.path.join(PKG, "host", "muse_window_test.cpp")
-    hdr = os.path.join(PKG, "host", "muse.hpp")
-    build()
-    if (not force and os.path.exists(WINDOW_TEST)
-            and os.path.getmtime(WINDOW_TEST) >= max(os.path.getmtime(src), os.path.getmtime(hdr), os.path.getmtime(LIB))):
-        return WINDOW_TEST
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(PKG, "host"), src, "-o", WINDOW_TEST,
-                           "-L" + LIBDIR, "-lmuse_hip", "-pthread", "-Wl,-rpath," + LIBDIR])
-    return WINDOW_TEST
-
-
 WINDOW_MANY_TEST = os.path.join(LIBDIR, "muse_window_many_test")
-
-
-def build_window_many_test(force=False):
-    """g++ build of the C++ host mirror's windowed many-references program (host/muse_window_many_test.cpp; tests/test_gpu_lag_window_many.py)."""
-    src = os.path.join(PKG, "host", "muse_window_many_test.cpp")
-    hdr = os.path.join(PKG, "host", "muse.hpp")
-    build()
-    if (not force and os.path.exists(WINDOW_MANY_TEST)
-            and os.path.getmtime(WINDOW_MANY_TEST) >= max(os.path.getmtime(src), os.path.getmtime(hdr), os.path.getmtime(LIB))):
-        return WINDOW_MANY_TEST
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(PKG, "host"), src, "-o", WINDOW_MANY_TEST,
-                           "-L" + LIBDIR, "-lmuse_hip", "-pthread", "-Wl,-rpath," + LIBDIR])
-    return WINDOW_MANY_TEST
-
-
 ROWS_WINDOW_TEST = os.path.join(LIBDIR, "muse_rows_window_test")
-
-
-def build_rows_window_test(force=False):
-    """g++ build of the C++ host mirror's windowed Muse.Run program (host/muse_rows_window_test.cpp; tests/test_gpu_window_rows.py)."""
-    src = os.path.join(PKG, "host", "muse_rows_window_test.cpp")
-    hdr = os.path.join(PKG, "host", "muse.hpp")
-    build()
-    if (not force and os.path.exists(ROWS_WINDOW_TEST)
-            and os.path.getmtime(ROWS_WINDOW_TEST) >= max(os.path.getmtime(src), os.path.getmtime(hdr), os.path.getmtime(LIB))):
-        return ROWS_WINDOW_TEST
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(PKG, "host"), src, "-o", ROWS_WINDOW_TEST,
-                           "-L" + LIBDIR, "-lmuse_hip", "-pthread", "-Wl,-rpath," + LIBDIR])
-    return ROWS_WINDOW_TEST
-
-
 IN_WINDOW_TEST = os.path.join(LIBDIR, "muse_in_window_test")
 
 
+def build_host_test(force=False):
+    """The C++ host mirror's test program."""
+    return _build_host_program("muse_host_test", "-O1", force)
+
+
+def build_ref_bench(force=False):
+    """The reference's own benchmark shapes over the host mirror (bench.py runs it)."""
+    return _build_host_program("muse_ref_bench", "-O2", force)
+
+
+def build_cold_phases(force=False):
+    """The cold-path phase breakdown (profiles/r06_cold_path.txt)."""
+    return _build_host_program("muse_cold_phases", "-O2", force)
+
+
+def build_resident_test(force=False):
+    """The host mirror's resident-row reuse test (tests/test_gpu_resident_rows.py)."""
+    return _build_host_program("muse_resident_test", "-O1", force)
+
+
+def build_window_test(force=False):
+    """The host mirror's lag-window program (tests/test_gpu_lag_window.py)."""
+    return _build_host_program("muse_window_test", "-O1", force)
+
+
+def build_window_many_test(force=False):
+    """The host mirror's windowed many-references program (tests/test_gpu_lag_window_many.py)."""
+    return _build_host_program("muse_window_many_test", "-O1", force)
+
+
+def build_rows_window_test(force=False):
+    """The host mirror's windowed Muse.Run program (tests/test_gpu_window_rows.py)."""
+    return _build_host_program("muse_rows_window_test", "-O1", force)
+
+
 def build_in_window_test(force=False):
-    """g++ build of the C++ host mirror's wide-window program (host/muse_in_window_test.cpp; tests/test_gpu_in_window.py)."""
-    src = os.path.join(PKG, "host", "muse_in_window_test.cpp")
-    hdr = os.path.join(PKG, "host", "muse.hpp")
-    build()
-    if (not force and os.path.exists(IN_WINDOW_TEST)
-            and os.path.getmtime(IN_WINDOW_TEST) >= max(os.path.getmtime(src), os.path.getmtime(hdr), os.path.getmtime(LIB))):
-        return IN_WINDOW_TEST
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(PKG, "host"), src, "-o", IN_WINDOW_TEST,
-                           "-L" + LIBDIR, "-lmuse_hip", "-pthread", "-Wl,-rpath," + LIBDIR])
-    return IN_WINDOW_TEST
+    """The host mirror's wide-window program (tests/test_gpu_in_window.py)."""
+    return _build_host_program("muse_in_window_test", "-O1", force)

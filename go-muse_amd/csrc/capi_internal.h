@@ -439,6 +439,13 @@ int spectrum_cache_policy(int64_t rows, int32_t N, bool f32, int mode, int64_t m
                           int64_t *rows_cached, int64_t *bytes);
 void group_drop_spectrum_cache(muse_group *g);             // capi_batch.hip: frees the segments (ready_mu held, compute stream idle)
 int score_windowed(muse_batch *b);                     // capi_window.hip: the all-scores pass of a batch with a lag window (scores allocated)
+// capi_window.hip, what every caller of the lag-window kernels shares.  check_window_request: the refusals of a window of max_lag >= 0
+// over b's reference (f32: the rows are float32 storage); window_tables: the shifted-reference image and its window sums of b for
+// window L in e / pw, once per window (cached under *cached_L: -1 = none; the caller drops it when the reference changes);
+// window_params: the kernels' arguments for b's group and scores with those tables
+int check_window_request(const muse_batch *b, int32_t max_lag, bool f32);
+int window_tables(muse_batch *b, int L, PoolBuf<double> &e, PoolBuf<double> &pw, int32_t *cached_L, hipStream_t st);
+muse::WindowParams window_params(const muse_batch *b, int L, const double *e, const double *pw);
 muse::FusedParams base_params(muse_batch *b);
 int ensure_select_ws(muse_batch *b, int64_t M, int64_t G, bool with_gid, int K, bool on_device);
 // the selection of a Run happens on the device (each chunk's best top_n) only beyond EXACT_FEED_MAX_GROUPS groups: capi_run.hip, run_select

@@ -231,28 +231,13 @@ static int slot_score_windowed(muse_ctx *ctx, RowsSlot *s, int32_t max_lag)
     muse_batch *b = &s->b;
     const hipStream_t st = b->stream();
     const int L = std::min(max_lag, b->n / 2);
-    if (s->win_serial != b->sp->serial || s->win_L != L) {
-        s->win_serial = 0;
-        const long long e_len = window_e_len(b->N);
-        HIP_TRY(s->win_e.ensure(ctx, e_len, st));
-        HIP_TRY(s->win_pw.ensure(ctx, 2 * MUSE_LAG_WINDOW_MAX + 1, st));
-        HIP_TRY(launch_window_tables(b->xs, b->N, b->n, L, s->win_e.p, e_len, s->win_pw.p, st));
-        s->win_serial = b->sp->serial;
-        s->win_L = L;
-    }
-    WindowParams p{};
-    p.rows = s->g.rows;
-    p.M = s->g.M;
-    p.stride = s->g.stride;
-    p.N = b->N;
-    p.L = L;
-    p.Lneg = 2 * L == b->n ? L - 1 : L; // index n / 2 is lag +n/2 (xcorr.go:192-194): it is scanned once
-    p.e = s->win_e.p;
-    p.pw = s->win_pw.p;
-    p.invN = 1.0 / (double)b->N;
-    p.invNm1 = 1.0 / (double)(b->N - 1);
-    p.mv = b->mv.p;
-    p.lag = b->lag.p;
+    if (s->win_serial != b->sp->serial) // (another reference: whatever window the tables were built for)
+        s->win_L = -1;
+    const int rc = window_tables(b, L, s->win_e, s->win_pw, &s->win_L, st);
+    if (rc)
+        return rc;
+    s->win_serial = b->sp->serial;
+    const WindowParams p = window_params(b, L, s->win_e.p, s->win_pw.p);
     const int chunks = (b->N + WIN_KC - 1) / WIN_KC;
     const int forced = ctx->win_rows_slices.load(std::memory_order_relaxed);
     const int S = forced >= 1 ? std::min(forced, chunks) : window_rows_plan(p.M, p.N, ctx->num_cus, nullptr);
@@ -341,12 +326,7 @@ static int check_window_call(const muse_batch *tmpl, int32_t max_lag)
     if (tmpl->windowed() && tmpl->lag_window != max_lag)
         return fail(MUSE_ERR_INVALID, "the template has a lag window of %d of its own: it must be off or equal to the call's (%d)",
                     tmpl->lag_window, max_lag);
-    if (max_lag > MUSE_LAG_WINDOW_MAX)
-        return fail(MUSE_ERR_UNSUPPORTED, "lag window %d > MUSE_LAG_WINDOW_MAX (%d): beyond it the direct product costs more than the transform",
-                    max_lag, MUSE_LAG_WINDOW_MAX);
-    if (tmpl->n > GENERIC_MAX_N || !tmpl->xs)
-        return fail(MUSE_ERR_UNSUPPORTED, "the lag-window pass is built for series of up to %d samples", GENERIC_MAX_N);
-    return MUSE_OK;
+    return check_window_request(tmpl, max_lag, false); // (the rows are the call's own float64: the template's group is not read)
 }
 
 // the private batch of a general path: like tmpl over g, with the call's window (if any); Run with G = 1; the test hook's scores

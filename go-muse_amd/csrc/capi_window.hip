@@ -8,6 +8,18 @@
 
 using namespace muse;
 
+int check_window_request(const muse_batch *b, int32_t max_lag, bool f32)
+{
+    if (max_lag > MUSE_LAG_WINDOW_MAX)
+        return fail(MUSE_ERR_UNSUPPORTED, "lag window %d > MUSE_LAG_WINDOW_MAX (%d): beyond it the direct product costs more than the transform",
+                    max_lag, MUSE_LAG_WINDOW_MAX);
+    if (f32)
+        return fail(MUSE_ERR_UNSUPPORTED, "the lag-window pass reads float64 groups only");
+    if (b->n > GENERIC_MAX_N || !b->xs)
+        return fail(MUSE_ERR_UNSUPPORTED, "the lag-window pass is built for series of up to %d samples", GENERIC_MAX_N);
+    return MUSE_OK;
+}
+
 extern "C" int muse_batch_set_lag_window(muse_batch *b, int32_t max_lag)
 {
     if (!b)
@@ -16,13 +28,9 @@ extern "C" int muse_batch_set_lag_window(muse_batch *b, int32_t max_lag)
         b->lag_window = -1;
         return MUSE_OK;
     }
-    if (max_lag > MUSE_LAG_WINDOW_MAX)
-        return fail(MUSE_ERR_UNSUPPORTED, "lag window %d > MUSE_LAG_WINDOW_MAX (%d): beyond it the direct product costs more than the transform",
-                    max_lag, MUSE_LAG_WINDOW_MAX);
-    if (b->g->f32)
-        return fail(MUSE_ERR_UNSUPPORTED, "the lag-window pass reads float64 groups only");
-    if (b->n > GENERIC_MAX_N || !b->xs)
-        return fail(MUSE_ERR_UNSUPPORTED, "the lag-window pass is built for series of up to %d samples", GENERIC_MAX_N);
+    const int rc = check_window_request(b, max_lag, b->g->f32);
+    if (rc)
+        return rc;
     b->lag_window = max_lag;
     return MUSE_OK;
 }
@@ -35,23 +43,20 @@ extern "C" int muse_batch_lag_window(muse_batch *b, int32_t *max_lag)
     return MUSE_OK;
 }
 
-// the shifted-reference image and its window sums for window L, once per window (cached under win_L)
-static int window_tables(muse_batch *b, int L)
+int window_tables(muse_batch *b, int L, PoolBuf<double> &e, PoolBuf<double> &pw, int32_t *cached_L, hipStream_t st)
 {
-    if (b->win_L == L)
+    if (*cached_L == L)
         return MUSE_OK;
-    muse_ctx *ctx = b->ctx;
-    const hipStream_t st = b->stream();
-    b->win_L = -1;
+    *cached_L = -1;
     const long long e_len = window_e_len(b->N);
-    HIP_TRY(b->win_e.ensure(ctx, e_len, st));
-    HIP_TRY(b->win_pw.ensure(ctx, 2 * MUSE_LAG_WINDOW_MAX + 1, st));
-    HIP_TRY(launch_window_tables(b->xs, b->N, b->n, L, b->win_e.p, e_len, b->win_pw.p, st));
-    b->win_L = L;
+    HIP_TRY(e.ensure(b->ctx, e_len, st));
+    HIP_TRY(pw.ensure(b->ctx, 2 * MUSE_LAG_WINDOW_MAX + 1, st));
+    HIP_TRY(launch_window_tables(b->xs, b->N, b->n, L, e.p, e_len, pw.p, st));
+    *cached_L = L;
     return MUSE_OK;
 }
 
-static WindowParams window_params(muse_batch *b, int L)
+WindowParams window_params(const muse_batch *b, int L, const double *e, const double *pw)
 {
     WindowParams p{};
     p.rows = b->g->rows;
@@ -60,13 +65,22 @@ static WindowParams window_params(muse_batch *b, int L)
     p.N = b->N;
     p.L = L;
     p.Lneg = 2 * L == b->n ? L - 1 : L; // index n / 2 is lag +n/2 (xcorr.go:192-194): it is scanned once
-    p.e = b->win_e.p;
-    p.pw = b->win_pw.p;
     p.invN = 1.0 / (double)b->N;
     p.invNm1 = 1.0 / (double)(b->N - 1);
+    p.e = e;
+    p.pw = pw;
     p.mv = b->mv.p;
     p.lag = b->lag.p;
     return p;
+}
+
+// a batch's own tables and arguments (win_e / win_pw under win_L)
+static int batch_window_params(muse_batch *b, int L, hipStream_t st, WindowParams *p)
+{
+    const int rc = window_tables(b, L, b->win_e, b->win_pw, &b->win_L, st);
+    if (!rc)
+        *p = window_params(b, L, b->win_e.p, b->win_pw.p);
+    return rc;
 }
 
 // muse_batch_score of a batch with a window (device selected, rows uploaded, M > 0, mv / lag allocated)
@@ -75,10 +89,10 @@ int score_windowed(muse_batch *b)
     muse_ctx *ctx = b->ctx;
     const hipStream_t st = b->stream();
     const int L = std::min(b->lag_window, b->n / 2);
-    int rc = window_tables(b, L);
+    WindowParams p;
+    const int rc = batch_window_params(b, L, st, &p);
     if (rc)
         return rc;
-    const WindowParams p = window_params(b, L);
     LaunchTimer timer(ctx, false, st);
     HIP_TRY(timer.begin());
     HIP_TRY(launch_window(p, st));
@@ -104,20 +118,16 @@ extern "C" int muse_batch_slide_score_windowed(muse_batch *b, const double *tail
         return fail(MUSE_ERR_INVALID, "the group has an open staging window");
     if (max_lag < 0)
         return fail(MUSE_ERR_INVALID, "a windowed pass needs a lag window >= 0");
-    if (max_lag > MUSE_LAG_WINDOW_MAX)
-        return fail(MUSE_ERR_UNSUPPORTED, "lag window %d > MUSE_LAG_WINDOW_MAX (%d): beyond it the direct product costs more than the transform",
-                    max_lag, MUSE_LAG_WINDOW_MAX);
-    if (g->f32)
-        return fail(MUSE_ERR_UNSUPPORTED, "the lag-window pass reads float64 groups only");
-    if (b->n > GENERIC_MAX_N || !b->xs)
-        return fail(MUSE_ERR_UNSUPPORTED, "the lag-window pass is built for series of up to %d samples", GENERIC_MAX_N);
+    int rc = check_window_request(b, max_lag, g->f32);
+    if (rc)
+        return rc;
     if (b->windowed() && b->lag_window != max_lag)
         return fail(MUSE_ERR_INVALID, "the batch has a lag window of %d of its own: it must be off or equal to the call's (%d)",
                     b->lag_window, max_lag);
     if (M == 0) // nothing to move, nothing to score
         return MUSE_OK;
     muse_ctx *ctx = b->ctx;
-    int rc = use_device(ctx);
+    rc = use_device(ctx);
     if (rc)
         return rc;
     const hipStream_t st = b->stream();
@@ -131,10 +141,10 @@ extern "C" int muse_batch_slide_score_windowed(muse_batch *b, const double *tail
     b->in_window_path = 0;
     b->scores_exact = true;
     const int L = std::min(max_lag, b->n / 2);
-    rc = window_tables(b, L);
+    WindowParams p;
+    rc = batch_window_params(b, L, st, &p);
     if (rc)
         return rc;
-    const WindowParams p = window_params(b, L);
     if (k == 0) { // nothing moves and nothing is invalidated: the windowed pass alone
         LaunchTimer timer(ctx, false, st);
         HIP_TRY(timer.begin());

@@ -51,14 +51,10 @@ static int check_many_windowed(muse_batch *const *bs, int32_t R, int32_t max_lag
     }
     if (max_lag < 0)
         return fail(MUSE_ERR_INVALID, "a windowed many-references pass needs a lag window >= 0");
-    if (max_lag > MUSE_LAG_WINDOW_MAX)
-        return fail(MUSE_ERR_UNSUPPORTED, "lag window %d > MUSE_LAG_WINDOW_MAX (%d): beyond it the direct product costs more than the transform",
-                    max_lag, MUSE_LAG_WINDOW_MAX);
-    if (bs[0]->g->f32)
-        return fail(MUSE_ERR_UNSUPPORTED, "the lag-window pass reads float64 groups only");
-    for (int r = 0; r < R; r++) {
-        if (bs[r]->n > GENERIC_MAX_N || !bs[r]->xs)
-            return fail(MUSE_ERR_UNSUPPORTED, "the lag-window pass is built for series of up to %d samples", GENERIC_MAX_N);
+    for (int r = 0; r < R; r++) { // (the batches share the group and the window: behind r = 0 only the length check can still refuse)
+        const int rc = check_window_request(bs[r], max_lag, bs[r]->g->f32);
+        if (rc)
+            return rc;
         if (bs[r]->windowed() && bs[r]->lag_window != max_lag)
             return fail(MUSE_ERR_INVALID, "batch %d has a lag window of %d of its own: it must be off or equal to the pass's (%d)", r,
                         bs[r]->lag_window, max_lag);
@@ -106,14 +102,9 @@ extern "C" int muse_batch_score_many_windowed(muse_batch *const *bs, int32_t R, 
     for (int r = 0; r < R; r++) {
         muse_batch *b = bs[r];
         const int Lb = std::min(max_lag, b->n / 2);
-        if (b->win_L != Lb) {
-            b->win_L = -1;
-            const long long e_len = window_e_len(b->N);
-            HIP_TRY(b->win_e.ensure(ctx, e_len, st));
-            HIP_TRY(b->win_pw.ensure(ctx, 2 * MUSE_LAG_WINDOW_MAX + 1, st));
-            HIP_TRY(launch_window_tables(b->xs, b->N, b->n, Lb, b->win_e.p, e_len, b->win_pw.p, st));
-            b->win_L = Lb;
-        }
+        rc = window_tables(b, Lb, b->win_e, b->win_pw, &b->win_L, st);
+        if (rc)
+            return rc;
     }
     bool packed = false;
     for (int r = 0; r + 1 < R; r++)
@@ -140,36 +131,17 @@ extern "C" int muse_batch_score_many_windowed(muse_batch *const *bs, int32_t R, 
             r1++;
         muse_batch *b = bs[r0];
         const int Lb = std::min(max_lag, b->n / 2);
+        const WindowParams p1 = window_params(b, Lb, b->win_e.p, b->win_pw.p);
         if (r1 - r0 == 1) { // a reference that fills its launch alone: the single-reference kernel
-            WindowParams p{};
-            p.rows = b->g->rows;
-            p.M = M;
-            p.stride = b->g->stride;
-            p.N = b->N;
-            p.L = Lb;
-            p.Lneg = 2 * Lb == b->n ? Lb - 1 : Lb; // index n / 2 is lag +n/2 (xcorr.go:192-194): it is scanned once
-            p.e = b->win_e.p;
-            p.pw = b->win_pw.p;
-            p.invN = 1.0 / (double)b->N;
-            p.invNm1 = 1.0 / (double)(b->N - 1);
-            p.mv = b->mv.p;
-            p.lag = b->lag.p;
-            HIP_TRY(launch_window(p, st));
+            HIP_TRY(launch_window(p1, st));
         } else {
             WindowManyParams p{};
-            p.rows = b->g->rows;
-            p.M = M;
-            p.stride = b->g->stride;
-            p.N = b->N;
-            p.L = Lb;
-            p.Lneg = 2 * Lb == b->n ? Lb - 1 : Lb;
+            static_cast<WindowShape &>(p) = p1;
             p.R = r1 - r0;
             p.e = (const double *const *)(tab_dev + r0);
             p.pw = (const double *const *)(tab_dev + R + r0);
             p.mv = (double *const *)(tab_dev + 2 * R + r0);
             p.lag = (int *const *)(tab_dev + 3 * R + r0);
-            p.invN = 1.0 / (double)b->N;
-            p.invNm1 = 1.0 / (double)(b->N - 1);
             HIP_TRY(launch_window_many(p, st));
         }
         for (int r = r0; r < r1; r++) {

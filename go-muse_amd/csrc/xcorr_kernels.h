@@ -151,14 +151,16 @@ static_assert(LONG_WGS_PER_CU <= GSCRATCH_SLICES_PER_CU && GENERIC_GLOBAL_WGS_PE
 constexpr int WIN_KC = 1024;    // samples per chunk of the reference image a workgroup stages in LDS
 constexpr int WIN_E_TAIL = 128; // >= 2 * MUSE_LAG_WINDOW_MAX + 2: what a chunk's image holds behind its WIN_KC samples
 static_assert(2 * MUSE_LAG_WINDOW_MAX + 2 <= WIN_E_TAIL, "the staged image covers every lag of the widest window");
-struct WindowParams {
+struct WindowShape {    // what every lag-window kernel takes: the rows and the window (capi_window.hip: window_params fills it)
     const double *rows; // M x N row-major float64, row stride `stride` elements
     long long M, stride;
     int N;
     int L, Lneg;        // lags -Lneg .. L (Lneg = L, or L - 1 when L == n / 2: index n / 2 is lag +n/2 only)
+    double invN, invNm1;
+};
+struct WindowParams : WindowShape {
     const double *e;    // [window_e_len(N)] e[v] = xs[(n - N + v - L) mod n], zero from N + 2 L on
     const double *pw;   // [2 L + 1] pw[v] = sum_t e[t + v]
-    double invN, invNm1;
     double *mv;         // out: M signed values
     int *lag;           // out: M lags
 };
@@ -192,17 +194,12 @@ hipError_t launch_window_split(const WindowParams &p, int S, double *slabs, hipS
 constexpr int WINM_MAX_TILES = 8;       // accumulator tiles of a launch: 128 packed (reference, lag) rows
 constexpr int WINM_PACK_MAX_ROWS = 48;   // wider windows (four tiles per reference) are not packed: one launch per reference
 constexpr int WINM_IMG_DOUBLES = 4608;  // LDS budget of a launch's staged reference images (36 KB: four workgroups per CU)
-struct WindowManyParams {
-    const double *rows; // as WindowParams
-    long long M, stride;
-    int N;
-    int L, Lneg;
+struct WindowManyParams : WindowShape {
     int R;                    // references of this launch: R (2 L + 1) <= 16 WINM_MAX_TILES
     const double *const *e;   // [R] each reference's WindowParams::e   (the four tables: device memory)
     const double *const *pw;  // [R] each reference's WindowParams::pw
     double *const *mv;        // [R] out: each reference's M signed values
     int *const *lag;          // [R] out: each reference's M lags
-    double invN, invNm1;
     int kc, img, buf, parts;  // filled in by launch_window_many: chunk length, image stride, doubles of the image / tile region, scan parts per reference
 };
 // the planner (pure host functions): image stride for window L and chunk length kc; the most references one launch takes; the chunk

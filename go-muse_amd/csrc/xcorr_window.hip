@@ -88,6 +88,10 @@ __global__ __launch_bounds__(WIN_THREADS) void xcorr_window_mfma(const WindowPar
         acc[i] = v4d{0.0, 0.0, 0.0, 0.0};
     double s1 = 0.0, s2 = 0.0;
 
+    // This loop is written out -- the staging, the piece's loads and the k-loop that the other kernels take from window_device.h
+    // (window_stage_e, window_load_piece, window_mac_piece; the same expressions, on the same window_k / window_a).  Through
+    // those functions the 4- and 8-tile builds of this kernel measured 2 ... 3 % slower, with the k-loop alone written out still
+    // 2.5 %: profiles/window_refactor.txt.  A change to the mapping or to the k-loop is made here as well.
     for (int T0 = 0; T0 < N; T0 += WIN_KC) {
         if (T0 > 0)
             __syncthreads();
@@ -104,29 +108,29 @@ __global__ __launch_bounds__(WIN_THREADS) void xcorr_window_mfma(const WindowPar
             if (WIDE && T + 64 <= N) {
 #pragma unroll
                 for (int mp = 0; mp < 8; mp++) {
-                    const double2 v = *reinterpret_cast<const double2 *>(y + T + 8 * mp + 2 * q);
+                    const double2 v = *reinterpret_cast<const double2 *>(y + T + window_a<true>(2 * mp) + window_k<true>(0, q));
                     d[2 * mp] = v.x - y0;
                     d[2 * mp + 1] = v.y - y0;
                 }
             } else if (T + 64 <= N) {
 #pragma unroll
                 for (int m = 0; m < 16; m++)
-                    d[m] = y[T + 4 * m + q] - y0;
+                    d[m] = y[T + window_k<false>(m, q)] - y0;
             } else {
 #pragma unroll
                 for (int m = 0; m < 16; m++) {
-                    const int tt = T + (WIDE ? 8 * (m >> 1) + 2 * q + (m & 1) : 4 * m + q);
+                    const int tt = T + window_k<WIDE>(m, q);
                     d[m] = tt < N ? y[tt] - y0 : 0.0;
                 }
             }
-            const double *a = lds + 64 * s + (WIDE ? 2 * q : q) + r;
+            const double *a = lds + 64 * s + window_k<WIDE>(0, q) + r;
 #pragma unroll
             for (int m = 0; m < 16; m++) {
                 s1 += d[m];
                 s2 = fma(d[m], d[m], s2);
 #pragma unroll
                 for (int i = 0; i < TILES; i++)
-                    acc[i] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[(WIDE ? 8 * (m >> 1) + (m & 1) : 4 * m) + 16 * i], d[m], acc[i], 0, 0, 0);
+                    acc[i] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[window_a<WIDE>(m) + 16 * i], d[m], acc[i], 0, 0, 0);
             }
         }
     }
@@ -137,32 +141,17 @@ hipError_t launch_window(const WindowParams &p, hipStream_t stream)
 {
     if (p.M <= 0)
         return hipSuccess;
-    if (p.L < 0 || p.L > MUSE_LAG_WINDOW_MAX || p.Lneg < 0 || p.Lneg > p.L || p.N < 2)
-        return hipErrorInvalidValue;
-    const long long blocks = (p.M + 15) / 16;
-    if (blocks > 0x7fffffffLL)
+    long long blocks;
+    if (window_launch_check(p, &blocks) != hipSuccess)
         return hipErrorInvalidValue;
     const dim3 grid((unsigned)blocks), block(WIN_THREADS);
-    const int W = 2 * p.L + 1; // lag + L runs up to 2 L whichever side the window drops
     const bool wide = window_wide(p.rows, p.stride);
-#define MUSE_WINDOW_LAUNCH(T)                                                    \
-    do {                                                                         \
-        if (wide)                                                                \
-            xcorr_window_mfma<T, true><<<grid, block, 0, stream>>>(p);           \
-        else                                                                     \
-            xcorr_window_mfma<T, false><<<grid, block, 0, stream>>>(p);          \
-    } while (0)
-    switch ((W + 15) / 16) { // accumulator tiles of 16 lags
-    case 1: MUSE_WINDOW_LAUNCH(1); break;
-    case 2: MUSE_WINDOW_LAUNCH(2); break;
-    case 3: MUSE_WINDOW_LAUNCH(3); break;
-    case 4: MUSE_WINDOW_LAUNCH(4); break;
-    case 5: MUSE_WINDOW_LAUNCH(5); break;
-    case 6: MUSE_WINDOW_LAUNCH(6); break;
-    case 7: MUSE_WINDOW_LAUNCH(7); break;
-    default: MUSE_WINDOW_LAUNCH(8); break;
-    }
-#undef MUSE_WINDOW_LAUNCH
+    window_with_tiles(window_tiles(p.L), [&](auto tiles) {
+        if (wide)
+            xcorr_window_mfma<tiles(), true><<<grid, block, 0, stream>>>(p);
+        else
+            xcorr_window_mfma<tiles(), false><<<grid, block, 0, stream>>>(p);
+    });
     return hipGetLastError();
 }
 

@@ -15,19 +15,17 @@
 //
 // Bit-identity with xcorr_window_mfma: an accumulator element sees the same A and B values in the same k slots of the same k-steps
 // in the same order (kc is a multiple of 256 samples, so the 64-sample piece p still goes to wave p mod 4, pieces in rising
-// order), the waves' tiles are summed in wave order, and the statistics and the scan are that kernel's expressions; the scan is
-// cut into parts differently, which strict '>' with the first index winning does not see.
-#include "xcorr_kernels.h"
+// order; the piece's load is that kernel's function and the k-loop its loop on the same mapping, window_device.h), the waves' tiles are summed in wave order by
+// the same function, and the statistics, the scoring of a position, the candidate update and the outcome are that kernel's functions
+// too; the scan is cut into parts differently, which strict '>' with the first index winning does not see.
+#include "window_device.h"
 
 namespace muse {
 
-typedef double v4d __attribute__((ext_vector_type(4)));
-
-constexpr int WINM_THREADS = 256;
 constexpr int WINM_STAGE = 3; // image samples per thread and reference in one batch of staging loads
 
 template <int TILES, bool WIDE>
-__global__ __launch_bounds__(WINM_THREADS) void xcorr_window_many_mfma(const WindowManyParams p)
+__global__ __launch_bounds__(WIN_THREADS) void xcorr_window_many_mfma(const WindowManyParams p)
 {
     // [max(R img, TILES 256)] the e images, then the summed tiles [tile][row][series] | [4 waves][16 series][2] | [R parts][16 series][3]
     extern __shared__ double lds[];
@@ -53,7 +51,7 @@ __global__ __launch_bounds__(WINM_THREADS) void xcorr_window_many_mfma(const Win
         if (rr >= R * Wv) // the empty rows behind the last reference compute the last row again (one LDS address: a broadcast); nothing of them is read
             rr = R * Wv - 1;
         const int ref = rr / Wv;
-        aoff[i] = ref * img + (rr - ref * Wv) + (WIDE ? 2 * q : q);
+        aoff[i] = ref * img + (rr - ref * Wv) + window_k<WIDE>(0, q);
     }
     double s1 = 0.0, s2 = 0.0;
 
@@ -67,18 +65,18 @@ __global__ __launch_bounds__(WINM_THREADS) void xcorr_window_many_mfma(const Win
 #pragma unroll
             for (int u = 0; u < 4; u++)
                 e[u] = p.e[ref0 + u < R ? ref0 + u : ref0] + T0;
-            for (int v0 = t; v0 < elen; v0 += WINM_STAGE * WINM_THREADS) {
+            for (int v0 = t; v0 < elen; v0 += WINM_STAGE * WIN_THREADS) {
                 double x[4][WINM_STAGE];
 #pragma unroll
                 for (int j = 0; j < WINM_STAGE; j++) {
-                    const int v = v0 + j * WINM_THREADS < elen ? v0 + j * WINM_THREADS : v0;
+                    const int v = v0 + j * WIN_THREADS < elen ? v0 + j * WIN_THREADS : v0;
 #pragma unroll
                     for (int u = 0; u < 4; u++)
                         x[u][j] = e[u][v];
                 }
 #pragma unroll
                 for (int j = 0; j < WINM_STAGE; j++) {
-                    const int v = v0 + j * WINM_THREADS;
+                    const int v = v0 + j * WIN_THREADS;
 #pragma unroll
                     for (int u = 0; u < 4; u++)
                         if (v < elen && ref0 + u < R)
@@ -91,26 +89,10 @@ __global__ __launch_bounds__(WINM_THREADS) void xcorr_window_many_mfma(const Win
             const int T = T0 + 64 * s;
             if (T >= N)
                 break;
-            // the k order of xcorr_window_mfma: WIDE, k-step m = 2 mp + h <-> sample T + 8 mp + 2 q + h; else m <-> T + 4 m + q
             double d[16];
-            if (WIDE && T + 64 <= N) {
-#pragma unroll
-                for (int mp = 0; mp < 8; mp++) {
-                    const double2 v = *reinterpret_cast<const double2 *>(y + T + 8 * mp + 2 * q);
-                    d[2 * mp] = v.x - y0;
-                    d[2 * mp + 1] = v.y - y0;
-                }
-            } else if (T + 64 <= N) {
-#pragma unroll
-                for (int m = 0; m < 16; m++)
-                    d[m] = y[T + 4 * m + q] - y0;
-            } else {
-#pragma unroll
-                for (int m = 0; m < 16; m++) {
-                    const int tt = T + (WIDE ? 8 * (m >> 1) + 2 * q + (m & 1) : 4 * m + q);
-                    d[m] = tt < N ? y[tt] - y0 : 0.0;
-                }
-            }
+            window_load_piece<WIDE>(d, y, y0, T, N, q);
+            // (the k-loop of window_mac_piece, written out: called through the function these builds are 2 ... 3 % slower at 4 and 8
+            // tiles -- the compiler spreads the accumulator copies through the MFMA run; profiles/window_refactor.txt)
             const double *a = lds + 64 * s;
 #pragma unroll
             for (int m = 0; m < 16; m++) {
@@ -118,99 +100,30 @@ __global__ __launch_bounds__(WINM_THREADS) void xcorr_window_many_mfma(const Win
                 s2 = fma(d[m], d[m], s2);
 #pragma unroll
                 for (int i = 0; i < TILES; i++)
-                    acc[i] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[(WIDE ? 8 * (m >> 1) + (m & 1) : 4 * m) + aoff[i]], d[m], acc[i], 0, 0, 0);
+                    acc[i] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[window_a<WIDE>(m) + aoff[i]], d[m], acc[i], 0, 0, 0);
             }
         }
     }
-    // statistics: the four k-lanes of a series, then (below) the four waves
-    s1 += __shfl_xor(s1, 16);
-    s2 += __shfl_xor(s2, 16);
-    s1 += __shfl_xor(s1, 32);
-    s2 += __shfl_xor(s2, 32);
-    if (q == 0) {
-        lds[STAT + wave * 32 + 2 * r] = s1;
-        lds[STAT + wave * 32 + 2 * r + 1] = s2;
-    }
-    __syncthreads(); // every wave is done with the e images
-    // C/D of v_mfma_f64_16x16x4_f64: register j of lane (r, q) = [row q + 4 j][column r]
-    for (int w = 0; w < 4; w++) {
-        if (wave == w) {
-#pragma unroll
-            for (int i = 0; i < TILES; i++)
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    const int at = i * 256 + (q + 4 * j) * 16 + r;
-                    lds[at] = w == 0 ? acc[i][j] : lds[at] + acc[i][j];
-                }
-        }
-        __syncthreads();
-    }
+    window_sum_tiles<TILES>(lds, STAT, acc, s1, s2, wave, r, q);
 
-    // the windowed maxAbsIndex per (series, reference): scan position pos = 0 .. W-1 <-> lag 0 .. L, -Lneg .. -1, cut into
-    // `parts` consecutive parts of `plen` positions per reference
+    // the windowed maxAbsIndex per (series, reference): the scan positions of a reference cut into `parts` consecutive parts of
+    // `plen` positions, one (reference, part) item per 16 threads at a time
     const int c = t & 15;
-    const int W = L + 1 + Lneg, parts = p.parts, plen = (W + parts - 1) / parts;
-    double t1 = 0.0, t2 = 0.0;
-#pragma unroll
-    for (int w = 0; w < 4; w++) {
-        t1 += lds[STAT + w * 32 + 2 * c];
-        t2 += lds[STAT + w * 32 + 2 * c + 1];
-    }
-    const double var = (t2 - t1 * t1 * p.invN) * p.invNm1;
-    const bool nan = !__builtin_isfinite(var);
-    const bool zero = !nan && !(var > 0.0);
-    const double mean = t1 * p.invN;
-    const double inv_sigma = 1.0 / sqrt(var);
+    const int parts = p.parts, plen = (L + 1 + Lneg + parts - 1) / parts;
+    const WindowStats st = window_stats(window_wave_sum(lds, STAT, 2 * c), window_wave_sum(lds, STAT, 2 * c + 1), p.invN, p.invNm1);
     for (int item = t >> 4; item < R * parts; item += 16) {
         const int ref = item / parts, part = item - ref * parts;
         const double *__restrict__ pw = p.pw[ref];
-        double best_abs = 0.0, best_val = 0.0, best_pos = -1.0;
-        for (int k = 0; k < plen; k++) {
-            const int pos = part * plen + k;
-            if (pos < W) {
-                const int v = pos <= L ? pos + L : pos - 1 - Lneg; // lag + L
-                const int rr = ref * Wv + v;
-                const double S = lds[(rr >> 4) * 256 + (rr & 15) * 16 + c];
-                const double val = (S - mean * pw[v]) * inv_sigma;
-                if (fabs(val) > best_abs) {
-                    best_abs = fabs(val);
-                    best_val = val;
-                    best_pos = (double)pos;
-                }
-            }
-        }
-        lds[CAND + (item * 16 + c) * 3] = best_abs;
-        lds[CAND + (item * 16 + c) * 3 + 1] = best_val;
-        lds[CAND + (item * 16 + c) * 3 + 2] = best_pos;
+        WindowBest best;
+        for (int k = 0; k < plen; k++)
+            window_scan_pos(best, lds, ref * Wv, part * plen + k, c, L, Lneg, st, pw);
+        window_put_best(lds + CAND + (item * 16 + c) * 3, best);
     }
     __syncthreads();
     if (row0 + c < p.M) {
         for (int ref = t >> 4; ref < R; ref += 16) {
-            double ba = 0.0, bv = 0.0;
-            int bp = -1;
-            for (int k = 0; k < parts; k++) {
-                const int at = CAND + ((ref * parts + k) * 16 + c) * 3;
-                const double a = lds[at];
-                if (a > ba) {
-                    ba = a;
-                    bv = lds[at + 1];
-                    bp = (int)lds[at + 2];
-                }
-            }
-            int lag = 0;
-            double mv;
-            if (nan) {
-                mv = __builtin_nan("");
-            } else if (zero) {
-                mv = 0.0; // sigma == 0: (nil, 0, 0), xcorr.go:165-168
-            } else if (bp < 0) { // only zeros or NaN in the window: index 0 stands
-                const int rr = ref * Wv + L;
-                mv = (lds[(rr >> 4) * 256 + (rr & 15) * 16 + c] - mean * p.pw[ref][L]) * inv_sigma;
-            } else {
-                mv = bv;
-                lag = bp <= L ? bp : bp - 1 - Lneg - L;
-            }
-            p.mv[ref][row0 + c] = mv;
+            int lag;
+            p.mv[ref][row0 + c] = window_outcome(lds, CAND, ref * parts, parts, ref * Wv, c, L, Lneg, st, p.pw[ref], &lag);
             p.lag[ref][row0 + c] = lag;
         }
     }
@@ -261,10 +174,8 @@ hipError_t launch_window_many(WindowManyParams p, hipStream_t stream)
 {
     if (p.M <= 0)
         return hipSuccess;
-    if (p.L < 0 || p.L > MUSE_LAG_WINDOW_MAX || p.Lneg < 0 || p.Lneg > p.L || p.N < 2 || p.R < 1 || p.R > window_many_max_refs(p.L))
-        return hipErrorInvalidValue;
-    const long long blocks = (p.M + 15) / 16;
-    if (blocks > 0x7fffffffLL)
+    long long blocks;
+    if (window_launch_check(p, &blocks) != hipSuccess || p.R < 1 || p.R > window_many_max_refs(p.L))
         return hipErrorInvalidValue;
     const int tiles = (p.R * (2 * p.L + 1) + 15) / 16;
     p.kc = window_many_kc(p.L, p.R);
@@ -274,26 +185,14 @@ hipError_t launch_window_many(WindowManyParams p, hipStream_t stream)
     const size_t lds_bytes = (size_t)(p.buf + 128 + p.R * p.parts * 16 * 3) * sizeof(double);
     if (tiles > WINM_MAX_TILES || lds_bytes > 64 * 1024)
         return hipErrorInvalidValue;
-    const dim3 grid((unsigned)blocks), block(WINM_THREADS);
+    const dim3 grid((unsigned)blocks), block(WIN_THREADS);
     const bool wide = window_wide(p.rows, p.stride);
-#define MUSE_WINDOW_MANY_LAUNCH(T)                                                        \
-    do {                                                                                  \
-        if (wide)                                                                         \
-            xcorr_window_many_mfma<T, true><<<grid, block, lds_bytes, stream>>>(p);       \
-        else                                                                              \
-            xcorr_window_many_mfma<T, false><<<grid, block, lds_bytes, stream>>>(p);      \
-    } while (0)
-    switch (tiles) {
-    case 1: MUSE_WINDOW_MANY_LAUNCH(1); break;
-    case 2: MUSE_WINDOW_MANY_LAUNCH(2); break;
-    case 3: MUSE_WINDOW_MANY_LAUNCH(3); break;
-    case 4: MUSE_WINDOW_MANY_LAUNCH(4); break;
-    case 5: MUSE_WINDOW_MANY_LAUNCH(5); break;
-    case 6: MUSE_WINDOW_MANY_LAUNCH(6); break;
-    case 7: MUSE_WINDOW_MANY_LAUNCH(7); break;
-    default: MUSE_WINDOW_MANY_LAUNCH(8); break;
-    }
-#undef MUSE_WINDOW_MANY_LAUNCH
+    window_with_tiles(tiles, [&](auto T) {
+        if (wide)
+            xcorr_window_many_mfma<T(), true><<<grid, block, lds_bytes, stream>>>(p);
+        else
+            xcorr_window_many_mfma<T(), false><<<grid, block, lds_bytes, stream>>>(p);
+    });
     return hipGetLastError();
 }
 

@@ -5,9 +5,10 @@
 // and every sample a lane has loaded for the product is also stored to position t of the same row: 2 x 8 N M bytes cross HBM where
 // muse_group_slide followed by the windowed pass moves 3 x.
 //
-// THE ARITHMETIC IS xcorr_window_mfma's, to the bit: 16 series per 256-thread workgroup, e staged per chunk of WIN_KC samples, piece
-// p of a chunk on wave p mod 4, the lane -> sample mapping of the WIDE / narrow build, d = y - y0, s1 / s2, the MFMA order, and
-// window_finish (window_device.h) behind it.  WIDE is the MAPPING and follows window_wide() of the rows, so that a later stand-alone
+// THE ARITHMETIC IS xcorr_window_mfma's, to the bit, because it is the same functions (window_device.h): 16 series per 256-thread
+// workgroup, e staged per chunk of WIN_KC samples (window_stage_e), piece p of a chunk on wave p mod 4, the lane -> sample mapping of
+// the WIDE / narrow build (window_k), d = y - y0, s1 / s2 and the MFMA order (the k-loop of window_mac_piece, written out below), and
+// window_finish behind it.  The loader is this kernel's own: two sources, the raw values kept for the store, explicit waits.  WIDE is the MAPPING and follows window_wide() of the rows, so that a later stand-alone
 // pass over the slid rows sums in the same order; LOAD16 is only the width of the loads (slide_score_plan): a WIDE lane's two
 // consecutive samples come from one 16-byte load when k is even (row + k, every tail row r k and N - k are then even: aligned, and
 // no pair straddles the kept / tail boundary), from two 8-byte loads otherwise.  Stores are 16-byte in WIDE builds (the destination
@@ -70,35 +71,34 @@ __global__ __launch_bounds__(WIN_THREADS) void xcorr_window_slide_mfma(const Win
     for (int T0 = 0; T0 < N; T0 += WIN_KC) {
         if (T0 > 0)
             __syncthreads();
-        for (int v = t; v < WIN_ELDS; v += WIN_THREADS) // (the table is padded with zeros to whole chunks)
-            lds[v] = p.e[T0 + v];
+        window_stage_e(lds, p.e + T0, t);
         __syncthreads();
         for (int s0 = 0; s0 < WIN_KC / 64 && T0 + 64 * s0 < N; s0 += 4) { // a round: uniform over the workgroup
             const int s = s0 + wave;
             const int T = T0 + 64 * s;
             const bool active = T < N;         // (wave-uniform) the round's last pieces may lie behind the row
             const bool kept = T + 64 <= keep;  // (wave-uniform) the whole piece comes from the old row
-            // the mapping of xcorr_window_mfma: WIDE: k-step m = 2 mp + h <-> sample T + 8 mp + 2 q + h; else k-step m <-> sample T + 4 m + q
+            // k-step m of this lane <-> sample T + window_k<WIDE>(m, q) (window_device.h)
             double raw[16];
             if (active && kept) {
                 const double *src = y + k + T;
                 if (LOAD16) {
 #pragma unroll
                     for (int mp = 0; mp < 8; mp++) {
-                        const double2 v = *reinterpret_cast<const double2 *>(src + 8 * mp + 2 * q);
+                        const double2 v = *reinterpret_cast<const double2 *>(src + window_a<true>(2 * mp) + window_k<true>(0, q));
                         raw[2 * mp] = v.x;
                         raw[2 * mp + 1] = v.y;
                     }
                 } else {
 #pragma unroll
                     for (int m = 0; m < 16; m++)
-                        raw[m] = src[WIDE ? 8 * (m >> 1) + 2 * q + (m & 1) : 4 * m + q];
+                        raw[m] = src[window_k<WIDE>(m, q)];
                 }
             } else if (active) {
                 if (LOAD16) { // N, k even: both samples of a pair lie on the same side of N - k and of N
 #pragma unroll
                     for (int mp = 0; mp < 8; mp++) {
-                        const int tt = T + 8 * mp + 2 * q;
+                        const int tt = T + window_k<true>(2 * mp, q);
                         const double *src = tt < keep ? y + tt + k : (tt < N ? tl + (tt - keep) : tl);
                         const double2 v = *reinterpret_cast<const double2 *>(src);
                         raw[2 * mp] = v.x;
@@ -107,7 +107,7 @@ __global__ __launch_bounds__(WIN_THREADS) void xcorr_window_slide_mfma(const Win
                 } else {
 #pragma unroll
                     for (int m = 0; m < 16; m++) {
-                        const int tt = T + (WIDE ? 8 * (m >> 1) + 2 * q + (m & 1) : 4 * m + q);
+                        const int tt = T + window_k<WIDE>(m, q);
                         const double *src = tt < keep ? y + tt + k : (tt < N ? tl + (tt - keep) : tl);
                         raw[m] = *src;
                     }
@@ -121,30 +121,31 @@ __global__ __launch_bounds__(WIN_THREADS) void xcorr_window_slide_mfma(const Win
                 if (WIDE) { // (N is even: a pair is stored whole or not at all)
 #pragma unroll
                     for (int mp = 0; mp < 8; mp++) {
-                        const int tt = T + 8 * mp + 2 * q;
+                        const int tt = T + window_k<true>(2 * mp, q);
                         if (tt < N)
                             *reinterpret_cast<double2 *>(y + tt) = double2{raw[2 * mp], raw[2 * mp + 1]};
                     }
                 } else {
 #pragma unroll
                     for (int m = 0; m < 16; m++) {
-                        const int tt = T + 4 * m + q;
+                        const int tt = T + window_k<false>(m, q);
                         if (tt < N)
                             y[tt] = raw[m];
                     }
                 }
             }
             const bool whole = T + 64 <= N;
-            const double *a = lds + 64 * s + (WIDE ? 2 * q : q) + r;
+            // (the k-loop of window_mac_piece, written out with d formed at use: through the function four shapes of
+            // tools/slide_score_bench.py measured 1 ... 2 % slower; profiles/window_refactor.txt)
+            const double *a = lds + 64 * s + window_k<WIDE>(0, q) + r;
 #pragma unroll
             for (int m = 0; m < 16; m++) {
-                const int tt = T + (WIDE ? 8 * (m >> 1) + 2 * q + (m & 1) : 4 * m + q);
-                const double d = whole || tt < N ? raw[m] - y0 : 0.0;
+                const double d = whole || T + window_k<WIDE>(m, q) < N ? raw[m] - y0 : 0.0;
                 s1 += d;
                 s2 = fma(d, d, s2);
 #pragma unroll
                 for (int i = 0; i < TILES; i++)
-                    acc[i] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[(WIDE ? 8 * (m >> 1) + (m & 1) : 4 * m) + 16 * i], d, acc[i], 0, 0, 0);
+                    acc[i] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[window_a<WIDE>(m) + 16 * i], d, acc[i], 0, 0, 0);
             }
         }
     }
@@ -162,39 +163,24 @@ hipError_t launch_window_slide(const WindowParams &p, const double *tails, int k
 {
     if (p.M <= 0)
         return hipSuccess;
-    if (p.L < 0 || p.L > MUSE_LAG_WINDOW_MAX || p.Lneg < 0 || p.Lneg > p.L || p.N < 2)
+    long long blocks;
+    if (window_launch_check(p, &blocks) != hipSuccess)
         return hipErrorInvalidValue;
     // dense rows (a group's: the slide is defined on them), 1 <= k <= N (k == 0 is launch_window's), tails 16-byte aligned
     if (p.stride != p.N || k < 1 || k > p.N || !tails || !p.rows || ((uintptr_t)tails & 15) != 0)
         return hipErrorInvalidValue;
-    const long long blocks = (p.M + 15) / 16;
-    if (blocks > 0x7fffffffLL)
-        return hipErrorInvalidValue;
     const dim3 grid((unsigned)blocks), block(WIN_THREADS);
-    const int W = 2 * p.L + 1; // lag + L runs up to 2 L whichever side the window drops
     const bool wide = window_wide(p.rows, p.stride);
     int load_bytes = 8, store_bytes = 8;
     slide_score_plan(p.N, k, wide, &load_bytes, &store_bytes);
-#define MUSE_WINDOW_SLIDE_LAUNCH(T)                                                              \
-    do {                                                                                         \
-        if (wide && load_bytes == 16)                                                            \
-            xcorr_window_slide_mfma<T, true, true><<<grid, block, 0, stream>>>(p, tails, k);     \
-        else if (wide)                                                                           \
-            xcorr_window_slide_mfma<T, true, false><<<grid, block, 0, stream>>>(p, tails, k);    \
-        else                                                                                     \
-            xcorr_window_slide_mfma<T, false, false><<<grid, block, 0, stream>>>(p, tails, k);   \
-    } while (0)
-    switch ((W + 15) / 16) { // accumulator tiles of 16 lags
-    case 1: MUSE_WINDOW_SLIDE_LAUNCH(1); break;
-    case 2: MUSE_WINDOW_SLIDE_LAUNCH(2); break;
-    case 3: MUSE_WINDOW_SLIDE_LAUNCH(3); break;
-    case 4: MUSE_WINDOW_SLIDE_LAUNCH(4); break;
-    case 5: MUSE_WINDOW_SLIDE_LAUNCH(5); break;
-    case 6: MUSE_WINDOW_SLIDE_LAUNCH(6); break;
-    case 7: MUSE_WINDOW_SLIDE_LAUNCH(7); break;
-    default: MUSE_WINDOW_SLIDE_LAUNCH(8); break;
-    }
-#undef MUSE_WINDOW_SLIDE_LAUNCH
+    window_with_tiles(window_tiles(p.L), [&](auto tiles) {
+        if (wide && load_bytes == 16)
+            xcorr_window_slide_mfma<tiles(), true, true><<<grid, block, 0, stream>>>(p, tails, k);
+        else if (wide)
+            xcorr_window_slide_mfma<tiles(), true, false><<<grid, block, 0, stream>>>(p, tails, k);
+        else
+            xcorr_window_slide_mfma<tiles(), false, false><<<grid, block, 0, stream>>>(p, tails, k);
+    });
     return hipGetLastError();
 }
 
