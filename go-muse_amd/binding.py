@@ -30,6 +30,7 @@ MUSE_ERR_NOMEM = -7
 MUSE_ERR_EMPTY = -8
 MUSE_LAG_WINDOW_MAX = 63
 MUSE_IN_WINDOW_UNSUPPORTED, MUSE_IN_WINDOW_PLAIN, MUSE_IN_WINDOW_MFMA, MUSE_IN_WINDOW_MASKED = 0, 1, 2, 3   # muse_hip_test.h
+MUSE_IN_WINDOW_MASKED_EACH = 4   # (muse_test_many_in_window_plan only)
 
 
 class MuseRecord(ctypes.Structure):
@@ -126,6 +127,10 @@ SIGNATURES = {
     "muse_batch_run_many_windowed": (ctypes.c_int, [ctypes.POINTER(_vp), _i32, _i32p, _i32, _i32, _i32, _f64, _i32, _i32,
                                                     _i64p, _i32p, _dp, _i32p, _dp]),
     "muse_test_window_many_plan": (ctypes.c_int, [_i32, _i32, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p]),
+    "muse_batch_score_many_in_window": (ctypes.c_int, [ctypes.POINTER(_vp), _i32, _i32]),
+    "muse_batch_run_many_in_window": (ctypes.c_int, [ctypes.POINTER(_vp), _i32, _i32p, _i32, _i32, _i32, _f64, _i32, _i32,
+                                                     _i64p, _i32p, _dp, _i32p, _dp]),
+    "muse_test_many_in_window_plan": (ctypes.c_int, [_i32, _i32, _i32, _i32, _i32p]),
     "muse_batch_run_many": (ctypes.c_int, [ctypes.POINTER(_vp), _i32, _i32p, _i32, _i32, _i32, _f64, _i32, _i32,
                                            _i64p, _i32p, _dp, _i32p, _dp]),
     "muse_batch_free": (ctypes.c_int, [_vp]),

@@ -767,7 +767,11 @@ extern "C" int muse_batch_kernel_name(muse_batch *b, char *name, int32_t cap)
     char k[96] = "xcorr_fused_generic";
     const char *padded = b->N < b->n ? "true" : "false", *f32 = b->g->f32 ? "true" : "false";
     if (b->in_window_path == MUSE_IN_WINDOW_MASKED) { // (as many_tiles below: the pass that filled mv / lag, an argument of a call)
-        if (b->n == 4096 && b->in_window_variant == KERNEL_R16_OCC3) // (the learned hand-off, or no correction table)
+        if (b->in_window_variant == IN_WINDOW_VARIANT_MANY && b->n == 4096) // (muse_batch_score_many_in_window's one pass)
+            snprintf(k, sizeof(k), "xcorr_fused_n4096_fold_multi<%s, %s, true>", padded, f32);
+        else if (b->in_window_variant == IN_WINDOW_VARIANT_MANY)
+            snprintf(k, sizeof(k), "xcorr_fused_small<%d, %s, true, false, true>", b->logn, padded);
+        else if (b->n == 4096 && b->in_window_variant == KERNEL_R16_OCC3) // (the learned hand-off, or no correction table)
             snprintf(k, sizeof(k), "xcorr_fused_n4096_occ4<%s, 3, false, %s, true>", padded, f32);
         else if (b->n == 4096)
             snprintf(k, sizeof(k), "xcorr_fused_n4096_fold<false, %s, %s, true>", padded, f32);

@@ -346,8 +346,10 @@ struct muse_batch {
     int32_t many_tiles = 0;
     // the path the batch's scores came by when the last scoring pass was muse_batch_score_in_window (MUSE_IN_WINDOW_*,
     // muse_hip_test.h; MASKED: in_window_L = the window, muse_batch_kernel_name names the masked instantiation); any other scoring pass clears it
-    int32_t in_window_path = 0, in_window_L = -1, in_window_variant = 0; // (_variant: the KERNEL_* the masked pass launched first)
+    // (_variant: the KERNEL_* the masked pass launched first; IN_WINDOW_VARIANT_MANY: the one masked pass of muse_batch_score_many_in_window)
+    int32_t in_window_path = 0, in_window_L = -1, in_window_variant = 0;
 };
+constexpr int32_t IN_WINDOW_VARIANT_MANY = -1; // (no KERNEL_* is negative)
 
 int use_device(muse_ctx *ctx);
 

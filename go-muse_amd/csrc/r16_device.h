@@ -115,6 +115,26 @@ __device__ __forceinline__ void mask_window(double2 (&v)[16], const int base, co
         v[k].y = in ? v[k].y : 0.0;
     }
 }
+// The same mask with the register number compared against the two QUOTIENTS floor(a / STEP) and ceil(b / STEP) (STEP a power of two:
+// arithmetic shifts): STEP m <= a iff m <= floor(a / STEP), STEP m >= b iff m >= ceil(b / STEP).  Every compare is against an inline
+// constant 0 ... 15.  For the many-references n = 4096 kernel, which runs at 256 vector registers with its scalar registers full:
+// the thirty literals 256 m +- 1 of mask_window were kept in scalar registers across the pair loop there, pushed seventeen others into
+// spill lanes, and the register holding those lanes pushed part of the pair's spectrum into scratch.
+template <bool BITREV, int STEP>
+__device__ __forceinline__ void mask_window_quot(double2 (&v)[16], const int base, const int lpos, const int nl)
+{
+    static_assert(STEP > 0 && (STEP & (STEP - 1)) == 0, "the quotients are shifts");
+    constexpr int SH = __builtin_ctz(STEP);
+    int a = (lpos - base) >> SH, b = (nl - base + STEP - 1) >> SH;
+    asm volatile("" : "+v"(a), "+v"(b));
+#pragma unroll
+    for (int m = 0; m < 16; m++) {
+        const int k = BITREV ? ((m & 1) << 3) | ((m & 2) << 1) | ((m & 4) >> 1) | ((m & 8) >> 3) : m;
+        const bool in = m <= a || m >= b;
+        v[k].x = in ? v[k].x : 0.0;
+        v[k].y = in ? v[k].y : 0.0;
+    }
+}
 
 // One LDS transpose in two half rounds through the 8 x 272 buffer (positions in
 // double2 units).  Layouts (same bank analysis as xcorr_kernels.hip):

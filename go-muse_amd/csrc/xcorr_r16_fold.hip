@@ -340,7 +340,9 @@ constexpr int MULTI_WGS_PER_CU = 2;
 // -m c1_r[index] (FusedParams::c1_many) before the argmax.
 // F32: float32-storage group (rows widened as they are consumed, float64 arithmetic)
 // TIMING: the phase-stamped build of tools/ablate/multi_phases.hip (FusedParams::dbg); the product kernel below is <.., false>.
-template <bool PADDED, bool F32, bool TIMING>
+// WIN: masked argmax (muse_batch_score_many_in_window): every reference's values outside the ONE lag window p.win_lpos / p.win_lneg
+// are replaced by +0.0 right in front of its argmax (behind the PADDED correction), as in xcorr_fused_n4096_fold
+template <bool PADDED, bool F32, bool TIMING, bool WIN = false>
 __device__ __forceinline__ void fold_multi_body(const FusedParams &p)
 {
     using namespace occ4;
@@ -457,6 +459,12 @@ __device__ __forceinline__ void fold_multi_body(const FusedParams &p)
                 }
             }
         }
+        if (WIN) { // cc index t + 256 m3 at v[BR16(m3)].  The thread's base is taken from t HERE: formed outside the loops, the two
+                   // bounds relative to it stay in registers across the whole pair loop, which has none to spare
+            int tw = t;
+            asm volatile("" : "+v"(tw));
+            mask_window_quot<true, 256>(v, tw, p.win_lpos, 4096 - p.win_lneg);
+        }
         clk.template stamp<11>();
         wave_argmax_store(v, wave, lane, tr + 6 * wave);
         if (wave == 0 && lane == 0) {
@@ -551,6 +559,12 @@ __device__ __forceinline__ void fold_multi_body(const FusedParams &p)
             // reference iteration (~ 5 us) ahead of their use
             nextpair = __builtin_amdgcn_readfirstlane(next_s[pp]);
             const long long nxt = nextpair < total ? nextpair : 0; // nothing left: pair 0 (L2-resident dummy)
+            if (WIN) { // (the spectrum as the loop left it: nothing derived from it for this stage -- nine negated components -- is formed
+                       // in front of the reference loop and carried across it; with the mask's registers they went to scratch)
+#pragma unroll
+                for (int k = 0; k < 16; k++)
+                    asm volatile("" : "+v"(Z[k].x), "+v"(Z[k].y));
+            }
             correlate(Z, xf, R - 1, st, std::true_type{}, [&]() __attribute__((always_inline)) { request_rows(nxt); }, [&]() __attribute__((always_inline)) {});
         }
         pp ^= 1;
@@ -564,10 +578,10 @@ __device__ __forceinline__ void fold_multi_body(const FusedParams &p)
     }
 }
 
-template <bool PADDED = false, bool F32 = false>
+template <bool PADDED = false, bool F32 = false, bool WIN = false>
 __global__ __launch_bounds__(OCC_THREADS, MULTI_WGS_PER_CU) void xcorr_fused_n4096_fold_multi(const FusedParams p)
 {
-    fold_multi_body<PADDED, F32, false>(p);
+    fold_multi_body<PADDED, F32, false, WIN>(p);
 }
 
 // R >= 1 references, n == 4096 (N < 4096: p.c1_many); p.ovf_count and p.work_counter zeroed; a resident grid
@@ -579,9 +593,24 @@ hipError_t launch_fused_multi(const FusedParams &p_in, int num_cus, hipStream_t 
     if (!p.work_counter || p.R < 1 || !p.g2 || !p.g3a || !p.g3b || !p.xcp_many || !p.mv_many || !p.lag_many)
         return hipErrorInvalidValue;
     const dim3 g((unsigned)grid), b(OCC_THREADS);
-    if (p.N < 4096) {
-        if (!p.c1_many)
+    if (p.N < 4096 && !p.c1_many)
+        return hipErrorInvalidValue;
+    if (p.win) { // the masked argmax, one window for every reference (muse_batch_score_many_in_window)
+        if (p.win_lpos < 0 || p.win_lneg < 0 || p.win_lpos > 2048 || p.win_lneg > p.win_lpos)
             return hipErrorInvalidValue;
+        if (p.rows32) {
+            if (p.N < 4096)
+                hipLaunchKernelGGL((xcorr_fused_n4096_fold_multi<true, true, true>), g, b, 0, stream, p);
+            else
+                hipLaunchKernelGGL((xcorr_fused_n4096_fold_multi<false, true, true>), g, b, 0, stream, p);
+        } else if (p.N < 4096) {
+            hipLaunchKernelGGL((xcorr_fused_n4096_fold_multi<true, false, true>), g, b, 0, stream, p);
+        } else {
+            hipLaunchKernelGGL((xcorr_fused_n4096_fold_multi<false, false, true>), g, b, 0, stream, p);
+        }
+        return hipGetLastError();
+    }
+    if (p.N < 4096) {
         if (p.rows32)
             hipLaunchKernelGGL((xcorr_fused_n4096_fold_multi<true, true>), g, b, 0, stream, p);
         else

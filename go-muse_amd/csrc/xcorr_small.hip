@@ -51,8 +51,9 @@ namespace muse {
 // consumed; the arithmetic is the float64 arithmetic of the float64 groups.
 // ZREG (MULTI, n <= 8192): the pair's spectrum stays in REGISTERS over the references (256 VGPRs: half the resident waves)
 // instead of being parked in the workgroup's slice of global scratch (n = 16384: 1024 threads per pair cap a lane at 128).
-// WIN (single reference, n <= 2048): masked argmax (muse_batch_score_in_window; r16_device.h, mask_window) -- the values outside the
-// lag window p.win_lpos / p.win_lneg are replaced by +0.0 right in front of the argmax
+// WIN (n <= 2048; float64 rows with MULTI): masked argmax (muse_batch_score_in_window, muse_batch_score_many_in_window; r16_device.h,
+// mask_window) -- the values outside the lag window p.win_lpos / p.win_lneg (MULTI: one window for every reference) are replaced by
+// +0.0 right in front of the argmax
 template <int LOGN, bool PADDED, bool MULTI, bool F32 = false, bool WIN = false>
 __global__ __launch_bounds__((LOGN >= 11 ? (1 << LOGN) / 16 : 256), ((MULTI && LOGN <= 13) ? 2 : 4)) void xcorr_fused_small(const FusedParams p)
 {
@@ -64,7 +65,7 @@ __global__ __launch_bounds__((LOGN >= 11 ? (1 << LOGN) / 16 : 256), ((MULTI && L
     constexpr int TPB = LOGN >= 11 ? S : 256;
     constexpr int G = TPB / S;  // pairs per workgroup iteration: 8, 4, 1, 1, 1
     static_assert((LOGN >= 9 && LOGN <= 11) || LOGN == 13 || LOGN == 14, "n = 512, 1024, 2048, 8192, 16384");
-    static_assert(!WIN || (!MULTI && LOGN <= 11), "the masked argmax is built for one reference at n = 512, 1024, 2048");
+    static_assert(!WIN || LOGN <= 11, "the masked argmax is built for n = 512, 1024, 2048");
     __shared__ double red[112]; // multi-wave pair reductions (n >= 2048): sums [4][16], maxima [2][16], indices [2][16] ints
     // pass 2's eight factors per phase m2 / R1: 8 x R1 distinct values for the whole workgroup.  Gathered per lane from the
     // W_65536 table they were the kernel's longest stall (scattered L2 lines in front of the first butterfly of a pass:
@@ -570,8 +571,8 @@ static hipError_t launch_small_n(const FusedParams &p, int num_cus, hipStream_t 
     constexpr int TPB = LOGN >= 11 ? (1 << LOGN) / 16 : 256;
     constexpr int G = TPB / ((1 << LOGN) / 16);
     const long long ngroups = (p.npairs + G - 1) / G;
-    if (p.R > 1 && p.win)
-        return hipErrorInvalidValue; // (the masked argmax is built for one reference)
+    if (p.R > 1 && p.win && LOGN > 11)
+        return hipErrorInvalidValue; // (the masked argmax is built for n = 512, 1024, 2048)
     if (p.R > 1) { // one pass for R references: exactly the resident workgroups (n = 16384: each with its slice of the spectrum scratch)
         constexpr bool ZREG = LOGN <= 13;
         if (!p.xcp_many || !p.mv_many || !p.lag_many || (!ZREG && !p.zscratch))
@@ -579,6 +580,17 @@ static hipError_t launch_small_n(const FusedParams &p, int num_cus, hipStream_t 
         const long long grid = std::min<long long>(ngroups, (long long)num_cus * (ZREG ? std::max(1, 512 / TPB) : 1024 / TPB));
         if (!ZREG && (size_t)grid * TPB * 16 > (size_t)p.zslots * 4096)
             return hipErrorInvalidValue;
+        if constexpr (LOGN <= 11) {
+            if (p.win) { // the masked argmax, one window for every reference (muse_batch_score_many_in_window)
+                if (p.pair_list || p.win_lpos < 0 || p.win_lneg < 0 || p.win_lpos > (1 << LOGN) / 2 || p.win_lneg > p.win_lpos)
+                    return hipErrorInvalidValue;
+                if (p.N < (1 << LOGN))
+                    hipLaunchKernelGGL((xcorr_fused_small<LOGN, true, true, false, true>), dim3((unsigned)grid), dim3(TPB), 0, stream, p);
+                else
+                    hipLaunchKernelGGL((xcorr_fused_small<LOGN, false, true, false, true>), dim3((unsigned)grid), dim3(TPB), 0, stream, p);
+                return hipGetLastError();
+            }
+        }
         if (p.N < (1 << LOGN))
             hipLaunchKernelGGL((xcorr_fused_small<LOGN, true, true>), dim3((unsigned)grid), dim3(TPB), 0, stream, p);
         else

@@ -916,6 +916,120 @@ func runMany(batches []*Batch, groupByLabels []string, windowed bool) error {
 	return nil
 }
 
+// RunManyInWindow is RunMany with the shared Results.MaxLag as a lag window of ANY width (muse_batch_run_many_in_window): every
+// batch receives what its own RunInWindow gives, from one pass over the rows where the lengths have a masked many-references
+// kernel (FFT lengths 512 ... 4096).  One device.  Results is fed as RunInWindow feeds it.  Batches that do not qualify for
+// RunMany are RunInWindow one after the other.
+func RunManyInWindow(batches []*Batch, groupByLabels []string) error {
+	if len(batches) == 0 {
+		return nil
+	}
+	b0 := batches[0]
+	same := true
+	for _, b := range batches {
+		r, r0 := b.Results, b0.Results
+		same = same && b.Comparison == b0.Comparison && r.MaxLag == r0.MaxLag && r.TopN == r0.TopN &&
+			r.Threshold == r0.Threshold && r.SignFilter == r0.SignFilter
+	}
+	if !same {
+		for _, b := range batches {
+			if err := b.RunInWindow(groupByLabels); err != nil {
+				return err
+			}
+		}
+		return nil
+	}
+	if b0.Results.MaxLag < 0 {
+		return fmt.Errorf("RunManyInWindow: MaxLag < 0")
+	}
+	if es := shardEngines(); es != nil {
+		return fmt.Errorf("RunManyInWindow runs on one device")
+	}
+	labelValuesSet := b0.Comparison.indexLabelValues(groupByLabels)
+	if len(labelValuesSet) == 0 {
+		return nil
+	}
+	e, err := getEngine()
+	if err != nil {
+		return err
+	}
+	dg, err := b0.Comparison.residentRows(e)
+	if err != nil {
+		return err
+	}
+	pos := make(map[string]int, len(b0.Comparison.order))
+	for i, s := range b0.Comparison.order {
+		pos[s.UID()] = i
+	}
+	gid := make([]C.int32_t, len(b0.Comparison.order))
+	gi := 0
+	for _, lv := range labelValuesSet {
+		for _, uid := range b0.Comparison.index[lv.ID(lv.Keys())] {
+			gid[pos[uid]] = C.int32_t(gi)
+		}
+		gi++
+	}
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	// the handle array lives in C memory: cgo forbids passing Go memory that holds pointers
+	R := len(batches)
+	hs := (**C.muse_batch)(C.malloc(C.size_t(R) * C.size_t(unsafe.Sizeof((*C.muse_batch)(nil)))))
+	defer C.free(unsafe.Pointer(hs))
+	hv := batchView(hs, R)
+	for i, b := range batches {
+		if b.batch == nil || b.batchGroup != dg {
+			if b.batch != nil {
+				C.muse_batch_free(b.batch)
+			}
+			st := C.muse_batch_create(e.ctx, dg, (*C.double)(unsafe.Pointer(&b.ref[0])), C.int32_t(len(b.ref)), &b.batch)
+			if err := hipError(st); err != nil {
+				return err
+			}
+			b.batchGroup = dg
+		}
+		// (as Run does: a window an earlier RunWindowed left on the handle goes; this pass takes its own as an argument)
+		if err := hipError(C.muse_batch_set_lag_window(b.batch, C.int32_t(b.window))); err != nil {
+			return err
+		}
+		hv[i] = b.batch
+	}
+	r := b0.Results
+	G := len(labelValuesSet)
+	topN, threshold, sign := r.TopN, r.Threshold, int(r.SignFilter)
+	if G <= exactFeedMaxGroups {
+		topN, threshold, sign = G, 0.0, 0
+	}
+	top := topN
+	if top < 1 {
+		top = 1
+	}
+	idx := make([]C.int64_t, R*top)
+	lag := make([]C.int32_t, R*top)
+	score := make([]C.double, R*top)
+	cnt := make([]C.int32_t, R)
+	mean := make([]C.double, R)
+	st := C.muse_batch_run_many_in_window(hs, C.int32_t(R), &gid[0], C.int32_t(G), C.int32_t(r.MaxLag), C.int32_t(topN),
+		C.double(threshold), C.int32_t(sign), 1, &idx[0], &lag[0], &score[0], &cnt[0], &mean[0])
+	if err := hipError(st); err != nil {
+		return err
+	}
+	if topN < 0 {
+		topN = 0
+	}
+	for i, b := range batches {
+		o := i * topN
+		order := make([]int, int(cnt[i]))
+		for k := range order {
+			order[k] = k
+		}
+		sort.SliceStable(order, func(a, c int) bool { return gid[idx[o+order[a]]] < gid[idx[o+order[c]]] })
+		for _, k := range order {
+			b.Results.Update(Score{Labels: b.Comparison.order[idx[o+k]].Labels(), Lag: int(lag[o+k]), PercentScore: float64(score[o+k])})
+		}
+	}
+	return nil
+}
+
 // xCorrBatch is xCorr (xcorr.go:102-153) for many independent (x, y) pairs in ONE launch (muse_xcorr_batch; SURVEY 8f-4):
 // xs[i] and ys[i] are pair i, every x of one length and every y of one length (each zero-padded on its own, xcorr.go:129-130),
 // n raised to max(n, lenx, leny) as in xcorr.go:104-106.  Returns per pair the lag, the signed value and whether the

@@ -1145,6 +1145,57 @@ public:
         run_many(batches, groupByLabels, true);
     }
 
+    // RunMany with the shared Results.MaxLag as a lag window of ANY width (muse_batch_run_many_in_window): every batch receives what
+    // its own RunInWindow gives, from one pass over the rows where the lengths have a masked many-references kernel (FFT lengths
+    // 512 ... 4096).  One device.  Results is fed as RunInWindow feeds it.  Batches that do not qualify for RunMany are RunInWindow
+    // one by one.
+    static void RunManyInWindow(const std::vector<std::shared_ptr<Batch>> &batches, const std::vector<std::string> &groupByLabels)
+    {
+        if (batches.empty())
+            return;
+        bool same = true;
+        for (auto &b : batches) {
+            same &= b->Comparison == batches[0]->Comparison && b->eng_ == batches[0]->eng_ && b->engines_.empty();
+            same &= b->Results_->MaxLag == batches[0]->Results_->MaxLag && b->Results_->TopN == batches[0]->Results_->TopN;
+            same &= b->Results_->Threshold == batches[0]->Results_->Threshold && b->Results_->Filter == batches[0]->Results_->Filter;
+        }
+        if (!same) {
+            for (auto &b : batches)
+                b->RunInWindow(groupByLabels);
+            return;
+        }
+        Batch &b0 = *batches[0];
+        if (b0.Results_->MaxLag < 0)
+            throw Error(MUSE_ERR_INVALID, "RunManyInWindow: MaxLag < 0");
+        std::vector<int32_t> gid;
+        auto lvs = b0.Comparison->indexLabelValues(groupByLabels, &gid);
+        if (lvs.empty())
+            return;
+        muse_group *dg = b0.Comparison->device(b0.eng_);
+        std::vector<muse_batch *> hs;
+        for (auto &b : batches) {
+            b->ensure(dg);
+            hs.push_back(b->batch_);
+        }
+        const bool exact = (int64_t)lvs.size() <= EXACT_FEED_MAX_GROUPS;
+        const int R = (int)hs.size(), top = exact ? (int32_t)lvs.size() : b0.Results_->TopN, cap = std::max(top, 1);
+        std::vector<int64_t> idx((size_t)R * cap);
+        std::vector<int32_t> lag((size_t)R * cap), cnt((size_t)R);
+        std::vector<double> score((size_t)R * cap), mean((size_t)R);
+        check(muse_batch_run_many_in_window(hs.data(), R, gid.data(), (int32_t)lvs.size(), (int32_t)b0.Results_->MaxLag, top,
+                                            exact ? 0.0 : b0.Results_->Threshold, exact ? 0 : (int32_t)b0.Results_->Filter, 1,
+                                            idx.data(), lag.data(), score.data(), cnt.data(), mean.data()));
+        for (int r = 0; r < R; r++) {
+            const size_t o = (size_t)r * std::max(top, 0);
+            std::vector<int> order(cnt[r]);
+            for (int i = 0; i < cnt[r]; i++)
+                order[i] = i;
+            std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return gid[idx[o + a]] < gid[idx[o + b]]; });
+            for (int k : order)
+                batches[r]->Results_->Update(Score{b0.Comparison->series()[idx[o + k]]->Labels(), lag[o + k], score[o + k]});
+        }
+    }
+
     // Batch.Run feeds Results one Score per label group (the reference's feed) up to this many groups
     // (settable: the tests also drive the pre-selecting path, which is otherwise only taken above this many groups)
     static inline int64_t EXACT_FEED_MAX_GROUPS = 65536;

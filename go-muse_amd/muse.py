@@ -817,6 +817,65 @@ def in_window_plan(N, f32, max_lag):
     return int(path.value)
 
 
+def score_many_in_window(batches, max_lag):
+    """muse_batch_score_many_in_window: R references against one resident group, each series' best match INSIDE +-max_lag for ANY
+    max_lag >= 0 and for float32-storage groups too -- at FFT lengths 512 ... 4096 ONE pass of the many-references transform
+    kernels with a masked argmax (asynchronous; results land in each DeviceBatch's own buffers; no batch's own window changes)."""
+    batches, arr = _batch_handles(batches)
+    B.check(B.load().muse_batch_score_many_in_window(arr, len(batches), int(max_lag)))
+
+
+def scores_many_in_window(batches, max_lag):
+    """score_many_in_window + copy back: list of (lag, mv), one per batch"""
+    batches, arr = _batch_handles(batches)
+    lib = B.load()
+    B.check(lib.muse_batch_score_many_in_window(arr, len(batches), int(max_lag)))
+    out = []
+    for b in batches:
+        M = b.dgroup.M
+        lag = np.zeros(M, dtype=np.int32)
+        mv = np.zeros(M)
+        if M:
+            B.check(lib.muse_batch_read_scores(b._h, B.i32ptr(lag), B.dptr(mv)))
+        out.append((lag, mv))
+    return out
+
+
+def run_many_in_window(batches, group_id=None, G=0, max_lag=10, top_n=20, threshold=0.0, sign_filter=0, abs_scores=True):
+    """muse_batch_run_many_in_window: Batch.RunInWindow for every reference (max_lag is the window and the Results.MaxLag);
+    returns a list of (series, lag, score, mean_abs), one per batch"""
+    batches, arr = _batch_handles(batches)
+    R = len(batches)
+    cap = max(int(top_n), 1)
+    o_s = np.zeros(R * cap, dtype=np.int64)
+    o_l = np.zeros(R * cap, dtype=np.int32)
+    o_v = np.zeros(R * cap)
+    cnt = np.zeros(R, dtype=np.int32)
+    mean = np.zeros(R)
+    gid = None
+    if group_id is not None:
+        gid = np.ascontiguousarray(group_id, dtype=np.int32)
+    B.check(B.load().muse_batch_run_many_in_window(
+        arr, R, B.i32ptr(gid) if gid is not None else None, int(G), int(max_lag), int(top_n),
+        float(threshold), int(sign_filter), 1 if abs_scores else 0,
+        B.i64ptr(o_s), B.i32ptr(o_l), B.dptr(o_v), B.i32ptr(cnt), B.dptr(mean)))
+    tn = max(int(top_n), 0)
+    res = []
+    for r in range(R):
+        c = int(cnt[r])
+        res.append((o_s[r * tn:r * tn + c].copy(), o_l[r * tn:r * tn + c].copy(), o_v[r * tn:r * tn + c].copy(),
+                    float(mean[r])))
+    return res
+
+
+def many_in_window_plan(N, f32, max_lag, R):
+    """muse_test_many_in_window_plan (no device): MUSE_IN_WINDOW_* -- the pass score_many_in_window takes for R references against
+    series of N samples (f32: float32 storage) and window max_lag"""
+    path = ctypes.c_int32(-1)
+    B.check(B.load().muse_test_many_in_window_plan(int(N), 1 if f32 else 0, int(max_lag), int(R), ctypes.byref(path)))
+    return int(path.value)
+
+
 def device_count():
     n = ctypes.c_int32(0)
     B.check(B.load().muse_device_count(ctypes.byref(n)))
@@ -1500,6 +1559,43 @@ def RunManyWindowed(batches, groupByLabels):
     gid = comp._group_ids()
     res = run_many_windowed([b._batch() for b in batches], gid, len(labelValuesSet), r0.MaxLag, r0.TopN, r0.Threshold,
                             r0.SignFilter, abs_scores=True)
+    for b, (idx, lag, score, _) in zip(batches, res):
+        order = np.argsort(gid[idx], kind="stable")
+        for k in order:
+            b.Results.Update(Score(series[int(idx[k])].Labels(), int(lag[k]), float(score[k])))
+    return None
+
+
+def RunManyInWindow(batches, groupByLabels):
+    """RunMany with the shared Results.MaxLag as a lag window of ANY width (muse_batch_run_many_in_window): every batch receives
+    what its own RunInWindow(groupByLabels) gives, from one pass over the rows where the lengths have a masked many-references
+    kernel.  One device.  Batches that do not qualify for RunMany are RunInWindow one after the other."""
+    batches = list(batches)
+    if not batches:
+        return None
+    b0 = batches[0]
+    r0 = b0.Results
+    same = all(b.Comparison is b0.Comparison and b._engine is b0._engine and not b._engines and
+               (b.Results.MaxLag, b.Results.TopN, b.Results.Threshold, b.Results.SignFilter) ==
+               (r0.MaxLag, r0.TopN, r0.Threshold, r0.SignFilter) for b in batches)
+    if not same:
+        for b in batches:
+            b.RunInWindow(groupByLabels)
+        return None
+    comp = b0.Comparison
+    labelValuesSet = comp.indexLabelValues(groupByLabels)
+    if not labelValuesSet:
+        return None
+    if r0.MaxLag < 0:
+        raise MuseError(B.MUSE_ERR_INVALID, "RunManyInWindow needs Results.MaxLag >= 0")
+    series = comp._series_list()
+    gid = comp._group_ids()
+    G = len(labelValuesSet)
+    dbs = [b._batch() for b in batches]
+    if G <= EXACT_FEED_MAX_GROUPS:   # (as RunInWindow: one Score per group in group order through Results.Update)
+        res = run_many_in_window(dbs, gid, G, r0.MaxLag, G, 0.0, SignFilter_ANY, abs_scores=True)
+    else:
+        res = run_many_in_window(dbs, gid, G, r0.MaxLag, r0.TopN, r0.Threshold, r0.SignFilter, abs_scores=True)
     for b, (idx, lag, score, _) in zip(batches, res):
         order = np.argsort(gid[idx], kind="stable")
         for k in order:

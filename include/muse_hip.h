@@ -485,6 +485,40 @@ int muse_batch_run_many_windowed(muse_batch *const *batches, int32_t R, const in
                                  int32_t max_lag, int32_t top_n, double threshold, int32_t sign_filter,
                                  int32_t abs_scores, int64_t *out_series, int32_t *out_lag, double *out_score,
                                  int32_t *out_count, double *out_mean_abs);
+/* Many references INSIDE A LAG WINDOW OF ANY WIDTH in one pass over the rows: per batch and series the (lag, mv) of
+ * muse_batch_score_in_window(b, max_lag), L = min(max_lag, n/2) -- the window an argument of the call, one window for every
+ * reference, no batch's own lag_window changed.  Which pass runs is decided from the length, the storage, L and R:
+ *   L == n/2 (the window is every lag)                               : muse_batch_score_many, bit for bit
+ *   float64 group, L <= MUSE_LAG_WINDOW_MAX, up to 65536 samples     : muse_batch_score_many_windowed, bit for bit
+ *   FFT length 512, 1024, 2048 or 4096 (256 < N <= 4096), L >
+ *   MUSE_LAG_WINDOW_MAX or a float32-storage group, R >= 2, and
+ *   muse_batch_score_many's own one-pass conditions (FFT length 4096
+ *   on either storage, 512 ... 2048 on float64; automatic kernel
+ *   selection; the correction tables where N < 4096)                 : ONE pass of the many-references transform kernels -- every pair
+ *                                                                      of series read and forward-transformed once -- with every
+ *                                                                      reference's argmax restricted to the window (cc[i] outside
+ *                                                                      it replaced by +0.0 in front of maxAbsIndex); pairs the
+ *                                                                      FFT length 4096 kernel lists (NaN / Inf, sigmas far apart)
+ *                                                                      are redone per reference with the same window.  Lags are
+ *                                                                      those of muse_batch_score_in_window, scores agree to
+ *                                                                      rounding (the arithmetic is muse_batch_score_many's)
+ *   the same lengths where those conditions do not hold (R == 1,
+ *   float32 storage below FFT length 4096, ...)                      : muse_batch_score_in_window(b, max_lag) batch after batch
+ *   anything else                                                    : MUSE_ERR_UNSUPPORTED, nothing changed
+ * The pass is exact fp64, never screened (muse_batch_last_run_path: MUSE_RUN_PATH_FP64), and neither reads, builds nor counts
+ * towards the group's spectrum cache.  A kernel variant forced by a test hook that has no masked build is refused
+ * (MUSE_ERR_UNSUPPORTED), never run unmasked.
+ *   The list is checked as muse_batch_score_many checks it (one context, one group, no duplicate, no NULL: MUSE_ERR_INVALID);
+ *   max_lag < 0, or a batch whose own window is on and differs from max_lag: MUSE_ERR_INVALID.
+ * Every refusal leaves the handles as they were.
+ * muse_batch_run_many_in_window is that pass followed by Batch.Run's selection for every batch, outputs as muse_batch_run_many;
+ * max_lag is both the window and the Results.MaxLag of the selection (as in muse_batch_run_many_windowed).  A sign_filter outside
+ * -1 .. 1 or a negative G with group_id is refused before anything is scored. */
+int muse_batch_score_many_in_window(muse_batch *const *batches, int32_t R, int32_t max_lag);
+int muse_batch_run_many_in_window(muse_batch *const *batches, int32_t R, const int32_t *group_id, int32_t G,
+                                  int32_t max_lag, int32_t top_n, double threshold, int32_t sign_filter,
+                                  int32_t abs_scores, int64_t *out_series, int32_t *out_lag, double *out_score,
+                                  int32_t *out_count, double *out_mean_abs);
 int muse_batch_free(muse_batch *b);
 
 /* ------------------------------------------- single-pair entry points */

@@ -125,6 +125,14 @@ int muse_test_in_window_force_transform(muse_ctx *ctx, int32_t on);
 /* The path (MUSE_IN_WINDOW_*) the batch's scores came by if its last scoring pass was muse_batch_score_in_window / _run_in_window;
  * 0 after any other scoring pass. */
 int muse_test_last_in_window_path(muse_batch *b, int32_t *path);
+/* muse_batch_score_many_in_window's dispatch, a pure host function (no device needed): the pass that scores R >= 1 references against
+ * series of N >= 2 samples (f32_storage: a float32-storage group) inside +-max_lag >= 0 -- *path = MUSE_IN_WINDOW_PLAIN
+ * (muse_batch_score_many), _MFMA (muse_batch_score_many_windowed), _MASKED (ONE many-references pass of the transform kernels with a
+ * masked argmax: R >= 2 at FFT length 4096, or at 512 ... 2048 on float64 storage), _MASKED_EACH (R single masked passes,
+ * muse_batch_score_in_window per batch) or _UNSUPPORTED.  What only the handles know (a forced kernel variant, a missing correction
+ * table) turns _MASKED into _MASKED_EACH when the call runs.  MUSE_ERR_INVALID for N < 2, max_lag < 0, R < 1 or a NULL out pointer. */
+#define MUSE_IN_WINDOW_MASKED_EACH 4
+int muse_test_many_in_window_plan(int32_t N, int32_t f32_storage, int32_t max_lag, int32_t R, int32_t *path);
 
 #ifdef __cplusplus
 }
