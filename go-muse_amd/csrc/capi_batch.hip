@@ -606,8 +606,7 @@ int batch_score(muse_batch *b, bool allow_spectrum_cache, int win_L)
     rc = ensure_scores(b);
     if (rc)
         return rc;
-    b->many_tiles = 0;
-    b->in_window_path = 0;
+    b->origin = ScoreOrigin{};
     if (win_L < 0 && b->windowed()) { // the best match inside +-MaxLag, directly (xcorr_window.hip): no transform, never screened
         b->scores_exact = true;
         return score_windowed(b);
@@ -636,10 +635,8 @@ int batch_score(muse_batch *b, bool allow_spectrum_cache, int win_L)
     if (win_L >= 0) { // the masked argmax: built into the default kernels of n = 512 ... 4096 and the rescaling kernel behind the n = 4096 one
         if (!(variant == KERNEL_R16_FOLD || variant == KERNEL_R16_OCC3 || (variant == KERNEL_SMALL && b->logn <= 11)) || 2 * win_L > b->n)
             return fail(MUSE_ERR_UNSUPPORTED, "the masked transform pass runs on the default kernels of FFT lengths 512 ... 4096");
-        b->in_window_variant = variant;
-        p.win = 1;
-        p.win_lpos = win_L;
-        p.win_lneg = 2 * win_L == b->n ? win_L - 1 : win_L; // index n / 2 is lag +n/2 (xcorr.go:192-194), as in window_params
+        b->origin = ScoreOrigin::in_window(MUSE_IN_WINDOW_MASKED, win_L, variant);
+        set_window(p, win_L);
     }
     if (variant == KERNEL_GENERIC && b->n <= GENERIC_LDS_MAX_N)
         p.gscratch = nullptr; // the generic kernel takes a non-NULL scratch pointer as "work in global memory"
@@ -766,22 +763,23 @@ extern "C" int muse_batch_kernel_name(muse_batch *b, char *name, int32_t cap)
     // (the names rocprofv3 prints for the instantiations: profiles/r*_counters.json is keyed by them)
     char k[96] = "xcorr_fused_generic";
     const char *padded = b->N < b->n ? "true" : "false", *f32 = b->g->f32 ? "true" : "false";
-    if (b->in_window_path == MUSE_IN_WINDOW_MASKED) { // (as many_tiles below: the pass that filled mv / lag, an argument of a call)
-        if (b->in_window_variant == IN_WINDOW_VARIANT_MANY && b->n == 4096) // (muse_batch_score_many_in_window's one pass)
+    const ScoreOrigin &o = b->origin; // (the in-window and packed kinds: an argument of a call, not a setting the next pass takes)
+    if (o.kind == ScoreOrigin::MASKED) {
+        if (o.variant == ScoreOrigin::MANY && b->n == 4096) // (muse_batch_score_many_in_window's one pass)
             snprintf(k, sizeof(k), "xcorr_fused_n4096_fold_multi<%s, %s, true>", padded, f32);
-        else if (b->in_window_variant == IN_WINDOW_VARIANT_MANY)
+        else if (o.variant == ScoreOrigin::MANY)
             snprintf(k, sizeof(k), "xcorr_fused_small<%d, %s, true, false, true>", b->logn, padded);
-        else if (b->n == 4096 && b->in_window_variant == KERNEL_R16_OCC3) // (the learned hand-off, or no correction table)
+        else if (b->n == 4096 && o.variant == KERNEL_R16_OCC3) // (the learned hand-off, or no correction table)
             snprintf(k, sizeof(k), "xcorr_fused_n4096_occ4<%s, 3, false, %s, true>", padded, f32);
         else if (b->n == 4096)
             snprintf(k, sizeof(k), "xcorr_fused_n4096_fold<false, %s, %s, true>", padded, f32);
         else
             snprintf(k, sizeof(k), "xcorr_fused_small<%d, %s, false, %s, true>", b->logn, padded, f32);
-    } else if (b->in_window_path == MUSE_IN_WINDOW_MFMA) { // (the direct product with the call's window, whatever the batch's own setting)
-        snprintf(k, sizeof(k), "xcorr_window_mfma<%d, %s>", (2 * b->in_window_L + 1 + 15) / 16,
+    } else if (o.kind == ScoreOrigin::MFMA) { // (the direct product with the call's window, whatever the batch's own setting)
+        snprintf(k, sizeof(k), "xcorr_window_mfma<%d, %s>", (2 * o.window + 1 + 15) / 16,
                  window_wide(b->g->rows, b->g->stride) ? "true" : "false");
-    } else if (b->many_tiles > 0) { // (the packed pass that filled mv / lag: it is an argument of a call, not a setting the next pass takes)
-        snprintf(k, sizeof(k), "xcorr_window_many_mfma<%d, %s>", b->many_tiles, window_wide(b->g->rows, b->g->stride) ? "true" : "false");
+    } else if (o.kind == ScoreOrigin::PACKED) {
+        snprintf(k, sizeof(k), "xcorr_window_many_mfma<%d, %s>", o.tiles, window_wide(b->g->rows, b->g->stride) ? "true" : "false");
     } else if (b->windowed()) {
         const int L = std::min(b->lag_window, b->n / 2);
         snprintf(k, sizeof(k), "xcorr_window_mfma<%d, %s>", (2 * L + 1 + 15) / 16,

@@ -259,6 +259,23 @@ struct muse_spectrum {
     double xmax = -1.0;   // max |X[f]| (lazily, by the first screened Run): scales the fp32 error bound
 };
 
+// Which pass filled a batch's mv / lag.  The in-window kinds carry the MUSE_IN_WINDOW_* value (muse_hip_test.h) they report.
+struct ScoreOrigin {
+    enum Kind : int32_t {
+        PACKED = -1, // a packed launch of muse_batch_score_many_windowed (capi_window_many.hip) of `tiles` accumulator tiles
+        OWN = 0,     // the batch's own setting: choose_kernel, or its own lag window (what the next muse_batch_score takes too)
+        PLAIN = MUSE_IN_WINDOW_PLAIN, MFMA = MUSE_IN_WINDOW_MFMA, MASKED = MUSE_IN_WINDOW_MASKED // muse_batch_score_in_window with `window`
+    };
+    static constexpr int32_t MANY = -1; // `variant` of muse_batch_score_many_in_window's one masked pass (no KERNEL_* is negative)
+    Kind kind = OWN;
+    int32_t window = -1; // PLAIN / MFMA / MASKED: min(the call's window, n / 2)
+    int32_t variant = 0; // MASKED: the KERNEL_* the pass launched first, or MANY
+    int32_t tiles = 0;   // PACKED
+    static ScoreOrigin packed(int32_t tiles) { return ScoreOrigin{PACKED, -1, 0, tiles}; }
+    static ScoreOrigin in_window(int32_t path, int32_t L, int32_t variant = 0) { return ScoreOrigin{(Kind)path, L, variant, 0}; }
+    int32_t in_window_path() const { return kind > OWN ? (int32_t)kind : 0; }
+};
+
 struct muse_batch {
     muse_ctx *ctx = nullptr;
     muse_group *g = nullptr;
@@ -341,15 +358,10 @@ struct muse_batch {
     int32_t win_L = -1;
     PoolBuf<double> win_e, win_pw;
     bool windowed() const { return lag_window >= 0; }
-    // > 0: the batch's scores come from a packed launch of muse_batch_score_many_windowed (capi_window_many.hip) of this many
-    // accumulator tiles (muse_batch_kernel_name names it); any other scoring pass of the batch clears it
-    int32_t many_tiles = 0;
-    // the path the batch's scores came by when the last scoring pass was muse_batch_score_in_window (MUSE_IN_WINDOW_*,
-    // muse_hip_test.h; MASKED: in_window_L = the window, muse_batch_kernel_name names the masked instantiation); any other scoring pass clears it
-    // (_variant: the KERNEL_* the masked pass launched first; IN_WINDOW_VARIANT_MANY: the one masked pass of muse_batch_score_many_in_window)
-    int32_t in_window_path = 0, in_window_L = -1, in_window_variant = 0;
+    // which pass filled mv / lag (muse_batch_kernel_name names it, muse_test_last_in_window_path reports it): every scoring pass
+    // assigns a whole value, a selection and a refused call leave it alone
+    ScoreOrigin origin;
 };
-constexpr int32_t IN_WINDOW_VARIANT_MANY = -1; // (no KERNEL_* is negative)
 
 int use_device(muse_ctx *ctx);
 
@@ -448,6 +460,17 @@ int score_windowed(muse_batch *b);                     // capi_window.hip: the a
 int check_window_request(const muse_batch *b, int32_t max_lag, bool f32);
 int window_tables(muse_batch *b, int L, PoolBuf<double> &e, PoolBuf<double> &pw, int32_t *cached_L, hipStream_t st);
 muse::WindowParams window_params(const muse_batch *b, int L, const double *e, const double *pw);
+// the lags a window +-L holds below zero at FFT length n: index n / 2 is lag +n/2 (xcorr.go:192-194), it is scanned once
+inline int window_lneg(int L, int n) { return 2 * L == n ? L - 1 : L; }
+// the masked argmax of the transform kernels (their WIN builds): the window +-L in the kernel's arguments
+inline void set_window(muse::FusedParams &p, int L)
+{
+    p.win = 1;
+    p.win_lpos = L;
+    p.win_lneg = window_lneg(L, p.n);
+}
+// capi_window.hip: a call's window against the batch's own, which must be off or equal (r: the batch's index in a list, -1: a single batch)
+int check_own_window(const muse_batch *b, int32_t max_lag, int r = -1);
 muse::FusedParams base_params(muse_batch *b);
 int ensure_select_ws(muse_batch *b, int64_t M, int64_t G, bool with_gid, int K, bool on_device);
 // the selection of a Run happens on the device (each chunk's best top_n) only beyond EXACT_FEED_MAX_GROUPS groups: capi_run.hip, run_select
@@ -464,6 +487,21 @@ int run_select(muse_batch *b, const int32_t *group_id, int32_t G_in, int64_t ser
                       std::vector<muse_record> &out, bool already_scored = false, bool prescreened = false);
 void emit(const std::vector<muse_record> &sel, int64_t *out_series, int32_t *out_lag, double *out_score,
                  int32_t *out_count, double *out_mean_abs);
-int upload_many_tab(muse_ctx *ctx, std::vector<void *> &tab, bool zscratch); // capi_many.hip
+// capi_run.hip: the selection's own argument checks (run_select applies them; a wrapper that moves or scores first applies them before)
+int check_select_args(const int32_t *group_id, int32_t G, int32_t sign_filter);
+// ---- capi_many.hip, what the many-references entry points share
+int upload_many_tab(muse_ctx *ctx, std::vector<void *> &tab, bool zscratch);
+// the list checks: a list, no NULL, one context and one group, no batch twice
+int check_batch_list(muse_batch *const *bs, int32_t R);
+// which one-pass kernel family serves the list, a pure host decision (NONE: the batches are scored one after the other)
+enum ManyKind { MANY_NONE, MANY_SMALL, MANY_MULTI, MANY_LONG, MANY_REAL };
+ManyKind many_kind(muse_batch *const *bs, int32_t R);
+// ONE pass of the `kind` kernels over the rows for every batch of a checked list; win_L >= 0: the argmax masked to +-win_L (SMALL at
+// n <= 2048 and MULTI only)
+int score_many_pass(muse_batch *const *bs, int32_t R, ManyKind kind, int win_L);
+// the Run of every batch of a scored list: run_select, then emit into row r of the caller's arrays
+int run_many_select(muse_batch *const *bs, int32_t R, const int32_t *group_id, int32_t G, int32_t max_lag, int32_t top_n,
+                    double threshold, int32_t sign_filter, int32_t abs_scores, bool prescreened, int64_t *out_series,
+                    int32_t *out_lag, double *out_score, int32_t *out_count, double *out_mean_abs);
 int screen_many(muse_batch *const *bs, int32_t R, const int32_t *group_id, int32_t G_in, int32_t max_lag,
                        int32_t top_n, double threshold, int32_t sign_filter, int32_t abs_scores, bool &done);

@@ -8,7 +8,7 @@ using namespace muse;
 
 
 // -------------------------------------------------------- many references
-// The device pointer table of a many-reference pass (muse_batch_score_many, screen_many): the caller's columns of R pointers
+// The device pointer table of a many-reference pass (score_many_pass, screen_many): the caller's columns of R pointers
 // each in `tab`, which becomes the host image the asynchronous copy reads (kept by the context until the next pass has waited
 // for the stream).  With `zscratch`, the one-pass kernels' scratch slices too (allocated on first use).
 int upload_many_tab(muse_ctx *ctx, std::vector<void *> &tab, bool zscratch)
@@ -48,7 +48,7 @@ extern "C" int muse_batch_read_scores(muse_batch *b, int32_t *lag, double *mv)
     return MUSE_OK;
 }
 
-extern "C" int muse_batch_score_many(muse_batch *const *bs, int32_t R)
+int check_batch_list(muse_batch *const *bs, int32_t R)
 {
     if (!bs || R < 1)
         return fail(MUSE_ERR_INVALID, "bad batch list");
@@ -61,9 +61,11 @@ extern "C" int muse_batch_score_many(muse_batch *const *bs, int32_t R)
             if (bs[q] == bs[r])
                 return fail(MUSE_ERR_INVALID, "the same batch appears twice in the list");
     }
-    for (int r = 0; r < R; r++)
-        if (bs[r]->windowed())
-            return fail(MUSE_ERR_UNSUPPORTED, "a batch with a lag window cannot take part in a many-references pass");
+    return MUSE_OK;
+}
+
+ManyKind many_kind(muse_batch *const *bs, int32_t R)
+{
     muse_batch *b0 = bs[0];
     muse_ctx *ctx = b0->ctx;
     // the one-pass kernel is built for N == n == 4096 (and is only taken under automatic kernel
@@ -83,18 +85,21 @@ extern "C" int muse_batch_score_many(muse_batch *const *bs, int32_t R)
                      (small_n && !b0->g->f32 && (ctx->variant == 0 || ctx->variant == 12)) || long_n || real_n);
     for (int r = 0; r < R && one_pass; r++)
         one_pass = bs[r]->N == b0->N && (small_n || real_n || b0->N == b0->n || bs[r]->c1 != nullptr) && (!long_n || bs[r]->xcp != nullptr);
-    if (!one_pass) {
-        for (int r = 0; r < R; r++) {
-            int rc = batch_score(bs[r], false); // (a many-references pass never builds or reads the spectrum cache)
-            if (rc)
-                return rc;
-        }
-        return MUSE_OK;
-    }
-    for (int r = 0; r < R; r++) {
-        bs[r]->many_tiles = 0;
-        bs[r]->in_window_path = 0;
-    }
+    if (!one_pass)
+        return MANY_NONE;
+    return small_n ? MANY_SMALL : real_n ? MANY_REAL : long_n ? MANY_LONG : MANY_MULTI;
+}
+
+int score_many_pass(muse_batch *const *bs, int32_t R, ManyKind kind, int win_L)
+{
+    muse_batch *b0 = bs[0];
+    muse_ctx *ctx = b0->ctx;
+    const bool small_n = kind == MANY_SMALL, real_n = kind == MANY_REAL, long_n = kind == MANY_LONG;
+    const bool masked = win_L >= 0;
+    // the unmasked pass is what each batch's own setting takes too: it says so from the start.  The masked pass is an argument of
+    // its call: it names itself once its launches are enqueued (below)
+    for (int r = 0; r < R && !masked; r++)
+        bs[r]->origin = ScoreOrigin{};
     int rc = use_device(ctx);
     if (rc)
         return rc;
@@ -109,6 +114,7 @@ extern "C" int muse_batch_score_many(muse_batch *const *bs, int32_t R)
         if (rc)
             return rc;
     }
+    // the two kinds that work in the context's scratch buffer size it differently:
     if (long_n) // two n-element slices per resident workgroup
         HIP_TRY(ensure_gscratch(ctx, b0->n, 2 * LONG_WGS_PER_CU));
     if (real_n) // (half an n-element slice per workgroup: the batches' own creation sized the buffer for far more)
@@ -120,7 +126,8 @@ extern "C" int muse_batch_score_many(muse_batch *const *bs, int32_t R)
         tab[(size_t)2 * R + r] = bs[r]->lag.p;
         tab[(size_t)3 * R + r] = bs[r]->c1;
     }
-    rc = upload_many_tab(ctx, tab, b0->n == 16384); // (every other length keeps the spectra in registers: no scratch)
+    // scratch slices at n = 16384 only: every other length keeps the spectra in registers (the masked lengths are among them)
+    rc = upload_many_tab(ctx, tab, b0->n == 16384);
     if (rc)
         return rc;
     void **const t = ctx->many_tab.p;
@@ -130,8 +137,10 @@ extern "C" int muse_batch_score_many(muse_batch *const *bs, int32_t R)
     p.mv_many = (double *const *)(t + R);
     p.lag_many = (int *const *)(t + 2 * R);
     p.c1_many = (const double *const *)(t + 3 * R);
-    p.zscratch = ctx->zscratch.p;
+    p.zscratch = ctx->zscratch.p; // (read at n = 16384 only)
     p.zslots = (int)(ctx->zscratch.cap / 4096);
+    if (masked)
+        set_window(p, win_L);
     HIP_TRY(b0->ovf_list.ensure(ctx, 2 * p.npairs, b0->stream()));
     p.ovf_count = b0->ovf_count;
     p.work_counter = b0->ovf_count + 1;
@@ -148,27 +157,26 @@ extern "C" int muse_batch_score_many(muse_batch *const *bs, int32_t R)
     HIP_TRY(timer.begin());
     if (small_n) { // (this kernel isolates dead series itself: nothing is handed on)
         HIP_TRY(launch_fused_small(p, ctx->num_cus, ctx->stream));
-        for (int r = 0; r < R; r++)
-            bs[r]->scores_exact = true;
     } else if (real_n) { // (one series per transform: nothing to isolate, no redo list)
         p.gsmall = ctx->gsmall[4];
         HIP_TRY(launch_fused_real_split(p, ctx->num_cus, ctx->stream));
-        for (int r = 0; r < R; r++)
-            bs[r]->scores_exact = true;
     } else if (long_n)
         HIP_TRY(launch_fused_long(p, ctx->num_cus, ctx->stream));
     else
         HIP_TRY(launch_fused_multi(p, ctx->num_cus, ctx->stream));
     HIP_TRY(timer.end());
-    // pairs holding a NaN/Inf series (listed once, by reference 0): redone per reference by the
-    // kernel that isolates the dead series before the shared transform
+    // pairs holding a NaN/Inf series or sigmas too far apart (listed once, by reference 0): redone per reference by the
+    // kernel that isolates and rescales the series before the shared transform
+    const bool redo = !small_n && !real_n;
     LaunchTimer redo_timer(ctx, true); // (one bracket around the R redo launches)
-    if (!small_n && !real_n)
+    if (redo)
         HIP_TRY(redo_timer.begin());
-    for (int r = 0; r < R && !small_n && !real_n; r++) {
+    for (int r = 0; r < R && redo; r++) {
         FusedParams q = base_params(bs[r]);
         q.pair_list = b0->ovf_list.p;
         q.pair_count = b0->ovf_count;
+        if (masked) // the redone pairs keep their window (the WIN build of the redo kernel)
+            set_window(q, win_L);
         if (long_n) { // (the four-step kernel that isolates and rescales first, as behind a single long-series pass)
             q.npairs = std::min<long long>(q.npairs, (long long)ctx->num_cus * STOCKHAM_GLOBAL_WGS_PER_CU);
             HIP_TRY(launch_fused(q, KERNEL_STOCKHAM, ctx->num_cus, ctx->stream));
@@ -176,9 +184,54 @@ extern "C" int muse_batch_score_many(muse_batch *const *bs, int32_t R)
             q.npairs = std::min<long long>(q.npairs, (long long)ctx->num_cus * 3);
             HIP_TRY(launch_fused(q, KERNEL_R16_OCC3, ctx->num_cus, ctx->stream));
         }
-        bs[r]->scores_exact = true; // mv / lag of every batch now hold fp64 results for every row
     }
     HIP_TRY(redo_timer.end());
+    for (int r = 0; r < R; r++) {
+        muse_batch *b = bs[r];
+        b->scores_exact = true; // mv / lag of every batch now hold fp64 results for every row
+        if (masked) { // as muse_batch_score_in_window leaves a batch; the unmasked pass, as muse_batch_score, leaves what the last Run did alone
+            b->last_path = MUSE_RUN_PATH_FP64;
+            b->last_screened = false;
+            b->origin = ScoreOrigin::in_window(MUSE_IN_WINDOW_MASKED, win_L, ScoreOrigin::MANY);
+        }
+    }
+    return MUSE_OK;
+}
+
+extern "C" int muse_batch_score_many(muse_batch *const *bs, int32_t R)
+{
+    int rc = check_batch_list(bs, R);
+    if (rc)
+        return rc;
+    for (int r = 0; r < R; r++)
+        if (bs[r]->windowed())
+            return fail(MUSE_ERR_UNSUPPORTED, "a batch with a lag window cannot take part in a many-references pass");
+    const ManyKind kind = many_kind(bs, R);
+    if (kind == MANY_NONE) {
+        for (int r = 0; r < R; r++) {
+            rc = batch_score(bs[r], false); // (a many-references pass never builds or reads the spectrum cache)
+            if (rc)
+                return rc;
+        }
+        return MUSE_OK;
+    }
+    return score_many_pass(bs, R, kind, -1);
+}
+
+int run_many_select(muse_batch *const *bs, int32_t R, const int32_t *group_id, int32_t G, int32_t max_lag, int32_t top_n,
+                    double threshold, int32_t sign_filter, int32_t abs_scores, bool prescreened, int64_t *out_series,
+                    int32_t *out_lag, double *out_score, int32_t *out_count, double *out_mean_abs)
+{
+    const size_t cap = (size_t)std::max(top_n, 0);
+    for (int r = 0; r < R; r++) {
+        std::vector<muse_record> sel;
+        const int rc = run_select(bs[r], group_id, G, 0, max_lag, top_n, threshold, sign_filter, abs_scores, sel, true, prescreened);
+        if (rc)
+            return rc;
+        emit(sel, out_series ? out_series + cap * r : nullptr, out_lag ? out_lag + cap * r : nullptr,
+             out_score ? out_score + cap * r : nullptr, out_count ? out_count + r : nullptr,
+             out_mean_abs ? out_mean_abs + r : nullptr);
+    }
     return MUSE_OK;
 }
 
@@ -187,7 +240,7 @@ extern "C" int muse_batch_run_many(muse_batch *const *bs, int32_t R, const int32
                                    int32_t abs_scores, int64_t *out_series, int32_t *out_lag, double *out_score,
                                    int32_t *out_count, double *out_mean_abs)
 {
-    for (int r = 0; bs && r < R; r++)
+    for (int r = 0; bs && r < R; r++) // (before the list is validated: a windowed batch in a bad list is reported as windowed)
         if (bs[r] && bs[r]->windowed())
             return fail(MUSE_ERR_UNSUPPORTED, "a batch with a lag window cannot take part in a many-references pass");
     bool prescreened = false;
@@ -199,15 +252,6 @@ extern "C" int muse_batch_run_many(muse_batch *const *bs, int32_t R, const int32
         if (rc)
             return rc;
     }
-    const size_t cap = (size_t)std::max(top_n, 0);
-    for (int r = 0; r < R; r++) {
-        std::vector<muse_record> sel;
-        rc = run_select(bs[r], group_id, G, 0, max_lag, top_n, threshold, sign_filter, abs_scores, sel, true, prescreened);
-        if (rc)
-            return rc;
-        emit(sel, out_series ? out_series + cap * r : nullptr, out_lag ? out_lag + cap * r : nullptr,
-             out_score ? out_score + cap * r : nullptr, out_count ? out_count + r : nullptr,
-             out_mean_abs ? out_mean_abs + r : nullptr);
-    }
-    return MUSE_OK;
+    return run_many_select(bs, R, group_id, G, max_lag, top_n, threshold, sign_filter, abs_scores, prescreened, out_series, out_lag,
+                           out_score, out_count, out_mean_abs);
 }

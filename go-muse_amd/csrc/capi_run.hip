@@ -239,6 +239,17 @@ static int direct_topn_reduce(muse_batch *b, const SelectParams &sp, int K, std:
     return MUSE_OK;
 }
 
+int check_select_args(const int32_t *group_id, int32_t G, int32_t sign_filter)
+{
+    if (sign_filter < -1 || sign_filter > 1)
+        return fail(MUSE_ERR_INVALID, "sign_filter must be -1, 0 or 1");
+    if (group_id && G < 0)
+        return fail(MUSE_ERR_INVALID, "negative group count");
+    return MUSE_OK;
+}
+
+// With already_scored (and not prescreened) the path is MUSE_RUN_PATH_FP64 (screen_path): nothing below scores, not the pass, not
+// the guard's redo.  mv / lag, and with them b->origin, stay those of the caller's pass: a wrapper has nothing to put back.
 int run_select(muse_batch *b, const int32_t *group_id, int32_t G_in, int64_t series_offset, int32_t max_lag,
                       int32_t top_n, double threshold, int32_t sign_filter, int32_t abs_scores,
                       std::vector<muse_record> &out, bool already_scored, bool prescreened)
@@ -246,17 +257,16 @@ int run_select(muse_batch *b, const int32_t *group_id, int32_t G_in, int64_t ser
     out.clear();
     muse_ctx *ctx = b->ctx;
     const int64_t M = b->g->M;
-    if (sign_filter < -1 || sign_filter > 1)
-        return fail(MUSE_ERR_INVALID, "sign_filter must be -1, 0 or 1");
-    if (group_id && G_in < 0)
-        return fail(MUSE_ERR_INVALID, "negative group count");
+    int rc = check_select_args(group_id, G_in, sign_filter);
+    if (rc)
+        return rc;
     // Batch.Run re-scores on every call (muse_batch.go:116-122)
     // (prescreened: muse_batch_run_many has run the screening pass for several batches at once and finished this one)
     const muse_batch::RunKey rkey = run_key(b, group_id, group_id ? (int64_t)G_in : 0, max_lag, top_n, threshold, sign_filter, abs_scores);
     const int32_t path = prescreened ? MUSE_RUN_PATH_SCREENED : screen_path(b, rkey, already_scored);
     const bool screened = path == MUSE_RUN_PATH_SCREENED;
     b->last_path = path;
-    int rc = (already_scored || screened) ? MUSE_OK : muse_batch_score(b);
+    rc = (already_scored || screened) ? MUSE_OK : muse_batch_score(b);
     if (rc)
         return rc;
     const int64_t G = group_id ? (int64_t)G_in : M;

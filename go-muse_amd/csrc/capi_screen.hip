@@ -186,8 +186,7 @@ static int screen_finish(muse_batch *b, int32_t top_n, double threshold, int32_t
     HIP_TRY(hipMemcpyAsync(b->refine_host, b->ovf_count, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipMemcpyAsync(b->err_host, b->err_dev, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
     b->scores_exact = false;
-    b->many_tiles = 0;
-    b->in_window_path = 0;
+    b->origin = ScoreOrigin{};
     return MUSE_OK;
 }
 

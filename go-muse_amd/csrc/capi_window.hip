@@ -20,6 +20,17 @@ int check_window_request(const muse_batch *b, int32_t max_lag, bool f32)
     return MUSE_OK;
 }
 
+int check_own_window(const muse_batch *b, int32_t max_lag, int r)
+{
+    if (!b->windowed() || b->lag_window == max_lag)
+        return MUSE_OK;
+    if (r < 0)
+        return fail(MUSE_ERR_INVALID, "the batch has a lag window of %d of its own: it must be off or equal to the call's (%d)",
+                    b->lag_window, max_lag);
+    return fail(MUSE_ERR_INVALID, "batch %d has a lag window of %d of its own: it must be off or equal to the pass's (%d)", r,
+                b->lag_window, max_lag);
+}
+
 extern "C" int muse_batch_set_lag_window(muse_batch *b, int32_t max_lag)
 {
     if (!b)
@@ -64,7 +75,7 @@ WindowParams window_params(const muse_batch *b, int L, const double *e, const do
     p.stride = b->g->stride;
     p.N = b->N;
     p.L = L;
-    p.Lneg = 2 * L == b->n ? L - 1 : L; // index n / 2 is lag +n/2 (xcorr.go:192-194): it is scanned once
+    p.Lneg = window_lneg(L, b->n);
     p.invN = 1.0 / (double)b->N;
     p.invNm1 = 1.0 / (double)(b->N - 1);
     p.e = e;
@@ -119,11 +130,10 @@ extern "C" int muse_batch_slide_score_windowed(muse_batch *b, const double *tail
     if (max_lag < 0)
         return fail(MUSE_ERR_INVALID, "a windowed pass needs a lag window >= 0");
     int rc = check_window_request(b, max_lag, g->f32);
+    if (!rc)
+        rc = check_own_window(b, max_lag);
     if (rc)
         return rc;
-    if (b->windowed() && b->lag_window != max_lag)
-        return fail(MUSE_ERR_INVALID, "the batch has a lag window of %d of its own: it must be off or equal to the call's (%d)",
-                    b->lag_window, max_lag);
     if (M == 0) // nothing to move, nothing to score
         return MUSE_OK;
     muse_ctx *ctx = b->ctx;
@@ -137,8 +147,7 @@ extern "C" int muse_batch_slide_score_windowed(muse_batch *b, const double *tail
     rc = ensure_scores(b);
     if (rc)
         return rc;
-    b->many_tiles = 0;
-    b->in_window_path = 0;
+    b->origin = ScoreOrigin{};
     b->scores_exact = true;
     const int L = std::min(max_lag, b->n / 2);
     WindowParams p;
@@ -173,11 +182,9 @@ extern "C" int muse_batch_slide_run_windowed(muse_batch *b, const double *tails,
                                              double *out_score, int32_t *out_count, double *out_mean_abs)
 {
     // (the selection's own argument checks come first: a refusal leaves the rows where they were)
-    if (sign_filter < -1 || sign_filter > 1)
-        return fail(MUSE_ERR_INVALID, "sign_filter must be -1, 0 or 1");
-    if (group_id && G < 0)
-        return fail(MUSE_ERR_INVALID, "negative group count");
-    int rc = muse_batch_slide_score_windowed(b, tails, k, tail_stride, max_lag);
+    int rc = check_select_args(group_id, G, sign_filter);
+    if (!rc)
+        rc = muse_batch_slide_score_windowed(b, tails, k, tail_stride, max_lag);
     if (rc)
         return rc;
     std::vector<muse_record> sel;
@@ -226,7 +233,7 @@ extern "C" int muse_test_last_in_window_path(muse_batch *b, int32_t *path)
 {
     if (!b || !path)
         return fail(MUSE_ERR_INVALID, "NULL argument");
-    *path = b->in_window_path;
+    *path = b->origin.in_window_path();
     return MUSE_OK;
 }
 
@@ -237,9 +244,9 @@ extern "C" int muse_batch_score_in_window(muse_batch *b, int32_t max_lag)
         return fail(MUSE_ERR_INVALID, "NULL batch");
     if (max_lag < 0)
         return fail(MUSE_ERR_INVALID, "a windowed pass needs a lag window >= 0");
-    if (b->windowed() && b->lag_window != max_lag)
-        return fail(MUSE_ERR_INVALID, "the batch has a lag window of %d of its own: it must be off or equal to the call's (%d)",
-                    b->lag_window, max_lag);
+    int rc = check_own_window(b, max_lag);
+    if (rc)
+        return rc;
     const int path = in_window_plan(b->N, b->g->f32, max_lag, b->ctx->in_window_force.load());
     if (path == MUSE_IN_WINDOW_UNSUPPORTED || (path == MUSE_IN_WINDOW_MFMA && !b->xs))
         return fail(MUSE_ERR_UNSUPPORTED, "a lag window of %d over series of %d samples%s is not built: wider than MUSE_LAG_WINDOW_MAX (%d) and for "
@@ -247,8 +254,7 @@ extern "C" int muse_batch_score_in_window(muse_batch *b, int32_t max_lag)
                     max_lag, b->N, b->g->f32 ? " in float32 storage" : "", MUSE_LAG_WINDOW_MAX);
     const int L = std::min(max_lag, b->n / 2);
     const int32_t own = b->lag_window;
-    int rc;
-    if (path == MUSE_IN_WINDOW_MASKED) {
+    if (path == MUSE_IN_WINDOW_MASKED) { // (batch_score records the origin: it knows the kernel it launches first)
         rc = batch_score(b, false, L);
     } else { // the pass a batch with (MFMA) / without (PLAIN) a window of its own takes; the setting is put back, whatever the outcome
         b->lag_window = path == MUSE_IN_WINDOW_MFMA ? max_lag : -1;
@@ -262,8 +268,8 @@ extern "C" int muse_batch_score_in_window(muse_batch *b, int32_t max_lag)
     b->scores_exact = true;
     b->last_path = MUSE_RUN_PATH_FP64;
     b->last_screened = false;
-    b->in_window_path = path;
-    b->in_window_L = L;
+    if (path != MUSE_IN_WINDOW_MASKED)
+        b->origin = ScoreOrigin::in_window(path, L);
     return MUSE_OK;
 }
 
@@ -272,20 +278,15 @@ extern "C" int muse_batch_run_in_window(muse_batch *b, const int32_t *group_id, 
                                         int32_t *out_lag, double *out_score, int32_t *out_count, double *out_mean_abs)
 {
     // (the selection's own argument checks come first, as in muse_batch_slide_run_windowed)
-    if (sign_filter < -1 || sign_filter > 1)
-        return fail(MUSE_ERR_INVALID, "sign_filter must be -1, 0 or 1");
-    if (group_id && G < 0)
-        return fail(MUSE_ERR_INVALID, "negative group count");
-    int rc = muse_batch_score_in_window(b, max_lag);
+    int rc = check_select_args(group_id, G, sign_filter);
+    if (!rc)
+        rc = muse_batch_score_in_window(b, max_lag);
     if (rc)
         return rc;
-    const int32_t path = b->in_window_path, L = b->in_window_L;
     std::vector<muse_record> sel;
     rc = run_select(b, group_id, G, 0, max_lag, top_n, threshold, sign_filter, abs_scores, sel, true, false);
     if (rc)
         return rc;
-    b->in_window_path = path; // (the selection scores nothing: the scores are still this pass's)
-    b->in_window_L = L;
     emit(sel, out_series, out_lag, out_score, out_count, out_mean_abs);
     return MUSE_OK;
 }

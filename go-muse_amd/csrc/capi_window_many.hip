@@ -35,38 +35,21 @@ extern "C" int muse_test_window_many_plan(int32_t R, int32_t L, int32_t *launche
     return MUSE_OK;
 }
 
-// the list checks of muse_batch_score_many, then the window's: nothing is changed before the last of them has passed
-static int check_many_windowed(muse_batch *const *bs, int32_t R, int32_t max_lag)
+extern "C" int muse_batch_score_many_windowed(muse_batch *const *bs, int32_t R, int32_t max_lag)
 {
-    if (!bs || R < 1)
-        return fail(MUSE_ERR_INVALID, "bad batch list");
-    for (int r = 0; r < R; r++) {
-        if (!bs[r])
-            return fail(MUSE_ERR_INVALID, "NULL batch in list");
-        if (bs[r]->ctx != bs[0]->ctx || bs[r]->g != bs[0]->g)
-            return fail(MUSE_ERR_INVALID, "batches of one pass must share the context and the comparison group");
-        for (int q = 0; q < r; q++)
-            if (bs[q] == bs[r])
-                return fail(MUSE_ERR_INVALID, "the same batch appears twice in the list");
-    }
+    // the list checks, then the window's: nothing is changed before the last of them has passed
+    int rc = check_batch_list(bs, R);
+    if (rc)
+        return rc;
     if (max_lag < 0)
         return fail(MUSE_ERR_INVALID, "a windowed many-references pass needs a lag window >= 0");
     for (int r = 0; r < R; r++) { // (the batches share the group and the window: behind r = 0 only the length check can still refuse)
-        const int rc = check_window_request(bs[r], max_lag, bs[r]->g->f32);
+        rc = check_window_request(bs[r], max_lag, bs[r]->g->f32);
+        if (!rc)
+            rc = check_own_window(bs[r], max_lag, r);
         if (rc)
             return rc;
-        if (bs[r]->windowed() && bs[r]->lag_window != max_lag)
-            return fail(MUSE_ERR_INVALID, "batch %d has a lag window of %d of its own: it must be off or equal to the pass's (%d)", r,
-                        bs[r]->lag_window, max_lag);
     }
-    return MUSE_OK;
-}
-
-extern "C" int muse_batch_score_many_windowed(muse_batch *const *bs, int32_t R, int32_t max_lag)
-{
-    int rc = check_many_windowed(bs, R, max_lag);
-    if (rc)
-        return rc;
     muse_batch *b0 = bs[0];
     muse_ctx *ctx = b0->ctx;
     rc = use_device(ctx);
@@ -148,8 +131,8 @@ extern "C" int muse_batch_score_many_windowed(muse_batch *const *bs, int32_t R, 
             bs[r]->scores_exact = true;
             bs[r]->last_path = MUSE_RUN_PATH_FP64;
             bs[r]->last_screened = false;
-            bs[r]->many_tiles = r1 - r0 > 1 ? tiles_of[(size_t)launch_of[(size_t)r0]] : 0;
-            bs[r]->in_window_path = 0;
+            // (a reference alone in its launch: the single-reference kernel, named as before the pass by the batch's own setting)
+            bs[r]->origin = r1 - r0 > 1 ? ScoreOrigin::packed(tiles_of[(size_t)launch_of[(size_t)r0]]) : ScoreOrigin{};
         }
         r0 = r1;
     }
@@ -162,18 +145,9 @@ extern "C" int muse_batch_run_many_windowed(muse_batch *const *bs, int32_t R, co
                                             int32_t abs_scores, int64_t *out_series, int32_t *out_lag, double *out_score,
                                             int32_t *out_count, double *out_mean_abs)
 {
-    int rc = muse_batch_score_many_windowed(bs, R, max_lag);
+    const int rc = muse_batch_score_many_windowed(bs, R, max_lag); // (no pre-check of the selection's arguments: run_select's own comes behind the pass)
     if (rc)
         return rc;
-    const size_t cap = (size_t)std::max(top_n, 0);
-    for (int r = 0; r < R; r++) {
-        std::vector<muse_record> sel;
-        rc = run_select(bs[r], group_id, G, 0, max_lag, top_n, threshold, sign_filter, abs_scores, sel, true, false);
-        if (rc)
-            return rc;
-        emit(sel, out_series ? out_series + cap * r : nullptr, out_lag ? out_lag + cap * r : nullptr,
-             out_score ? out_score + cap * r : nullptr, out_count ? out_count + r : nullptr,
-             out_mean_abs ? out_mean_abs + r : nullptr);
-    }
-    return MUSE_OK;
+    return run_many_select(bs, R, group_id, G, max_lag, top_n, threshold, sign_filter, abs_scores, false, out_series, out_lag,
+                           out_score, out_count, out_mean_abs);
 }

@@ -34,117 +34,19 @@ extern "C" int muse_test_many_in_window_plan(int32_t N, int32_t f32, int32_t max
     return MUSE_OK;
 }
 
-// the list checks of muse_batch_score_many, then the window's: nothing is changed before the last of them has passed
-static int check_many_in_window(muse_batch *const *bs, int32_t R, int32_t max_lag)
-{
-    if (!bs || R < 1)
-        return fail(MUSE_ERR_INVALID, "bad batch list");
-    for (int r = 0; r < R; r++) {
-        if (!bs[r])
-            return fail(MUSE_ERR_INVALID, "NULL batch in list");
-        if (bs[r]->ctx != bs[0]->ctx || bs[r]->g != bs[0]->g)
-            return fail(MUSE_ERR_INVALID, "batches of one pass must share the context and the comparison group");
-        for (int q = 0; q < r; q++)
-            if (bs[q] == bs[r])
-                return fail(MUSE_ERR_INVALID, "the same batch appears twice in the list");
-    }
-    if (max_lag < 0)
-        return fail(MUSE_ERR_INVALID, "a windowed many-references pass needs a lag window >= 0");
-    for (int r = 0; r < R; r++)
-        if (bs[r]->windowed() && bs[r]->lag_window != max_lag)
-            return fail(MUSE_ERR_INVALID, "batch %d has a lag window of %d of its own: it must be off or equal to the pass's (%d)", r,
-                        bs[r]->lag_window, max_lag);
-    return MUSE_OK;
-}
-
-// the one masked pass over the rows: muse_batch_score_many's launch sequence with the window in the kernels' arguments
-// (device selected by the caller's checks; n in {512, 1024, 2048, 4096}, the one-pass conditions hold)
-static int score_many_masked(muse_batch *const *bs, int32_t R, int L)
-{
-    muse_batch *b0 = bs[0];
-    muse_ctx *ctx = b0->ctx;
-    int rc = use_device(ctx);
-    if (rc)
-        return rc;
-    rc = group_ready(b0->g);
-    if (rc)
-        return rc;
-    const int64_t M = b0->g->M;
-    if (M == 0)
-        return MUSE_OK;
-    for (int r = 0; r < R; r++) {
-        rc = ensure_scores(bs[r]);
-        if (rc)
-            return rc;
-    }
-    const bool small_n = b0->n < 4096;
-    std::vector<void *> tab((size_t)R * 4);
-    for (int r = 0; r < R; r++) {
-        tab[(size_t)r] = small_n ? bs[r]->xc : bs[r]->xcp;
-        tab[(size_t)R + r] = bs[r]->mv.p;
-        tab[(size_t)2 * R + r] = bs[r]->lag.p;
-        tab[(size_t)3 * R + r] = bs[r]->c1;
-    }
-    rc = upload_many_tab(ctx, tab, false); // (these lengths keep the spectra in registers: no scratch)
-    if (rc)
-        return rc;
-    void **const t = ctx->many_tab.p;
-    FusedParams p = base_params(b0);
-    p.R = R;
-    p.xcp_many = (const double2 *const *)t;
-    p.mv_many = (double *const *)(t + R);
-    p.lag_many = (int *const *)(t + 2 * R);
-    p.c1_many = (const double *const *)(t + 3 * R);
-    p.win = 1;
-    p.win_lpos = L;
-    p.win_lneg = 2 * L == b0->n ? L - 1 : L; // index n / 2 is lag +n/2 (xcorr.go:192-194), as in window_params
-    HIP_TRY(b0->ovf_list.ensure(ctx, 2 * p.npairs, b0->stream()));
-    p.ovf_count = b0->ovf_count;
-    p.work_counter = b0->ovf_count + 1;
-    p.ovf_list = b0->ovf_list.p;
-    LaunchTimer timer(ctx);
-    HIP_TRY(hipMemsetAsync(b0->ovf_count, 0, 2 * sizeof(int), ctx->stream));
-    HIP_TRY(timer.begin());
-    if (small_n) // (this kernel isolates dead series itself: nothing is handed on)
-        HIP_TRY(launch_fused_small(p, ctx->num_cus, ctx->stream));
-    else
-        HIP_TRY(launch_fused_multi(p, ctx->num_cus, ctx->stream));
-    HIP_TRY(timer.end());
-    // n = 4096: pairs holding a NaN/Inf series or sigmas too far apart (listed once, by reference 0) are redone per reference by
-    // the WIN build of the kernel that isolates and rescales before the shared transform: they keep their window
-    LaunchTimer redo_timer(ctx, true); // (one bracket around the R redo launches)
-    if (!small_n)
-        HIP_TRY(redo_timer.begin());
-    for (int r = 0; r < R && !small_n; r++) {
-        FusedParams q = base_params(bs[r]);
-        q.pair_list = b0->ovf_list.p;
-        q.pair_count = b0->ovf_count;
-        q.win = 1;
-        q.win_lpos = p.win_lpos;
-        q.win_lneg = p.win_lneg;
-        q.npairs = std::min<long long>(q.npairs, (long long)ctx->num_cus * 3);
-        HIP_TRY(launch_fused(q, KERNEL_R16_OCC3, ctx->num_cus, ctx->stream));
-    }
-    HIP_TRY(redo_timer.end());
-    for (int r = 0; r < R; r++) {
-        muse_batch *b = bs[r];
-        b->many_tiles = 0;
-        b->scores_exact = true; // mv / lag of every batch hold fp64 results for every row
-        b->last_path = MUSE_RUN_PATH_FP64;
-        b->last_screened = false;
-        b->in_window_path = MUSE_IN_WINDOW_MASKED;
-        b->in_window_L = L;
-        b->in_window_variant = IN_WINDOW_VARIANT_MANY;
-    }
-    return MUSE_OK;
-}
-
 extern "C" int muse_batch_score_many_in_window(muse_batch *const *bs, int32_t R, int32_t max_lag)
 {
     // everything is checked before anything is enqueued: on a refusal every batch is unchanged
-    int rc = check_many_in_window(bs, R, max_lag);
+    int rc = check_batch_list(bs, R);
     if (rc)
         return rc;
+    if (max_lag < 0)
+        return fail(MUSE_ERR_INVALID, "a windowed many-references pass needs a lag window >= 0");
+    for (int r = 0; r < R; r++) {
+        rc = check_own_window(bs[r], max_lag, r);
+        if (rc)
+            return rc;
+    }
     muse_batch *b0 = bs[0];
     muse_ctx *ctx = b0->ctx;
     const bool f32 = b0->g->f32;
@@ -170,22 +72,16 @@ extern "C" int muse_batch_score_many_in_window(muse_batch *const *bs, int32_t R,
     const int v = ctx->variant;
     if (!(b0->n == 4096 ? (v == 0 || v == 10 || v == 7) : (v == 0 || v == 12)))
         return fail(MUSE_ERR_UNSUPPORTED, "the masked transform pass runs on the default kernels of FFT lengths 512 ... 4096");
-    if (path == MUSE_IN_WINDOW_MASKED) { // muse_batch_score_many's own one-pass conditions
-        bool one_pass = b0->n == 4096 ? (v == 0 || v == 10) : (v == 0 || v == 12);
-        for (int r = 0; r < R && one_pass; r++)
-            one_pass = bs[r]->N == b0->N && (b0->n < 4096 || b0->N == b0->n || bs[r]->c1 != nullptr);
-        if (!one_pass)
-            path = MUSE_IN_WINDOW_MASKED_EACH;
+    // ONE pass where muse_batch_score_many would take one at these lengths (the masked builds: n = 4096, and the small lengths up to 2048)
+    const ManyKind kind = path == MUSE_IN_WINDOW_MASKED ? many_kind(bs, R) : MANY_NONE;
+    if (kind == MANY_MULTI || (kind == MANY_SMALL && b0->n <= 2048))
+        return score_many_pass(bs, R, kind, std::min(max_lag, b0->n / 2));
+    for (int r = 0; r < R; r++) {
+        rc = muse_batch_score_in_window(bs[r], max_lag);
+        if (rc)
+            return rc;
     }
-    if (path == MUSE_IN_WINDOW_MASKED_EACH) {
-        for (int r = 0; r < R; r++) {
-            rc = muse_batch_score_in_window(bs[r], max_lag);
-            if (rc)
-                return rc;
-        }
-        return MUSE_OK;
-    }
-    return score_many_masked(bs, R, std::min(max_lag, b0->n / 2));
+    return MUSE_OK;
 }
 
 extern "C" int muse_batch_run_many_in_window(muse_batch *const *bs, int32_t R, const int32_t *group_id, int32_t G,
@@ -194,28 +90,11 @@ extern "C" int muse_batch_run_many_in_window(muse_batch *const *bs, int32_t R, c
                                              int32_t *out_count, double *out_mean_abs)
 {
     // (the selection's own argument checks come first, as in muse_batch_run_in_window)
-    if (sign_filter < -1 || sign_filter > 1)
-        return fail(MUSE_ERR_INVALID, "sign_filter must be -1, 0 or 1");
-    if (group_id && G < 0)
-        return fail(MUSE_ERR_INVALID, "negative group count");
-    int rc = muse_batch_score_many_in_window(bs, R, max_lag);
+    int rc = check_select_args(group_id, G, sign_filter);
+    if (!rc)
+        rc = muse_batch_score_many_in_window(bs, R, max_lag);
     if (rc)
         return rc;
-    const size_t cap = (size_t)std::max(top_n, 0);
-    for (int r = 0; r < R; r++) {
-        muse_batch *b = bs[r];
-        const int32_t path = b->in_window_path, L = b->in_window_L, variant = b->in_window_variant, tiles = b->many_tiles;
-        std::vector<muse_record> sel;
-        rc = run_select(b, group_id, G, 0, max_lag, top_n, threshold, sign_filter, abs_scores, sel, true, false);
-        if (rc)
-            return rc;
-        b->in_window_path = path; // (the selection scores nothing: the scores are still this pass's)
-        b->in_window_L = L;
-        b->in_window_variant = variant;
-        b->many_tiles = tiles;
-        emit(sel, out_series ? out_series + cap * r : nullptr, out_lag ? out_lag + cap * r : nullptr,
-             out_score ? out_score + cap * r : nullptr, out_count ? out_count + r : nullptr,
-             out_mean_abs ? out_mean_abs + r : nullptr);
-    }
-    return MUSE_OK;
+    return run_many_select(bs, R, group_id, G, max_lag, top_n, threshold, sign_filter, abs_scores, false, out_series, out_lag,
+                           out_score, out_count, out_mean_abs);
 }

@@ -687,19 +687,12 @@ def _batch_handles(batches):
     return batches, arr
 
 
-def score_many(batches):
-    """muse_batch_score_many: R references against one resident group in ONE pass over the rows
-    (asynchronous; results land in each DeviceBatch's own buffers)."""
+def _scores_many(fn, batches, *window):
+    """the C pass `fn` over the batches (and its window, if it takes one), then every batch's scores read back: list of (lag, mv)"""
     batches, arr = _batch_handles(batches)
-    B.check(B.load().muse_batch_score_many(arr, len(batches)))
-
-
-def scores_many(batches):
-    """score_many + copy back: list of (lag, mv), one per batch"""
-    batches, arr = _batch_handles(batches)
-    B.check(B.load().muse_batch_score_many(arr, len(batches)))
-    out = []
     lib = B.load()
+    B.check(getattr(lib, fn)(arr, len(batches), *window))
+    out = []
     for b in batches:
         M = b.dgroup.M
         lag = np.zeros(M, dtype=np.int32)
@@ -710,9 +703,8 @@ def scores_many(batches):
     return out
 
 
-def run_many(batches, group_id=None, G=0, max_lag=10, top_n=20, threshold=0.0, sign_filter=0, abs_scores=True):
-    """muse_batch_run_many: Batch.Run for every reference with one pass over the rows;
-    returns a list of (series, lag, score, mean_abs), one per batch"""
+def _run_many(fn, batches, group_id, G, max_lag, top_n, threshold, sign_filter, abs_scores):
+    """the C Run `fn` over the batches into R x top_n outputs: list of (series, lag, score, mean_abs), one per batch"""
     batches, arr = _batch_handles(batches)
     R = len(batches)
     cap = max(int(top_n), 1)
@@ -724,7 +716,7 @@ def run_many(batches, group_id=None, G=0, max_lag=10, top_n=20, threshold=0.0, s
     gid = None
     if group_id is not None:
         gid = np.ascontiguousarray(group_id, dtype=np.int32)
-    B.check(B.load().muse_batch_run_many(
+    B.check(getattr(B.load(), fn)(
         arr, R, B.i32ptr(gid) if gid is not None else None, int(G), int(max_lag), int(top_n),
         float(threshold), int(sign_filter), 1 if abs_scores else 0,
         B.i64ptr(o_s), B.i32ptr(o_l), B.dptr(o_v), B.i32ptr(cnt), B.dptr(mean)))
@@ -735,6 +727,24 @@ def run_many(batches, group_id=None, G=0, max_lag=10, top_n=20, threshold=0.0, s
         res.append((o_s[r * tn:r * tn + c].copy(), o_l[r * tn:r * tn + c].copy(), o_v[r * tn:r * tn + c].copy(),
                     float(mean[r])))
     return res
+
+
+def score_many(batches):
+    """muse_batch_score_many: R references against one resident group in ONE pass over the rows
+    (asynchronous; results land in each DeviceBatch's own buffers)."""
+    batches, arr = _batch_handles(batches)
+    B.check(B.load().muse_batch_score_many(arr, len(batches)))
+
+
+def scores_many(batches):
+    """score_many + copy back: list of (lag, mv), one per batch"""
+    return _scores_many("muse_batch_score_many", batches)
+
+
+def run_many(batches, group_id=None, G=0, max_lag=10, top_n=20, threshold=0.0, sign_filter=0, abs_scores=True):
+    """muse_batch_run_many: Batch.Run for every reference with one pass over the rows;
+    returns a list of (series, lag, score, mean_abs), one per batch"""
+    return _run_many("muse_batch_run_many", batches, group_id, G, max_lag, top_n, threshold, sign_filter, abs_scores)
 
 
 def score_many_windowed(batches, max_lag):
@@ -747,45 +757,13 @@ def score_many_windowed(batches, max_lag):
 
 def scores_many_windowed(batches, max_lag):
     """score_many_windowed + copy back: list of (lag, mv), one per batch"""
-    batches, arr = _batch_handles(batches)
-    lib = B.load()
-    B.check(lib.muse_batch_score_many_windowed(arr, len(batches), int(max_lag)))
-    out = []
-    for b in batches:
-        M = b.dgroup.M
-        lag = np.zeros(M, dtype=np.int32)
-        mv = np.zeros(M)
-        if M:
-            B.check(lib.muse_batch_read_scores(b._h, B.i32ptr(lag), B.dptr(mv)))
-        out.append((lag, mv))
-    return out
+    return _scores_many("muse_batch_score_many_windowed", batches, int(max_lag))
 
 
 def run_many_windowed(batches, group_id=None, G=0, max_lag=10, top_n=20, threshold=0.0, sign_filter=0, abs_scores=True):
     """muse_batch_run_many_windowed: Batch.RunWindowed for every reference (max_lag is the window and the Results.MaxLag);
     returns a list of (series, lag, score, mean_abs), one per batch"""
-    batches, arr = _batch_handles(batches)
-    R = len(batches)
-    cap = max(int(top_n), 1)
-    o_s = np.zeros(R * cap, dtype=np.int64)
-    o_l = np.zeros(R * cap, dtype=np.int32)
-    o_v = np.zeros(R * cap)
-    cnt = np.zeros(R, dtype=np.int32)
-    mean = np.zeros(R)
-    gid = None
-    if group_id is not None:
-        gid = np.ascontiguousarray(group_id, dtype=np.int32)
-    B.check(B.load().muse_batch_run_many_windowed(
-        arr, R, B.i32ptr(gid) if gid is not None else None, int(G), int(max_lag), int(top_n),
-        float(threshold), int(sign_filter), 1 if abs_scores else 0,
-        B.i64ptr(o_s), B.i32ptr(o_l), B.dptr(o_v), B.i32ptr(cnt), B.dptr(mean)))
-    tn = max(int(top_n), 0)
-    res = []
-    for r in range(R):
-        c = int(cnt[r])
-        res.append((o_s[r * tn:r * tn + c].copy(), o_l[r * tn:r * tn + c].copy(), o_v[r * tn:r * tn + c].copy(),
-                    float(mean[r])))
-    return res
+    return _run_many("muse_batch_run_many_windowed", batches, group_id, G, max_lag, top_n, threshold, sign_filter, abs_scores)
 
 
 def window_many_plan(R, L):
@@ -827,45 +805,13 @@ def score_many_in_window(batches, max_lag):
 
 def scores_many_in_window(batches, max_lag):
     """score_many_in_window + copy back: list of (lag, mv), one per batch"""
-    batches, arr = _batch_handles(batches)
-    lib = B.load()
-    B.check(lib.muse_batch_score_many_in_window(arr, len(batches), int(max_lag)))
-    out = []
-    for b in batches:
-        M = b.dgroup.M
-        lag = np.zeros(M, dtype=np.int32)
-        mv = np.zeros(M)
-        if M:
-            B.check(lib.muse_batch_read_scores(b._h, B.i32ptr(lag), B.dptr(mv)))
-        out.append((lag, mv))
-    return out
+    return _scores_many("muse_batch_score_many_in_window", batches, int(max_lag))
 
 
 def run_many_in_window(batches, group_id=None, G=0, max_lag=10, top_n=20, threshold=0.0, sign_filter=0, abs_scores=True):
     """muse_batch_run_many_in_window: Batch.RunInWindow for every reference (max_lag is the window and the Results.MaxLag);
     returns a list of (series, lag, score, mean_abs), one per batch"""
-    batches, arr = _batch_handles(batches)
-    R = len(batches)
-    cap = max(int(top_n), 1)
-    o_s = np.zeros(R * cap, dtype=np.int64)
-    o_l = np.zeros(R * cap, dtype=np.int32)
-    o_v = np.zeros(R * cap)
-    cnt = np.zeros(R, dtype=np.int32)
-    mean = np.zeros(R)
-    gid = None
-    if group_id is not None:
-        gid = np.ascontiguousarray(group_id, dtype=np.int32)
-    B.check(B.load().muse_batch_run_many_in_window(
-        arr, R, B.i32ptr(gid) if gid is not None else None, int(G), int(max_lag), int(top_n),
-        float(threshold), int(sign_filter), 1 if abs_scores else 0,
-        B.i64ptr(o_s), B.i32ptr(o_l), B.dptr(o_v), B.i32ptr(cnt), B.dptr(mean)))
-    tn = max(int(top_n), 0)
-    res = []
-    for r in range(R):
-        c = int(cnt[r])
-        res.append((o_s[r * tn:r * tn + c].copy(), o_l[r * tn:r * tn + c].copy(), o_v[r * tn:r * tn + c].copy(),
-                    float(mean[r])))
-    return res
+    return _run_many("muse_batch_run_many_in_window", batches, group_id, G, max_lag, top_n, threshold, sign_filter, abs_scores)
 
 
 def many_in_window_plan(N, f32, max_lag, R):
@@ -1503,104 +1449,63 @@ def NewBatch(ref, comp, results, cc, engine=None, engines=None):
     return Batch(ref, comp, results, cc, engine, engines)
 
 
-def RunMany(batches, groupByLabels):
-    """Batch.Run for several batches that share one Comparison group and the same Results settings
-    (README.md:10-13: many references against one set of series): the resident rows are read and
-    transformed once for all references (muse_batch_run_many).  Not part of the reference's API;
-    batches that do not qualify are run one after the other."""
+def _run_many_labels(batches, groupByLabels, each, run, sharded_ok, exact_feed):
+    """the label-level many-references Run: `run` (run_many*) over batches that share the Comparison, the engine and the Results
+    settings, every Results fed in group order; batches that do not qualify (sharded ones too unless sharded_ok) take their own
+    `each` method one after the other.  exact_feed: MaxLag is a window (>= 0) and Results is fed as RunInWindow feeds it"""
     batches = list(batches)
     if not batches:
         return None
     b0 = batches[0]
     r0 = b0.Results
-    same = all(b.Comparison is b0.Comparison and b._engine is b0._engine and
+    same = all(b.Comparison is b0.Comparison and b._engine is b0._engine and (sharded_ok or not b._engines) and
                (b.Results.MaxLag, b.Results.TopN, b.Results.Threshold, b.Results.SignFilter) ==
                (r0.MaxLag, r0.TopN, r0.Threshold, r0.SignFilter) for b in batches)
     if not same:
         for b in batches:
-            b.Run(groupByLabels)
+            getattr(b, each)(groupByLabels)
         return None
     comp = b0.Comparison
     labelValuesSet = comp.indexLabelValues(groupByLabels)
     if not labelValuesSet:
         return None
+    if exact_feed and r0.MaxLag < 0:
+        raise MuseError(B.MUSE_ERR_INVALID, "RunManyInWindow needs Results.MaxLag >= 0")
     series = comp._series_list()
     gid = comp._group_ids()
-    res = run_many([b._batch() for b in batches], gid, len(labelValuesSet), r0.MaxLag, r0.TopN, r0.Threshold,
-                   r0.SignFilter, abs_scores=True)
+    G = len(labelValuesSet)
+    dbs = [b._batch() for b in batches]
+    if exact_feed and G <= EXACT_FEED_MAX_GROUPS:   # (as RunInWindow: one Score per group in group order through Results.Update)
+        res = run(dbs, gid, G, r0.MaxLag, G, 0.0, SignFilter_ANY, abs_scores=True)
+    else:
+        res = run(dbs, gid, G, r0.MaxLag, r0.TopN, r0.Threshold, r0.SignFilter, abs_scores=True)
     for b, (idx, lag, score, _) in zip(batches, res):
         order = np.argsort(gid[idx], kind="stable")
         for k in order:
             b.Results.Update(Score(series[int(idx[k])].Labels(), int(lag[k]), float(score[k])))
     return None
+
+
+def RunMany(batches, groupByLabels):
+    """Batch.Run for several batches that share one Comparison group and the same Results settings
+    (README.md:10-13: many references against one set of series): the resident rows are read and
+    transformed once for all references (muse_batch_run_many).  Not part of the reference's API;
+    batches that do not qualify are run one after the other."""
+    return _run_many_labels(batches, groupByLabels, "Run", run_many, True, False)
 
 
 def RunManyWindowed(batches, groupByLabels):
     """RunMany with the shared Results.MaxLag as a LAG WINDOW (muse_batch_run_many_windowed): every batch receives what its own
     RunWindowed(groupByLabels) gives, from one pass over the rows whose matrix product holds the windows of all references.
     Batches that do not qualify for RunMany are RunWindowed one after the other."""
-    batches = list(batches)
-    if not batches:
-        return None
-    b0 = batches[0]
-    r0 = b0.Results
-    same = all(b.Comparison is b0.Comparison and b._engine is b0._engine and
-               (b.Results.MaxLag, b.Results.TopN, b.Results.Threshold, b.Results.SignFilter) ==
-               (r0.MaxLag, r0.TopN, r0.Threshold, r0.SignFilter) for b in batches)
-    if not same:
-        for b in batches:
-            b.RunWindowed(groupByLabels)
-        return None
-    comp = b0.Comparison
-    labelValuesSet = comp.indexLabelValues(groupByLabels)
-    if not labelValuesSet:
-        return None
-    series = comp._series_list()
-    gid = comp._group_ids()
-    res = run_many_windowed([b._batch() for b in batches], gid, len(labelValuesSet), r0.MaxLag, r0.TopN, r0.Threshold,
-                            r0.SignFilter, abs_scores=True)
-    for b, (idx, lag, score, _) in zip(batches, res):
-        order = np.argsort(gid[idx], kind="stable")
-        for k in order:
-            b.Results.Update(Score(series[int(idx[k])].Labels(), int(lag[k]), float(score[k])))
-    return None
+    return _run_many_labels(batches, groupByLabels, "RunWindowed", run_many_windowed, True, False)
 
 
 def RunManyInWindow(batches, groupByLabels):
     """RunMany with the shared Results.MaxLag as a lag window of ANY width (muse_batch_run_many_in_window): every batch receives
     what its own RunInWindow(groupByLabels) gives, from one pass over the rows where the lengths have a masked many-references
     kernel.  One device.  Batches that do not qualify for RunMany are RunInWindow one after the other."""
-    batches = list(batches)
-    if not batches:
-        return None
-    b0 = batches[0]
-    r0 = b0.Results
-    same = all(b.Comparison is b0.Comparison and b._engine is b0._engine and not b._engines and
-               (b.Results.MaxLag, b.Results.TopN, b.Results.Threshold, b.Results.SignFilter) ==
-               (r0.MaxLag, r0.TopN, r0.Threshold, r0.SignFilter) for b in batches)
-    if not same:
-        for b in batches:
-            b.RunInWindow(groupByLabels)
-        return None
-    comp = b0.Comparison
-    labelValuesSet = comp.indexLabelValues(groupByLabels)
-    if not labelValuesSet:
-        return None
-    if r0.MaxLag < 0:
-        raise MuseError(B.MUSE_ERR_INVALID, "RunManyInWindow needs Results.MaxLag >= 0")
-    series = comp._series_list()
-    gid = comp._group_ids()
-    G = len(labelValuesSet)
-    dbs = [b._batch() for b in batches]
-    if G <= EXACT_FEED_MAX_GROUPS:   # (as RunInWindow: one Score per group in group order through Results.Update)
-        res = run_many_in_window(dbs, gid, G, r0.MaxLag, G, 0.0, SignFilter_ANY, abs_scores=True)
-    else:
-        res = run_many_in_window(dbs, gid, G, r0.MaxLag, r0.TopN, r0.Threshold, r0.SignFilter, abs_scores=True)
-    for b, (idx, lag, score, _) in zip(batches, res):
-        order = np.argsort(gid[idx], kind="stable")
-        for k in order:
-            b.Results.Update(Score(series[int(idx[k])].Labels(), int(lag[k]), float(score[k])))
-    return None
+    return _run_many_labels(batches, groupByLabels, "RunInWindow", run_many_in_window, False, True)
 
 
 # ----------------------------------------------------------------- muse.go

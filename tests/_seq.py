@@ -563,7 +563,7 @@ def generate(cls, seed):
             if rop is not None and rop["kind"] in ("scores_many_w", "run_many_w") and len(rop["js"]) >= 2 and rop["L"] <= 16 and \
                     rng.random() < 0.5:
                 packed_hint = list(rop["js"])
-                break                                                  # (the next stretch slides one of them: many_tiles goes stale there)
+                break                                                  # (the next stretch slides one of them: the packed origin goes stale there)
         if rng.random() < 0.2:
             fk = REFUSALS[int(rng.integers(len(REFUSALS)))]
             if emit(fk) is not None:

@@ -8,7 +8,7 @@ seeds without a device).
 State that outlives a call and that these sequences cross: the group's spectrum cache (zc_state, zc_rows, zc_rewrites, its segments),
 the kept statistics of huge rows (hstats_rows), the rewrites counter, the staging pair, open staging windows and the gather's index
 list; a batch's kernel-selection memory (handoff_M, handoff_rewrites), scores_exact / last_screened / costly_key of the
-filter-and-refine Run, many_tiles, the window setting and its table cache (lag_window, win_L), gid_valid; the context's pooled
+filter-and-refine Run, the score origin, the window setting and its table cache (lag_window, win_L), gid_valid; the context's pooled
 Muse.Run slots and their window tables, the screening switch and the cache limits.
 
 A failure prints the seed, the failing step and the operation list so far as a _seq.replay(...) call; MUSE_TEST_SEQ_SEED=<int> adds a

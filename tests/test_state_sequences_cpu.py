@@ -122,7 +122,7 @@ def test_every_refusal_and_every_operation_kind_occurs(sequences):
 
 def test_the_states_the_suite_cannot_reach_otherwise_occur(sequences):
     """a screened Run in every sequence that switches screening on; a packed many-references pass followed by a fused slide of one of
-    its batches with no other scoring pass of that batch between (muse_batch::many_tiles); a slide between two unwindowed passes of
+    its batches with no other scoring pass of that batch between (muse_batch::origin, PACKED); a slide between two unwindowed passes of
     one batch (the spectrum cache in class a, the kept statistics in class f, the learned hand-off in class g)"""
     stale_tiles, slid = 0, set()
     for (cls, seed), ops in sequences.items():
