@@ -142,6 +142,7 @@ SIGNATURES = {
     "muse_group_spectrum_cache": (ctypes.c_int, [_vp, _i64p, _i64p]),
     "muse_group_drop_spectrum_cache": (ctypes.c_int, [_vp]),
     "muse_test_spectrum_cache_limits": (ctypes.c_int, [_vp, _i64, _i64]),
+    "muse_test_spectrum_cache_reader": (ctypes.c_int, [_vp, _i32]),
     "muse_test_spectrum_cache_policy": (ctypes.c_int, [_i64, _i32, _i32, _i32, _i64, _i64, _i64, _i32p, _i64p, _i64p]),
     "muse_test_batch_redo_pairs": (ctypes.c_int, [_vp, _i64p, _i64, _i64p]),
     "muse_next_pow2": (_i64, [_f64]),

@@ -551,6 +551,16 @@ extern "C" int muse_test_spectrum_cache_limits(muse_ctx *ctx, int64_t min_rows, 
     return MUSE_OK;
 }
 
+extern "C" int muse_test_spectrum_cache_reader(muse_ctx *ctx, int32_t reader)
+{
+    if (!ctx)
+        return fail(MUSE_ERR_INVALID, "NULL context");
+    if (reader != 0 && reader != 1)
+        return fail(MUSE_ERR_INVALID, "spectrum cache reader %d (0 = two workgroups per CU, 1 = four)", (int)reader);
+    ctx->zc_reader.store(reader);
+    return MUSE_OK;
+}
+
 extern "C" int muse_test_spectrum_cache_policy(int64_t rows, int32_t N, int32_t f32, int32_t mode, int64_t min_rows,
                                                int64_t free_bytes, int64_t budget_bytes, int32_t *decision,
                                                int64_t *rows_cached, int64_t *bytes)
@@ -671,11 +681,12 @@ int batch_score(muse_batch *b, bool allow_spectrum_cache, int win_L)
                 launched = true;
                 return e;
             };
+            const bool occ4_reader = ctx->zc_reader.load() == 1;
             for (const auto &sg : plan.readers) {
                 FusedParams r = p;
                 r.npairs = sg.pairs;
                 HIP_TRY(next_launch());
-                HIP_TRY(launch_cached(r, SpectrumCacheArgs{sg.zc(), sg.zstat(), sg.pair0, sg.pairs}, ctx->num_cus, st));
+                HIP_TRY(launch_cached(r, SpectrumCacheArgs{sg.zc(), sg.zstat(), sg.pair0, sg.pairs}, ctx->num_cus, st, occ4_reader));
             }
             if (plan.tail_pair0 < p.npairs) {
                 FusedParams w = p;
@@ -799,7 +810,7 @@ extern "C" int muse_batch_kernel_name(muse_batch *b, char *name, int32_t cap)
                          spectrum_cache_policy(b->g->M, b->N, false, b->ctx->zc_mode.load(), b->ctx->zc_min_rows.load(), 0, 0, &rc_, &by_) != ZC_POLICY_NONE;
             }
             if (cached)
-                snprintf(k, sizeof(k), "xcorr_cached_n4096<%s>", padded);
+                snprintf(k, sizeof(k), "xcorr_cached_n4096%s<%s>", b->ctx->zc_reader.load() == 1 ? "_occ4" : "", padded);
             else
                 snprintf(k, sizeof(k), "xcorr_fused_n4096_fold<false, %s, %s>", padded, f32);
             break;

@@ -163,6 +163,7 @@ struct muse_ctx {
     std::atomic<int> zc_mode{1};
     std::atomic<int64_t> zc_min_rows{ZC_MIN_ROWS};
     std::atomic<int64_t> zc_budget{-1};
+    std::atomic<int> zc_reader{0}; // test hook (muse_test_spectrum_cache_reader): 1 = the reader at four workgroups per CU
     std::atomic<int> win_rows_slices{0}; // test hook (muse_test_window_rows_slices): 0 = window_rows_plan; S >= 1 forces the slice count of the windowed Muse.Run
     std::atomic<bool> in_window_force{false}; // test hook (muse_test_in_window_force_transform): float64 windows <= MUSE_LAG_WINDOW_MAX of muse_batch_score_in_window take the masked transform kernels
     std::atomic<bool> gather_nt{false}; // measurement hook (muse_test_gather_nontemporal): the row gather's stores bypass the caches

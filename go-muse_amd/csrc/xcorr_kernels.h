@@ -113,7 +113,7 @@ struct SpectrumCacheArgs {
     long long zpairs;
 };
 hipError_t launch_cache_fill(const FusedParams &p, const SpectrumCacheArgs &c, int num_cus, hipStream_t stream); // from the rows; the first c.zpairs pairs into the cache
-hipError_t launch_cached(const FusedParams &p, const SpectrumCacheArgs &c, int num_cus, hipStream_t stream);     // from the cache
+hipError_t launch_cached(const FusedParams &p, const SpectrumCacheArgs &c, int num_cus, hipStream_t stream, bool occ4 = false); // from the cache (occ4: the four-workgroup reader, a test hook)
 hipError_t launch_fused_small(const FusedParams &p, int num_cus, hipStream_t stream); // xcorr_small.hip (n = 512, 1024, 2048: default)
 hipError_t launch_fused_stockham(const FusedParams &p, int num_cus, hipStream_t stream); // xcorr_stockham.hip (n = 512 .. 2048, 8192 .. 65536)
 hipError_t launch_fused_long(const FusedParams &p, int num_cus, hipStream_t stream); // xcorr_long.hip (n = 65536: default; 16384, 32768)

@@ -13,9 +13,12 @@
 //
 // xcorr_cache_fill_n4096: the plain kernel plus the stores (results unchanged) over pairs [pair0, pair0 + npairs); the first
 //                         `zpairs` of them are cached (0: none -- the plain arithmetic on a tail of the group).
-// xcorr_cached_n4096:     per pair sixteen 16-byte loads of Z, requested one pair ahead where the plain kernel requests rows,
-//                         the statistics through the scalar cache, then the plain kernel's second half, function by function:
-//                         the same operations on the same doubles, so mv and lag come out bit for bit as from the rows.
+// xcorr_cached_n4096:     per pair sixteen 16-byte loads of Z, requested a whole pair ahead, the statistics through the scalar
+//                         cache, then the plain kernel's second half, function by function: the same operations on the same
+//                         doubles, so mv and lag come out bit for bit as from the rows.  Two workgroups per CU: the reference's
+//                         table stays in registers for the whole launch; pairs are claimed two per atomic add.
+// xcorr_cached_n4096_occ4: the reader at four workgroups per CU that one replaced (table from L2 in every pair, Z requested at
+//                         the end of the pair before, one add per pair), behind a test hook to compare against.
 // Pairs with NaN / Inf statistics or sigmas too far apart are listed exactly as by the plain kernel and redone FROM THE ROWS
 // by the rescaling kernel behind the pass.
 #include <hip/hip_runtime.h>
@@ -212,8 +215,197 @@ __global__ __launch_bounds__(OCC_THREADS, 4) void xcorr_cache_fill_n4096(const F
 }
 
 // ---------------------------------------------------------------------------------------------------------------- reader
+// pass 3's factors from the two kept table entries, each one computed where it is asked for (G3Derived's formulas on the same
+// doubles): eight factors kept across the pair loop would be 32 registers the reader does not have
+struct G3Lazy {
+    double2 w8, w16;
+    __device__ __forceinline__ double2 operator()(int s) const
+    {
+        constexpr double H = 0.70710678118654752440;
+        switch (s) {
+        case 0: return foldk::G3Derived::sq(foldk::G3Derived::sq(w8));
+        case 1: return foldk::G3Derived::sq(w8);
+        case 2: return w8;
+        case 3: return make_double2(H * (w8.x + w8.y), H * (w8.y - w8.x));
+        case 4: return w16;
+        case 5: return foldk::G3Derived::mulc(w16, fold::C16_1, fold::S16_1);
+        case 6: return make_double2(H * (w16.x + w16.y), H * (w16.y - w16.x));
+        default: return foldk::G3Derived::mulc(w16, fold::S16_1, fold::C16_1);
+        }
+    }
+};
+
+// Pairs are handed out in chunks of ZC_CLAIM consecutive pairs per add on the work counter.  One add per pair is 500 000 adds
+// on ONE word per launch over 1 M rows, 71 per microsecond at 7 ms -- a single word takes about 88 (MI355X_MICROARCH.md,
+// "dequeue") -- and the hand-out, not the stream or the arithmetic, paced the reader: with 2 pairs per add it takes 0.83 - 0.85
+// of the time (profiles/spectrum_cache_reader_bench.txt; 3, 4, 8 and 16 pairs per add: 0.86).
+constexpr int ZC_CLAIM = 2;
+
+// Two workgroups per CU, 256 registers: what does not change from pair to pair stays in registers (the sixteen factors of the
+// reference's table and the two entries pass 3's factors derive from), and the next pair's spectrum is requested right behind
+// the multiply at the top of a pair, a whole pair before it is used: no load of the loop is waited for in the pair that
+// requests it.  The full 16 x 272 buffer takes the workgroup transpose in one round: three barriers per pair.
 template <bool PADDED>
-__global__ __launch_bounds__(OCC_THREADS, 4) void xcorr_cached_n4096(const FusedParams p, const SpectrumCacheArgs c)
+__global__ __launch_bounds__(OCC_THREADS, 2) void xcorr_cached_n4096(const FusedParams p, const SpectrumCacheArgs c)
+{
+    using namespace occ4;
+    using namespace fold;
+    using namespace foldk;
+    __shared__ double2 xbuf[OCC_XBUF_FULL];
+    __shared__ double2 g2s[128];
+    __shared__ double red[2 * REC];
+    __shared__ int next_s[2];
+    const int t = threadIdx.x;
+    const int lane = t & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    double2 *const xw = xbuf + 1088 * wave;
+    const double invN = PADDED ? p.invN : 1.0 / 4096.0, invNm1 = PADDED ? p.invNm1 : 1.0 / 4095.0;
+    const long long first = c.pair0, total = c.pair0 + p.npairs;
+    // N < 4096 has the -m c1 correction's registers on top and would spill with the request at the top of the pair: it requests
+    // behind pass 3 and the correction's loads, in front of the argmax
+    constexpr bool AHEAD = !PADDED;
+    constexpr int ch = ZC_CLAIM;
+
+    if (t < 128)
+        g2s[t] = p.g2[t];
+    if (t < 2)
+        red[REC * (t) + 34] = -1.0; // no previous pair yet (either parity)
+    if (t == 0) // the workgroup's second chunk (the loop claims two chunks ahead); slot 1: the first chunk writes slot 0
+        next_s[1] = (int)gridDim.x + atomicAdd(p.work_counter, 1);
+    d2v zn[16]; // the next pair's spectrum, in flight
+    const auto request_z = [&](long long pr) __attribute__((always_inline)) { // (addresses: see the four-workgroup reader below)
+#pragma unroll
+        for (int i = 0; i < 16; i++)
+            zn[i] = __builtin_nontemporal_load((gptr<d2v>)scalar_ptr_at(c.zc, (pr - first) * 4096 + 256 * ((i + 1) & ~1)) + (t - 256 * (i & 1)));
+    };
+    request_z(first + (long long)ch * blockIdx.x); // (the grid has at most ceil(npairs / ch) workgroups)
+    // launch-invariant: the reference's factors of this thread (xc for k3 = j) and pass 3's table entries of planes 2 and 4
+    double2 xf[16];
+#pragma unroll
+    for (int j = 0; j < 16; j++)
+        xf[j] = ldg2(scalar_ptr_at(p.xcp, 256 * ((j + 1) & ~1)), t - 256 * (j & 1));
+    G3Lazy g3{G3Fetch{p.g3b, t}(2), G3Fetch{p.g3b, t}(4)};
+    __syncthreads();
+
+    int parity = 0, cpar = 0;
+    long long pair = first + (long long)ch * blockIdx.x;
+    long long cbeg = pair, cend = pair + ch < total ? pair + ch : total; // the chunk of pairs in hand
+    long long nchunk = first + (long long)ch * __builtin_amdgcn_readfirstlane(next_s[1]), after = 0;
+    while (pair < total) {
+        const bool claiming = pair == cbeg;
+        const long long nextpair = pair + 1 < cend ? pair + 1 : nchunk;
+        const long long rA = 2 * pair;
+        const bool hasB = rA + 1 < p.M;
+        double *const rec = red + REC * parity;
+        const double *const prec = red + REC * (parity ^ 1);
+        // the pair's statistics (a wave-uniform address: the scalar cache), used behind the workgroup transpose below
+        double st[10];
+#if defined(__HIP_DEVICE_COMPILE__)
+        {
+            const zstat_in_ptr sp = (zstat_in_ptr)(unsigned long long)(c.zstat + (pair - first) * ZC_STAT);
+#pragma unroll
+            for (int k = 0; k < 10; k++)
+                st[k] = sp[k];
+        }
+#endif
+        // ================= ccA + i ccB = FFT(Z conj(X)/n) (unscaled by 1/sigma) =================
+        double2 v[16];
+#pragma unroll
+        for (int i = 0; i < 16; i++)
+            v[i] = make_double2(zn[i].x, zn[i].y);
+        xc_stage1_pre(v, xf);
+        // the spectrum's registers are free again: the next pair's request goes out here, a whole pair before its use (in front of
+        // the multiply the compiler would have to copy the sixteen registers out of the way first).
+        // A chunk's first pair claims the chunk after the next one here too (relative to pair0 / ZC_CLAIM): published in front of
+        // this pair's barriers, read behind them.  The counter's address goes through a vector register: with a uniform address the
+        // compiler rewrites the add into a wave reduction that waits for the returned value on the spot, a round trip to L2; and
+        // it stands behind the multiply, whose last wait for the spectrum would otherwise cover the add as well.
+        int claim = 0;
+#pragma unroll
+        for (int i = 0; i < 16; i += 4) // (the products are complete HERE: the compiler would sink them below the branch of the add)
+            asm volatile("" : "+v"(v[i].x), "+v"(v[i].y), "+v"(v[i + 1].x), "+v"(v[i + 1].y), "+v"(v[i + 2].x), "+v"(v[i + 2].y), "+v"(v[i + 3].x), "+v"(v[i + 3].y));
+#if defined(__HIP_DEVICE_COMPILE__)
+        if (claiming && t == 0) {
+            unsigned long long wc = (unsigned long long)p.work_counter;
+            asm volatile("" : "+v"(wc));
+            claim = __hip_atomic_fetch_add((int __attribute__((address_space(1))) *)wc, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+#endif
+        const long long nxt = nextpair < total ? nextpair : first; // past the end: a dummy request
+        if (AHEAD) {
+            fence();
+            request_z(nxt);
+            fence();
+        }
+        // (the compiler would otherwise derive all eight of pass 3's factors once, in front of the loop: 32 registers, spills)
+        asm volatile("" : "+v"(g3.w8.x), "+v"(g3.w8.y), "+v"(g3.w16.x), "+v"(g3.w16.y));
+        dft16_rn_s234(v);
+        exchange_local_full<0>(v, xw, t);
+        gdft16_nr(v, G2Fetch{g2s, t & 15});
+        if (claiming && t == 0)
+            next_s[cpar] = (int)gridDim.x + claim;
+        exchange_cross_full<1, 1>(v, xbuf, t);
+        lds_barrier(); // the reads are done: the next pair's wave-local transpose writes without a barrier of its own
+        // behind the barriers: the previous pair's record is complete and visible, and nobody reads this parity's record any more
+        // (its last reader was the finalize of the pair before the previous one, in front of these barriers)
+        finalize_prev(prec, wave, lane, invN, invNm1, p);
+        if (t == 0) {
+#pragma unroll
+            for (int k = 0; k < 10; k++)
+                rec[24 + k] = st[k];
+            rec[34] = (double)rA;
+            rec[35] = hasB ? 1.0 : 0.0;
+        }
+        if (claiming) {
+            after = first + (long long)ch * __builtin_amdgcn_readfirstlane(next_s[cpar]);
+            cpar ^= 1;
+        }
+        gdft16_nr_l2(v, g3);
+        if (PADDED) { // cc(d - m 1_valid) = cc(d) - m c1, m = sum d / N
+            const auto c1l = [&](int k) __attribute__((always_inline)) {
+                return scalar_ptr_at(p.c1, 256 * ((k + 1) & ~1))[t - 256 * (k & 1)];
+            };
+            const double mA = st[8] * invN, mB = st[9] * invN;
+            // all sixteen c1 values in front of the request: loads return in order, one behind it would wait for the spectrum
+            double cq[16];
+#pragma unroll
+            for (int k = 0; k < 16; k++)
+                cq[k] = c1l(k);
+            fence();
+            request_z(nxt);
+            fence();
+#pragma unroll
+            for (int k = 0; k < 16; k++) {
+                const int r = BR16(k);
+                v[r] = make_double2(fma(-mA, cq[k], v[r].x), fma(-mB, cq[k], v[r].y));
+            }
+        }
+        wave_argmax_store(v, wave, lane, rec + 6 * wave);
+        parity ^= 1;
+        if (pair + 1 < cend) {
+            pair++;
+        } else {
+            pair = cbeg = nchunk;
+            cend = pair + ch < total ? pair + ch : total;
+            nchunk = after;
+        }
+    }
+    lds_barrier();
+    {
+        const double *const prec = red + REC * (parity ^ 1);
+        if (t < 2 && prec[34] >= 0.0 && (t == 0 || prec[35] != 0.0)) {
+            const long long row = (long long)prec[34] + t;
+            if (finalize(prec, t, invN, invNm1, p.mv + row, p.lag + row)) {
+                const int slot = atomicAdd(p.ovf_count, 1);
+                p.ovf_list[slot] = row >> 1;
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- the reader at four workgroups per CU (test hook: muse_test_spectrum_cache_reader)
+template <bool PADDED>
+__global__ __launch_bounds__(OCC_THREADS, 4) void xcorr_cached_n4096_occ4(const FusedParams p, const SpectrumCacheArgs c)
 {
     using namespace occ4;
     using namespace fold;
@@ -360,14 +552,21 @@ hipError_t launch_cache_fill(const FusedParams &p_in, const SpectrumCacheArgs &c
     return hipGetLastError();
 }
 
-// pairs [c.pair0, c.pair0 + p.npairs) from the cache (all of them cached: c.zpairs >= p.npairs)
-hipError_t launch_cached(const FusedParams &p_in, const SpectrumCacheArgs &c, int num_cus, hipStream_t stream)
+// pairs [c.pair0, c.pair0 + p.npairs) from the cache (all of them cached: c.zpairs >= p.npairs); occ4: the reader at four
+// workgroups per CU (test hook)
+hipError_t launch_cached(const FusedParams &p_in, const SpectrumCacheArgs &c, int num_cus, hipStream_t stream, bool occ4)
 {
     const FusedParams p = with_reciprocals(p_in);
     if (!cache_launch_ok(p, c) || !c.zc || !c.zstat || c.zpairs < p.npairs || 2 * (c.pair0 + p.npairs) > p.M)
         return hipErrorInvalidValue;
-    const dim3 g((unsigned)std::min<long long>(p.npairs, (long long)num_cus * 4)), b(OCC_THREADS);
-    if (p.N < 4096)
+    const dim3 g((unsigned)(occ4 ? std::min<long long>(p.npairs, (long long)num_cus * 4)
+                                 : std::min<long long>((p.npairs + ZC_CLAIM - 1) / ZC_CLAIM, (long long)num_cus * 2))), b(OCC_THREADS);
+    if (occ4) {
+        if (p.N < 4096)
+            hipLaunchKernelGGL((xcorr_cached_n4096_occ4<true>), g, b, 0, stream, p, c);
+        else
+            hipLaunchKernelGGL((xcorr_cached_n4096_occ4<false>), g, b, 0, stream, p, c);
+    } else if (p.N < 4096)
         hipLaunchKernelGGL((xcorr_cached_n4096<true>), g, b, 0, stream, p, c);
     else
         hipLaunchKernelGGL((xcorr_cached_n4096<false>), g, b, 0, stream, p, c);

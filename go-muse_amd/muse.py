@@ -94,6 +94,10 @@ class Engine:
         """test hook (include/muse_hip_test.h): smallest cached group and a byte budget (0 = always decline); negative = default"""
         B.check(B.load().muse_test_spectrum_cache_limits(self._h, int(min_rows), int(budget_bytes)))
 
+    def spectrum_cache_reader(self, reader=0):
+        """test hook (include/muse_hip_test.h): 0 = the reader at two workgroups per CU (the default), 1 = the one at four it replaced"""
+        B.check(B.load().muse_test_spectrum_cache_reader(self._h, int(reader)))
+
     def trim(self):
         """muse_ctx_trim: hands the context's cached device / pinned blocks back to the system"""
         B.check(B.load().muse_ctx_trim(self._h))

@@ -75,6 +75,10 @@ int muse_test_slide_plan(int32_t N, int32_t k, int32_t f32_storage, int32_t *uni
 /* Spectrum cache (muse_ctx_set_spectrum_cache): the smallest group that is cached (default 65 536 rows; negative = default) and
  * a byte budget for a group's cache in place of half the free device memory (0 = always decline; negative = no override). */
 int muse_test_spectrum_cache_limits(muse_ctx *ctx, int64_t min_rows, int64_t budget_bytes);
+/* Which kernel scores from a valid cache: 0 (the default) = xcorr_cached_n4096, two workgroups per CU with the reference's table in
+ * registers; 1 = xcorr_cached_n4096_occ4, the reader at four workgroups per CU it replaced (kept to compare against: results are
+ * bit-identical).  Anything else: MUSE_ERR_INVALID. */
+int muse_test_spectrum_cache_reader(muse_ctx *ctx, int32_t reader);
 /* The cache's policy, a pure host function (no device needed): what the second pass over `rows` rows of length N decides with
  * free_bytes of device memory free -- *decision = 0 no cache, 1 build one of *bytes for rows [0, *rows_cached), 2 declined for
  * lack of memory.  min_rows / budget_bytes as in muse_test_spectrum_cache_limits. */
