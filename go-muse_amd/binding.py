@@ -31,6 +31,7 @@ MUSE_ERR_EMPTY = -8
 MUSE_LAG_WINDOW_MAX = 63
 MUSE_IN_WINDOW_UNSUPPORTED, MUSE_IN_WINDOW_PLAIN, MUSE_IN_WINDOW_MFMA, MUSE_IN_WINDOW_MASKED = 0, 1, 2, 3   # muse_hip_test.h
 MUSE_IN_WINDOW_MASKED_EACH = 4   # (muse_test_many_in_window_plan only)
+MUSE_SLIDE_IN_WINDOW_UNSUPPORTED, MUSE_SLIDE_IN_WINDOW_MFMA, MUSE_SLIDE_IN_WINDOW_FUSED, MUSE_SLIDE_IN_WINDOW_TWO_STEP = 0, 1, 2, 3   # muse_hip_test.h
 
 
 class MuseRecord(ctypes.Structure):
@@ -79,6 +80,14 @@ SIGNATURES = {
     "muse_batch_slide_run_windowed": (ctypes.c_int, [_vp, _dp, _i32, _i64, _i32p, _i32, _i32, _i32, _f64, _i32, _i32,
                                                      _i64p, _i32p, _dp, _i32p, _dp]),
     "muse_test_slide_score_plan": (ctypes.c_int, [_i32, _i32, _i32, _i32p, _i32p]),
+    "muse_batch_slide_score_in_window": (ctypes.c_int, [_vp, _dp, _i32, _i64, _i32]),
+    "muse_batch_slide_run_in_window": (ctypes.c_int, [_vp, _dp, _i32, _i64, _i32p, _i32, _i32, _i32, _f64, _i32, _i32,
+                                                      _i64p, _i32p, _dp, _i32p, _dp]),
+    "muse_batch_slide_run": (ctypes.c_int, [_vp, _dp, _i32, _i64, _i32p, _i32, _i32, _i32, _f64, _i32, _i32,
+                                            _i64p, _i32p, _dp, _i32p, _dp]),
+    "muse_test_slide_in_window_plan": (ctypes.c_int, [_i32, _i32, _i32, _i32, _i32p]),
+    "muse_test_slide_in_window_force": (ctypes.c_int, [_vp, _i32]),
+    "muse_test_last_slide_path": (ctypes.c_int, [_vp, _i32p]),
     "muse_ctx_trim": (ctypes.c_int, [_vp]),
     "muse_batch_fft_len": (ctypes.c_int, [_vp, _i32p]),
     "muse_batch_spectrum": (ctypes.c_int, [_vp, _dp]),

@@ -598,7 +598,24 @@ extern "C" int muse_batch_score(muse_batch *b)
     return batch_score(b, true);
 }
 
-int batch_score(muse_batch *b, bool allow_spectrum_cache, int win_L)
+// (the refusals below in the order batch_score meets them)
+int batch_score_check(muse_batch *b, int win_L, int *variant)
+{
+    *variant = -1;
+    if (win_L < 0 && b->windowed())
+        return MUSE_OK;
+    if (b->n > GENERIC_MAX_N)
+        return b->g->f32 ? fail(MUSE_ERR_UNSUPPORTED, "float32-storage groups run on the default kernels only (FFT lengths 512 ... 16384)") : MUSE_OK;
+    const KernelChoice kc = choose_kernel(b, (b->g->M + 1) / 2);
+    if (kc.error)
+        return fail(MUSE_ERR_UNSUPPORTED, "%s", kc.error);
+    if (win_L >= 0 && (!(kc.variant == KERNEL_R16_FOLD || kc.variant == KERNEL_R16_OCC3 || (kc.variant == KERNEL_SMALL && b->logn <= 11)) || 2 * win_L > b->n))
+        return fail(MUSE_ERR_UNSUPPORTED, "the masked transform pass runs on the default kernels of FFT lengths 512 ... 4096");
+    *variant = kc.variant;
+    return MUSE_OK;
+}
+
+int batch_score(muse_batch *b, bool allow_spectrum_cache, int win_L, const SlideFuse *slide)
 {
     if (!b)
         return fail(MUSE_ERR_INVALID, "NULL batch");
@@ -647,6 +664,12 @@ int batch_score(muse_batch *b, bool allow_spectrum_cache, int win_L)
             return fail(MUSE_ERR_UNSUPPORTED, "the masked transform pass runs on the default kernels of FFT lengths 512 ... 4096");
         b->origin = ScoreOrigin::in_window(MUSE_IN_WINDOW_MASKED, win_L, variant);
         set_window(p, win_L);
+    }
+    if (slide) { // (the rows are rewritten by the launch: only the kernel that was built for it may see the tails)
+        if (variant != KERNEL_R16_FOLD || allow_spectrum_cache)
+            return fail(MUSE_ERR_INVALID, "the fused slide runs in the default n = 4096 kernel, off the rows");
+        p.slide_tails = slide->tails;
+        p.slide_k = slide->k;
     }
     if (variant == KERNEL_GENERIC && b->n <= GENERIC_LDS_MAX_N)
         p.gscratch = nullptr; // the generic kernel takes a non-NULL scratch pointer as "work in global memory"
@@ -702,6 +725,8 @@ int batch_score(muse_batch *b, bool allow_spectrum_cache, int win_L)
         }
         HIP_TRY(timer.end());
         FusedParams q = p;
+        q.slide_tails = nullptr; // (the rescaling kernel reads the rows as the launch in front of it left them)
+        q.slide_k = 0;
         q.pair_list = b->ovf_list.p;
         q.pair_count = b->ovf_count;
         // a dense list (the same threshold as the hand-off rule above) makes the redo kernel redo EVERY pair: the results of a
@@ -775,7 +800,9 @@ extern "C" int muse_batch_kernel_name(muse_batch *b, char *name, int32_t cap)
     char k[96] = "xcorr_fused_generic";
     const char *padded = b->N < b->n ? "true" : "false", *f32 = b->g->f32 ? "true" : "false";
     const ScoreOrigin &o = b->origin; // (the in-window and packed kinds: an argument of a call, not a setting the next pass takes)
-    if (o.kind == ScoreOrigin::MASKED) {
+    if (o.slide == MUSE_SLIDE_IN_WINDOW_FUSED) { // (muse_batch_slide_score_in_window's one kernel: plain or masked argmax)
+        snprintf(k, sizeof(k), "xcorr_fused_n4096_fold<false, %s, %s, %s, true>", padded, f32, o.kind == ScoreOrigin::MASKED ? "true" : "false");
+    } else if (o.kind == ScoreOrigin::MASKED) {
         if (o.variant == ScoreOrigin::MANY && b->n == 4096) // (muse_batch_score_many_in_window's one pass)
             snprintf(k, sizeof(k), "xcorr_fused_n4096_fold_multi<%s, %s, true>", padded, f32);
         else if (o.variant == ScoreOrigin::MANY)

@@ -166,6 +166,7 @@ struct muse_ctx {
     std::atomic<int> zc_reader{0}; // test hook (muse_test_spectrum_cache_reader): 1 = the reader at four workgroups per CU
     std::atomic<int> win_rows_slices{0}; // test hook (muse_test_window_rows_slices): 0 = window_rows_plan; S >= 1 forces the slice count of the windowed Muse.Run
     std::atomic<bool> in_window_force{false}; // test hook (muse_test_in_window_force_transform): float64 windows <= MUSE_LAG_WINDOW_MAX of muse_batch_score_in_window take the masked transform kernels
+    std::atomic<int> slide_in_window_force{0}; // test hook (muse_test_slide_in_window_force): 1 = muse_batch_slide_score_in_window never takes the fused n = 4096 kernel (TWO_STEP)
     std::atomic<bool> gather_nt{false}; // measurement hook (muse_test_gather_nontemporal): the row gather's stores bypass the caches
     // Handles may be released in any order (Go finalizers, Python GC): the
     // context lives until it is destroyed AND its last group/batch is freed.
@@ -272,6 +273,7 @@ struct ScoreOrigin {
     int32_t window = -1; // PLAIN / MFMA / MASKED: min(the call's window, n / 2)
     int32_t variant = 0; // MASKED: the KERNEL_* the pass launched first, or MANY
     int32_t tiles = 0;   // PACKED
+    int32_t slide = 0;   // the MUSE_SLIDE_IN_WINDOW_* path if the pass was muse_batch_slide_score_in_window's and moved the rows, 0 otherwise
     static ScoreOrigin packed(int32_t tiles) { return ScoreOrigin{PACKED, -1, 0, tiles}; }
     static ScoreOrigin in_window(int32_t path, int32_t L, int32_t variant = 0) { return ScoreOrigin{(Kind)path, L, variant, 0}; }
     int32_t in_window_path() const { return kind > OWN ? (int32_t)kind : 0; }
@@ -446,7 +448,18 @@ int ensure_scores(muse_batch *b);
 // capi_batch.hip: muse_batch_score (the many-references fallback passes false).  win_L >= 0: the MASKED pass of muse_batch_score_in_window --
 // the same launch sequence with the argmax of the transform kernels restricted to +-win_L (n = 512 ... 4096; the batch's own window and
 // the group's spectrum cache are neither read nor touched)
-int batch_score(muse_batch *b, bool allow_spectrum_cache, int win_L = -1);
+// slide != nullptr: the slide of the group's rows fused into the pass (muse_batch_slide_score_in_window, FUSED): the n = 4096 kernel reads the
+// rows moved forward by slide->k samples (slide->tails: the group's device image of the tails) and stores them in place on the way; the
+// caller has made sure of the kernel (batch_score_check: KERNEL_R16_FOLD) and keeps the spectrum cache out (allow_spectrum_cache false)
+struct SlideFuse {
+    const void *tails;
+    int32_t k;
+};
+int batch_score(muse_batch *b, bool allow_spectrum_cache, int win_L = -1, const SlideFuse *slide = nullptr);
+// what batch_score(b, ., win_L) would refuse for the batch as it stands (kernel selection, storage, length), without enqueueing
+// anything -- for a caller that moves rows before it scores; *variant = the KERNEL_* the pass would launch first (-1: none of them:
+// the batch's own window or a series longer than 65 536 samples)
+int batch_score_check(muse_batch *b, int win_L, int *variant);
 // the spectrum cache's policy, a pure host function: what a pass over `rows` rows of length N does about a cache
 // that does not exist yet -- nothing, build one of *bytes for *rows_cached rows, or decline for lack of memory
 enum { ZC_POLICY_NONE = 0, ZC_POLICY_BUILD = 1, ZC_POLICY_DECLINED = 2 };

@@ -111,25 +111,35 @@ int score_windowed(muse_batch *b)
     return MUSE_OK;
 }
 
-// ---- the slide and the windowed pass in one kernel (xcorr_window_slide.hip)
-extern "C" int muse_batch_slide_score_windowed(muse_batch *b, const double *tails, int32_t k, int64_t tail_stride, int32_t max_lag)
+// the slide arguments of the calls that move the whole group of a batch and score it (muse_group_slide's refusals)
+static int check_slide_args(const muse_batch *b, const double *tails, int32_t k, int64_t tail_stride)
 {
-    // everything is checked before anything is enqueued: on an error the batch and the group are unchanged
     if (!b)
         return fail(MUSE_ERR_INVALID, "NULL batch");
-    muse_group *g = b->g;
-    const int64_t M = g->M;
+    const muse_group *g = b->g;
     if (k < 0 || k > g->N)
         return fail(MUSE_ERR_INVALID, "slide by %d samples: outside 0 .. N = %d", k, g->N);
     if (tail_stride < k)
         return fail(MUSE_ERR_INVALID, "tail_stride %lld is smaller than k = %d", (long long)tail_stride, k);
-    if (!tails && M > 0 && k > 0)
+    if (!tails && g->M > 0 && k > 0)
         return fail(MUSE_ERR_INVALID, "tails is NULL");
     if (g->win_rows)
         return fail(MUSE_ERR_INVALID, "the group has an open staging window");
+    return MUSE_OK;
+}
+
+// ---- the slide and the windowed pass in one kernel (xcorr_window_slide.hip)
+extern "C" int muse_batch_slide_score_windowed(muse_batch *b, const double *tails, int32_t k, int64_t tail_stride, int32_t max_lag)
+{
+    // everything is checked before anything is enqueued: on an error the batch and the group are unchanged
+    int rc = check_slide_args(b, tails, k, tail_stride);
+    if (rc)
+        return rc;
+    muse_group *g = b->g;
+    const int64_t M = g->M;
     if (max_lag < 0)
         return fail(MUSE_ERR_INVALID, "a windowed pass needs a lag window >= 0");
-    int rc = check_window_request(b, max_lag, g->f32);
+    rc = check_window_request(b, max_lag, g->f32);
     if (!rc)
         rc = check_own_window(b, max_lag);
     if (rc)
@@ -281,6 +291,190 @@ extern "C" int muse_batch_run_in_window(muse_batch *b, const int32_t *group_id, 
     int rc = check_select_args(group_id, G, sign_filter);
     if (!rc)
         rc = muse_batch_score_in_window(b, max_lag);
+    if (rc)
+        return rc;
+    std::vector<muse_record> sel;
+    rc = run_select(b, group_id, G, 0, max_lag, top_n, threshold, sign_filter, abs_scores, sel, true, false);
+    if (rc)
+        return rc;
+    emit(sel, out_series, out_lag, out_score, out_count, out_mean_abs);
+    return MUSE_OK;
+}
+
+// ---- the slide and the pass of any window in one call (muse_batch_slide_score_in_window)
+// The dispatch, a pure host function: how series of N samples (float32 storage or not) are slid by k and scored inside +-max_lag.
+//   in_window_plan says UNSUPPORTED                    : not built
+//   in_window_plan says MFMA                           : muse_batch_slide_score_windowed (xcorr_window_slide.hip)
+//   PLAIN or MASKED at FFT length 4096                 : the SLIDE builds of xcorr_fused_n4096_fold (one read and one write of the rows)
+//   anything else                                      : launch_row_slide and then the pass
+// Measured (tools/slide_in_window_bench.py, profiles/slide_in_window_bench.txt): the fused kernel against the two kernels
+// it replaces, per listed shape; no k is routed away from it.
+static int slide_in_window_plan(int32_t N, bool f32, int32_t max_lag, int32_t k, bool force_transform)
+{
+    (void)k;
+    const int pass = in_window_plan(N, f32, max_lag, force_transform);
+    if (pass == MUSE_IN_WINDOW_UNSUPPORTED)
+        return MUSE_SLIDE_IN_WINDOW_UNSUPPORTED;
+    if (pass == MUSE_IN_WINDOW_MFMA)
+        return MUSE_SLIDE_IN_WINDOW_MFMA;
+    return muse_next_pow2((double)N) == 4096 ? MUSE_SLIDE_IN_WINDOW_FUSED : MUSE_SLIDE_IN_WINDOW_TWO_STEP;
+}
+
+extern "C" int muse_test_slide_in_window_plan(int32_t N, int32_t f32, int32_t max_lag, int32_t k, int32_t *path)
+{
+    if (!path || N < 2 || max_lag < 0 || k < 0 || k > N)
+        return fail(MUSE_ERR_INVALID, "bad slide-in-window plan arguments (N >= 2, max_lag >= 0, 0 <= k <= N)");
+    *path = slide_in_window_plan(N, f32 != 0, max_lag, k, false);
+    return MUSE_OK;
+}
+
+extern "C" int muse_test_slide_in_window_force(muse_ctx *ctx, int32_t mode)
+{
+    if (!ctx || mode < 0 || mode > 1)
+        return fail(MUSE_ERR_INVALID, "the slide-in-window hook takes a context and mode 0 (the table) or 1 (two steps)");
+    ctx->slide_in_window_force.store(mode);
+    return MUSE_OK;
+}
+
+extern "C" int muse_test_last_slide_path(muse_batch *b, int32_t *path)
+{
+    if (!b || !path)
+        return fail(MUSE_ERR_INVALID, "NULL argument");
+    *path = b->origin.slide;
+    return MUSE_OK;
+}
+
+extern "C" int muse_batch_slide_score_in_window(muse_batch *b, const double *tails, int32_t k, int64_t tail_stride, int32_t max_lag)
+{
+    // everything is checked before anything is enqueued: on a refusal the rows, the batch and the group are unchanged
+    int rc = check_slide_args(b, tails, k, tail_stride);
+    if (rc)
+        return rc;
+    muse_group *g = b->g;
+    muse_ctx *ctx = b->ctx;
+    const int64_t M = g->M;
+    if (max_lag < 0)
+        return fail(MUSE_ERR_INVALID, "a windowed pass needs a lag window >= 0");
+    rc = check_own_window(b, max_lag);
+    if (rc)
+        return rc;
+    const bool force_transform = ctx->in_window_force.load();
+    const int pass = in_window_plan(b->N, g->f32, max_lag, force_transform);
+    int path = slide_in_window_plan(b->N, g->f32, max_lag, k, force_transform);
+    if (path == MUSE_SLIDE_IN_WINDOW_UNSUPPORTED || (path == MUSE_SLIDE_IN_WINDOW_MFMA && !b->xs))
+        return fail(MUSE_ERR_UNSUPPORTED, "a lag window of %d over series of %d samples%s is not built: wider than MUSE_LAG_WINDOW_MAX (%d) and for "
+                    "float32 storage the window is a masked argmax of the transform kernels of FFT lengths 512 ... 4096",
+                    max_lag, b->N, g->f32 ? " in float32 storage" : "", MUSE_LAG_WINDOW_MAX);
+    if (M == 0) // nothing to move, nothing to score
+        return MUSE_OK;
+    if (k == 0) // nothing moves and nothing is invalidated: the pass alone
+        return muse_batch_score_in_window(b, max_lag);
+    const int L = std::min(max_lag, b->n / 2);
+    if (path == MUSE_SLIDE_IN_WINDOW_MFMA) { // the direct product has a slide kernel of its own; the origin is muse_batch_score_in_window's
+        rc = muse_batch_slide_score_windowed(b, tails, k, tail_stride, max_lag);
+        if (rc)
+            return rc;
+        b->last_path = MUSE_RUN_PATH_FP64;
+        b->last_screened = false;
+        b->origin = ScoreOrigin::in_window(MUSE_IN_WINDOW_MFMA, L);
+        b->origin.slide = path;
+        return MUSE_OK;
+    }
+    // the pass as muse_batch_score_in_window launches it: the masked one with the window in the kernel's arguments, the plain one
+    // with the batch's own setting (equal to the call's, or off) out of the way
+    const int win_L = pass == MUSE_IN_WINDOW_MASKED ? L : -1;
+    const int32_t own = b->lag_window;
+    b->lag_window = -1;
+    int variant = -1;
+    rc = batch_score_check(b, win_L, &variant);
+    b->lag_window = own;
+    if (rc)
+        return rc;
+    // FUSED is the default n = 4096 kernel's build: a forced variant, a missing correction table or a hand-off learned from the rows
+    // as they are sends the call the long way round (and so do rows the kernel cannot move in its 16-byte units: never a group's)
+    if (path == MUSE_SLIDE_IN_WINDOW_FUSED &&
+        (ctx->slide_in_window_force.load() == 1 || variant != KERNEL_R16_FOLD || g->stride != g->N ||
+         (b->N == 4096 && !g->f32 && !window_wide(g->rows, g->stride))))
+        path = MUSE_SLIDE_IN_WINDOW_TWO_STEP;
+    rc = use_device(ctx);
+    if (rc)
+        return rc;
+    const hipStream_t st = b->stream();
+    rc = group_ready(g, st); // rows packed but not sent yet go first
+    if (rc)
+        return rc;
+    rc = ensure_scores(b);
+    if (rc)
+        return rc;
+    rc = slide_upload_tails(g, M, tails, k, tail_stride);
+    if (rc)
+        return rc;
+    // as muse_group_slide: the kernels rewrite rows that work enqueued earlier on any stream of the device may still be reading (the
+    // tails have landed with it), and the call returns once they have finished
+    HIP_TRY(hipDeviceSynchronize());
+    slide_invalidate(g, 0);
+    b->lag_window = -1;
+    if (path == MUSE_SLIDE_IN_WINDOW_FUSED) {
+        const SlideFuse fuse{g->slide_dev.p, k};
+        rc = batch_score(b, false, win_L, &fuse);
+    } else {
+        rc = MUSE_OK;
+        {
+            LaunchTimer timer(ctx, false, st);
+            hipError_t e = timer.begin();
+            if (e == hipSuccess)
+                e = launch_row_slide(g->base(), g->f32, M, g->N, k, g->slide_dev.p, ctx->num_cus, st);
+            if (e == hipSuccess)
+                e = timer.end();
+            if (e != hipSuccess)
+                rc = fail(MUSE_ERR_HIP, "the row slide failed: %s", hipGetErrorString(e));
+        }
+        if (!rc)
+            rc = batch_score(b, false, win_L);
+    }
+    b->lag_window = own; // (put back, whatever the outcome)
+    if (rc)
+        return rc;
+    HIP_TRY(hipStreamSynchronize(st));
+    b->scores_exact = true;
+    b->last_path = MUSE_RUN_PATH_FP64;
+    b->last_screened = false;
+    if (pass != MUSE_IN_WINDOW_MASKED) // (batch_score records the masked origin: it knows the kernel it launches first)
+        b->origin = ScoreOrigin::in_window(pass, L);
+    b->origin.slide = path;
+    return MUSE_OK;
+}
+
+extern "C" int muse_batch_slide_run_in_window(muse_batch *b, const double *tails, int32_t k, int64_t tail_stride,
+                                              const int32_t *group_id, int32_t G, int32_t max_lag, int32_t top_n, double threshold,
+                                              int32_t sign_filter, int32_t abs_scores, int64_t *out_series, int32_t *out_lag,
+                                              double *out_score, int32_t *out_count, double *out_mean_abs)
+{
+    // (the selection's own argument checks come first: a refusal leaves the rows where they were)
+    int rc = check_select_args(group_id, G, sign_filter);
+    if (!rc)
+        rc = muse_batch_slide_score_in_window(b, tails, k, tail_stride, max_lag);
+    if (rc)
+        return rc;
+    std::vector<muse_record> sel;
+    rc = run_select(b, group_id, G, 0, max_lag, top_n, threshold, sign_filter, abs_scores, sel, true, false);
+    if (rc)
+        return rc;
+    emit(sel, out_series, out_lag, out_score, out_count, out_mean_abs);
+    return MUSE_OK;
+}
+
+// the reference's Run on the slid rows: the global argmax of every series, then the filter on Results.MaxLag
+extern "C" int muse_batch_slide_run(muse_batch *b, const double *tails, int32_t k, int64_t tail_stride,
+                                    const int32_t *group_id, int32_t G, int32_t max_lag, int32_t top_n, double threshold,
+                                    int32_t sign_filter, int32_t abs_scores, int64_t *out_series, int32_t *out_lag,
+                                    double *out_score, int32_t *out_count, double *out_mean_abs)
+{
+    int rc = check_select_args(group_id, G, sign_filter);
+    if (!rc && b && b->windowed())
+        rc = fail(MUSE_ERR_INVALID, "the batch has a lag window of %d of its own: muse_batch_slide_run scores every lag", b->lag_window);
+    if (!rc)
+        rc = muse_batch_slide_score_in_window(b, tails, k, tail_stride, b ? b->n / 2 : 0);
     if (rc)
         return rc;
     std::vector<muse_record> sel;

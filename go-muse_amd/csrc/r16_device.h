@@ -385,6 +385,134 @@ __device__ __forceinline__ void widen_rows(RawPair &r)
     }
 }
 
+// ---- the SLIDE builds of xcorr_fused_n4096_fold (muse_batch_slide_score_in_window): the loaders read the NEW row -- old row[k .. N)
+// followed by the row's k tail samples (FusedParams::slide_tails, dense M x k in the group's storage type) -- into the registers
+// and on the lane-to-column mapping of the stand-alone loaders above, and the raw values are stored back to the row in place once
+// every load of the pair has returned (the ordering rules: xcorr_r16_fold.hip).
+#if defined(__HIP_DEVICE_COMPILE__)
+template <typename T>
+using gwptr = T __attribute__((address_space(1))) *;
+#else
+template <typename T>
+using gwptr = T *;
+#endif
+// A new row as two wave-uniform byte addresses that sample j is taken relative to: old row[j + k] in front of keep = N - k, the
+// row's tail[j - keep] from there on.  The ADDRESS is selected per lane, not the value: one load per sample and no branch around it.
+struct SlidRow {
+    unsigned long long kept, tail; // &row[k], &tail[-keep]
+};
+template <typename T>
+__device__ __forceinline__ SlidRow slid_row(const T *rows, const FusedParams &p, long long r, int k, int keep)
+{
+    SlidRow s;
+    s.kept = (unsigned long long)(rows + r * p.stride + k);
+    s.tail = (unsigned long long)((const T *)p.slide_tails + r * k - keep);
+    asm volatile("" : "+s"(s.kept), "+s"(s.tail)); // (formed per call in scalar registers, as scalar_ptr_at's bases)
+    return s;
+}
+template <typename T>
+__device__ __forceinline__ gptr<T> slid_addr(const SlidRow &s, unsigned j, int keep)
+{
+    return (gptr<T>)(((int)j < keep ? s.kept : s.tail) + (unsigned long long)(j * (unsigned)sizeof(T)));
+}
+// issue_row_loads on the new rows: position j = t + 256 i - pad of both rows; a pad position (PADDED, j < 0) loads the new row's
+// first sample, which is also ka / kb.  The lane's index is made opaque per call: left visible, the sixteen selects and offsets are
+// loop-invariant, get hoisted out of the pair loop and are parked in scratch (as issue_row_loads found for its clamped offsets).
+template <bool PADDED, typename T>
+__device__ __forceinline__ void issue_row_loads_slide(RawPair &r, const T *rows, const FusedParams &p, long long pair, int t, int pad)
+{
+    const long long rA = 2 * pair;
+    const long long rB = (rA + 1 < p.M) ? rA + 1 : rA;
+    const int k = p.slide_k, keep = p.N - k;
+    const SlidRow a = slid_row(rows, p, rA, k, keep), b = slid_row(rows, p, rB, k, keep);
+    asm volatile("" : "+v"(t));
+    r.ka = (double)*slid_addr<T>(a, 0u, keep);
+    r.kb = (double)*slid_addr<T>(b, 0u, keep);
+#pragma unroll
+    for (int i = 0; i < 16; i++) {
+        int j = t + 256 * i - pad;
+        if (PADDED)
+            j = j < 0 ? 0 : j;
+        r.a[i] = (double)__builtin_nontemporal_load(slid_addr<T>(a, (unsigned)j, keep));
+        r.b[i] = (double)__builtin_nontemporal_load(slid_addr<T>(b, (unsigned)j, keep));
+    }
+}
+// a wave-uniform store base p + off, formed where it is used (scalar_ptr_at for a pointer that is written through)
+template <typename T>
+__device__ __forceinline__ gwptr<T> scalar_wptr_at(T *p, long long off)
+{
+    unsigned long long u = (unsigned long long)p;
+    asm volatile("" : "+s"(u));
+    u += (unsigned long long)(off * (long long)sizeof(T));
+    asm volatile("" : "+s"(u));
+    return (gwptr<T>)u;
+}
+// what issue_row_loads_slide loaded, back to positions 0 <= j < N of rows rA and (if the pair has one) rA + 1: one scalar base per
+// 256-sample slice + the lane's offset; a pad position (j < 0) is not stored
+template <bool PADDED, typename T>
+__device__ __forceinline__ void store_slid_rows(const RawPair &r, T *rows, const FusedParams &p, long long pair, int t, int pad)
+{
+    const long long rA = 2 * pair;
+    const bool hasB = rA + 1 < p.M;
+    asm volatile("" : "+v"(t));
+#pragma unroll
+    for (int i = 0; i < 16; i++) {
+        if (!PADDED || t + 256 * i - pad >= 0) {
+            __builtin_nontemporal_store((T)r.a[i], scalar_wptr_at(rows + rA * p.stride, 256 * i - pad) + (unsigned)t);
+            if (hasB)
+                __builtin_nontemporal_store((T)r.b[i], scalar_wptr_at(rows + (rA + 1) * p.stride, 256 * i - pad) + (unsigned)t);
+        }
+    }
+}
+// issue_row_loads_wide on the new rows (N == n == 4096, float64): the same two consecutive samples 256 (i' + 8 h) + 64 w + 2 m (+1)
+// into the same registers -- one 16-byte load where k is even (source and boundary are 16-byte aligned then), two 8-byte loads
+// otherwise (a wave-uniform branch) -- so that widen_rows() leaves the stand-alone kernel's columns in every lane
+__device__ __forceinline__ int wide_sample0(int t) { return ((t >> 5) & 1) * 2048 + (t >> 6) * 64 + (t & 31) * 2; }
+__device__ __forceinline__ void issue_row_loads_wide_slide(RawPair &r, const FusedParams &p, long long pair, int t)
+{
+    const long long rA = 2 * pair;
+    const long long rB = (rA + 1 < p.M) ? rA + 1 : rA;
+    const int k = p.slide_k, keep = 4096 - k;
+    const SlidRow a = slid_row(p.rows, p, rA, k, keep), b = slid_row(p.rows, p, rB, k, keep);
+    asm volatile("" : "+v"(t));
+    r.ka = *slid_addr<double>(a, 0u, keep);
+    r.kb = *slid_addr<double>(b, 0u, keep);
+    const unsigned j0 = (unsigned)wide_sample0(t);
+    if ((k & 1) == 0) {
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            const d2v xa = __builtin_nontemporal_load((gptr<d2v>)slid_addr<double>(a, j0 + 256 * i, keep));
+            const d2v xb = __builtin_nontemporal_load((gptr<d2v>)slid_addr<double>(b, j0 + 256 * i, keep));
+            r.a[i] = xa.x;
+            r.a[i + 8] = xa.y;
+            r.b[i] = xb.x;
+            r.b[i + 8] = xb.y;
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            r.a[i] = __builtin_nontemporal_load(slid_addr<double>(a, j0 + 256 * i, keep));
+            r.a[i + 8] = __builtin_nontemporal_load(slid_addr<double>(a, j0 + 256 * i + 1, keep));
+            r.b[i] = __builtin_nontemporal_load(slid_addr<double>(b, j0 + 256 * i, keep));
+            r.b[i + 8] = __builtin_nontemporal_load(slid_addr<double>(b, j0 + 256 * i + 1, keep));
+        }
+    }
+}
+// the raw pairs (before widen_rows) back to samples j0 + 256 i (+1): always one aligned 16-byte store
+__device__ __forceinline__ void store_slid_rows_wide(const RawPair &r, const FusedParams &p, long long pair, int t)
+{
+    const long long rA = 2 * pair;
+    const bool hasB = rA + 1 < p.M;
+    asm volatile("" : "+v"(t));
+    const unsigned u0 = (unsigned)wide_sample0(t) >> 1; // in 16-byte units
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        __builtin_nontemporal_store(d2v{r.a[i], r.a[i + 8]}, (gwptr<d2v>)scalar_wptr_at(const_cast<double *>(p.rows) + rA * p.stride, 256 * i) + u0);
+        if (hasB)
+            __builtin_nontemporal_store(d2v{r.b[i], r.b[i + 8]}, (gwptr<d2v>)scalar_wptr_at(const_cast<double *>(p.rows) + (rA + 1) * p.stride, 256 * i) + u0);
+    }
+}
+
 // shifted sums of one series: sum d, sum d^2  (d = x - x[0])
 struct Stat {
     double s1, s2;

@@ -84,6 +84,12 @@ struct FusedParams {
     // index i of cc takes part in maxAbsIndex iff i <= win_lpos || i >= n - win_lneg (WindowParams::L / ::Lneg); every other value
     // is replaced by +0.0 in front of the argmax.  Last in the structure: the offsets of everything above are what they were.
     int win, win_lpos, win_lneg;
+    // the slide fused into the n = 4096 pass (the SLIDE builds of xcorr_r16_fold.hip; muse_batch_slide_score_in_window): slide_tails != 0 ->
+    // the kernel scores the rows moved forward by 1 <= slide_k <= N samples -- old row[slide_k .. N) followed by slide_tails[r * slide_k + 0 .. slide_k),
+    // a dense M x slide_k device image in the group's storage type, 256-byte aligned -- and stores them in place on the way (rows and
+    // rows32 are written).  Behind everything else, for the same reason as the window.
+    const void *slide_tails;
+    int slide_k;
 };
 inline FusedParams with_reciprocals(FusedParams p)
 {

@@ -33,7 +33,26 @@ namespace muse {
 // F32: float32-storage group (half the HBM bytes; samples widened exactly on consumption, same float64 arithmetic)
 // WIN: masked argmax (muse_batch_score_in_window): the values outside the lag window p.win_lpos / p.win_lneg are replaced by +0.0
 // right in front of the argmax (behind the PADDED correction); everything else is the kernel as it is
-template <bool TIMING = false, bool PADDED = false, bool F32 = false, bool WIN = false>
+// SLIDE: the slide of the group's rows fused into the pass (muse_batch_slide_score_in_window): the loaders read the NEW row -- old
+// row[slide_k .. N) followed by the row's tail samples (p.slide_tails), on the lane-to-column mapping of the stand-alone build, so the
+// scores are its bits -- and every thread stores the raw values it loaded back to the same positions of the row: one read and one
+// write of the rows where launch_row_slide and this kernel move them three times.  Everything behind the loads is the kernel as it
+// is.  A shift inside a row overlaps its own source; the rules that keep it free of races (as row_slide.hip and
+// xcorr_window_slide.hip state theirs):
+//   1. A pair's rows are touched by ONE workgroup, ONCE: the pair hand-out gives every pair to exactly one workgroup.
+//   2. Every load of a pair by every thread of the workgroup has RETURNED before any store to that pair: an explicit
+//      s_waitcnt vmcnt(0) lgkmcnt(0) (not the per-register waits in front of a store's operand; a row's first sample may come through
+//      the scalar cache), then a workgroup barrier, then the stores.
+//   3. That barrier is an extra one, in front of d = x - K: the raw pair is consumed there (128 registers: it cannot live on to one
+//      of the transposes' barriers).
+//   4. The prefetch of the next pair reads another pair's rows and tails: nothing to order.
+//   5. The last iteration's dummy prefetch of pair 0 is only loaded: the stores sit at the head of an iteration, which a
+//      workgroup enters for a pair it has claimed (pair < npairs) and for nothing else.
+//   6. With M odd the last pair's row B is a clamped copy of row A: loaded, never stored (hasB).
+//   7. Stores go to samples 0 <= j < N of rows r < M only: a pad position (PADDED, j < 0) is loaded from the row's first sample and
+//      never stored; the guard in front of row 0 and the rows behind the last one are never written.
+//   8. The rescaling launch over ovf_list runs behind this kernel on the stream and reads the slid rows, as it is.
+template <bool TIMING = false, bool PADDED = false, bool F32 = false, bool WIN = false, bool SLIDE = false>
 __global__ __launch_bounds__(OCC_THREADS, 4) void xcorr_fused_n4096_fold(const FusedParams p)
 {
     using namespace occ4;
@@ -75,7 +94,13 @@ __global__ __launch_bounds__(OCC_THREADS, 4) void xcorr_fused_n4096_fold(const F
     // N == n float64 rows: 16-byte requests on relabelled columns (r16_device.h, issue_row_loads_wide): -1.6 % (profiles/r03_fold_variants.txt)
     constexpr bool WIDE = !PADDED && !F32;
     const auto request_rows = [&](long long pr) __attribute__((always_inline)) {
-        if (WIDE)
+        if (SLIDE && WIDE)
+            issue_row_loads_wide_slide(raw, p, pr, t);
+        else if (SLIDE && F32)
+            issue_row_loads_slide<PADDED>(raw, p.rows32, p, pr, t, pad);
+        else if (SLIDE)
+            issue_row_loads_slide<PADDED>(raw, p.rows, p, pr, t, pad);
+        else if (WIDE)
             issue_row_loads_wide(raw, p, pr, t);
         else
             issue_row_loads<PADDED, F32>(raw, p, pr, t, pad);
@@ -90,6 +115,17 @@ __global__ __launch_bounds__(OCC_THREADS, 4) void xcorr_fused_n4096_fold(const F
         const double *const prec = red + REC * (parity ^ 1);
         if (t == 0) // the pair after this one: claimed now, read behind this pair's barriers
             next_s[parity] = (int)gridDim.x + atomicAdd(p.work_counter, 1);
+        if (SLIDE) { // rules 2 and 3: every load of this pair has returned in every wave, then the new rows go back in place
+            fence();
+            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+            fence();
+            if (WIDE)
+                store_slid_rows_wide(raw, p, pair, t);
+            else if (F32)
+                store_slid_rows<PADDED>(raw, const_cast<float *>(p.rows32), p, pair, t, pad);
+            else
+                store_slid_rows<PADDED>(raw, const_cast<double *>(p.rows), p, pair, t, pad);
+        }
         // ---- consume the prefetched rows: d = x - K (K = the row's first sample) bounds the cancellation in
         // sum d^2 - (sum d)^2 / N and keeps a large level out of the transform's rounding; sum d is read off the DC bin
         double2 v[16];
@@ -634,9 +670,28 @@ hipError_t launch_fused_fold(const FusedParams &p_in, int num_cus, hipStream_t s
     if (p.N < 4096 && !p.c1) // leading zero pad: needs the batch's correction table
         return hipErrorInvalidValue;
     const dim3 g((unsigned)grid), b(OCC_THREADS);
-    if (p.win) { // the masked argmax (muse_batch_score_in_window)
-        if (p.win_lpos < 0 || p.win_lneg < 0 || p.win_lpos > 2048 || p.win_lneg > p.win_lpos)
+    if (p.win && (p.win_lpos < 0 || p.win_lneg < 0 || p.win_lpos > 2048 || p.win_lneg > p.win_lpos))
+        return hipErrorInvalidValue;
+    if (p.slide_tails) { // the slide fused into the pass (muse_batch_slide_score_in_window): the rows are rewritten in place
+        // every pair is claimed once (pair_list / dense_total belong to the rescaling kernel); the rows are dense float64 pairs of
+        // 16-byte aligned rows where the kernel moves them in 16-byte units
+        if (p.slide_k < 1 || p.slide_k > p.N || p.N <= 2048 || p.N > 4096 || p.stride < p.N || p.pair_list || p.npairs != (p.M + 1) / 2 ||
+            (p.N == 4096 && !p.rows32 && !window_wide(p.rows, p.stride)))
             return hipErrorInvalidValue;
+        const int inst = (p.N < 4096 ? 4 : 0) | (p.rows32 ? 2 : 0) | (p.win ? 1 : 0);
+        switch (inst) {
+        case 0: hipLaunchKernelGGL((xcorr_fused_n4096_fold<false, false, false, false, true>), g, b, 0, stream, p); break;
+        case 1: hipLaunchKernelGGL((xcorr_fused_n4096_fold<false, false, false, true, true>), g, b, 0, stream, p); break;
+        case 2: hipLaunchKernelGGL((xcorr_fused_n4096_fold<false, false, true, false, true>), g, b, 0, stream, p); break;
+        case 3: hipLaunchKernelGGL((xcorr_fused_n4096_fold<false, false, true, true, true>), g, b, 0, stream, p); break;
+        case 4: hipLaunchKernelGGL((xcorr_fused_n4096_fold<false, true, false, false, true>), g, b, 0, stream, p); break;
+        case 5: hipLaunchKernelGGL((xcorr_fused_n4096_fold<false, true, false, true, true>), g, b, 0, stream, p); break;
+        case 6: hipLaunchKernelGGL((xcorr_fused_n4096_fold<false, true, true, false, true>), g, b, 0, stream, p); break;
+        default: hipLaunchKernelGGL((xcorr_fused_n4096_fold<false, true, true, true, true>), g, b, 0, stream, p); break;
+        }
+        return hipGetLastError();
+    }
+    if (p.win) { // the masked argmax (muse_batch_score_in_window)
         if (p.rows32) {
             if (p.N < 4096)
                 hipLaunchKernelGGL((xcorr_fused_n4096_fold<false, true, true, true>), g, b, 0, stream, p);

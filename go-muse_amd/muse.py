@@ -124,6 +124,11 @@ class Engine:
         """test hook: the windowed Muse.Run scores in S slices (0 = the planner, 1 = the unsplit kernel; muse_test_window_rows_slices)"""
         B.check(B.load().muse_test_window_rows_slices(self._h, int(S)))
 
+    def slide_in_window_force(self, mode):
+        """test hook: 1 = slide_score_in_window takes two steps (the row slide, then the pass) wherever the table says FUSED; 0 = the
+        table (muse_test_slide_in_window_force)"""
+        B.check(B.load().muse_test_slide_in_window_force(self._h, int(mode)))
+
     def in_window_force_transform(self, on):
         """test hook: score_in_window sends float64 windows up to MUSE_LAG_WINDOW_MAX through the masked transform kernels too
         (muse_test_in_window_force_transform)"""
@@ -661,6 +666,53 @@ class DeviceBatch:
         c = cnt.value
         return o_s[:c].copy(), o_l[:c].copy(), o_v[:c].copy(), float(mean.value)
 
+    # ---- the same for a window of any width and both storage types (row level only, as slide_score_windowed: DESIGN 8.10)
+    def slide_score_in_window(self, tails, max_lag):
+        """muse_batch_slide_score_in_window: DeviceGroup.slide(tails) over the WHOLE group and score_in_window(max_lag) over the new
+        rows in one call -- the same rows and the same scores (read_scores), bit for bit; tails: (M, k).  At FFT length 4096 the rows
+        cross HBM twice instead of three times (the default kernel writes them back while it scores them).  max_lag >= n/2 is the
+        unwindowed pass.  Waits for the device and returns when the kernels have finished."""
+        tails, k, stride, moved = self._tails2d(tails)
+        B.check(B.load().muse_batch_slide_score_in_window(self._h, tails.ctypes.data_as(B._dp), k, stride, int(max_lag)))
+        if moved:
+            self.dgroup.slides += 1
+
+    def _slide_run(self, fn, tails, max_lag, group_id, G, top_n, threshold, sign_filter, abs_scores):
+        tails, k, stride, moved = self._tails2d(tails)
+        cap = max(int(top_n), 1)
+        o_s = np.zeros(cap, dtype=np.int64)
+        o_l = np.zeros(cap, dtype=np.int32)
+        o_v = np.zeros(cap)
+        cnt, mean = ctypes.c_int32(0), ctypes.c_double(0)
+        gid = None
+        if group_id is not None:
+            gid = np.ascontiguousarray(group_id, dtype=np.int32)
+        B.check(getattr(B.load(), fn)(
+            self._h, tails.ctypes.data_as(B._dp), k, stride, B.i32ptr(gid) if gid is not None else None, int(G), int(max_lag),
+            int(top_n), float(threshold), int(sign_filter), 1 if abs_scores else 0,
+            B.i64ptr(o_s), B.i32ptr(o_l), B.dptr(o_v), ctypes.byref(cnt), ctypes.byref(mean)))
+        if moved:
+            self.dgroup.slides += 1
+        c = cnt.value
+        return o_s[:c].copy(), o_l[:c].copy(), o_v[:c].copy(), float(mean.value)
+
+    def slide_run_in_window(self, tails, max_lag, group_id=None, G=0, top_n=20, threshold=0.0, sign_filter=0, abs_scores=True):
+        """muse_batch_slide_run_in_window: slide_score_in_window followed by Batch.Run's selection (max_lag is the window and the
+        Results.MaxLag); -> (series, lag, score, mean_abs) as run()"""
+        return self._slide_run("muse_batch_slide_run_in_window", tails, max_lag, group_id, G, top_n, threshold, sign_filter, abs_scores)
+
+    def slide_run(self, tails, group_id=None, G=0, max_lag=10, top_n=20, threshold=0.0, sign_filter=0, abs_scores=True):
+        """muse_batch_slide_run: the reference's Run on the slid rows -- DeviceGroup.slide(tails) + run(...): the unwindowed pass, then
+        the selection with Results.MaxLag = max_lag; -> (series, lag, score, mean_abs) as run()"""
+        return self._slide_run("muse_batch_slide_run", tails, max_lag, group_id, G, top_n, threshold, sign_filter, abs_scores)
+
+    def last_slide_path(self):
+        """test hook: MUSE_SLIDE_IN_WINDOW_* of the last slide_score_in_window / slide_run_in_window / slide_run that moved rows, 0
+        after any other scoring pass"""
+        w = ctypes.c_int32(0)
+        B.check(B.load().muse_test_last_slide_path(self._h, ctypes.byref(w)))
+        return int(w.value)
+
     def run_groups(self, group_id, G, series_offset=0, abs_scores=True):
         """this shard's winner per label group, unfiltered (muse_batch_run_groups): (records[G], state[G])"""
         rec = np.zeros(max(int(G), 1), dtype=B.RECORD_DTYPE)
@@ -796,6 +848,14 @@ def in_window_plan(N, f32, max_lag):
     (f32: float32 storage) and window max_lag"""
     path = ctypes.c_int32(-1)
     B.check(B.load().muse_test_in_window_plan(int(N), 1 if f32 else 0, int(max_lag), ctypes.byref(path)))
+    return int(path.value)
+
+
+def slide_in_window_plan(N, f32, max_lag, k):
+    """muse_test_slide_in_window_plan (no device): MUSE_SLIDE_IN_WINDOW_* -- how slide_score_in_window moves and scores series of N
+    samples (f32: float32 storage) slid by k inside +-max_lag"""
+    path = ctypes.c_int32(-1)
+    B.check(B.load().muse_test_slide_in_window_plan(int(N), 1 if f32 else 0, int(max_lag), int(k), ctypes.byref(path)))
     return int(path.value)
 
 

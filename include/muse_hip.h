@@ -375,6 +375,39 @@ int muse_batch_score_in_window(muse_batch *b, int32_t max_lag);
 int muse_batch_run_in_window(muse_batch *b, const int32_t *group_id, int32_t G, int32_t max_lag, int32_t top_n,
                              double threshold, int32_t sign_filter, int32_t abs_scores, int64_t *out_series,
                              int32_t *out_lag, double *out_score, int32_t *out_count, double *out_mean_abs);
+/* THE SLIDE AND THE PASS OF ANY WINDOW IN ONE CALL.  muse_batch_slide_score_in_window is equivalent to
+ *   muse_group_slide(the batch's group, 0, M, tails, k, tail_stride)  followed by  muse_batch_score_in_window(b, max_lag):
+ * afterwards the group holds the slid rows -- BIT FOR BIT those of muse_group_slide -- and muse_batch_read_scores returns, BIT FOR
+ * BIT, what muse_batch_score_in_window(max_lag) gives over them; max_lag >= n/2 is the unwindowed pass (the reference's own scoring).
+ * Any window width and both storage types.  How the rows move is decided from the length, the storage and the window:
+ *   float64 group, L <= MUSE_LAG_WINDOW_MAX, up to 65536 samples     : muse_batch_slide_score_windowed's kernel (one read, one write)
+ *   FFT length 4096 (2048 < N <= 4096), any other window or storage  : the default transform kernel reads the new rows -- old row[k..N)
+ *                                                                      and the tails -- and writes them back in place while it scores
+ *                                                                      them: one read and one write of the rows instead of a read and
+ *                                                                      a write for the slide and a read for the pass
+ *   every other length both calls support                            : muse_group_slide's kernel and then the pass, inside the one
+ *                                                                      call (one upload of the tails, one wait for the device)
+ * Everything muse_group_slide says about ordering (the call waits until the device is idle and returns after its kernels have
+ * finished), about `tails` and about what goes with the old rows holds here; the whole group always slides.  The pass is exact fp64
+ * (muse_batch_last_run_path: MUSE_RUN_PATH_FP64) and always reads the rows: the group's spectrum cache is neither used, built nor
+ * counted towards.  k == 0 or M == 0 is not an error: nothing moves and nothing is invalidated (with M > 0 the call is
+ * muse_batch_score_in_window alone).  Refused with the codes of muse_batch_slide_score_windowed's slide arguments and of
+ * muse_batch_score_in_window, every handle, the rows and the scores of the last pass left as they were (everything is checked before
+ * anything is enqueued).
+ * muse_batch_slide_run_in_window is that call followed by Batch.Run's selection over the scores, outputs as muse_batch_run; max_lag
+ * is both the window and the Results.MaxLag.  muse_batch_slide_run is the reference's Run on the slid rows: the unwindowed pass (the
+ * scoring of max_lag = n/2 above; the batch's own lag window must be off), then the selection with Results.MaxLag = max_lag -- the
+ * records of muse_group_slide + muse_batch_run with screening off.  In both, a sign_filter outside -1 .. 1 or a negative G with
+ * group_id is refused before anything moves. */
+int muse_batch_slide_score_in_window(muse_batch *b, const double *tails, int32_t k, int64_t tail_stride, int32_t max_lag);
+int muse_batch_slide_run_in_window(muse_batch *b, const double *tails, int32_t k, int64_t tail_stride,
+                                   const int32_t *group_id, int32_t G, int32_t max_lag, int32_t top_n, double threshold,
+                                   int32_t sign_filter, int32_t abs_scores, int64_t *out_series, int32_t *out_lag,
+                                   double *out_score, int32_t *out_count, double *out_mean_abs);
+int muse_batch_slide_run(muse_batch *b, const double *tails, int32_t k, int64_t tail_stride,
+                         const int32_t *group_id, int32_t G, int32_t max_lag, int32_t top_n, double threshold,
+                         int32_t sign_filter, int32_t abs_scores, int64_t *out_series, int32_t *out_lag,
+                         double *out_score, int32_t *out_count, double *out_mean_abs);
 /* muse_batch_score + D2H of the per-series results (lag[M], mv[M]). */
 int muse_batch_scores(muse_batch *b, int32_t *lag, double *mv);
 /* Batch.Run + Results.Update + Results.Fetch (muse_batch.go:99-130,

@@ -137,6 +137,26 @@ int muse_test_last_in_window_path(muse_batch *b, int32_t *path);
  * table) turns _MASKED into _MASKED_EACH when the call runs.  MUSE_ERR_INVALID for N < 2, max_lag < 0, R < 1 or a NULL out pointer. */
 #define MUSE_IN_WINDOW_MASKED_EACH 4
 int muse_test_many_in_window_plan(int32_t N, int32_t f32_storage, int32_t max_lag, int32_t R, int32_t *path);
+/* muse_batch_slide_score_in_window's dispatch, a pure host function (no device needed): how a group of series of N >= 2 samples
+ * (f32_storage: a float32-storage group) is slid by 0 <= k <= N samples and scored inside +-max_lag >= 0 --
+ *   _UNSUPPORTED : muse_test_in_window_plan says so (the call returns MUSE_ERR_UNSUPPORTED, nothing moves)
+ *   _MFMA        : muse_test_in_window_plan says _MFMA: muse_batch_slide_score_windowed's kernel
+ *   _FUSED       : the plain or masked transform pass at FFT length 4096 (2048 < N <= 4096): the SLIDE build of the default kernel
+ *                  moves the rows while it scores them.  What only the handles know -- a forced kernel variant, a missing correction
+ *                  table, a learned hand-off to the rescaling kernel -- turns it into _TWO_STEP when the call runs.
+ *   _TWO_STEP    : everything else both calls support: muse_group_slide's kernel, then the pass, inside the one call
+ * (k = 0 moves nothing whatever the path).  MUSE_ERR_INVALID for N < 2, max_lag < 0, k outside 0 .. N or a NULL out pointer. */
+#define MUSE_SLIDE_IN_WINDOW_UNSUPPORTED 0
+#define MUSE_SLIDE_IN_WINDOW_MFMA 1
+#define MUSE_SLIDE_IN_WINDOW_FUSED 2
+#define MUSE_SLIDE_IN_WINDOW_TWO_STEP 3
+int muse_test_slide_in_window_plan(int32_t N, int32_t f32_storage, int32_t max_lag, int32_t k, int32_t *path);
+/* mode = 1: muse_batch_slide_score_in_window takes _TWO_STEP wherever the table says _FUSED (the parent's kernels: cross-checks and
+ * tools/slide_in_window_bench.py); 0 (default): the table.  Anything else: MUSE_ERR_INVALID. */
+int muse_test_slide_in_window_force(muse_ctx *ctx, int32_t mode);
+/* The path (MUSE_SLIDE_IN_WINDOW_*) the batch's last scoring pass took if it was a muse_batch_slide_score_in_window / _slide_run_in_window /
+ * _slide_run that moved rows; 0 after any other scoring pass (k = 0 included). */
+int muse_test_last_slide_path(muse_batch *b, int32_t *path);
 
 #ifdef __cplusplus
 }
