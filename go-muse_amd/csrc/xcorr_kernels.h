@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "muse_hip.h"
 
@@ -96,6 +97,26 @@ inline FusedParams with_reciprocals(FusedParams p)
     p.invN = 1.0 / (double)p.N;
     p.invNm1 = 1.0 / (double)(p.N - 1);
     return p;
+}
+// the masked argmax's window as the n = 4096 launchers accept it (no window: nothing to check)
+inline bool window_bounds_ok(const FusedParams &p)
+{
+    return !p.win || (p.win_lpos >= 0 && p.win_lneg >= 0 && p.win_lpos <= 2048 && p.win_lneg <= p.win_lpos);
+}
+// run-time booleans -> template arguments: with_bools(f, b0, b1, ...) calls f(std::bool_constant<b0>{}, std::bool_constant<b1>{}, ...),
+// so a launcher names its kernel once, with decltype(flag)::value for each flag, and every combination is instantiated
+template <typename F>
+inline void with_bools(F f)
+{
+    f();
+}
+template <typename F, typename... Rest>
+inline void with_bools(F f, bool b, Rest... rest)
+{
+    if (b)
+        with_bools([&](auto... flags) { f(std::true_type{}, flags...); }, rest...);
+    else
+        with_bools([&](auto... flags) { f(std::false_type{}, flags...); }, rest...);
 }
 
 hipError_t launch_fused(const FusedParams &p, int variant, int num_cus, hipStream_t stream);

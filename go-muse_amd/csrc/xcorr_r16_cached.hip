@@ -25,193 +25,38 @@
 #include <stdint.h>
 #include <algorithm>
 
-#include "foldk_device.h"
+#include "n4096_pair_device.h"
 
 namespace muse {
 
-namespace foldk {
-
-#if defined(__HIP_DEVICE_COMPILE__)
-typedef d2v __attribute__((address_space(1))) *zc_out_ptr;
-typedef double __attribute__((address_space(1))) *zstat_out_ptr;
-typedef const double __attribute__((address_space(4))) *zstat_in_ptr;
-#endif
-
-// the previous pair's results from its complete record: lane 0 of waves 0 / 1 writes one series each
-__device__ __forceinline__ void finalize_prev(const double *prec, const int wave, const int lane, const double invN,
-                                              const double invNm1, const FusedParams &p)
-{
-    if (lane == 0 && wave < 2 && prec[34] >= 0.0 && (wave == 0 || prec[35] != 0.0)) {
-        const long long row = (long long)prec[34] + wave;
-        if (finalize(prec, wave, invN, invNm1, p.mv + row, p.lag + row)) {
-            const int slot = atomicAdd(p.ovf_count, 1);
-            p.ovf_list[slot] = row >> 1;
-        }
-    }
-}
-
-} // namespace foldk
-
 // ---------------------------------------------------------------------------------------------------------------- writer
+// The cache: what the reader starts from, stored right behind the first transform (the sums of squares of this pair's record are
+// visible behind the barriers of the transpose in front and stay until the pair after the next one begins, many barriers away)
+struct CacheTap {
+    const SpectrumCacheArgs c;
+    const long long first;
+    __device__ __forceinline__ void operator()(const double2 (&v)[16], const double *rec, const double s1a, const double s1b,
+                                               const long long rel, const int t) const
+    {
+#if defined(__HIP_DEVICE_COMPILE__)
+        if (rel < c.zpairs) {
+            const foldk::zc_out_ptr zo = (foldk::zc_out_ptr)(unsigned long long)(c.zc + rel * 4096) + t;
+#pragma unroll
+            for (int i = 0; i < 16; i++)
+                __builtin_nontemporal_store(occ4::d2v{v[i].x, v[i].y}, zo + 256 * i);
+            if (t < 10) {
+                const foldk::zstat_out_ptr so = (foldk::zstat_out_ptr)(unsigned long long)(c.zstat + rel * ZC_STAT);
+                so[t] = t < 8 ? rec[24 + t] : (t == 8 ? s1a : s1b);
+            }
+        }
+#endif
+    }
+};
+
 template <bool PADDED>
 __global__ __launch_bounds__(OCC_THREADS, 4) void xcorr_cache_fill_n4096(const FusedParams p, const SpectrumCacheArgs c)
 {
-    using namespace occ4;
-    using namespace fold;
-    using namespace foldk;
-    __shared__ double2 xbuf[OCC_XBUF];
-    __shared__ double2 g2s[128];
-    __shared__ double red[2 * REC];
-    __shared__ int next_s[2];
-    const int t = threadIdx.x;
-    const int lane = t & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
-    double2 *const xw = xbuf + XW * wave;
-    const int pad = PADDED ? 4096 - p.N : 0;
-    const double invN = PADDED ? p.invN : 1.0 / 4096.0, invNm1 = PADDED ? p.invNm1 : 1.0 / 4095.0;
-
-    if (t < 128)
-        g2s[t] = p.g2[t];
-    if (t < 2)
-        red[REC * (t) + 34] = -1.0; // no previous pair yet (either parity)
-    __syncthreads();
-    const auto tl = [&]() __attribute__((always_inline)) { // (see xcorr_fused_n4096_fold)
-        int x = t;
-        if (PADDED)
-            asm volatile("" : "+v"(x));
-        return x;
-    };
-
-    int parity = 0;
-    const long long first = c.pair0, total = c.pair0 + p.npairs;
-    RawPair raw;
-    constexpr bool WIDE = !PADDED;
-    const auto request_rows = [&](long long pr) __attribute__((always_inline)) {
-        if (WIDE)
-            issue_row_loads_wide(raw, p, pr, t);
-        else
-            issue_row_loads<PADDED, false>(raw, p, pr, t, pad);
-    };
-    request_rows(first + blockIdx.x < total ? first + (long long)blockIdx.x : first);
-
-    long long nextpair = 0;
-    for (long long pair = first + blockIdx.x; pair < total; pair = nextpair) {
-        const long long rA = 2 * pair;
-        const bool hasB = rA + 1 < p.M;
-        double *const rec = red + REC * parity;
-        const double *const prec = red + REC * (parity ^ 1);
-        if (t == 0) // the pair after this one (relative to pair0): claimed now, read behind this pair's barriers
-            next_s[parity] = (int)gridDim.x + atomicAdd(p.work_counter, 1);
-        double2 v[16];
-        {
-            const double KA = raw.ka, KB = raw.kb;
-            double qa = 0.0, qb = 0.0;
-            if (WIDE)
-                widen_rows(raw);
-#pragma unroll
-            for (int i = 0; i < 16; i++) {
-                const double da = raw.a[i] - KA, db = raw.b[i] - KB;
-                v[i] = make_double2(da, db);
-                qa = fma(da, da, qa);
-                qb = fma(db, db, qb);
-            }
-            qa = wave_sum_dpp(qa);
-            qb = wave_sum_dpp(qb);
-            if (lane == 0) {
-                rec[24 + 2 * wave] = qa;
-                rec[24 + 2 * wave + 1] = qb;
-            }
-            if (t == 0) {
-                rec[34] = (double)rA;
-                rec[35] = hasB ? 1.0 : 0.0;
-            }
-        }
-        // ================= Z = FFT(dA + i dB) =================
-        dft16_nr(v);
-        exchange_cross<0, 1, true>(v, xbuf, wave, t, WIDE ? wide_column(t) : -1);
-        finalize_prev(prec, wave, lane, invN, invNm1, p);
-        gdft16_nr(v, G2Fetch{g2s, t >> 4});
-        exchange_local<1>(v, xw, tl());
-        gdft16_nr_l2(v, G3Derived(p.g3a, t));
-        double s1a, s1b;
-        {
-            s1a = readlane_f64(v[0].x, 0);
-            s1b = readlane_f64(v[0].y, 0);
-            if (!PADDED) {
-                v[0].x = (t == 0) ? 0.0 : v[0].x;
-                v[0].y = (t == 0) ? 0.0 : v[0].y;
-            }
-        }
-        // ---- the cache: what the reader starts from (the sums of squares of this pair's record are visible behind the
-        // barriers of the transpose above and stay until the pair after the next one begins, many barriers away)
-        if (pair - first < c.zpairs) {
-#if defined(__HIP_DEVICE_COMPILE__)
-            const zc_out_ptr zo = (zc_out_ptr)(unsigned long long)(c.zc + (pair - first) * 4096) + t;
-#pragma unroll
-            for (int i = 0; i < 16; i++)
-                __builtin_nontemporal_store(d2v{v[i].x, v[i].y}, zo + 256 * i);
-            if (t < 10) {
-                const zstat_out_ptr so = (zstat_out_ptr)(unsigned long long)(c.zstat + (pair - first) * ZC_STAT);
-                so[t] = t < 8 ? rec[24 + t] : (t == 8 ? s1a : s1b);
-            }
-#endif
-        }
-        // ================= ccA + i ccB = FFT(Z conj(X)/n) (unscaled by 1/sigma) =================
-        xc_stage1(v, [&](int j) __attribute__((always_inline)) {
-            return ldg2(scalar_ptr_at(p.xcp, 256 * ((j + 1) & ~1)), t - 256 * (j & 1));
-        });
-        dft16_rn_s234(v);
-        exchange_local<0>(v, xw, tl());
-        if (PADDED && wave == 0 && lane == 0) {
-            rec[32] = s1a;
-            rec[33] = s1b;
-        }
-        gdft16_nr(v, G2Fetch{g2s, t & 15});
-        exchange_cross<1, 1>(v, xbuf, wave, t);
-        nextpair = first + __builtin_amdgcn_readfirstlane(next_s[parity]);
-        long long nxt = nextpair;
-        nxt = nxt < total ? nxt : first; // last iteration: a dummy request
-        gdft16_nr_l2(v, G3Derived(p.g3b, t));
-        if (PADDED) { // cc(d - m 1_valid) = cc(d) - m c1, m = sum d / N
-            const auto c1l = [&](int k) __attribute__((always_inline)) {
-                return scalar_ptr_at(p.c1, 256 * ((k + 1) & ~1))[t - 256 * (k & 1)];
-            };
-            const double mA = rec[32] * invN, mB = rec[33] * invN;
-#pragma unroll
-            for (int h = 0; h < 2; h++) {
-                double cq[8];
-#pragma unroll
-                for (int k = 0; k < 8; k++)
-                    cq[k] = c1l(8 * h + k);
-                fence();
-#pragma unroll
-                for (int k = 0; k < 8; k++) {
-                    const int r = BR16(8 * h + k);
-                    v[r] = make_double2(fma(-mA, cq[k], v[r].x), fma(-mB, cq[k], v[r].y));
-                }
-            }
-        }
-        wave_argmax_store(v, wave, lane, rec + 6 * wave);
-        fence();
-        request_rows(nxt);
-        fence();
-        if (wave == 0 && lane == 0) {
-            rec[32] = s1a;
-            rec[33] = s1b;
-        }
-        parity ^= 1;
-    }
-    lds_barrier();
-    {
-        const double *const prec = red + REC * (parity ^ 1);
-        if (t < 2 && prec[34] >= 0.0 && (t == 0 || prec[35] != 0.0)) {
-            const long long row = (long long)prec[34] + t;
-            if (finalize(prec, t, invN, invNm1, p.mv + row, p.lag + row)) {
-                const int slot = atomicAdd(p.ovf_count, 1);
-                p.ovf_list[slot] = row >> 1;
-            }
-        }
-    }
+    foldk::pair_loop_from_rows<false, PADDED, false, false, false>(p, CacheTap{c, c.pair0});
 }
 
 // ---------------------------------------------------------------------------------------------------------------- reader
@@ -255,35 +100,25 @@ __global__ __launch_bounds__(OCC_THREADS, 2) void xcorr_cached_n4096(const Fused
     __shared__ double2 g2s[128];
     __shared__ double red[2 * REC];
     __shared__ int next_s[2];
-    const int t = threadIdx.x;
-    const int lane = t & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    const PairThread th = pair_prologue<PADDED>(p, g2s, red + 34, REC);
+    const int t = th.t, lane = th.lane, wave = th.wave;
+    const double invN = th.invN, invNm1 = th.invNm1;
     double2 *const xw = xbuf + 1088 * wave;
-    const double invN = PADDED ? p.invN : 1.0 / 4096.0, invNm1 = PADDED ? p.invNm1 : 1.0 / 4095.0;
     const long long first = c.pair0, total = c.pair0 + p.npairs;
     // N < 4096 has the -m c1 correction's registers on top and would spill with the request at the top of the pair: it requests
     // behind pass 3 and the correction's loads, in front of the argmax
     constexpr bool AHEAD = !PADDED;
     constexpr int ch = ZC_CLAIM;
 
-    if (t < 128)
-        g2s[t] = p.g2[t];
-    if (t < 2)
-        red[REC * (t) + 34] = -1.0; // no previous pair yet (either parity)
     if (t == 0) // the workgroup's second chunk (the loop claims two chunks ahead); slot 1: the first chunk writes slot 0
         next_s[1] = (int)gridDim.x + atomicAdd(p.work_counter, 1);
     d2v zn[16]; // the next pair's spectrum, in flight
-    const auto request_z = [&](long long pr) __attribute__((always_inline)) { // (addresses: see the four-workgroup reader below)
-#pragma unroll
-        for (int i = 0; i < 16; i++)
-            zn[i] = __builtin_nontemporal_load((gptr<d2v>)scalar_ptr_at(c.zc, (pr - first) * 4096 + 256 * ((i + 1) & ~1)) + (t - 256 * (i & 1)));
-    };
-    request_z(first + (long long)ch * blockIdx.x); // (the grid has at most ceil(npairs / ch) workgroups)
+    request_z(zn, c, first + (long long)ch * blockIdx.x, t); // (the grid has at most ceil(npairs / ch) workgroups)
     // launch-invariant: the reference's factors of this thread (xc for k3 = j) and pass 3's table entries of planes 2 and 4
     double2 xf[16];
 #pragma unroll
     for (int j = 0; j < 16; j++)
-        xf[j] = ldg2(scalar_ptr_at(p.xcp, 256 * ((j + 1) & ~1)), t - 256 * (j & 1));
+        xf[j] = XcFetch{p.xcp, t}(j);
     G3Lazy g3{G3Fetch{p.g3b, t}(2), G3Fetch{p.g3b, t}(4)};
     __syncthreads();
 
@@ -298,16 +133,8 @@ __global__ __launch_bounds__(OCC_THREADS, 2) void xcorr_cached_n4096(const Fused
         const bool hasB = rA + 1 < p.M;
         double *const rec = red + REC * parity;
         const double *const prec = red + REC * (parity ^ 1);
-        // the pair's statistics (a wave-uniform address: the scalar cache), used behind the workgroup transpose below
-        double st[10];
-#if defined(__HIP_DEVICE_COMPILE__)
-        {
-            const zstat_in_ptr sp = (zstat_in_ptr)(unsigned long long)(c.zstat + (pair - first) * ZC_STAT);
-#pragma unroll
-            for (int k = 0; k < 10; k++)
-                st[k] = sp[k];
-        }
-#endif
+        double st[10]; // the pair's statistics, used behind the workgroup transpose below
+        load_pair_stats(st, c.zstat, pair - first);
         // ================= ccA + i ccB = FFT(Z conj(X)/n) (unscaled by 1/sigma) =================
         double2 v[16];
 #pragma unroll
@@ -334,7 +161,7 @@ __global__ __launch_bounds__(OCC_THREADS, 2) void xcorr_cached_n4096(const Fused
         const long long nxt = nextpair < total ? nextpair : first; // past the end: a dummy request
         if (AHEAD) {
             fence();
-            request_z(nxt);
+            request_z(zn, c, nxt, t);
             fence();
         }
         // (the compiler would otherwise derive all eight of pass 3's factors once, in front of the loop: 32 registers, spills)
@@ -348,38 +175,18 @@ __global__ __launch_bounds__(OCC_THREADS, 2) void xcorr_cached_n4096(const Fused
         lds_barrier(); // the reads are done: the next pair's wave-local transpose writes without a barrier of its own
         // behind the barriers: the previous pair's record is complete and visible, and nobody reads this parity's record any more
         // (its last reader was the finalize of the pair before the previous one, in front of these barriers)
-        finalize_prev(prec, wave, lane, invN, invNm1, p);
-        if (t == 0) {
-#pragma unroll
-            for (int k = 0; k < 10; k++)
-                rec[24 + k] = st[k];
-            rec[34] = (double)rA;
-            rec[35] = hasB ? 1.0 : 0.0;
-        }
+        finalize_pair(prec, wave, lane == 0, invN, invNm1, p);
+        publish_pair_stats(rec, st, t, rA, hasB);
         if (claiming) {
             after = first + (long long)ch * __builtin_amdgcn_readfirstlane(next_s[cpar]);
             cpar ^= 1;
         }
         gdft16_nr_l2(v, g3);
-        if (PADDED) { // cc(d - m 1_valid) = cc(d) - m c1, m = sum d / N
-            const auto c1l = [&](int k) __attribute__((always_inline)) {
-                return scalar_ptr_at(p.c1, 256 * ((k + 1) & ~1))[t - 256 * (k & 1)];
-            };
-            const double mA = st[8] * invN, mB = st[9] * invN;
-            // all sixteen c1 values in front of the request: loads return in order, one behind it would wait for the spectrum
-            double cq[16];
-#pragma unroll
-            for (int k = 0; k < 16; k++)
-                cq[k] = c1l(k);
-            fence();
-            request_z(nxt);
-            fence();
-#pragma unroll
-            for (int k = 0; k < 16; k++) {
-                const int r = BR16(k);
-                v[r] = make_double2(fma(-mA, cq[k], v[r].x), fma(-mB, cq[k], v[r].y));
-            }
-        }
+        if (PADDED) // all sixteen c1 values in front of the request: loads return in order, one behind it would wait for the spectrum
+            correct_padded<16>(v, p.c1, t, st[8] * invN, st[9] * invN, [&]() __attribute__((always_inline)) {
+                request_z(zn, c, nxt, t);
+                fence();
+            });
         wave_argmax_store(v, wave, lane, rec + 6 * wave);
         parity ^= 1;
         if (pair + 1 < cend) {
@@ -391,16 +198,7 @@ __global__ __launch_bounds__(OCC_THREADS, 2) void xcorr_cached_n4096(const Fused
         }
     }
     lds_barrier();
-    {
-        const double *const prec = red + REC * (parity ^ 1);
-        if (t < 2 && prec[34] >= 0.0 && (t == 0 || prec[35] != 0.0)) {
-            const long long row = (long long)prec[34] + t;
-            if (finalize(prec, t, invN, invNm1, p.mv + row, p.lag + row)) {
-                const int slot = atomicAdd(p.ovf_count, 1);
-                p.ovf_list[slot] = row >> 1;
-            }
-        }
-    }
+    finalize_pair(red + REC * (parity ^ 1), t, true, invN, invNm1, p);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- the reader at four workgroups per CU (test hook: muse_test_spectrum_cache_reader)
@@ -414,34 +212,16 @@ __global__ __launch_bounds__(OCC_THREADS, 4) void xcorr_cached_n4096_occ4(const 
     __shared__ double2 g2s[128];
     __shared__ double red[2 * REC];
     __shared__ int next_s[2];
-    const int t = threadIdx.x;
-    const int lane = t & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    const PairThread th = pair_prologue<PADDED>(p, g2s, red + 34, REC);
+    const int t = th.t, lane = th.lane, wave = th.wave;
+    const double invN = th.invN, invNm1 = th.invNm1;
     double2 *const xw = xbuf + XW * wave;
-    const double invN = PADDED ? p.invN : 1.0 / 4096.0, invNm1 = PADDED ? p.invNm1 : 1.0 / 4095.0;
-
-    if (t < 128)
-        g2s[t] = p.g2[t];
-    if (t < 2)
-        red[REC * (t) + 34] = -1.0; // no previous pair yet (either parity)
     __syncthreads();
-    const auto tl = [&]() __attribute__((always_inline)) {
-        int x = t;
-        if (PADDED)
-            asm volatile("" : "+v"(x));
-        return x;
-    };
 
     int parity = 0;
     const long long first = c.pair0, total = c.pair0 + p.npairs;
     d2v zn[16]; // the next pair's spectrum, in flight
-    // one scalar base per two registers (the odd one at immediate offset -4096 B) + the shared lane offset 16 t; read once: non-temporal
-    const auto request_z = [&](long long pr) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < 16; i++)
-            zn[i] = __builtin_nontemporal_load((gptr<d2v>)scalar_ptr_at(c.zc, (pr - first) * 4096 + 256 * ((i + 1) & ~1)) + (t - 256 * (i & 1)));
-    };
-    request_z(first + blockIdx.x < total ? first + (long long)blockIdx.x : first);
+    request_z(zn, c, first + blockIdx.x < total ? first + (long long)blockIdx.x : first, t);
 
     long long nextpair = 0;
     for (long long pair = first + blockIdx.x; pair < total; pair = nextpair) {
@@ -451,82 +231,39 @@ __global__ __launch_bounds__(OCC_THREADS, 4) void xcorr_cached_n4096_occ4(const 
         const double *const prec = red + REC * (parity ^ 1);
         if (t == 0)
             next_s[parity] = (int)gridDim.x + atomicAdd(p.work_counter, 1);
-        // the pair's statistics (a wave-uniform address: the scalar cache), used behind the workgroup transpose below
-        double st[10];
-#if defined(__HIP_DEVICE_COMPILE__)
-        {
-            const zstat_in_ptr sp = (zstat_in_ptr)(unsigned long long)(c.zstat + (pair - first) * ZC_STAT);
-#pragma unroll
-            for (int k = 0; k < 10; k++)
-                st[k] = sp[k];
-        }
-#endif
+        double st[10]; // the pair's statistics, used behind the workgroup transpose below
+        load_pair_stats(st, c.zstat, pair - first);
         double2 v[16];
 #pragma unroll
         for (int i = 0; i < 16; i++)
             v[i] = make_double2(zn[i].x, zn[i].y);
         // ================= ccA + i ccB = FFT(Z conj(X)/n) (unscaled by 1/sigma) =================
-        xc_stage1(v, [&](int j) __attribute__((always_inline)) {
-            return ldg2(scalar_ptr_at(p.xcp, 256 * ((j + 1) & ~1)), t - 256 * (j & 1));
-        });
+        xc_stage1(v, XcFetch{p.xcp, t});
         dft16_rn_s234(v);
-        exchange_local<0>(v, xw, tl());
+        exchange_local<0>(v, xw, tl<PADDED>(t));
         gdft16_nr(v, G2Fetch{g2s, t & 15});
         // the tail barrier frees the waves' private quarters for the next pair's wave-local transpose (the plain kernel has
         // the first transform's workgroup transpose, which begins with a barrier, in between)
         exchange_cross<1, 1, true>(v, xbuf, wave, t);
-        // behind the barriers: the previous pair's record is complete and visible, and nobody reads this parity's record any more
-        // (its last reader was the finalize of the pair before the previous one, in front of these barriers)
-        finalize_prev(prec, wave, lane, invN, invNm1, p);
-        if (t == 0) {
-#pragma unroll
-            for (int k = 0; k < 10; k++)
-                rec[24 + k] = st[k];
-            rec[34] = (double)rA;
-            rec[35] = hasB ? 1.0 : 0.0;
-        }
+        // behind the barriers: as in xcorr_cached_n4096
+        finalize_pair(prec, wave, lane == 0, invN, invNm1, p);
+        publish_pair_stats(rec, st, t, rA, hasB);
         nextpair = first + __builtin_amdgcn_readfirstlane(next_s[parity]);
         long long nxt = nextpair;
         nxt = nxt < total ? nxt : first; // last iteration: a dummy request
         gdft16_nr_l2(v, G3Derived(p.g3b, t));
-        if (PADDED) { // cc(d - m 1_valid) = cc(d) - m c1, m = sum d / N
-            const auto c1l = [&](int k) __attribute__((always_inline)) {
-                return scalar_ptr_at(p.c1, 256 * ((k + 1) & ~1))[t - 256 * (k & 1)];
-            };
-            const double mA = st[8] * invN, mB = st[9] * invN;
-#pragma unroll
-            for (int h = 0; h < 2; h++) {
-                double cq[8];
-#pragma unroll
-                for (int k = 0; k < 8; k++)
-                    cq[k] = c1l(8 * h + k);
-                fence();
-#pragma unroll
-                for (int k = 0; k < 8; k++) {
-                    const int r = BR16(8 * h + k);
-                    v[r] = make_double2(fma(-mA, cq[k], v[r].x), fma(-mB, cq[k], v[r].y));
-                }
-            }
-        }
+        if (PADDED)
+            correct_padded<8>(v, p.c1, t, st[8] * invN, st[9] * invN);
         wave_argmax_store(v, wave, lane, rec + 6 * wave);
         // (requesting half of the next spectrum in front of the argmax fits the registers and changes nothing: 7.08 ms either
         // way at 1 M x 4096; all of it there, or any of it in front of pass 3, spills)
         fence();
-        request_z(nxt);
+        request_z(zn, c, nxt, t);
         fence();
         parity ^= 1;
     }
     lds_barrier();
-    {
-        const double *const prec = red + REC * (parity ^ 1);
-        if (t < 2 && prec[34] >= 0.0 && (t == 0 || prec[35] != 0.0)) {
-            const long long row = (long long)prec[34] + t;
-            if (finalize(prec, t, invN, invNm1, p.mv + row, p.lag + row)) {
-                const int slot = atomicAdd(p.ovf_count, 1);
-                p.ovf_list[slot] = row >> 1;
-            }
-        }
-    }
+    finalize_pair(red + REC * (parity ^ 1), t, true, invN, invNm1, p);
 }
 
 static bool cache_launch_ok(const FusedParams &p, const SpectrumCacheArgs &c)
@@ -536,8 +273,8 @@ static bool cache_launch_ok(const FusedParams &p, const SpectrumCacheArgs &c)
            (p.N == 4096 || p.c1);
 }
 
-// pairs [c.pair0, c.pair0 + p.npairs) of the group from the ROWS, the first c.zpairs of them into the cache; p.ovf_count is
-// added to (not reset), p.work_counter must be zero
+// pairs [c.pair0, c.pair0 + p.npairs) of the group from the ROWS, the first c.zpairs of them into the cache (0: none -- the plain
+// arithmetic on a tail of the group); p.ovf_count is added to (not reset), p.work_counter must be zero
 hipError_t launch_cache_fill(const FusedParams &p_in, const SpectrumCacheArgs &c, int num_cus, hipStream_t stream)
 {
     const FusedParams p = with_reciprocals(p_in);
@@ -545,10 +282,7 @@ hipError_t launch_cache_fill(const FusedParams &p_in, const SpectrumCacheArgs &c
         2 * (c.pair0 + c.zpairs) > p.M) // (only pairs of two rows are cached)
         return hipErrorInvalidValue;
     const dim3 g((unsigned)std::min<long long>(p.npairs, (long long)num_cus * 4)), b(OCC_THREADS);
-    if (p.N < 4096)
-        hipLaunchKernelGGL((xcorr_cache_fill_n4096<true>), g, b, 0, stream, p, c);
-    else
-        hipLaunchKernelGGL((xcorr_cache_fill_n4096<false>), g, b, 0, stream, p, c);
+    with_bools([&](auto padded) { hipLaunchKernelGGL((xcorr_cache_fill_n4096<decltype(padded)::value>), g, b, 0, stream, p, c); }, p.N < 4096);
     return hipGetLastError();
 }
 
@@ -561,16 +295,15 @@ hipError_t launch_cached(const FusedParams &p_in, const SpectrumCacheArgs &c, in
         return hipErrorInvalidValue;
     const dim3 g((unsigned)(occ4 ? std::min<long long>(p.npairs, (long long)num_cus * 4)
                                  : std::min<long long>((p.npairs + ZC_CLAIM - 1) / ZC_CLAIM, (long long)num_cus * 2))), b(OCC_THREADS);
-    if (occ4) {
-        if (p.N < 4096)
-            hipLaunchKernelGGL((xcorr_cached_n4096_occ4<true>), g, b, 0, stream, p, c);
+    with_bools([&](auto four, auto padded) {
+        if (decltype(four)::value)
+            hipLaunchKernelGGL((xcorr_cached_n4096_occ4<decltype(padded)::value>), g, b, 0, stream, p, c);
         else
-            hipLaunchKernelGGL((xcorr_cached_n4096_occ4<false>), g, b, 0, stream, p, c);
-    } else if (p.N < 4096)
-        hipLaunchKernelGGL((xcorr_cached_n4096<true>), g, b, 0, stream, p, c);
-    else
-        hipLaunchKernelGGL((xcorr_cached_n4096<false>), g, b, 0, stream, p, c);
+            hipLaunchKernelGGL((xcorr_cached_n4096<decltype(padded)::value>), g, b, 0, stream, p, c);
+    }, occ4, p.N < 4096);
     return hipGetLastError();
 }
 
 } // namespace muse
+
+#undef MUSE_CONSUME_ROWS // (n4096_pair_device.h: used through pair_loop_from_rows only)

@@ -23,10 +23,9 @@
 #include <algorithm>
 #include <type_traits>
 
-#include "foldk_device.h"
+#include "n4096_pair_device.h"
 
 namespace muse {
-
 
 // PADDED (2048 < N < 4096, leading zero pad): as in xcorr_r16_fast.hip -- the transforms run on d, sum d is read
 // off the DC bin and the 16 values a lane ends with are corrected by -m c1[index] before the argmax.
@@ -55,227 +54,7 @@ namespace muse {
 template <bool TIMING = false, bool PADDED = false, bool F32 = false, bool WIN = false, bool SLIDE = false>
 __global__ __launch_bounds__(OCC_THREADS, 4) void xcorr_fused_n4096_fold(const FusedParams p)
 {
-    using namespace occ4;
-    using namespace fold;
-    using namespace foldk;
-    __shared__ double2 xbuf[OCC_XBUF];
-    __shared__ double2 g2s[128];
-    __shared__ double red[2 * REC];
-    __shared__ int next_s[2];
-    const int t = threadIdx.x;
-    const int lane = t & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(t >> 6); // wave-uniform by construction
-    const int hi = t >> 4, lo = t & 15;
-    double2 *const xw = xbuf + XW * wave;
-    const int pad = PADDED ? 4096 - p.N : 0;
-    // (PADDED: the launcher's quotients, kernel arguments in scalar registers -- formed here they came out of the vector divider and
-    // were parked in scratch across the whole pair loop)
-    const double invN = PADDED ? p.invN : 1.0 / 4096.0, invNm1 = PADDED ? p.invNm1 : 1.0 / 4095.0;
-
-    if (t < 128)
-        g2s[t] = p.g2[t];
-    if (t < 2)
-        red[REC * (t) + 34] = -1.0; // no previous pair yet (either parity)
-    __syncthreads();
-    PhaseClock<TIMING> clk;
-    clk.start();
-    // (PADDED: the wave-local transposes' LDS addresses are formed where they are used -- hoisted out of the pair loop they were
-    // parked in scratch and reloaded behind an s_waitcnt vmcnt(0) in the middle of every pair)
-    const auto tl = [&]() __attribute__((always_inline)) {
-        int x = t;
-        if (PADDED)
-            asm volatile("" : "+v"(x));
-        return x;
-    };
-
-    int parity = 0;
-    const long long total = p.npairs;
-    RawPair raw;
-    // N == n float64 rows: 16-byte requests on relabelled columns (r16_device.h, issue_row_loads_wide): -1.6 % (profiles/r03_fold_variants.txt)
-    constexpr bool WIDE = !PADDED && !F32;
-    const auto request_rows = [&](long long pr) __attribute__((always_inline)) {
-        if (SLIDE && WIDE)
-            issue_row_loads_wide_slide(raw, p, pr, t);
-        else if (SLIDE && F32)
-            issue_row_loads_slide<PADDED>(raw, p.rows32, p, pr, t, pad);
-        else if (SLIDE)
-            issue_row_loads_slide<PADDED>(raw, p.rows, p, pr, t, pad);
-        else if (WIDE)
-            issue_row_loads_wide(raw, p, pr, t);
-        else
-            issue_row_loads<PADDED, F32>(raw, p, pr, t, pad);
-    };
-    request_rows(blockIdx.x < total ? (long long)blockIdx.x : 0ll);
-
-    long long nextpair = 0;
-    for (long long pair = blockIdx.x; pair < total; pair = nextpair) {
-        const long long rA = 2 * pair;
-        const bool hasB = rA + 1 < p.M;
-        double *const rec = red + REC * parity;
-        const double *const prec = red + REC * (parity ^ 1);
-        if (t == 0) // the pair after this one: claimed now, read behind this pair's barriers
-            next_s[parity] = (int)gridDim.x + atomicAdd(p.work_counter, 1);
-        if (SLIDE) { // rules 2 and 3: every load of this pair has returned in every wave, then the new rows go back in place
-            fence();
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-            fence();
-            if (WIDE)
-                store_slid_rows_wide(raw, p, pair, t);
-            else if (F32)
-                store_slid_rows<PADDED>(raw, const_cast<float *>(p.rows32), p, pair, t, pad);
-            else
-                store_slid_rows<PADDED>(raw, const_cast<double *>(p.rows), p, pair, t, pad);
-        }
-        // ---- consume the prefetched rows: d = x - K (K = the row's first sample) bounds the cancellation in
-        // sum d^2 - (sum d)^2 / N and keeps a large level out of the transform's rounding; sum d is read off the DC bin
-        double2 v[16];
-        {
-            const double KA = raw.ka, KB = raw.kb;
-            double qa = 0.0, qb = 0.0;
-            if (TIMING)
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            clk.template stamp<0>();
-            if (WIDE)
-                widen_rows(raw);
-#pragma unroll
-            for (int i = 0; i < 16; i++) {
-                // (PADDED: a pad position was loaded from the clamped index 0, i.e. it holds the row's first
-                // sample K itself, so d = K - K = 0 without any masking)
-                const double da = raw.a[i] - KA, db = raw.b[i] - KB;
-                v[i] = make_double2(da, db);
-                qa = fma(da, da, qa);
-                qb = fma(db, db, qb);
-            }
-            qa = wave_sum_dpp(qa);
-            qb = wave_sum_dpp(qb);
-            if (lane == 0) {
-                rec[24 + 2 * wave] = qa;
-                rec[24 + 2 * wave + 1] = qb;
-            }
-            if (t == 0) {
-                rec[34] = (double)rA;
-                rec[35] = hasB ? 1.0 : 0.0;
-            }
-        }
-        clk.template stamp<1>();
-        // ================= Z = FFT(dA + i dB) =================
-        // pass 1: plain DFT over a (thread (b, c) = (hi, lo)) -> k1 at v[BR16(k1)]
-        dft16_nr(v);
-        clk.template stamp<2>();
-        // -> thread (k1 = hi, c = lo), input b at v[b]; the tail barrier frees the wave's private quarter for the
-        // wave-local transpose below while the waves are still in step
-        exchange_cross<0, 1, true>(v, xbuf, wave, t, WIDE ? wide_column(t) : -1);
-        // the previous pair's record is complete and visible: lane 0 of waves 0 / 1 writes one series' result each
-        if (lane == 0 && wave < 2 && prec[34] >= 0.0 && (wave == 0 || prec[35] != 0.0)) {
-            const long long row = (long long)prec[34] + wave;
-            if (finalize(prec, wave, invN, invNm1, p.mv + row, p.lag + row)) {
-                const int slot = atomicAdd(p.ovf_count, 1);
-                p.ovf_list[slot] = row >> 1;
-            }
-        }
-        clk.template stamp<3>();
-        // pass 2: generalised DFT over b, delta = k1 / 16 (carries W_256^(b k1))
-        gdft16_nr(v, G2Fetch{g2s, t >> 4});
-        clk.template stamp<4>();
-        exchange_local<1>(v, xw, tl()); // -> thread (k1 = hi, k2 = lo), input c at v[c]
-        clk.template stamp<5>();
-        // pass 3: generalised DFT over c, delta = (k1 + 16 k2) / 256 (carries W_4096^(c k1) W_256^(c k2));
-        // Z[hi + 16 lo + 256 k3] at v[BR16(k3)]
-        gdft16_nr_l2(v, G3Derived(p.g3a, t));
-        double s1a, s1b;
-        {
-            // bin 0 (lane 0 of wave 0) = (sum dA, sum dB): kept in SGPRs until the record is written; the centred
-            // series' DC bin is exactly 0.  Branch-free on purpose.
-            s1a = readlane_f64(v[0].x, 0);
-            s1b = readlane_f64(v[0].y, 0);
-            if (!PADDED) {
-                v[0].x = (t == 0) ? 0.0 : v[0].x;
-                v[0].y = (t == 0) ? 0.0 : v[0].y;
-            }
-        }
-        clk.template stamp<6>();
-        // ================= ccA + i ccB = FFT(Z conj(X)/n) (unscaled by 1/sigma) =================
-        // element f = 256 a' + 16 b' + c' with a' = k3 (register BR16(a')), b' = lo, c' = hi
-        // pass 1: plain DFT over a' with the spectrum factors folded into its first stage -> m1 at v[m1]
-        xc_stage1(v, [&](int j) __attribute__((always_inline)) {
-            return ldg2(scalar_ptr_at(p.xcp, 256 * ((j + 1) & ~1)), t - 256 * (j & 1));
-        });
-        dft16_rn_s234(v);
-        clk.template stamp<7>();
-        exchange_local<0>(v, xw, tl()); // (c' = hi, b' = lo) -> (c' = hi, m1 = lo), input b' at v[b']: same wave
-        if (PADDED && wave == 0 && lane == 0) { // every lane needs the means before its argmax: visible behind
-            rec[32] = s1a;                      // the four barriers of the transpose below
-            rec[33] = s1b;
-        }
-        clk.template stamp<8>();
-        // pass 2: generalised DFT over b', delta = m1 / 16, m1 = lo
-        gdft16_nr(v, G2Fetch{g2s, t & 15});
-        clk.template stamp<9>();
-        exchange_cross<1, 1>(v, xbuf, wave, t); // -> thread (m1 = lo, m2 = hi), input c' at v[c']
-        clk.template stamp<10>();
-        // pass 3: generalised DFT over c', delta = (m1 + 16 m2) / 256 = t / 256: cc index t + 256 m3 at v[BR16(m3)]
-        nextpair = __builtin_amdgcn_readfirstlane(next_s[parity]);
-        long long nxt = nextpair; // last iteration: pair 0 (L2-resident dummy)
-        nxt = nxt < total ? nxt : 0;
-        gdft16_nr_l2(v, G3Derived(p.g3b, t));
-        if (PADDED) { // cc(d - m 1_valid) = cc(d) - m c1, m = sum d / N
-            const auto c1l = [&](int k) __attribute__((always_inline)) {
-                return scalar_ptr_at(p.c1, 256 * ((k + 1) & ~1))[t - 256 * (k & 1)];
-            };
-            const double mA = rec[32] * invN, mB = rec[33] * invN;
-#pragma unroll
-            for (int h = 0; h < 2; h++) {
-                double cq[8];
-#pragma unroll
-                for (int k = 0; k < 8; k++)
-                    cq[k] = c1l(8 * h + k);
-                fence();
-#pragma unroll
-                for (int k = 0; k < 8; k++) {
-                    const int r = BR16(8 * h + k);
-                    v[r] = make_double2(fma(-mA, cq[k], v[r].x), fma(-mB, cq[k], v[r].y));
-                }
-            }
-        }
-        if (WIN) // cc index t + 256 m3 at v[BR16(m3)]
-            mask_window<true, 256>(v, tl(), p.win_lpos, 4096 - p.win_lneg);
-        clk.template stamp<11>();
-        // float32 rows take 34 registers instead of 66: room to request them BEFORE the argmax, which then runs under
-        // the HBM latency (float64 rows: behind it, there is no register left to land them in)
-        if (F32) {
-            fence();
-            request_rows(nxt);
-            fence();
-        }
-        wave_argmax_store(v, wave, lane, rec + 6 * wave);
-        clk.template stamp<13>();
-        fence();
-        if (!F32)
-            request_rows(nxt);
-        fence();
-        if (wave == 0 && lane == 0) {
-            rec[32] = s1a;
-            rec[33] = s1b;
-        }
-        parity ^= 1;
-        clk.template stamp<12>();
-    }
-    lds_barrier();
-    {
-        const double *const prec = red + REC * (parity ^ 1);
-        if (t < 2 && prec[34] >= 0.0 && (t == 0 || prec[35] != 0.0)) {
-            const long long row = (long long)prec[34] + t;
-            if (finalize(prec, t, invN, invNm1, p.mv + row, p.lag + row)) {
-                const int slot = atomicAdd(p.ovf_count, 1);
-                p.ovf_list[slot] = row >> 1;
-            }
-        }
-    }
-    if (TIMING && p.dbg && lane == 0) {
-#pragma unroll
-        for (int i = 0; i < NPHASE; i++)
-            p.dbg[((long long)blockIdx.x * 4 + wave) * NPHASE + i] = clk.acc[i];
-    }
+    foldk::pair_loop_from_rows<TIMING, PADDED, F32, WIN, SLIDE>(p, foldk::NoTap{});
 }
 
 // ============================================================================
@@ -389,19 +168,13 @@ __device__ __forceinline__ void fold_multi_body(const FusedParams &p)
     __shared__ double stats[2 * MSTAT];
     __shared__ double trip[2 * MTRIP];
     __shared__ int next_s[2];
-    const int t = threadIdx.x;
-    const int lane = t & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    const PairThread th = pair_prologue<PADDED>(p, g2s, trip + 24, MTRIP);
+    const int t = th.t, lane = th.lane, wave = th.wave;
+    const double invN = th.invN, invNm1 = th.invNm1;
     double2 *const xw = xbuf + 1088 * wave;
     const int pad = PADDED ? 4096 - p.N : 0;
-    const double invN = PADDED ? p.invN : 1.0 / 4096.0, invNm1 = PADDED ? p.invNm1 : 1.0 / 4095.0; // (the launcher's quotients: scalar registers)
     const int R = p.R;
     PhaseClock<TIMING> clk;
-
-    if (t < 128)
-        g2s[t] = p.g2[t];
-    if (t < 2)
-        trip[MTRIP * t + 24] = -1.0;
     __syncthreads();
     clk.start();
 
@@ -409,25 +182,13 @@ __device__ __forceinline__ void fold_multi_body(const FusedParams &p)
     const long long total = p.npairs;
     RawPair raw;
     constexpr bool WIDE = !PADDED && !F32;
-    const auto request_rows = [&](long long pr) __attribute__((always_inline)) {
-        if (WIDE)
-            issue_row_loads_wide(raw, p, pr, t);
-        else
-            issue_row_loads<PADDED, F32>(raw, p, pr, t, pad);
-    };
-    request_rows(blockIdx.x < total ? (long long)blockIdx.x : 0ll);
+    request_rows<PADDED, F32>(raw, p, blockIdx.x < total ? (long long)blockIdx.x : 0ll, t, pad);
     // reference r's sixteen spectrum factors of this thread (lane-ordered table, L2): requested one iteration ahead
     const auto request_spectrum = [&](double2 (&xf)[16], const int r) __attribute__((always_inline)) {
-        const double2 *xr;
-        { // the table pointer is wave-uniform: keep it in SGPRs
-            const unsigned long long u = (unsigned long long)p.xcp_many[r];
-            const unsigned lo32 = __builtin_amdgcn_readfirstlane((unsigned)u);
-            const unsigned hi32 = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
-            xr = (const double2 *)(((unsigned long long)hi32 << 32) | lo32);
-        }
+        const XcFetch xr{uniform_ptr(p.xcp_many[r]), t}; // the table pointer is wave-uniform: kept in SGPRs
 #pragma unroll
         for (int j = 0; j < 16; j++)
-            xf[j] = ldg2(scalar_ptr_at(xr, 256 * ((j + 1) & ~1)), t - 256 * (j & 1));
+            xf[j] = xr(j);
     };
 
     // one reference: V = Z conj(X_r) / n (factors xf, requested earlier), cc = FFT(V), argmax -> trip[ip]; `v` holds Z on entry.
@@ -472,35 +233,10 @@ __device__ __forceinline__ void fold_multi_body(const FusedParams &p)
         ahead();
         fence();
         gdft16_nr_s4(v, g3[4], g3[5], g3[6], g3[7]);
-        if (PADDED) { // cc(d - m 1_valid) = cc(d) - m c1_r
-            const double *c1r;
-            {
-                const unsigned long long u = (unsigned long long)p.c1_many[r];
-                const unsigned lo32 = __builtin_amdgcn_readfirstlane((unsigned)u);
-                const unsigned hi32 = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
-                c1r = (const double *)(((unsigned long long)hi32 << 32) | lo32);
-            }
-            const double mA = st[8] * invN, mB = st[9] * invN;
-#pragma unroll
-            for (int h = 0; h < 4; h++) {
-                double cq[4];
-#pragma unroll
-                for (int k = 0; k < 4; k++)
-                    cq[k] = scalar_ptr_at(c1r, 256 * ((4 * h + k + 1) & ~1))[t - 256 * ((4 * h + k) & 1)];
-                fence();
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    const int q = BR16(4 * h + k);
-                    v[q] = make_double2(fma(-mA, cq[k], v[q].x), fma(-mB, cq[k], v[q].y));
-                }
-            }
-        }
-        if (WIN) { // cc index t + 256 m3 at v[BR16(m3)].  The thread's base is taken from t HERE: formed outside the loops, the two
-                   // bounds relative to it stay in registers across the whole pair loop, which has none to spare
-            int tw = t;
-            asm volatile("" : "+v"(tw));
-            mask_window_quot<true, 256>(v, tw, p.win_lpos, 4096 - p.win_lneg);
-        }
+        if (PADDED) // with reference r's table
+            correct_padded<4>(v, uniform_ptr(p.c1_many[r]), t, st[8] * invN, st[9] * invN);
+        if (WIN) // cc index t + 256 m3 at v[BR16(m3)]
+            mask_window_quot<true, 256>(v, tl<true>(t), p.win_lpos, 4096 - p.win_lneg);
         clk.template stamp<11>();
         wave_argmax_store(v, wave, lane, tr + 6 * wave);
         if (wave == 0 && lane == 0) {
@@ -521,29 +257,7 @@ __device__ __forceinline__ void fold_multi_body(const FusedParams &p)
             next_s[pp] = (int)gridDim.x + atomicAdd(p.work_counter, 1);
         // ---------- rows -> Z = FFT(dA + i dB), as in xcorr_fused_n4096_fold
         double2 Z[16];
-        {
-            const double KA = raw.ka, KB = raw.kb;
-            double qa = 0.0, qb = 0.0;
-            if (WIDE)
-                widen_rows(raw);
-#pragma unroll
-            for (int i = 0; i < 16; i++) {
-                const double da = raw.a[i] - KA, db = raw.b[i] - KB;
-                Z[i] = make_double2(da, db);
-                qa = fma(da, da, qa);
-                qb = fma(db, db, qb);
-            }
-            qa = wave_sum_dpp(qa);
-            qb = wave_sum_dpp(qb);
-            if (lane == 0) {
-                st[2 * wave] = qa;
-                st[2 * wave + 1] = qb;
-            }
-            if (t == 0) {
-                st[10] = (double)rA;
-                st[11] = hasB ? 1.0 : 0.0;
-            }
-        }
+        MUSE_CONSUME_ROWS(WIDE, raw, Z, st, t, lane, wave, rA, hasB)
         double2 xf[16];
         fence();
         clk.template stamp<0>();
@@ -569,11 +283,8 @@ __device__ __forceinline__ void fold_multi_body(const FusedParams &p)
             gdft16_nr_s4(Z, g3[4], g3[5], g3[6], g3[7]);
         }
         {
-            const double s1a = readlane_f64(Z[0].x, 0), s1b = readlane_f64(Z[0].y, 0);
-            if (!PADDED) {
-                Z[0].x = (t == 0) ? 0.0 : Z[0].x;
-                Z[0].y = (t == 0) ? 0.0 : Z[0].y;
-            }
+            double s1a, s1b;
+            take_dc<PADDED>(Z, t, s1a, s1b);
             if (wave == 0 && lane == 0) { // (PADDED: every lane needs the means before each argmax of this pair: many barriers away)
                 st[8] = s1a;
                 st[9] = s1b;
@@ -601,7 +312,7 @@ __device__ __forceinline__ void fold_multi_body(const FusedParams &p)
                 for (int k = 0; k < 16; k++)
                     asm volatile("" : "+v"(Z[k].x), "+v"(Z[k].y));
             }
-            correlate(Z, xf, R - 1, st, std::true_type{}, [&]() __attribute__((always_inline)) { request_rows(nxt); }, [&]() __attribute__((always_inline)) {});
+            correlate(Z, xf, R - 1, st, std::true_type{}, [&]() __attribute__((always_inline)) { request_rows<PADDED, F32>(raw, p, nxt, t, pad); }, [&]() __attribute__((always_inline)) {});
         }
         pp ^= 1;
     }
@@ -629,33 +340,11 @@ hipError_t launch_fused_multi(const FusedParams &p_in, int num_cus, hipStream_t 
     if (!p.work_counter || p.R < 1 || !p.g2 || !p.g3a || !p.g3b || !p.xcp_many || !p.mv_many || !p.lag_many)
         return hipErrorInvalidValue;
     const dim3 g((unsigned)grid), b(OCC_THREADS);
-    if (p.N < 4096 && !p.c1_many)
+    if ((p.N < 4096 && !p.c1_many) || !window_bounds_ok(p)) // (one window for every reference: muse_batch_score_many_in_window)
         return hipErrorInvalidValue;
-    if (p.win) { // the masked argmax, one window for every reference (muse_batch_score_many_in_window)
-        if (p.win_lpos < 0 || p.win_lneg < 0 || p.win_lpos > 2048 || p.win_lneg > p.win_lpos)
-            return hipErrorInvalidValue;
-        if (p.rows32) {
-            if (p.N < 4096)
-                hipLaunchKernelGGL((xcorr_fused_n4096_fold_multi<true, true, true>), g, b, 0, stream, p);
-            else
-                hipLaunchKernelGGL((xcorr_fused_n4096_fold_multi<false, true, true>), g, b, 0, stream, p);
-        } else if (p.N < 4096) {
-            hipLaunchKernelGGL((xcorr_fused_n4096_fold_multi<true, false, true>), g, b, 0, stream, p);
-        } else {
-            hipLaunchKernelGGL((xcorr_fused_n4096_fold_multi<false, false, true>), g, b, 0, stream, p);
-        }
-        return hipGetLastError();
-    }
-    if (p.N < 4096) {
-        if (p.rows32)
-            hipLaunchKernelGGL((xcorr_fused_n4096_fold_multi<true, true>), g, b, 0, stream, p);
-        else
-            hipLaunchKernelGGL((xcorr_fused_n4096_fold_multi<true, false>), g, b, 0, stream, p);
-    } else if (p.rows32) {
-        hipLaunchKernelGGL((xcorr_fused_n4096_fold_multi<false, true>), g, b, 0, stream, p);
-    } else {
-        hipLaunchKernelGGL((xcorr_fused_n4096_fold_multi<false, false>), g, b, 0, stream, p);
-    }
+    with_bools([&](auto padded, auto f32, auto win) {
+        hipLaunchKernelGGL((xcorr_fused_n4096_fold_multi<decltype(padded)::value, decltype(f32)::value, decltype(win)::value>), g, b, 0, stream, p);
+    }, p.N < 4096, p.rows32 != nullptr, p.win != 0);
     return hipGetLastError();
 }
 
@@ -670,51 +359,20 @@ hipError_t launch_fused_fold(const FusedParams &p_in, int num_cus, hipStream_t s
     if (p.N < 4096 && !p.c1) // leading zero pad: needs the batch's correction table
         return hipErrorInvalidValue;
     const dim3 g((unsigned)grid), b(OCC_THREADS);
-    if (p.win && (p.win_lpos < 0 || p.win_lneg < 0 || p.win_lpos > 2048 || p.win_lneg > p.win_lpos))
+    if (!window_bounds_ok(p)) // (the masked argmax: muse_batch_score_in_window)
         return hipErrorInvalidValue;
-    if (p.slide_tails) { // the slide fused into the pass (muse_batch_slide_score_in_window): the rows are rewritten in place
-        // every pair is claimed once (pair_list / dense_total belong to the rescaling kernel); the rows are dense float64 pairs of
-        // 16-byte aligned rows where the kernel moves them in 16-byte units
-        if (p.slide_k < 1 || p.slide_k > p.N || p.N <= 2048 || p.N > 4096 || p.stride < p.N || p.pair_list || p.npairs != (p.M + 1) / 2 ||
-            (p.N == 4096 && !p.rows32 && !window_wide(p.rows, p.stride)))
-            return hipErrorInvalidValue;
-        const int inst = (p.N < 4096 ? 4 : 0) | (p.rows32 ? 2 : 0) | (p.win ? 1 : 0);
-        switch (inst) {
-        case 0: hipLaunchKernelGGL((xcorr_fused_n4096_fold<false, false, false, false, true>), g, b, 0, stream, p); break;
-        case 1: hipLaunchKernelGGL((xcorr_fused_n4096_fold<false, false, false, true, true>), g, b, 0, stream, p); break;
-        case 2: hipLaunchKernelGGL((xcorr_fused_n4096_fold<false, false, true, false, true>), g, b, 0, stream, p); break;
-        case 3: hipLaunchKernelGGL((xcorr_fused_n4096_fold<false, false, true, true, true>), g, b, 0, stream, p); break;
-        case 4: hipLaunchKernelGGL((xcorr_fused_n4096_fold<false, true, false, false, true>), g, b, 0, stream, p); break;
-        case 5: hipLaunchKernelGGL((xcorr_fused_n4096_fold<false, true, false, true, true>), g, b, 0, stream, p); break;
-        case 6: hipLaunchKernelGGL((xcorr_fused_n4096_fold<false, true, true, false, true>), g, b, 0, stream, p); break;
-        default: hipLaunchKernelGGL((xcorr_fused_n4096_fold<false, true, true, true, true>), g, b, 0, stream, p); break;
-        }
-        return hipGetLastError();
-    }
-    if (p.win) { // the masked argmax (muse_batch_score_in_window)
-        if (p.rows32) {
-            if (p.N < 4096)
-                hipLaunchKernelGGL((xcorr_fused_n4096_fold<false, true, true, true>), g, b, 0, stream, p);
-            else
-                hipLaunchKernelGGL((xcorr_fused_n4096_fold<false, false, true, true>), g, b, 0, stream, p);
-        } else if (p.N < 4096) {
-            hipLaunchKernelGGL((xcorr_fused_n4096_fold<false, true, false, true>), g, b, 0, stream, p);
-        } else {
-            hipLaunchKernelGGL((xcorr_fused_n4096_fold<false, false, false, true>), g, b, 0, stream, p);
-        }
-        return hipGetLastError();
-    }
-    if (p.rows32) {
-        if (p.N < 4096)
-            hipLaunchKernelGGL((xcorr_fused_n4096_fold<false, true, true>), g, b, 0, stream, p);
-        else
-            hipLaunchKernelGGL((xcorr_fused_n4096_fold<false, false, true>), g, b, 0, stream, p);
-    } else if (p.N < 4096) {
-        hipLaunchKernelGGL((xcorr_fused_n4096_fold<false, true>), g, b, 0, stream, p);
-    } else {
-        hipLaunchKernelGGL((xcorr_fused_n4096_fold<false, false>), g, b, 0, stream, p);
-    }
+    // the slide fused into the pass (muse_batch_slide_score_in_window): the rows are rewritten in place.  Every pair is claimed once
+    // (pair_list / dense_total belong to the rescaling kernel); the rows are dense float64 pairs of 16-byte aligned rows where the
+    // kernel moves them in 16-byte units
+    if (p.slide_tails && (p.slide_k < 1 || p.slide_k > p.N || p.N <= 2048 || p.N > 4096 || p.stride < p.N || p.pair_list || p.npairs != (p.M + 1) / 2 ||
+                          (p.N == 4096 && !p.rows32 && !window_wide(p.rows, p.stride))))
+        return hipErrorInvalidValue;
+    with_bools([&](auto padded, auto f32, auto win, auto slide) {
+        hipLaunchKernelGGL((xcorr_fused_n4096_fold<false, decltype(padded)::value, decltype(f32)::value, decltype(win)::value, decltype(slide)::value>), g, b, 0, stream, p);
+    }, p.N < 4096, p.rows32 != nullptr, p.win != 0, p.slide_tails != nullptr);
     return hipGetLastError();
 }
 
 } // namespace muse
+
+#undef MUSE_CONSUME_ROWS // (n4096_pair_device.h: this file is its last user)

@@ -378,29 +378,11 @@ hipError_t launch_fused_occ4(const FusedParams &p_in, int num_cus, hipStream_t s
     if (grid > cap)
         grid = cap;
     const dim3 g((unsigned)grid), b(OCC_THREADS);
-    if (p.win) { // the masked argmax (muse_batch_score_in_window)
-        if (p.win_lpos < 0 || p.win_lneg < 0 || p.win_lpos > 2048 || p.win_lneg > p.win_lpos)
-            return hipErrorInvalidValue;
-        if (p.rows32) {
-            if (p.N < 4096)
-                hipLaunchKernelGGL((xcorr_fused_n4096_occ4<true, 3, false, true, true>), g, b, 0, stream, p);
-            else
-                hipLaunchKernelGGL((xcorr_fused_n4096_occ4<false, 3, false, true, true>), g, b, 0, stream, p);
-        } else if (p.N < 4096)
-            hipLaunchKernelGGL((xcorr_fused_n4096_occ4<true, 3, false, false, true>), g, b, 0, stream, p);
-        else
-            hipLaunchKernelGGL((xcorr_fused_n4096_occ4<false, 3, false, false, true>), g, b, 0, stream, p);
-        return hipGetLastError();
-    }
-    if (p.rows32) {
-        if (p.N < 4096)
-            hipLaunchKernelGGL((xcorr_fused_n4096_occ4<true, 3, false, true>), g, b, 0, stream, p);
-        else
-            hipLaunchKernelGGL((xcorr_fused_n4096_occ4<false, 3, false, true>), g, b, 0, stream, p);
-    } else if (p.N < 4096)
-        hipLaunchKernelGGL((xcorr_fused_n4096_occ4<true, 3>), g, b, 0, stream, p);
-    else
-        hipLaunchKernelGGL((xcorr_fused_n4096_occ4<false, 3>), g, b, 0, stream, p);
+    if (!window_bounds_ok(p)) // (the masked argmax: muse_batch_score_in_window)
+        return hipErrorInvalidValue;
+    with_bools([&](auto padded, auto f32, auto win) {
+        hipLaunchKernelGGL((xcorr_fused_n4096_occ4<decltype(padded)::value, 3, false, decltype(f32)::value, decltype(win)::value>), g, b, 0, stream, p);
+    }, p.N < 4096, p.rows32 != nullptr, p.win != 0);
     return hipGetLastError();
 }
 
