@@ -89,6 +89,7 @@ WINDOW_MANY_TEST = os.path.join(LIBDIR, "muse_window_many_test")
 ROWS_WINDOW_TEST = os.path.join(LIBDIR, "muse_rows_window_test")
 IN_WINDOW_TEST = os.path.join(LIBDIR, "muse_in_window_test")
 MANY_IN_WINDOW_TEST = os.path.join(LIBDIR, "muse_many_in_window_test")
+LAG_RANGE_TEST = os.path.join(LIBDIR, "muse_lag_range_test")
 
 
 def build_host_test(force=False):
@@ -129,6 +130,11 @@ def build_rows_window_test(force=False):
 def build_in_window_test(force=False):
     """The host mirror's wide-window program (tests/test_gpu_in_window.py)."""
     return _build_host_program("muse_in_window_test", "-O1", force)
+
+
+def build_lag_range_test(force=False):
+    """The host mirror's one-sided / asymmetric window program (tests/test_gpu_lag_range.py)."""
+    return _build_host_program("muse_lag_range_test", "-O1", force)
 
 
 def build_many_in_window_test(force=False):

@@ -615,7 +615,7 @@ int batch_score_check(muse_batch *b, int win_L, int *variant)
     return MUSE_OK;
 }
 
-int batch_score(muse_batch *b, bool allow_spectrum_cache, int win_L, const SlideFuse *slide)
+int batch_score(muse_batch *b, bool allow_spectrum_cache, int win_L, const SlideFuse *slide, int win_lneg)
 {
     if (!b)
         return fail(MUSE_ERR_INVALID, "NULL batch");
@@ -662,8 +662,15 @@ int batch_score(muse_batch *b, bool allow_spectrum_cache, int win_L, const Slide
     if (win_L >= 0) { // the masked argmax: built into the default kernels of n = 512 ... 4096 and the rescaling kernel behind the n = 4096 one
         if (!(variant == KERNEL_R16_FOLD || variant == KERNEL_R16_OCC3 || (variant == KERNEL_SMALL && b->logn <= 11)) || 2 * win_L > b->n)
             return fail(MUSE_ERR_UNSUPPORTED, "the masked transform pass runs on the default kernels of FFT lengths 512 ... 4096");
-        b->origin = ScoreOrigin::in_window(MUSE_IN_WINDOW_MASKED, win_L, variant);
-        set_window(p, win_L);
+        if (win_lneg >= 0) { // a lag range: the two bounds as the caller clipped them
+            if (2 * win_lneg > b->n - 2)
+                return fail(MUSE_ERR_UNSUPPORTED, "the masked transform pass takes at most n / 2 - 1 lags below zero");
+            b->origin = ScoreOrigin::in_lag_range(MUSE_IN_WINDOW_MASKED, win_L, win_lneg, variant);
+            set_window(p, win_L, win_lneg);
+        } else {
+            b->origin = ScoreOrigin::in_window(MUSE_IN_WINDOW_MASKED, win_L, variant);
+            set_window(p, win_L);
+        }
     }
     if (slide) { // (the rows are rewritten by the launch: only the kernel that was built for it may see the tails)
         if (variant != KERNEL_R16_FOLD || allow_spectrum_cache)
@@ -814,7 +821,7 @@ extern "C" int muse_batch_kernel_name(muse_batch *b, char *name, int32_t cap)
         else
             snprintf(k, sizeof(k), "xcorr_fused_small<%d, %s, false, %s, true>", b->logn, padded, f32);
     } else if (o.kind == ScoreOrigin::MFMA) { // (the direct product with the call's window, whatever the batch's own setting)
-        snprintf(k, sizeof(k), "xcorr_window_mfma<%d, %s>", (2 * o.window + 1 + 15) / 16,
+        snprintf(k, sizeof(k), "xcorr_window_mfma<%d, %s>", o.mfma_tiles(),
                  window_wide(b->g->rows, b->g->stride) ? "true" : "false");
     } else if (o.kind == ScoreOrigin::PACKED) {
         snprintf(k, sizeof(k), "xcorr_window_many_mfma<%d, %s>", o.tiles, window_wide(b->g->rows, b->g->stride) ? "true" : "false");

@@ -274,9 +274,20 @@ struct ScoreOrigin {
     int32_t variant = 0; // MASKED: the KERNEL_* the pass launched first, or MANY
     int32_t tiles = 0;   // PACKED
     int32_t slide = 0;   // the MUSE_SLIDE_IN_WINDOW_* path if the pass was muse_batch_slide_score_in_window's and moved the rows, 0 otherwise
+    // a lag range's two bounds (muse_batch_score_in_lag_range, lags -window_neg .. window): window_neg >= 0; -1: a symmetric window,
+    // whose negative bound is window_lneg(window, n)
+    int32_t window_neg = -1;
     static ScoreOrigin packed(int32_t tiles) { return ScoreOrigin{PACKED, -1, 0, tiles}; }
     static ScoreOrigin in_window(int32_t path, int32_t L, int32_t variant = 0) { return ScoreOrigin{(Kind)path, L, variant, 0}; }
+    static ScoreOrigin in_lag_range(int32_t path, int32_t lpos, int32_t lneg, int32_t variant = 0)
+    {
+        ScoreOrigin o{(Kind)path, lpos, variant, 0};
+        o.window_neg = lneg;
+        return o;
+    }
     int32_t in_window_path() const { return kind > OWN ? (int32_t)kind : 0; }
+    // MFMA: the accumulator tiles of the direct product (rows 0 .. 2 window of a symmetric window's table, 0 .. window + window_neg of a range's)
+    int32_t mfma_tiles() const { return ((window_neg < 0 ? 2 * window : window + window_neg) + 1 + 15) / 16; }
 };
 
 struct muse_batch {
@@ -356,7 +367,7 @@ struct muse_batch {
     uint64_t guard_salt = 0;            // varies the guard's row sample from Run to Run
     // lag window (muse_batch_set_lag_window, capi_window.hip): < 0 = off; otherwise every scoring pass takes xcorr_window.hip
     // with L = min(lag_window, n / 2).  win_e / win_pw: the shifted-reference image and its window sums for win_L (built by
-    // the first windowed pass; -1: none yet)
+    // the first windowed pass; -1: none yet; window_range_key(): the tables of a lag range, muse_batch_score_in_lag_range)
     int32_t lag_window = -1;
     int32_t win_L = -1;
     PoolBuf<double> win_e, win_pw;
@@ -455,7 +466,9 @@ struct SlideFuse {
     const void *tails;
     int32_t k;
 };
-int batch_score(muse_batch *b, bool allow_spectrum_cache, int win_L = -1, const SlideFuse *slide = nullptr);
+// win_lneg >= 0 (with win_L >= 0): the masked pass over the lag range -win_lneg .. win_L, the two bounds independent of each other
+// (muse_batch_score_in_lag_range; win_L <= n / 2, win_lneg <= n / 2 - 1)
+int batch_score(muse_batch *b, bool allow_spectrum_cache, int win_L = -1, const SlideFuse *slide = nullptr, int win_lneg = -1);
 // what batch_score(b, ., win_L) would refuse for the batch as it stands (kernel selection, storage, length), without enqueueing
 // anything -- for a caller that moves rows before it scores; *variant = the KERNEL_* the pass would launch first (-1: none of them:
 // the batch's own window or a series longer than 65 536 samples)
@@ -473,6 +486,9 @@ int score_windowed(muse_batch *b);                     // capi_window.hip: the a
 // window_params: the kernels' arguments for b's group and scores with those tables
 int check_window_request(const muse_batch *b, int32_t max_lag, bool f32);
 int window_tables(muse_batch *b, int L, PoolBuf<double> &e, PoolBuf<double> &pw, int32_t *cached_L, hipStream_t st);
+// the key a lag range's tables (origin = its lags below zero, W rows) are cached under: no window +-L (L <= MUSE_LAG_WINDOW_MAX) has it,
+// so a symmetric pass never takes a range's tables or the other way round
+inline int32_t window_range_key(int origin, int W) { return 0x10000 + origin * 256 + W; }
 muse::WindowParams window_params(const muse_batch *b, int L, const double *e, const double *pw);
 // the lags a window +-L holds below zero at FFT length n: index n / 2 is lag +n/2 (xcorr.go:192-194), it is scanned once
 inline int window_lneg(int L, int n) { return 2 * L == n ? L - 1 : L; }
@@ -482,6 +498,13 @@ inline void set_window(muse::FusedParams &p, int L)
     p.win = 1;
     p.win_lpos = L;
     p.win_lneg = window_lneg(L, p.n);
+}
+// the same for a lag range: cc indices 0 .. lpos and n - lneg .. n - 1
+inline void set_window(muse::FusedParams &p, int lpos, int lneg)
+{
+    p.win = 1;
+    p.win_lpos = lpos;
+    p.win_lneg = lneg;
 }
 // capi_window.hip: a call's window against the batch's own, which must be off or equal (r: the batch's index in a list, -1: a single batch)
 int check_own_window(const muse_batch *b, int32_t max_lag, int r = -1);

@@ -1,6 +1,7 @@
 // capi_window.hip -- the lag window of a batch (muse_batch_set_lag_window): the setting, its tables, the windowed all-scores pass,
 // that pass fused with the slide of the group's rows (muse_batch_slide_score_windowed / _slide_run_windowed), and the window of any
-// width as an argument (muse_batch_score_in_window / _run_in_window: the direct product or the masked transform kernels)
+// width as an argument (muse_batch_score_in_window / _run_in_window: the direct product or the masked transform kernels), one-sided
+// and asymmetric too (muse_batch_score_in_lag_range / _run_in_lag_range)
 // Part of the implementation of the C ABI declared in include/muse_hip.h (capi_internal.h: the handles and the helpers the
 // parts share).  Host-side orchestration only; there is no CPU compute fallback anywhere: without a gfx950 device every
 // compute entry point returns MUSE_ERR_NO_DEVICE.
@@ -78,6 +79,7 @@ WindowParams window_params(const muse_batch *b, int L, const double *e, const do
     p.Lneg = window_lneg(L, b->n);
     p.invN = 1.0 / (double)b->N;
     p.invNm1 = 1.0 / (double)(b->N - 1);
+    p.origin = L;
     p.e = e;
     p.pw = pw;
     p.mv = b->mv.p;
@@ -293,6 +295,135 @@ extern "C" int muse_batch_run_in_window(muse_batch *b, const int32_t *group_id, 
         rc = muse_batch_score_in_window(b, max_lag);
     if (rc)
         return rc;
+    std::vector<muse_record> sel;
+    rc = run_select(b, group_id, G, 0, max_lag, top_n, threshold, sign_filter, abs_scores, sel, true, false);
+    if (rc)
+        return rc;
+    emit(sel, out_series, out_lag, out_score, out_count, out_mean_abs);
+    return MUSE_OK;
+}
+
+// ---- one-sided and asymmetric windows: the best match inside lag_lo .. lag_hi, lag_lo <= 0 <= lag_hi (muse_batch_score_in_lag_range)
+// The range as the passes take it: hi = min(lag_hi, n / 2) lags above zero, lneg = min(-lag_lo, n / 2 - 1) below.
+struct LagRange {
+    int hi, lneg;
+    int W() const { return hi + lneg + 1; }
+};
+static LagRange clip_lag_range(int64_t n, int32_t lag_lo, int32_t lag_hi)
+{
+    return LagRange{(int)std::min<int64_t>(lag_hi, n / 2), (int)std::min<int64_t>(-(int64_t)lag_lo, n / 2 - 1)};
+}
+// The dispatch, a pure host function: which pass scores series of N samples (float32 storage or not) inside lag_lo .. lag_hi; W = the
+// lags of the clipped range.  For lag_lo == -lag_hi it is in_window_plan's table row for row.
+//   the range is every lag                            : the plain pass of batch_score, any length, any storage
+//   float64, W <= 2 MUSE_LAG_WINDOW_MAX + 1, n <= 65536 : the direct product, its table starting at the lowest lag (unless `force_transform`
+//                                                       and the length has masked kernels)
+//   n in {512, 1024, 2048, 4096}, wider or float32    : the transform kernels with a masked argmax, the two bounds set independently
+//   anything else                                     : not built
+static int lag_range_plan(int32_t N, bool f32, int32_t lag_lo, int32_t lag_hi, bool force_transform)
+{
+    const int64_t n = muse_next_pow2((double)N);
+    const LagRange r = clip_lag_range(n, lag_lo, lag_hi);
+    if (2 * (int64_t)r.hi == n && r.lneg == n / 2 - 1)
+        return MUSE_IN_WINDOW_PLAIN;
+    const bool masked_len = n == 512 || n == 1024 || n == 2048 || n == 4096;
+    if (!f32 && r.W() <= 2 * MUSE_LAG_WINDOW_MAX + 1 && n <= GENERIC_MAX_N && !(force_transform && masked_len))
+        return MUSE_IN_WINDOW_MFMA;
+    return masked_len ? MUSE_IN_WINDOW_MASKED : MUSE_IN_WINDOW_UNSUPPORTED;
+}
+
+extern "C" int muse_test_lag_range_plan(int32_t N, int32_t f32, int32_t lag_lo, int32_t lag_hi, int32_t *path)
+{
+    if (!path || N < 2 || lag_lo > 0 || lag_hi < 0)
+        return fail(MUSE_ERR_INVALID, "bad lag-range plan arguments (N >= 2, lag_lo <= 0 <= lag_hi)");
+    *path = lag_range_plan(N, f32 != 0, lag_lo, lag_hi, false);
+    return MUSE_OK;
+}
+
+extern "C" int muse_batch_score_in_lag_range(muse_batch *b, int32_t lag_lo, int32_t lag_hi)
+{
+    // everything is checked before anything is enqueued: on a refusal the batch is unchanged
+    if (!b)
+        return fail(MUSE_ERR_INVALID, "NULL batch");
+    if (lag_lo > 0 || lag_hi < 0)
+        return fail(MUSE_ERR_INVALID, "the lag range %d .. %d does not hold lag 0 (lag_lo <= 0 <= lag_hi)", lag_lo, lag_hi);
+    if ((int64_t)lag_lo == -(int64_t)lag_hi) // by definition: the symmetric window's pass, bit for bit on every path
+        return muse_batch_score_in_window(b, lag_hi);
+    if (b->windowed())
+        return fail(MUSE_ERR_INVALID, "the batch has a lag window of %d of its own: it must be off, or equal to a range -L .. L", b->lag_window);
+    const int path = lag_range_plan(b->N, b->g->f32, lag_lo, lag_hi, b->ctx->in_window_force.load());
+    if (path == MUSE_IN_WINDOW_UNSUPPORTED || (path == MUSE_IN_WINDOW_MFMA && !b->xs))
+        return fail(MUSE_ERR_UNSUPPORTED, "the lag range %d .. %d over series of %d samples%s is not built: more than %d lags and float32 "
+                    "storage take the masked argmax of the transform kernels of FFT lengths 512 ... 4096",
+                    lag_lo, lag_hi, b->N, b->g->f32 ? " in float32 storage" : "", 2 * MUSE_LAG_WINDOW_MAX + 1);
+    const LagRange r = clip_lag_range(b->n, lag_lo, lag_hi);
+    int rc;
+    if (path != MUSE_IN_WINDOW_MFMA) { // (what batch_score would refuse -- a forced kernel without a masked build -- before it touches the batch)
+        int variant = -1;
+        rc = batch_score_check(b, path == MUSE_IN_WINDOW_MASKED ? r.hi : -1, &variant);
+        if (rc)
+            return rc;
+    }
+    if (path == MUSE_IN_WINDOW_MASKED) { // (batch_score records the origin: it knows the kernel it launches first)
+        rc = batch_score(b, false, r.hi, nullptr, r.lneg);
+    } else if (path == MUSE_IN_WINDOW_PLAIN) { // (the batch has no window of its own here)
+        rc = batch_score(b, true);
+    } else { // the direct product over a table whose row v is lag v - lneg: W rows, ceil(W / 16) accumulator tiles
+        muse_ctx *ctx = b->ctx;
+        rc = use_device(ctx);
+        if (rc)
+            return rc;
+        const hipStream_t st = b->stream();
+        rc = group_ready(b->g, st); // rows packed but not sent yet go first
+        if (rc)
+            return rc;
+        if (b->g->M == 0)
+            return MUSE_OK;
+        rc = ensure_scores(b);
+        if (rc)
+            return rc;
+        const int32_t key = window_range_key(r.lneg, r.W());
+        if (b->win_L != key) {
+            b->win_L = -1;
+            const long long e_len = window_e_len(b->N);
+            HIP_TRY(b->win_e.ensure(ctx, e_len, st));
+            HIP_TRY(b->win_pw.ensure(ctx, 2 * MUSE_LAG_WINDOW_MAX + 1, st));
+            HIP_TRY(launch_window_tables(b->xs, b->N, b->n, r.lneg, r.W(), b->win_e.p, e_len, b->win_pw.p, st));
+            b->win_L = key;
+        }
+        WindowParams p = window_params(b, r.hi, b->win_e.p, b->win_pw.p);
+        p.Lneg = r.lneg;
+        p.origin = r.lneg;
+        LaunchTimer timer(ctx, false, st);
+        HIP_TRY(timer.begin());
+        HIP_TRY(launch_window(p, st));
+        HIP_TRY(timer.end());
+    }
+    if (rc)
+        return rc;
+    if (b->g->M == 0)
+        return MUSE_OK;
+    b->scores_exact = true;
+    b->last_path = MUSE_RUN_PATH_FP64;
+    b->last_screened = false;
+    if (path != MUSE_IN_WINDOW_MASKED)
+        b->origin = ScoreOrigin::in_lag_range(path, r.hi, r.lneg);
+    return MUSE_OK;
+}
+
+extern "C" int muse_batch_run_in_lag_range(muse_batch *b, const int32_t *group_id, int32_t G, int32_t lag_lo, int32_t lag_hi,
+                                           int32_t top_n, double threshold, int32_t sign_filter, int32_t abs_scores,
+                                           int64_t *out_series, int32_t *out_lag, double *out_score, int32_t *out_count,
+                                           double *out_mean_abs)
+{
+    // (the selection's own argument checks come first, as in muse_batch_run_in_window)
+    int rc = check_select_args(group_id, G, sign_filter);
+    if (!rc)
+        rc = muse_batch_score_in_lag_range(b, lag_lo, lag_hi);
+    if (rc)
+        return rc;
+    // Results.MaxLag = max(-lag_lo, lag_hi): every lag of the range passes the lag filter
+    const int32_t max_lag = (int32_t)std::min<int64_t>(std::max<int64_t>(-(int64_t)lag_lo, lag_hi), INT32_MAX);
     std::vector<muse_record> sel;
     rc = run_select(b, group_id, G, 0, max_lag, top_n, threshold, sign_filter, abs_scores, sel, true, false);
     if (rc)

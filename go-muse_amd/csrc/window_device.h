@@ -148,7 +148,8 @@ __device__ __forceinline__ double window_wave_sum(const double *lds, const int S
 
 // ---- the pieces of the scan: the windowed maxAbsIndex in the order of the definition, scan position pos = 0 .. W-1 <-> lag 0 .. L,
 // -Lneg .. -1, strict '>', first index wins (xcorr.go:39-50).  How the positions are cut into parts is each kernel's own: strict '>'
-// with the first index winning cannot see the cut.
+// with the first index winning cannot see the cut.  Row v of the summed tiles and of pw is lag v - origin (WindowShape::origin: L for
+// a symmetric window, Lneg for a lag range whose table starts at its lowest lag); L and Lneg are independent of each other.
 struct WindowStats {
     double mean, inv_sigma;
     bool nan, zero;
@@ -159,7 +160,7 @@ __device__ __forceinline__ WindowStats window_stats(const double t1, const doubl
     const bool nan = !__builtin_isfinite(var);
     return WindowStats{t1 * invN, 1.0 / sqrt(var), nan, !nan && !(var > 0.0)};
 }
-// cc at window row v (= lag + L) of series c; row0: the first of the reference's rows in the summed tiles (one reference: 0)
+// cc at window row v (= lag + origin) of series c; row0: the first of the reference's rows in the summed tiles (one reference: 0)
 __device__ __forceinline__ double window_score(const double *lds, const int row0, const int v, const int c, const WindowStats &st,
                                                const double *__restrict__ pw)
 {
@@ -170,10 +171,10 @@ struct WindowBest { // (pos as a double: the candidates lie in LDS as three doub
     double abs = 0.0, val = 0.0, pos = -1.0;
 };
 __device__ __forceinline__ void window_scan_pos(WindowBest &best, const double *lds, const int row0, const int pos, const int c, const int L,
-                                                const int Lneg, const WindowStats &st, const double *__restrict__ pw)
+                                                const int Lneg, const int origin, const WindowStats &st, const double *__restrict__ pw)
 {
     if (pos < L + 1 + Lneg) {
-        const int v = pos <= L ? pos + L : pos - 1 - Lneg; // lag + L
+        const int v = (pos <= L ? pos : pos - 1 - Lneg - L) + origin; // lag + origin
         const double val = window_score(lds, row0, v, c, st, pw);
         if (fabs(val) > best.abs) {
             best.abs = fabs(val);
@@ -190,7 +191,7 @@ __device__ __forceinline__ void window_put_best(double *cand, const WindowBest &
 }
 // parts slot0 .. slot0 + parts - 1 of series c merged in their order, and the outcome: the value, and through *lag its lag
 __device__ __forceinline__ double window_outcome(const double *lds, const int CAND, const int slot0, const int parts, const int row0,
-                                                 const int c, const int L, const int Lneg, const WindowStats &st,
+                                                 const int c, const int L, const int Lneg, const int origin, const WindowStats &st,
                                                  const double *__restrict__ pw, int *lag)
 {
     double ba = 0.0, bv = 0.0;
@@ -210,7 +211,7 @@ __device__ __forceinline__ double window_outcome(const double *lds, const int CA
     if (st.zero)
         return 0.0; // sigma == 0: (nil, 0, 0), xcorr.go:165-168
     if (bp < 0) // only zeros or NaN in the window: index 0 stands
-        return window_score(lds, row0, L, c, st, pw);
+        return window_score(lds, row0, origin, c, st, pw);
     *lag = bp <= L ? bp : bp - 1 - Lneg - L;
     return bv;
 }
@@ -226,12 +227,12 @@ __device__ __forceinline__ void window_scan_write(double *lds, const int CAND, c
     WindowBest best;
 #pragma unroll
     for (int k = 0; k < TILES; k++)
-        window_scan_pos(best, lds, 0, part * TILES + k, c, p.L, p.Lneg, st, p.pw);
+        window_scan_pos(best, lds, 0, part * TILES + k, c, p.L, p.Lneg, p.origin, st, p.pw);
     window_put_best(lds + CAND + (part * 16 + c) * 3, best);
     __syncthreads();
     if (t < 16 && row0 + t < p.M) {
         int lag;
-        p.mv[row0 + t] = window_outcome(lds, CAND, 0, 16, 0, c, p.L, p.Lneg, st, p.pw, &lag);
+        p.mv[row0 + t] = window_outcome(lds, CAND, 0, 16, 0, c, p.L, p.Lneg, p.origin, st, p.pw, &lag);
         p.lag[row0 + t] = lag;
     }
 }
@@ -251,7 +252,8 @@ __device__ __forceinline__ void window_finish(double *lds, const v4d (&acc)[TILE
 // ---- the launch side: the checks every launch makes on a window's shape, and the tile count as a compile-time constant
 inline hipError_t window_launch_check(const WindowShape &p, long long *blocks)
 {
-    if (p.L < 0 || p.L > MUSE_LAG_WINDOW_MAX || p.Lneg < 0 || p.Lneg > p.L || p.N < 2)
+    // rows origin - Lneg .. origin + L of the table: inside the eight tiles, pw and the staged image's tail (2 MUSE_LAG_WINDOW_MAX + 1 rows)
+    if (p.L < 0 || p.Lneg < 0 || p.L + p.Lneg > 2 * MUSE_LAG_WINDOW_MAX || p.origin < p.Lneg || p.origin + p.L > 2 * MUSE_LAG_WINDOW_MAX || p.N < 2)
         return hipErrorInvalidValue;
     *blocks = (p.M + 15) / 16;
     return *blocks > 0x7fffffffLL ? hipErrorInvalidValue : hipSuccess;
@@ -271,5 +273,6 @@ template <class F> inline void window_with_tiles(const int tiles, F &&f)
     }
 }
 inline int window_tiles(int L) { return (2 * L + 1 + 15) / 16; } // lag + L runs up to 2 L whichever side the window drops
+inline int window_tiles(const WindowShape &p) { return (p.origin + p.L + 1 + 15) / 16; } // rows 0 .. origin + L (symmetric: the line above)
 
 } // namespace muse

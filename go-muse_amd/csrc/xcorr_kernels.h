@@ -82,7 +82,8 @@ struct FusedParams {
     // divider, and wave-uniform values in vector registers were what those builds parked in scratch
     double invN, invNm1;
     // masked argmax (the WIN builds of xcorr_r16_fold.hip, xcorr_r16_occ4.hip and xcorr_small.hip; muse_batch_score_in_window): win != 0 ->
-    // index i of cc takes part in maxAbsIndex iff i <= win_lpos || i >= n - win_lneg (WindowParams::L / ::Lneg); every other value
+    // index i of cc takes part in maxAbsIndex iff i <= win_lpos || i >= n - win_lneg (WindowParams::L / ::Lneg; the two bounds are
+    // independent: 0 <= win_lpos <= n / 2, 0 <= win_lneg <= n / 2 - 1, muse_batch_score_in_lag_range); every other value
     // is replaced by +0.0 in front of the argmax.  Last in the structure: the offsets of everything above are what they were.
     int win, win_lpos, win_lneg;
     // the slide fused into the n = 4096 pass (the SLIDE builds of xcorr_r16_fold.hip; muse_batch_slide_score_in_window): slide_tails != 0 ->
@@ -101,7 +102,7 @@ inline FusedParams with_reciprocals(FusedParams p)
 // the masked argmax's window as the n = 4096 launchers accept it (no window: nothing to check)
 inline bool window_bounds_ok(const FusedParams &p)
 {
-    return !p.win || (p.win_lpos >= 0 && p.win_lneg >= 0 && p.win_lpos <= 2048 && p.win_lneg <= p.win_lpos);
+    return !p.win || (p.win_lpos >= 0 && p.win_lneg >= 0 && p.win_lpos <= 2048 && p.win_lneg <= 2047);
 }
 // run-time booleans -> template arguments: with_bools(f, b0, b1, ...) calls f(std::bool_constant<b0>{}, std::bool_constant<b1>{}, ...),
 // so a launcher names its kernel once, with decltype(flag)::value for each flag, and every combination is instantiated
@@ -182,18 +183,25 @@ struct WindowShape {    // what every lag-window kernel takes: the rows and the 
     const double *rows; // M x N row-major float64, row stride `stride` elements
     long long M, stride;
     int N;
-    int L, Lneg;        // lags -Lneg .. L (Lneg = L, or L - 1 when L == n / 2: index n / 2 is lag +n/2 only)
+    int L, Lneg;        // lags -Lneg .. L (a symmetric window: Lneg = L, or L - 1 when L == n / 2: index n / 2 is lag +n/2 only)
     double invN, invNm1;
+    int origin;         // row v of the product table is lag v - origin, Lneg <= origin: L for a symmetric window (rows L - Lneg .. 2 L),
+                        // Lneg for a lag range (muse_batch_score_in_lag_range: rows 0 .. L + Lneg).  Last: the offsets above are what they were
 };
 struct WindowParams : WindowShape {
-    const double *e;    // [window_e_len(N)] e[v] = xs[(n - N + v - L) mod n], zero from N + 2 L on
-    const double *pw;   // [2 L + 1] pw[v] = sum_t e[t + v]
+    const double *e;    // [window_e_len(N)] e[v] = xs[(n - N + v - origin) mod n], zero from N + origin + L on
+    const double *pw;   // [origin + L + 1] pw[v] = sum_t e[t + v]
     double *mv;         // out: M signed values
     int *lag;           // out: M lags
 };
 inline bool window_wide(const double *rows, long long stride) { return stride % 2 == 0 && ((uintptr_t)rows & 15) == 0; } // every row 16-byte aligned
 inline long long window_e_len(int N) { return (long long)((N + WIN_KC - 1) / WIN_KC) * WIN_KC + WIN_E_TAIL; }
-hipError_t launch_window_tables(const double *xs, int N, int n, int L, double *e, long long e_len, double *pw, hipStream_t stream);
+// the tables of a window whose row v is lag v - origin, rows 0 .. W - 1 (a symmetric window +-L: origin = L, W = 2 L + 1)
+hipError_t launch_window_tables(const double *xs, int N, int n, int origin, int W, double *e, long long e_len, double *pw, hipStream_t stream);
+inline hipError_t launch_window_tables(const double *xs, int N, int n, int L, double *e, long long e_len, double *pw, hipStream_t stream)
+{
+    return launch_window_tables(xs, N, n, L, 2 * L + 1, e, e_len, pw, stream);
+}
 hipError_t launch_window(const WindowParams &p, hipStream_t stream);
 // ---- the same while the rows slide (xcorr_window_slide.hip; muse_batch_slide_score_windowed): xcorr_window_mfma over the NEW rows
 // -- old row[k .. N) followed by tails[r * k + 0 .. k), a dense M x k device buffer, 16-byte aligned -- which are stored in place on

@@ -582,7 +582,7 @@ static hipError_t launch_small_n(const FusedParams &p, int num_cus, hipStream_t 
             return hipErrorInvalidValue;
         if constexpr (LOGN <= 11) {
             if (p.win) { // the masked argmax, one window for every reference (muse_batch_score_many_in_window)
-                if (p.pair_list || p.win_lpos < 0 || p.win_lneg < 0 || p.win_lpos > (1 << LOGN) / 2 || p.win_lneg > p.win_lpos)
+                if (p.pair_list || p.win_lpos < 0 || p.win_lneg < 0 || p.win_lpos > (1 << LOGN) / 2 || p.win_lneg > (1 << LOGN) / 2 - 1)
                     return hipErrorInvalidValue;
                 if (p.N < (1 << LOGN))
                     hipLaunchKernelGGL((xcorr_fused_small<LOGN, true, true, false, true>), dim3((unsigned)grid), dim3(TPB), 0, stream, p);
@@ -600,7 +600,7 @@ static hipError_t launch_small_n(const FusedParams &p, int num_cus, hipStream_t 
     const long long grid = std::min<long long>(ngroups, (long long)num_cus * (1024 / TPB) * 8);
     if (p.win) { // the masked argmax (muse_batch_score_in_window): n = 512, 1024, 2048
         if constexpr (LOGN <= 11) {
-            if (p.pair_list || p.win_lpos < 0 || p.win_lneg < 0 || p.win_lpos > (1 << LOGN) / 2 || p.win_lneg > p.win_lpos)
+            if (p.pair_list || p.win_lpos < 0 || p.win_lneg < 0 || p.win_lpos > (1 << LOGN) / 2 || p.win_lneg > (1 << LOGN) / 2 - 1)
                 return hipErrorInvalidValue;
             if (p.rows32) {
                 if (p.N < (1 << LOGN))

@@ -22,16 +22,17 @@
 
 namespace muse {
 
-// e[v], v < len: the reference at padded index (pad + v - L) mod n for v < N + 2L, zero behind (the last chunk reads on)
-__global__ __launch_bounds__(256) void window_table_e(const double *__restrict__ xs, int N, int n, int L, long long len,
+// e[v], v < len: the reference at padded index (pad + v - origin) mod n for v < N + W - 1 (row v of the W rows of the product is lag
+// v - origin; the symmetric window: origin = L, W = 2 L + 1), zero behind (the last chunk reads on)
+__global__ __launch_bounds__(256) void window_table_e(const double *__restrict__ xs, int N, int n, int origin, int W, long long len,
                                                       double *__restrict__ e)
 {
     const long long v = (long long)blockIdx.x * 256 + threadIdx.x;
     if (v >= len)
         return;
     double x = 0.0;
-    if (v < (long long)N + 2 * L) {
-        long long idx = ((long long)(n - N) + v - L) % n;
+    if (v < (long long)N + W - 1) {
+        long long idx = ((long long)(n - N) + v - origin) % n;
         if (idx < 0)
             idx += n;
         x = xs[idx];
@@ -58,10 +59,12 @@ __global__ __launch_bounds__(256) void window_table_p(const double *__restrict__
         pw[v] = part[0];
 }
 
-hipError_t launch_window_tables(const double *xs, int N, int n, int L, double *e, long long e_len, double *pw, hipStream_t stream)
+hipError_t launch_window_tables(const double *xs, int N, int n, int origin, int W, double *e, long long e_len, double *pw, hipStream_t stream)
 {
-    window_table_e<<<dim3((unsigned)((e_len + 255) / 256)), dim3(256), 0, stream>>>(xs, N, n, L, e_len, e);
-    window_table_p<<<dim3((unsigned)(2 * L + 1)), dim3(256), 0, stream>>>(e, N, pw);
+    if (origin < 0 || W < origin + 1 || W > 2 * MUSE_LAG_WINDOW_MAX + 1) // (pw holds 2 MUSE_LAG_WINDOW_MAX + 1 sums, a chunk's image WIN_E_TAIL more samples)
+        return hipErrorInvalidValue;
+    window_table_e<<<dim3((unsigned)((e_len + 255) / 256)), dim3(256), 0, stream>>>(xs, N, n, origin, W, e_len, e);
+    window_table_p<<<dim3((unsigned)W), dim3(256), 0, stream>>>(e, N, pw);
     return hipGetLastError();
 }
 
@@ -146,7 +149,7 @@ hipError_t launch_window(const WindowParams &p, hipStream_t stream)
         return hipErrorInvalidValue;
     const dim3 grid((unsigned)blocks), block(WIN_THREADS);
     const bool wide = window_wide(p.rows, p.stride);
-    window_with_tiles(window_tiles(p.L), [&](auto tiles) {
+    window_with_tiles(window_tiles(p), [&](auto tiles) {
         if (wide)
             xcorr_window_mfma<tiles(), true><<<grid, block, 0, stream>>>(p);
         else

@@ -116,14 +116,14 @@ __global__ __launch_bounds__(WIN_THREADS) void xcorr_window_many_mfma(const Wind
         const double *__restrict__ pw = p.pw[ref];
         WindowBest best;
         for (int k = 0; k < plen; k++)
-            window_scan_pos(best, lds, ref * Wv, part * plen + k, c, L, Lneg, st, pw);
+            window_scan_pos(best, lds, ref * Wv, part * plen + k, c, L, Lneg, L, st, pw);
         window_put_best(lds + CAND + (item * 16 + c) * 3, best);
     }
     __syncthreads();
     if (row0 + c < p.M) {
         for (int ref = t >> 4; ref < R; ref += 16) {
             int lag;
-            p.mv[ref][row0 + c] = window_outcome(lds, CAND, ref * parts, parts, ref * Wv, c, L, Lneg, st, p.pw[ref], &lag);
+            p.mv[ref][row0 + c] = window_outcome(lds, CAND, ref * parts, parts, ref * Wv, c, L, Lneg, L, st, p.pw[ref], &lag);
             p.lag[ref][row0 + c] = lag;
         }
     }
@@ -175,7 +175,8 @@ hipError_t launch_window_many(WindowManyParams p, hipStream_t stream)
     if (p.M <= 0)
         return hipSuccess;
     long long blocks;
-    if (window_launch_check(p, &blocks) != hipSuccess || p.R < 1 || p.R > window_many_max_refs(p.L))
+    // (the packed references' windows are symmetric: every table's row v is lag v - L)
+    if (window_launch_check(p, &blocks) != hipSuccess || p.origin != p.L || p.Lneg > p.L || p.R < 1 || p.R > window_many_max_refs(p.L))
         return hipErrorInvalidValue;
     const int tiles = (p.R * (2 * p.L + 1) + 15) / 16;
     p.kc = window_many_kc(p.L, p.R);

@@ -164,7 +164,7 @@ hipError_t launch_window_slide(const WindowParams &p, const double *tails, int k
     if (p.M <= 0)
         return hipSuccess;
     long long blocks;
-    if (window_launch_check(p, &blocks) != hipSuccess)
+    if (window_launch_check(p, &blocks) != hipSuccess || p.origin != p.L || p.Lneg > p.L) // (its callers' windows are symmetric)
         return hipErrorInvalidValue;
     // dense rows (a group's: the slide is defined on them), 1 <= k <= N (k == 0 is launch_window's), tails 16-byte aligned
     if (p.stride != p.N || k < 1 || k > p.N || !tails || !p.rows || ((uintptr_t)tails & 15) != 0)

@@ -125,7 +125,8 @@ hipError_t launch_window_split(const WindowParams &p, int S, double *slabs, hipS
         return hipSuccess;
     const int chunks = (p.N + WIN_KC - 1) / WIN_KC;
     long long blocks;
-    if (window_launch_check(p, &blocks) != hipSuccess || S < 2 || S > chunks || !slabs)
+    // (its callers' windows are symmetric, and the slabs are sized by window_split_slab_doubles(L))
+    if (window_launch_check(p, &blocks) != hipSuccess || p.origin != p.L || p.Lneg > p.L || S < 2 || S > chunks || !slabs)
         return hipErrorInvalidValue;
     const dim3 grid((unsigned)blocks, (unsigned)S), fgrid((unsigned)blocks), block(WIN_THREADS);
     const bool wide = window_wide(p.rows, p.stride);

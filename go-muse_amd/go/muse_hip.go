@@ -540,6 +540,25 @@ func (b *Batch) RunInWindow(groupByLabels []string) error {
 	if es := shardEngines(); es != nil {
 		return fmt.Errorf("RunInWindow runs on one device")
 	}
+	return b.feedInWindow(groupByLabels, false, 0, 0)
+}
+
+// RunInLagRange is RunInWindow for a one-sided or asymmetric window (muse_batch_run_in_lag_range): every series contributes its
+// best match inside the lags lagLo .. lagHi, lagLo <= 0 <= lagHi (a negative lag: the series trails the reference).  One device.
+// Results is fed exactly as RunInWindow feeds it; Results.Update applies the Results' own filters unchanged.
+func (b *Batch) RunInLagRange(groupByLabels []string, lagLo, lagHi int) error {
+	if lagLo > 0 || lagHi < 0 {
+		return fmt.Errorf("RunInLagRange: lagLo <= 0 <= lagHi")
+	}
+	if es := shardEngines(); es != nil {
+		return fmt.Errorf("RunInLagRange runs on one device")
+	}
+	return b.feedInWindow(groupByLabels, true, lagLo, lagHi)
+}
+
+// feedInWindow is what RunInWindow and RunInLagRange share: the label groups, the resident rows, the call (ranged: the lag range
+// lagLo .. lagHi, otherwise the window Results.MaxLag) and the feed of Results in group order.
+func (b *Batch) feedInWindow(groupByLabels []string, ranged bool, lagLo, lagHi int) error {
 	labelValuesSet := b.Comparison.indexLabelValues(groupByLabels)
 	if len(labelValuesSet) == 0 {
 		return nil
@@ -595,8 +614,14 @@ func (b *Batch) RunInWindow(groupByLabels []string) error {
 	score := make([]C.double, top)
 	var cnt C.int32_t
 	var mean C.double
-	st := C.muse_batch_run_in_window(b.batch, &gid[0], C.int32_t(G), C.int32_t(r.MaxLag), C.int32_t(topN),
-		C.double(threshold), C.int32_t(sign), 1, &idx[0], &lag[0], &score[0], &cnt, &mean)
+	var st C.int
+	if ranged {
+		st = C.muse_batch_run_in_lag_range(b.batch, &gid[0], C.int32_t(G), C.int32_t(lagLo), C.int32_t(lagHi), C.int32_t(topN),
+			C.double(threshold), C.int32_t(sign), 1, &idx[0], &lag[0], &score[0], &cnt, &mean)
+	} else {
+		st = C.muse_batch_run_in_window(b.batch, &gid[0], C.int32_t(G), C.int32_t(r.MaxLag), C.int32_t(topN),
+			C.double(threshold), C.int32_t(sign), 1, &idx[0], &lag[0], &score[0], &cnt, &mean)
+	}
 	if err := hipError(st); err != nil {
 		return err
 	}

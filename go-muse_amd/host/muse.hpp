@@ -1101,6 +1101,33 @@ public:
             throw Error(MUSE_ERR_INVALID, "RunInWindow: MaxLag < 0");
         if (!engines_.empty())
             throw Error(MUSE_ERR_UNSUPPORTED, "RunInWindow runs on one device");
+        const int32_t max_lag = (int32_t)Results_->MaxLag;
+        feed_in_window(groupByLabels, [&](const int32_t *gid, int32_t G, int32_t top, double threshold, int32_t sign, int64_t *idx,
+                                          int32_t *lag, double *score, int32_t *cnt, double *mean) {
+            return muse_batch_run_in_window(batch_, gid, G, max_lag, top, threshold, sign, 1, idx, lag, score, cnt, mean);
+        });
+    }
+
+    // RunInWindow for a one-sided or asymmetric window (muse_batch_run_in_lag_range): every series contributes its best match
+    // inside the lags lagLo .. lagHi, lagLo <= 0 <= lagHi (a negative lag: the series trails the reference).  One device.  Results
+    // is fed exactly as RunInWindow feeds it; Results.Update applies the Results' own filters unchanged.
+    void RunInLagRange(const std::vector<std::string> &groupByLabels, int lagLo, int lagHi)
+    {
+        if (lagLo > 0 || lagHi < 0)
+            throw Error(MUSE_ERR_INVALID, "RunInLagRange: lagLo <= 0 <= lagHi");
+        if (!engines_.empty())
+            throw Error(MUSE_ERR_UNSUPPORTED, "RunInLagRange runs on one device");
+        feed_in_window(groupByLabels, [&](const int32_t *gid, int32_t G, int32_t top, double threshold, int32_t sign, int64_t *idx,
+                                          int32_t *lag, double *score, int32_t *cnt, double *mean) {
+            return muse_batch_run_in_lag_range(batch_, gid, G, (int32_t)lagLo, (int32_t)lagHi, top, threshold, sign, 1, idx, lag, score,
+                                               cnt, mean);
+        });
+    }
+
+    // what RunInWindow and RunInLagRange share: the label groups, the resident rows, the call (one of the library's _run_in_ entry
+    // points) and the feed of Results in group order
+    template <class Call> void feed_in_window(const std::vector<std::string> &groupByLabels, Call call)
+    {
         std::vector<int32_t> gid;
         std::vector<LabelsPtr> lvs;
         const std::function<void()> side = [&] { lvs = Comparison->indexLabelValues(groupByLabels, &gid); };
@@ -1116,9 +1143,8 @@ public:
         std::vector<double> score(cap);
         int32_t cnt = 0;
         double mean = 0;
-        check(muse_batch_run_in_window(batch_, gid.data(), (int32_t)lvs.size(), (int32_t)Results_->MaxLag, top,
-                                       exact ? 0.0 : Results_->Threshold, exact ? 0 : (int32_t)Results_->Filter, 1, idx.data(),
-                                       lag.data(), score.data(), &cnt, &mean));
+        check(call(gid.data(), (int32_t)lvs.size(), top, exact ? 0.0 : Results_->Threshold, exact ? 0 : (int32_t)Results_->Filter,
+                   idx.data(), lag.data(), score.data(), &cnt, &mean));
         std::vector<int> order(cnt);
         for (int i = 0; i < cnt; i++)
             order[i] = i;

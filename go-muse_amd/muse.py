@@ -458,8 +458,40 @@ class DeviceBatch:
         c = cnt.value
         return o_s[:c].copy(), o_l[:c].copy(), o_v[:c].copy(), float(mean.value)
 
+    def score_in_lag_range(self, lag_lo, lag_hi):
+        """muse_batch_score_in_lag_range: an all-scores pass with every series' best match inside the lags lag_lo .. lag_hi
+        (lag_lo <= 0 <= lag_hi; negative lags: the series trails the reference).  Up to 127 lags on float64 groups: the direct
+        product over a table that starts at lag_lo; wider, or float32 storage: the transform kernels with a masked argmax (FFT
+        lengths 512 ... 4096).  (-L, L) is score_in_window(L).  This batch's own lag window must be off (or that L) and is not
+        touched.  Results: read_scores()."""
+        B.check(B.load().muse_batch_score_in_lag_range(self._h, int(lag_lo), int(lag_hi)))
+
+    def scores_in_lag_range(self, lag_lo, lag_hi):
+        """score_in_lag_range + copy back: (lag, mv)"""
+        self.score_in_lag_range(lag_lo, lag_hi)
+        return self.read_scores()
+
+    def run_in_lag_range(self, lag_lo, lag_hi, group_id=None, G=0, top_n=20, threshold=0.0, sign_filter=0, abs_scores=True):
+        """muse_batch_run_in_lag_range: score_in_lag_range followed by Batch.Run's selection with Results.MaxLag =
+        max(-lag_lo, lag_hi); -> (series, lag, score, mean_abs) as run()"""
+        cap = max(int(top_n), 1)
+        o_s = np.zeros(cap, dtype=np.int64)
+        o_l = np.zeros(cap, dtype=np.int32)
+        o_v = np.zeros(cap)
+        cnt, mean = ctypes.c_int32(0), ctypes.c_double(0)
+        gid = None
+        if group_id is not None:
+            gid = np.ascontiguousarray(group_id, dtype=np.int32)
+        B.check(B.load().muse_batch_run_in_lag_range(
+            self._h, B.i32ptr(gid) if gid is not None else None, int(G), int(lag_lo), int(lag_hi), int(top_n), float(threshold),
+            int(sign_filter), 1 if abs_scores else 0, B.i64ptr(o_s), B.i32ptr(o_l), B.dptr(o_v), ctypes.byref(cnt),
+            ctypes.byref(mean)))
+        c = cnt.value
+        return o_s[:c].copy(), o_l[:c].copy(), o_v[:c].copy(), float(mean.value)
+
     def last_in_window_path(self):
-        """test hook: MUSE_IN_WINDOW_* of the last score_in_window / run_in_window, 0 after any other scoring pass"""
+        """test hook: MUSE_IN_WINDOW_* of the last score_in_window / run_in_window / score_in_lag_range / run_in_lag_range, 0 after
+        any other scoring pass"""
         w = ctypes.c_int32(0)
         B.check(B.load().muse_test_last_in_window_path(self._h, ctypes.byref(w)))
         return int(w.value)
@@ -848,6 +880,14 @@ def in_window_plan(N, f32, max_lag):
     (f32: float32 storage) and window max_lag"""
     path = ctypes.c_int32(-1)
     B.check(B.load().muse_test_in_window_plan(int(N), 1 if f32 else 0, int(max_lag), ctypes.byref(path)))
+    return int(path.value)
+
+
+def lag_range_plan(N, f32, lag_lo, lag_hi):
+    """muse_test_lag_range_plan (no device): MUSE_IN_WINDOW_* -- the pass score_in_lag_range takes for series of N samples
+    (f32: float32 storage) and the lags lag_lo .. lag_hi"""
+    path = ctypes.c_int32(-1)
+    B.check(B.load().muse_test_lag_range_plan(int(N), 1 if f32 else 0, int(lag_lo), int(lag_hi), ctypes.byref(path)))
     return int(path.value)
 
 
@@ -1426,6 +1466,31 @@ class Batch:
             idx, lag, score, _ = self._batch().run_in_window(r.MaxLag, gid, G, G, 0.0, SignFilter_ANY, abs_scores=True)
         else:
             idx, lag, score, _ = self._batch().run_in_window(r.MaxLag, gid, G, r.TopN, r.Threshold, r.SignFilter, abs_scores=True)
+        order = np.argsort(gid[idx], kind="stable")
+        for k in order:
+            r.Update(Score(series[int(idx[k])].Labels(), int(lag[k]), float(score[k])))
+        return None
+
+    def RunInLagRange(self, groupByLabels, lagLo, lagHi):
+        """RunInWindow for a one-sided or asymmetric window (muse_batch_run_in_lag_range): every series contributes its best match
+        inside the lags lagLo .. lagHi, lagLo <= 0 <= lagHi (negative lags: the series trails the reference).  One device.  Results
+        is fed exactly as RunInWindow feeds it, and Results.Update applies the Results' own filters unchanged."""
+        comp = self.Comparison
+        labelValuesSet = comp.indexLabelValues(groupByLabels)
+        if not labelValuesSet:
+            return None
+        if self._engines:
+            raise MuseError(B.MUSE_ERR_UNSUPPORTED, "RunInLagRange runs on one device")
+        r = self.Results
+        if lagLo > 0 or lagHi < 0:
+            raise MuseError(B.MUSE_ERR_INVALID, "RunInLagRange needs lagLo <= 0 <= lagHi")
+        series = comp._series_list()
+        gid = comp._group_ids()
+        G = len(labelValuesSet)
+        if G <= EXACT_FEED_MAX_GROUPS:
+            idx, lag, score, _ = self._batch().run_in_lag_range(lagLo, lagHi, gid, G, G, 0.0, SignFilter_ANY, abs_scores=True)
+        else:
+            idx, lag, score, _ = self._batch().run_in_lag_range(lagLo, lagHi, gid, G, r.TopN, r.Threshold, r.SignFilter, abs_scores=True)
         order = np.argsort(gid[idx], kind="stable")
         for k in order:
             r.Update(Score(series[int(idx[k])].Labels(), int(lag[k]), float(score[k])))

@@ -375,6 +375,42 @@ int muse_batch_score_in_window(muse_batch *b, int32_t max_lag);
 int muse_batch_run_in_window(muse_batch *b, const int32_t *group_id, int32_t G, int32_t max_lag, int32_t top_n,
                              double threshold, int32_t sign_filter, int32_t abs_scores, int64_t *out_series,
                              int32_t *out_lag, double *out_score, int32_t *out_count, double *out_mean_abs);
+/* ONE-SIDED AND ASYMMETRIC WINDOWS.  muse_batch_score_in_lag_range is an all-scores pass whose per-series (lag, mv) is the best
+ * match inside the lags lag_lo .. lag_hi, lag_lo <= 0 <= lag_hi.  A negative lag means the series trails the reference, a positive
+ * one that it leads it (xcorr.go:103), so (lag_lo, 0) and (0, lag_hi) answer two different questions; filtering the symmetric
+ * window's answer afterwards loses every series whose strongest peak lies on the other side.  Definition, per series, with n the FFT
+ * length, hi = min(lag_hi, n/2), lo = max(lag_lo, -(n/2 - 1)), cc[0 .. n-1] the slice xCorrWithX computes and lag(i) as at
+ * muse_batch_set_lag_window: maxAbsIndex runs over the indices 0 .. hi and then n + lo .. n - 1 in ascending order (no wrapped
+ * index when lo == 0), from (0, 0.0), with the strict '>' -- the first index wins ties, a window of zeros or NaN gives (0, cc[0]), a
+ * NaN / Inf series (0, NaN), a series with sigma == 0 (0, 0.0): the rules of the symmetric window.  hi == n/2 with lo == -(n/2 - 1)
+ * is every lag: the unwindowed result.  lag_lo == -lag_hi is by definition muse_batch_score_in_window(b, lag_hi), bit for bit on
+ * every path.  Results land in the batch's score buffers (muse_batch_read_scores); the pass is exact fp64 and never screened
+ * (muse_batch_last_run_path: MUSE_RUN_PATH_FP64); the batch's own lag_window must be off, or on with lag_lo == -lag_hi equal to it,
+ * and is not touched.  Which pass runs is decided from the length, the storage and the W = hi - lo + 1 lags of the clipped range:
+ *   the range is every lag, any length, any storage                  : muse_batch_score's pass with the window off, bit for bit
+ *   float64 group, W <= 2 MUSE_LAG_WINDOW_MAX + 1, up to 65536 samples : the direct product over a table that starts at lag lo: W lag
+ *                                                                      rows, ceil(W / 16) accumulator tiles (a one-sided window
+ *                                                                      half those of the symmetric one, and up to 126 lags wide).
+ *                                                                      The value at a lag has the bits the symmetric window's
+ *                                                                      direct product gives at that lag
+ *   FFT length 512, 1024, 2048 or 4096, W wider or float32 storage   : the transform kernels with their argmax restricted to the
+ *                                                                      range (the two bounds set independently); always reads the
+ *                                                                      rows: the group's spectrum cache is neither used, built
+ *                                                                      nor counted towards
+ *   anything else                                                    : MUSE_ERR_UNSUPPORTED, nothing changed
+ * MUSE_ERR_INVALID, nothing changed (everything is checked before anything is enqueued; the scores of the last pass stay): a NULL
+ * batch, lag_lo > 0 or lag_hi < 0 (a range that excludes lag 0: the (0, cc[0]) fallback needs index 0), a batch whose own window is
+ * on and is not this range.
+ * muse_batch_run_in_lag_range is that pass followed by Batch.Run's selection over the scores, outputs as muse_batch_run, with
+ * Results.MaxLag = max(-lag_lo, lag_hi): every lag of the range passes the lag filter.  A sign_filter outside -1 .. 1 or a negative
+ * G with group_id is refused before anything is scored.
+ * Limits: ranges that exclude lag 0; the many-references, Muse.Run-rows (muse_batch_run_rows_windowed ...) and slide forms of a range;
+ * the multi-device layer; ranges of more than 127 lags, or float32 storage, outside FFT lengths 512 ... 4096; series longer than
+ * 65536 samples (other than the whole range); narrow float64 ranges are never routed to the masked pass. */
+int muse_batch_score_in_lag_range(muse_batch *b, int32_t lag_lo, int32_t lag_hi);
+int muse_batch_run_in_lag_range(muse_batch *b, const int32_t *group_id, int32_t G, int32_t lag_lo, int32_t lag_hi,
+                                int32_t top_n, double threshold, int32_t sign_filter, int32_t abs_scores,
+                                int64_t *out_series, int32_t *out_lag, double *out_score, int32_t *out_count, double *out_mean_abs);
 /* THE SLIDE AND THE PASS OF ANY WINDOW IN ONE CALL.  muse_batch_slide_score_in_window is equivalent to
  *   muse_group_slide(the batch's group, 0, M, tails, k, tail_stride)  followed by  muse_batch_score_in_window(b, max_lag):
  * afterwards the group holds the slid rows -- BIT FOR BIT those of muse_group_slide -- and muse_batch_read_scores returns, BIT FOR

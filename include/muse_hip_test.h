@@ -126,9 +126,15 @@ int muse_test_in_window_plan(int32_t N, int32_t f32_storage, int32_t max_lag, in
 /* on = 1: muse_batch_score_in_window sends float64 windows up to MUSE_LAG_WINDOW_MAX through the masked transform kernels too, where
  * the length has them (FFT lengths 512 ... 4096) -- cross-checks of the two mechanisms and tools/in_window_bench.py; 0 (default): the table. */
 int muse_test_in_window_force_transform(muse_ctx *ctx, int32_t on);
-/* The path (MUSE_IN_WINDOW_*) the batch's scores came by if its last scoring pass was muse_batch_score_in_window / _run_in_window;
- * 0 after any other scoring pass. */
+/* The path (MUSE_IN_WINDOW_*) the batch's scores came by if its last scoring pass was muse_batch_score_in_window / _run_in_window
+ * or muse_batch_score_in_lag_range / _run_in_lag_range; 0 after any other scoring pass. */
 int muse_test_last_in_window_path(muse_batch *b, int32_t *path);
+/* muse_batch_score_in_lag_range's dispatch, a pure host function (no device needed): the pass that scores series of N >= 2 samples
+ * (f32_storage: a float32-storage group) inside the lags lag_lo .. lag_hi -- *path = MUSE_IN_WINDOW_PLAIN (the clipped range is
+ * every lag), _MFMA (the direct product: float64, at most 2 MUSE_LAG_WINDOW_MAX + 1 lags, up to 65536 samples), _MASKED (the
+ * transform kernels with a masked argmax) or _UNSUPPORTED.  For lag_lo == -lag_hi it is muse_test_in_window_plan(N, ., lag_hi).
+ * MUSE_ERR_INVALID for N < 2, lag_lo > 0, lag_hi < 0 or a NULL out pointer. */
+int muse_test_lag_range_plan(int32_t N, int32_t f32_storage, int32_t lag_lo, int32_t lag_hi, int32_t *path);
 /* muse_batch_score_many_in_window's dispatch, a pure host function (no device needed): the pass that scores R >= 1 references against
  * series of N >= 2 samples (f32_storage: a float32-storage group) inside +-max_lag >= 0 -- *path = MUSE_IN_WINDOW_PLAIN
  * (muse_batch_score_many), _MFMA (muse_batch_score_many_windowed), _MASKED (ONE many-references pass of the transform kernels with a
