@@ -489,6 +489,21 @@ int window_tables(muse_batch *b, int L, PoolBuf<double> &e, PoolBuf<double> &pw,
 // the key a lag range's tables (origin = its lags below zero, W rows) are cached under: no window +-L (L <= MUSE_LAG_WINDOW_MAX) has it,
 // so a symmetric pass never takes a range's tables or the other way round
 inline int32_t window_range_key(int origin, int W) { return 0x10000 + origin * 256 + W; }
+// a lag range lag_lo .. lag_hi (lag_lo <= 0 <= lag_hi) as the passes take it at FFT length n: hi = min(lag_hi, n / 2) lags above zero,
+// lneg = min(-lag_lo, n / 2 - 1) below
+struct LagRange {
+    int hi, lneg;
+    int W() const { return hi + lneg + 1; }
+};
+inline LagRange clip_lag_range(int64_t n, int32_t lag_lo, int32_t lag_hi)
+{
+    return LagRange{(int)std::min<int64_t>(lag_hi, n / 2), (int)std::min<int64_t>(-(int64_t)lag_lo, n / 2 - 1)};
+}
+// capi_window.hip: b's own tables (win_e / win_pw) of a lag range whose table has W rows and starts `origin` lags below zero, once
+// per range (cached under window_range_key)
+int window_range_tables(muse_batch *b, int origin, int W, hipStream_t st);
+// capi_window.hip: muse_batch_score_in_lag_range's dispatch (MUSE_IN_WINDOW_*), a pure host function
+int lag_range_plan(int32_t N, bool f32, int32_t lag_lo, int32_t lag_hi, bool force_transform);
 muse::WindowParams window_params(const muse_batch *b, int L, const double *e, const double *pw);
 // the lags a window +-L holds below zero at FFT length n: index n / 2 is lag +n/2 (xcorr.go:192-194), it is scanned once
 inline int window_lneg(int L, int n) { return 2 * L == n ? L - 1 : L; }
@@ -534,8 +549,11 @@ int check_batch_list(muse_batch *const *bs, int32_t R);
 enum ManyKind { MANY_NONE, MANY_SMALL, MANY_MULTI, MANY_LONG, MANY_REAL };
 ManyKind many_kind(muse_batch *const *bs, int32_t R);
 // ONE pass of the `kind` kernels over the rows for every batch of a checked list; win_L >= 0: the argmax masked to +-win_L (SMALL at
-// n <= 2048 and MULTI only)
-int score_many_pass(muse_batch *const *bs, int32_t R, ManyKind kind, int win_L);
+// n <= 2048 and MULTI only), or with win_lneg >= 0 to the lag range -win_lneg .. win_L, the two bounds independent of each other
+int score_many_pass(muse_batch *const *bs, int32_t R, ManyKind kind, int win_L, int win_lneg = -1);
+// capi_window_many.hip: the direct product for a checked list of float64 batches with time-domain references, packed launches where
+// the planner packs; range == nullptr: the window +-max_lag, otherwise that (clipped) lag range for batches of one length
+int score_many_direct(muse_batch *const *bs, int32_t R, int32_t max_lag, const LagRange *range);
 // the Run of every batch of a scored list: run_select, then emit into row r of the caller's arrays
 int run_many_select(muse_batch *const *bs, int32_t R, const int32_t *group_id, int32_t G, int32_t max_lag, int32_t top_n,
                     double threshold, int32_t sign_filter, int32_t abs_scores, bool prescreened, int64_t *out_series,

@@ -90,12 +90,12 @@ ManyKind many_kind(muse_batch *const *bs, int32_t R)
     return small_n ? MANY_SMALL : real_n ? MANY_REAL : long_n ? MANY_LONG : MANY_MULTI;
 }
 
-int score_many_pass(muse_batch *const *bs, int32_t R, ManyKind kind, int win_L)
+int score_many_pass(muse_batch *const *bs, int32_t R, ManyKind kind, int win_L, int win_lneg)
 {
     muse_batch *b0 = bs[0];
     muse_ctx *ctx = b0->ctx;
     const bool small_n = kind == MANY_SMALL, real_n = kind == MANY_REAL, long_n = kind == MANY_LONG;
-    const bool masked = win_L >= 0;
+    const bool masked = win_L >= 0, range = masked && win_lneg >= 0; // (a lag range: the two bounds as the caller clipped them)
     // the unmasked pass is what each batch's own setting takes too: it says so from the start.  The masked pass is an argument of
     // its call: it names itself once its launches are enqueued (below)
     for (int r = 0; r < R && !masked; r++)
@@ -139,7 +139,9 @@ int score_many_pass(muse_batch *const *bs, int32_t R, ManyKind kind, int win_L)
     p.c1_many = (const double *const *)(t + 3 * R);
     p.zscratch = ctx->zscratch.p; // (read at n = 16384 only)
     p.zslots = (int)(ctx->zscratch.cap / 4096);
-    if (masked)
+    if (range)
+        set_window(p, win_L, win_lneg);
+    else if (masked)
         set_window(p, win_L);
     HIP_TRY(b0->ovf_list.ensure(ctx, 2 * p.npairs, b0->stream()));
     p.ovf_count = b0->ovf_count;
@@ -175,7 +177,9 @@ int score_many_pass(muse_batch *const *bs, int32_t R, ManyKind kind, int win_L)
         FusedParams q = base_params(bs[r]);
         q.pair_list = b0->ovf_list.p;
         q.pair_count = b0->ovf_count;
-        if (masked) // the redone pairs keep their window (the WIN build of the redo kernel)
+        if (range) // the redone pairs keep their window (the WIN build of the redo kernel)
+            set_window(q, win_L, win_lneg);
+        else if (masked)
             set_window(q, win_L);
         if (long_n) { // (the four-step kernel that isolates and rescales first, as behind a single long-series pass)
             q.npairs = std::min<long long>(q.npairs, (long long)ctx->num_cus * STOCKHAM_GLOBAL_WGS_PER_CU);
@@ -192,7 +196,8 @@ int score_many_pass(muse_batch *const *bs, int32_t R, ManyKind kind, int win_L)
         if (masked) { // as muse_batch_score_in_window leaves a batch; the unmasked pass, as muse_batch_score, leaves what the last Run did alone
             b->last_path = MUSE_RUN_PATH_FP64;
             b->last_screened = false;
-            b->origin = ScoreOrigin::in_window(MUSE_IN_WINDOW_MASKED, win_L, ScoreOrigin::MANY);
+            b->origin = range ? ScoreOrigin::in_lag_range(MUSE_IN_WINDOW_MASKED, win_L, win_lneg, ScoreOrigin::MANY)
+                              : ScoreOrigin::in_window(MUSE_IN_WINDOW_MASKED, win_L, ScoreOrigin::MANY);
         }
     }
     return MUSE_OK;

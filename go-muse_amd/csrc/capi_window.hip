@@ -304,14 +304,19 @@ extern "C" int muse_batch_run_in_window(muse_batch *b, const int32_t *group_id, 
 }
 
 // ---- one-sided and asymmetric windows: the best match inside lag_lo .. lag_hi, lag_lo <= 0 <= lag_hi (muse_batch_score_in_lag_range)
-// The range as the passes take it: hi = min(lag_hi, n / 2) lags above zero, lneg = min(-lag_lo, n / 2 - 1) below.
-struct LagRange {
-    int hi, lneg;
-    int W() const { return hi + lneg + 1; }
-};
-static LagRange clip_lag_range(int64_t n, int32_t lag_lo, int32_t lag_hi)
+// The range as the passes take it: clip_lag_range (capi_internal.h).  Its tables, the batch's own, start at its lowest lag:
+int window_range_tables(muse_batch *b, int origin, int W, hipStream_t st)
 {
-    return LagRange{(int)std::min<int64_t>(lag_hi, n / 2), (int)std::min<int64_t>(-(int64_t)lag_lo, n / 2 - 1)};
+    const int32_t key = window_range_key(origin, W);
+    if (b->win_L == key)
+        return MUSE_OK;
+    b->win_L = -1;
+    const long long e_len = window_e_len(b->N);
+    HIP_TRY(b->win_e.ensure(b->ctx, e_len, st));
+    HIP_TRY(b->win_pw.ensure(b->ctx, 2 * MUSE_LAG_WINDOW_MAX + 1, st));
+    HIP_TRY(launch_window_tables(b->xs, b->N, b->n, origin, W, b->win_e.p, e_len, b->win_pw.p, st));
+    b->win_L = key;
+    return MUSE_OK;
 }
 // The dispatch, a pure host function: which pass scores series of N samples (float32 storage or not) inside lag_lo .. lag_hi; W = the
 // lags of the clipped range.  For lag_lo == -lag_hi it is in_window_plan's table row for row.
@@ -320,7 +325,7 @@ static LagRange clip_lag_range(int64_t n, int32_t lag_lo, int32_t lag_hi)
 //                                                       and the length has masked kernels)
 //   n in {512, 1024, 2048, 4096}, wider or float32    : the transform kernels with a masked argmax, the two bounds set independently
 //   anything else                                     : not built
-static int lag_range_plan(int32_t N, bool f32, int32_t lag_lo, int32_t lag_hi, bool force_transform)
+int lag_range_plan(int32_t N, bool f32, int32_t lag_lo, int32_t lag_hi, bool force_transform)
 {
     const int64_t n = muse_next_pow2((double)N);
     const LagRange r = clip_lag_range(n, lag_lo, lag_hi);
@@ -382,15 +387,9 @@ extern "C" int muse_batch_score_in_lag_range(muse_batch *b, int32_t lag_lo, int3
         rc = ensure_scores(b);
         if (rc)
             return rc;
-        const int32_t key = window_range_key(r.lneg, r.W());
-        if (b->win_L != key) {
-            b->win_L = -1;
-            const long long e_len = window_e_len(b->N);
-            HIP_TRY(b->win_e.ensure(ctx, e_len, st));
-            HIP_TRY(b->win_pw.ensure(ctx, 2 * MUSE_LAG_WINDOW_MAX + 1, st));
-            HIP_TRY(launch_window_tables(b->xs, b->N, b->n, r.lneg, r.W(), b->win_e.p, e_len, b->win_pw.p, st));
-            b->win_L = key;
-        }
+        rc = window_range_tables(b, r.lneg, r.W(), st);
+        if (rc)
+            return rc;
         WindowParams p = window_params(b, r.hi, b->win_e.p, b->win_pw.p);
         p.Lneg = r.lneg;
         p.origin = r.lneg;

@@ -6,17 +6,15 @@
 
 using namespace muse;
 
-// test hook: the planner alone (xcorr_window_many.hip), no device
-extern "C" int muse_test_window_many_plan(int32_t R, int32_t L, int32_t *launches, int32_t *launch_of, int32_t *tiles_of,
-                                          int32_t *max_refs, int32_t *img_of, int32_t *kc_of)
+// test hooks: the planner alone (xcorr_window_many.hip), no device; W = the rows of a reference's table
+static void plan_rows(int32_t R, int32_t W, int32_t *launches, int32_t *launch_of, int32_t *tiles_of, int32_t *max_refs, int32_t *img_of,
+                      int32_t *kc_of)
 {
-    if (R < 1 || L < 0 || L > MUSE_LAG_WINDOW_MAX || !launches)
-        return fail(MUSE_ERR_INVALID, "window plan: R >= 1, 0 <= L <= %d", MUSE_LAG_WINDOW_MAX);
     std::vector<int> of((size_t)R), tiles((size_t)R);
-    const int n = window_many_plan(R, L, of.data(), tiles.data());
+    const int n = window_many_plan(R, W, of.data(), tiles.data());
     *launches = n;
     if (max_refs)
-        *max_refs = window_many_max_refs(L);
+        *max_refs = window_many_max_refs(W);
     std::vector<int> refs((size_t)n, 0);
     for (int r = 0; r < R; r++) {
         refs[(size_t)of[(size_t)r]]++;
@@ -24,14 +22,31 @@ extern "C" int muse_test_window_many_plan(int32_t R, int32_t L, int32_t *launche
             launch_of[r] = of[(size_t)r];
     }
     for (int l = 0; l < n; l++) {
-        const int kc = refs[(size_t)l] > 1 ? window_many_kc(L, refs[(size_t)l]) : WIN_KC; // (one reference: xcorr_window_mfma's chunk)
+        const int kc = refs[(size_t)l] > 1 ? window_many_kc(W, refs[(size_t)l]) : WIN_KC; // (one reference: xcorr_window_mfma's chunk)
         if (tiles_of)
             tiles_of[l] = tiles[(size_t)l];
         if (kc_of)
             kc_of[l] = kc;
         if (img_of)
-            img_of[l] = refs[(size_t)l] > 1 ? window_many_img(L, kc) : WIN_KC + WIN_E_TAIL;
+            img_of[l] = refs[(size_t)l] > 1 ? window_many_img(W, kc) : WIN_KC + WIN_E_TAIL;
     }
+}
+
+extern "C" int muse_test_window_many_plan(int32_t R, int32_t L, int32_t *launches, int32_t *launch_of, int32_t *tiles_of,
+                                          int32_t *max_refs, int32_t *img_of, int32_t *kc_of)
+{
+    if (R < 1 || L < 0 || L > MUSE_LAG_WINDOW_MAX || !launches)
+        return fail(MUSE_ERR_INVALID, "window plan: R >= 1, 0 <= L <= %d", MUSE_LAG_WINDOW_MAX);
+    plan_rows(R, 2 * L + 1, launches, launch_of, tiles_of, max_refs, img_of, kc_of);
+    return MUSE_OK;
+}
+
+extern "C" int muse_test_window_many_plan_rows(int32_t R, int32_t W, int32_t *launches, int32_t *launch_of, int32_t *tiles_of,
+                                               int32_t *max_refs, int32_t *img_of, int32_t *kc_of)
+{
+    if (R < 1 || W < 1 || W > 2 * MUSE_LAG_WINDOW_MAX + 1 || !launches)
+        return fail(MUSE_ERR_INVALID, "window plan: R >= 1, 1 <= W <= %d", 2 * MUSE_LAG_WINDOW_MAX + 1);
+    plan_rows(R, W, launches, launch_of, tiles_of, max_refs, img_of, kc_of);
     return MUSE_OK;
 }
 
@@ -50,9 +65,18 @@ extern "C" int muse_batch_score_many_windowed(muse_batch *const *bs, int32_t R, 
         if (rc)
             return rc;
     }
+    return score_many_direct(bs, R, max_lag, nullptr);
+}
+
+// The direct product for a checked list, in as few launches as the planner gives.  range == nullptr: the window +-max_lag, each
+// batch's tables under win_L = L as score_windowed caches them.  Otherwise the lag range -range->lneg .. range->hi, clipped to the
+// (shared) FFT length by the caller: tables whose row v is lag v - lneg, under window_range_key as muse_batch_score_in_lag_range
+// caches them -- the packed and the single pass serve each other's tables, and neither key is ever the other kind's.
+int score_many_direct(muse_batch *const *bs, int32_t R, int32_t max_lag, const LagRange *range)
+{
     muse_batch *b0 = bs[0];
     muse_ctx *ctx = b0->ctx;
-    rc = use_device(ctx);
+    int rc = use_device(ctx);
     if (rc)
         return rc;
     rc = group_ready(b0->g);
@@ -68,24 +92,26 @@ extern "C" int muse_batch_score_many_windowed(muse_batch *const *bs, int32_t R, 
             return rc;
     }
     // one window for the pass: batches of one group share N, and with it (muse_batch_create) the FFT length; a list that does
-    // not is scored reference by reference
+    // not is scored reference by reference (a range's caller has sent such a list elsewhere: its clipping is per length)
     bool same = true;
     for (int r = 1; r < R; r++)
         same = same && bs[r]->N == b0->N && bs[r]->n == b0->n;
-    const int L = std::min(max_lag, b0->n / 2);
+    if (range && !same)
+        return fail(MUSE_ERR_INVALID, "a packed lag range needs batches of one length");
+    const int L = range ? range->hi : std::min(max_lag, b0->n / 2);
+    const int W = range ? range->W() : 2 * L + 1;
     std::vector<int> launch_of((size_t)R), tiles_of((size_t)R);
     int launches = R;
     if (same) {
-        launches = window_many_plan(R, L, launch_of.data(), tiles_of.data());
+        launches = window_many_plan(R, W, launch_of.data(), tiles_of.data());
     } else {
         for (int r = 0; r < R; r++)
             launch_of[(size_t)r] = r;
     }
-    // each batch's tables, cached under win_L exactly as score_windowed caches them: the same buffers serve both forms
+    // each batch's tables, cached under win_L exactly as the single form caches them: the same buffers serve both forms
     for (int r = 0; r < R; r++) {
         muse_batch *b = bs[r];
-        const int Lb = std::min(max_lag, b->n / 2);
-        rc = window_tables(b, Lb, b->win_e, b->win_pw, &b->win_L, st);
+        rc = range ? window_range_tables(b, range->lneg, W, st) : window_tables(b, std::min(max_lag, b->n / 2), b->win_e, b->win_pw, &b->win_L, st);
         if (rc)
             return rc;
     }
@@ -113,8 +139,11 @@ extern "C" int muse_batch_score_many_windowed(muse_batch *const *bs, int32_t R, 
         while (r1 < R && launch_of[(size_t)r1] == launch_of[(size_t)r0])
             r1++;
         muse_batch *b = bs[r0];
-        const int Lb = std::min(max_lag, b->n / 2);
-        const WindowParams p1 = window_params(b, Lb, b->win_e.p, b->win_pw.p);
+        WindowParams p1 = window_params(b, range ? L : std::min(max_lag, b->n / 2), b->win_e.p, b->win_pw.p);
+        if (range) { // (muse_batch_score_in_lag_range's shape)
+            p1.Lneg = range->lneg;
+            p1.origin = range->lneg;
+        }
         if (r1 - r0 == 1) { // a reference that fills its launch alone: the single-reference kernel
             HIP_TRY(launch_window(p1, st));
         } else {
@@ -131,8 +160,11 @@ extern "C" int muse_batch_score_many_windowed(muse_batch *const *bs, int32_t R, 
             bs[r]->scores_exact = true;
             bs[r]->last_path = MUSE_RUN_PATH_FP64;
             bs[r]->last_screened = false;
-            // (a reference alone in its launch: the single-reference kernel, named as before the pass by the batch's own setting)
-            bs[r]->origin = r1 - r0 > 1 ? ScoreOrigin::packed(tiles_of[(size_t)launch_of[(size_t)r0]]) : ScoreOrigin{};
+            // (a reference alone in its launch: the single-reference kernel, named as before the pass by the batch's own setting, or as
+            // the single range pass names it)
+            bs[r]->origin = r1 - r0 > 1 ? ScoreOrigin::packed(tiles_of[(size_t)launch_of[(size_t)r0]])
+                            : range     ? ScoreOrigin::in_lag_range(MUSE_IN_WINDOW_MFMA, range->hi, range->lneg)
+                                        : ScoreOrigin{};
         }
         r0 = r1;
     }

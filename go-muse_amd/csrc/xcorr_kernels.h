@@ -230,20 +230,21 @@ constexpr int WINM_MAX_TILES = 8;       // accumulator tiles of a launch: 128 pa
 constexpr int WINM_PACK_MAX_ROWS = 48;   // wider windows (four tiles per reference) are not packed: one launch per reference
 constexpr int WINM_IMG_DOUBLES = 4608;  // LDS budget of a launch's staged reference images (36 KB: four workgroups per CU)
 struct WindowManyParams : WindowShape {
-    int R;                    // references of this launch: R (2 L + 1) <= 16 WINM_MAX_TILES
+    int R;                    // references of this launch: R W <= 16 WINM_MAX_TILES, W = origin + L + 1 the rows of each one's table
     const double *const *e;   // [R] each reference's WindowParams::e   (the four tables: device memory)
     const double *const *pw;  // [R] each reference's WindowParams::pw
     double *const *mv;        // [R] out: each reference's M signed values
     int *const *lag;          // [R] out: each reference's M lags
     int kc, img, buf, parts;  // filled in by launch_window_many: chunk length, image stride, doubles of the image / tile region, scan parts per reference
 };
-// the planner (pure host functions): image stride for window L and chunk length kc; the most references one launch takes; the chunk
-// length of a launch of `refs` references; the cut of R references into consecutive launches (returns their number; launch_of[R],
-// tiles_of[launches <= R])
-int window_many_img(int L, int kc);
-int window_many_max_refs(int L);
-int window_many_kc(int L, int refs);
-int window_many_plan(int R, int L, int *launch_of, int *tiles_of);
+// the planner (pure host functions) in the rows W of a reference's table (a window +-L: 2 L + 1; a lag range: its lags): image
+// stride for W rows and chunk length kc; the most references one launch takes; the chunk length of a launch of `refs` references;
+// the cut of R references into consecutive launches (returns their number; launch_of[R], tiles_of[launches <= R])
+int window_many_img(int W, int kc);
+int window_many_max_refs(int W);
+int window_many_kc(int W, int refs);
+int window_many_plan(int R, int W, int *launch_of, int *tiles_of);
+// (every reference's table has the shape's origin and rows: origin + L <= 2 MUSE_LAG_WINDOW_MAX, Lneg <= origin)
 hipError_t launch_window_many(WindowManyParams p, hipStream_t stream);
 hipError_t launch_direct(const double *x, int lenx, const double *y, int leny, int n, int normalize_x,
                          int normalize_y, double x_scale, double cc_scale, double *cc, int *lag, double *mv,

@@ -3,15 +3,23 @@
 //
 // xcorr_window.hip computes S[v][series] = sum_t d[t] e[t + v] with the 2L+1 window rows of ONE reference on the A rows of
 // v_mfma_f64_16x16x4_f64 and leaves the rest of its last tile empty (L = 7: 15 of 16 rows; L = 3: 7 of 16; L = 1: 3 of 16).  Here
-// the A rows are the packed list (reference r, window row v), A row index r (2L+1) + v, cut into tiles of 16 wherever they fall: a
-// tile may hold rows of several references.  Everything that depends on the rows alone -- the loads, d = y - y[0], s1, s2 -- is done
+// the A rows are the packed list (reference r, table row v), A row index r W + v, cut into tiles of 16 wherever they fall: a
+// tile may hold rows of several references.  W = origin + L + 1 is the rows of a reference's table, whose row v is lag v - origin
+// (WindowShape): 2L+1 for a symmetric window (origin = L), the lags of a lag range whose table starts at its lowest lag (origin =
+// Lneg; muse_batch_score_many_in_lag_range).  Everything that depends on the rows alone -- the loads, d = y - y[0], s1, s2 -- is done
 // once per series for all references of the launch.
 //
 // Per chunk of `kc` samples the workgroup stages one image of e per reference in LDS, `img` doubles apart; lane (r, q) of tile i
-// reads A from (image of its row's reference) + k + v: per lane and tile one offset, formed in front of the k loop.  img = 2L + 3
-// mod 32 (window_many_img): the 32 lanes that one LDS cycle of a ds_read_b64 serves (16 rows x 2 k-lanes, at most two doubles
-// apart in k) then read 16 + 2 (references in the tile) <= 32 consecutive doubles modulo the 64 banks -- a tile that straddles
-// references collides no more than one that does not (2L+1 >= 3).
+// reads A from (image of its row's reference) + k + v: per lane and tile one offset, formed in front of the k loop.  img = W + 2
+// mod 32 (window_many_img): modulo the 64 banks (32 doubles) reference j's row v on a k-lane that is koff doubles along lies at
+// j (W + 2) + v + koff, as if every reference took W + 2 consecutive doubles.  The 32 lanes that one LDS cycle of a ds_read_b64
+// serves are 16 rows x 2 k-lanes, koff <= 2 apart: the two doubles behind a reference's last row are what its second k-lane reads,
+// and the next reference's row 0 begins behind them.  A tile with rows of m references so reads 16 + 2 m consecutive doubles modulo
+// the banks (equal addresses -- the clamped empty rows -- are one broadcast): no conflict while m <= 8.  Nothing here asks W to be
+// odd.  A tile of 16 packed rows holds rows of at most floor(14 / W) + 2 references: 6 at W = 3 (22 ... 28 doubles), 4 at W = 4, 5
+// and 6, fewer beyond.  W = 2 (the ranges -1 .. 0 and 0 .. 1): the tiles start at multiples of 16, which 2 divides, so a tile holds
+// the rows of exactly eight references, never nine: 32 doubles, every bank once.  Only W = 1 (the window +-0, 16 references in a
+// tile, 48 doubles) wraps: its second k-lane meets the first one's banks two ways at six (8-byte loads: five) of the 32 addresses.
 //
 // Bit-identity with xcorr_window_mfma: an accumulator element sees the same A and B values in the same k slots of the same k-steps
 // in the same order (kc is a multiple of 256 samples, so the 64-sample piece p still goes to wave p mod 4, pieces in rising
@@ -33,7 +41,7 @@ __global__ __launch_bounds__(WIN_THREADS) void xcorr_window_many_mfma(const Wind
     const int lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int r = lane & 15, q = lane >> 4;
-    const int N = p.N, R = p.R, L = p.L, Lneg = p.Lneg, Wv = 2 * L + 1, kc = p.kc, img = p.img, elen = kc + 2 * L;
+    const int N = p.N, R = p.R, L = p.L, Lneg = p.Lneg, origin = p.origin, Wv = origin + L + 1, kc = p.kc, img = p.img, elen = kc + Wv - 1;
     const int STAT = p.buf, CAND = STAT + 128;
     const long long row0 = (long long)blockIdx.x * 16;
     long long row = row0 + r;
@@ -116,56 +124,57 @@ __global__ __launch_bounds__(WIN_THREADS) void xcorr_window_many_mfma(const Wind
         const double *__restrict__ pw = p.pw[ref];
         WindowBest best;
         for (int k = 0; k < plen; k++)
-            window_scan_pos(best, lds, ref * Wv, part * plen + k, c, L, Lneg, L, st, pw);
+            window_scan_pos(best, lds, ref * Wv, part * plen + k, c, L, Lneg, origin, st, pw);
         window_put_best(lds + CAND + (item * 16 + c) * 3, best);
     }
     __syncthreads();
     if (row0 + c < p.M) {
         for (int ref = t >> 4; ref < R; ref += 16) {
             int lag;
-            p.mv[ref][row0 + c] = window_outcome(lds, CAND, ref * parts, parts, ref * Wv, c, L, Lneg, L, st, p.pw[ref], &lag);
+            p.mv[ref][row0 + c] = window_outcome(lds, CAND, ref * parts, parts, ref * Wv, c, L, Lneg, origin, st, p.pw[ref], &lag);
             p.lag[ref][row0 + c] = lag;
         }
     }
 }
 
-// ---- the planner (pure host code: muse_test_window_many_plan)
-int window_many_img(int L, int kc)
+// ---- the planner (pure host code: muse_test_window_many_plan, muse_test_window_many_plan_rows), in the rows W of a reference's table
+// (a symmetric window +-L: W = 2 L + 1; a lag range: W = its lags)
+int window_many_img(int W, int kc)
 {
-    const int want = (2 * L + 3) & 31; // one reference's 16-lane read group ends where the next one's begins, modulo the banks
-    int img = kc + 2 * L;
+    const int want = (W + 2) & 31; // one reference's 16-lane read group ends where the next one's begins, modulo the banks
+    int img = kc + W - 1;
     while ((img & 31) != want)
         img++;
     return img;
 }
 
-int window_many_max_refs(int L)
+int window_many_max_refs(int W)
 {
-    // a reference that fills four tiles by itself (2L+1 > 48) is bound by the matrix pipe in its own pass: two of them in one launch
+    // a reference that fills four tiles by itself (W > 48) is bound by the matrix pipe in its own pass: two of them in one launch
     // save no time (measured 0.97 ... 1.06 of two single passes at L = 31, profiles/window_many_bench.txt): one launch each
-    if (2 * L + 1 > WINM_PACK_MAX_ROWS)
+    if (W > WINM_PACK_MAX_ROWS)
         return 1;
-    const int by_rows = (16 * WINM_MAX_TILES) / (2 * L + 1), by_lds = WINM_IMG_DOUBLES / window_many_img(L, 256);
+    const int by_rows = (16 * WINM_MAX_TILES) / W, by_lds = WINM_IMG_DOUBLES / window_many_img(W, 256);
     return std::max(1, std::min(by_rows, by_lds));
 }
 
-int window_many_kc(int L, int refs)
+int window_many_kc(int W, int refs)
 {
     for (int kc = WIN_KC; kc > 256; kc /= 2)
-        if ((long long)refs * window_many_img(L, kc) <= WINM_IMG_DOUBLES)
+        if ((long long)refs * window_many_img(W, kc) <= WINM_IMG_DOUBLES)
             return kc;
     return 256;
 }
 
-int window_many_plan(int R, int L, int *launch_of, int *tiles_of)
+int window_many_plan(int R, int W, int *launch_of, int *tiles_of)
 {
-    const int per = window_many_max_refs(L);
+    const int per = window_many_max_refs(W);
     int launches = 0;
     for (int r0 = 0; r0 < R; r0 += per, launches++) {
         const int refs = std::min(per, R - r0);
         for (int r = r0; r < r0 + refs; r++)
             launch_of[r] = launches;
-        tiles_of[launches] = (refs * (2 * L + 1) + 15) / 16;
+        tiles_of[launches] = (refs * W + 15) / 16;
     }
     return launches;
 }
@@ -175,12 +184,14 @@ hipError_t launch_window_many(WindowManyParams p, hipStream_t stream)
     if (p.M <= 0)
         return hipSuccess;
     long long blocks;
-    // (the packed references' windows are symmetric: every table's row v is lag v - L)
-    if (window_launch_check(p, &blocks) != hipSuccess || p.origin != p.L || p.Lneg > p.L || p.R < 1 || p.R > window_many_max_refs(p.L))
+    // (every packed reference's table has the one shape: row v is lag v - origin, rows 0 .. origin + L; the shape check bounds
+    // origin + L by 2 MUSE_LAG_WINDOW_MAX and Lneg by origin)
+    const int W = p.origin + p.L + 1;
+    if (window_launch_check(p, &blocks) != hipSuccess || p.R < 1 || p.R > window_many_max_refs(W))
         return hipErrorInvalidValue;
-    const int tiles = (p.R * (2 * p.L + 1) + 15) / 16;
-    p.kc = window_many_kc(p.L, p.R);
-    p.img = window_many_img(p.L, p.kc);
+    const int tiles = (p.R * W + 15) / 16;
+    p.kc = window_many_kc(W, p.R);
+    p.img = window_many_img(W, p.kc);
     p.buf = std::max(p.R * p.img, tiles * 256);
     p.parts = std::max(1, 16 / p.R);
     const size_t lds_bytes = (size_t)(p.buf + 128 + p.R * p.parts * 16 * 3) * sizeof(double);

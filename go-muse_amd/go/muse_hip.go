@@ -949,6 +949,48 @@ func RunManyInWindow(batches []*Batch, groupByLabels []string) error {
 	if len(batches) == 0 {
 		return nil
 	}
+	maxLag := batches[0].Results.MaxLag
+	return runManyInLags(batches, groupByLabels, "RunManyInWindow",
+		func(b *Batch) error { return b.RunInWindow(groupByLabels) },
+		func() error {
+			if maxLag < 0 {
+				return fmt.Errorf("RunManyInWindow: MaxLag < 0")
+			}
+			return nil
+		},
+		func(hs **C.muse_batch, R, G, topN C.int32_t, gid *C.int32_t, threshold C.double, sign C.int32_t, idx *C.int64_t,
+			lag *C.int32_t, score *C.double, cnt *C.int32_t, mean *C.double) C.int {
+			return C.muse_batch_run_many_in_window(hs, R, gid, G, C.int32_t(maxLag), topN, threshold, sign, 1, idx, lag, score, cnt, mean)
+		})
+}
+
+// RunManyInLagRange is RunMany inside the lags lagLo .. lagHi, lagLo <= 0 <= lagHi (muse_batch_run_many_in_lag_range): every batch
+// receives what its own RunInLagRange gives, from one pass over the rows -- up to 48 lags with the references' table rows packed
+// into one matrix product.  One device.  Results is fed as RunInWindow feeds it.  Batches that do not qualify for RunMany are
+// RunInLagRange one after the other.
+func RunManyInLagRange(batches []*Batch, groupByLabels []string, lagLo, lagHi int) error {
+	if lagLo > 0 || lagHi < 0 {
+		return fmt.Errorf("RunManyInLagRange: lagLo <= 0 <= lagHi")
+	}
+	return runManyInLags(batches, groupByLabels, "RunManyInLagRange",
+		func(b *Batch) error { return b.RunInLagRange(groupByLabels, lagLo, lagHi) },
+		func() error { return nil },
+		func(hs **C.muse_batch, R, G, topN C.int32_t, gid *C.int32_t, threshold C.double, sign C.int32_t, idx *C.int64_t,
+			lag *C.int32_t, score *C.double, cnt *C.int32_t, mean *C.double) C.int {
+			return C.muse_batch_run_many_in_lag_range(hs, R, gid, G, C.int32_t(lagLo), C.int32_t(lagHi), topN, threshold, sign, 1, idx,
+				lag, score, cnt, mean)
+		})
+}
+
+// runManyInLags is what RunManyInWindow and RunManyInLagRange share: the batches that qualify (otherwise each, batch after batch),
+// pre (the form's own refusal once they do), the label groups, the resident rows, the handles, the call (one of the library's
+// _run_many_in_ entry points) and the feed of every Results in group order.
+func runManyInLags(batches []*Batch, groupByLabels []string, name string, each func(*Batch) error, pre func() error,
+	call func(hs **C.muse_batch, R, G, topN C.int32_t, gid *C.int32_t, threshold C.double, sign C.int32_t, idx *C.int64_t,
+		lag *C.int32_t, score *C.double, cnt *C.int32_t, mean *C.double) C.int) error {
+	if len(batches) == 0 {
+		return nil
+	}
 	b0 := batches[0]
 	same := true
 	for _, b := range batches {
@@ -958,17 +1000,17 @@ func RunManyInWindow(batches []*Batch, groupByLabels []string) error {
 	}
 	if !same {
 		for _, b := range batches {
-			if err := b.RunInWindow(groupByLabels); err != nil {
+			if err := each(b); err != nil {
 				return err
 			}
 		}
 		return nil
 	}
-	if b0.Results.MaxLag < 0 {
-		return fmt.Errorf("RunManyInWindow: MaxLag < 0")
+	if err := pre(); err != nil {
+		return err
 	}
 	if es := shardEngines(); es != nil {
-		return fmt.Errorf("RunManyInWindow runs on one device")
+		return fmt.Errorf("%s runs on one device", name)
 	}
 	labelValuesSet := b0.Comparison.indexLabelValues(groupByLabels)
 	if len(labelValuesSet) == 0 {
@@ -1033,8 +1075,8 @@ func RunManyInWindow(batches []*Batch, groupByLabels []string) error {
 	score := make([]C.double, R*top)
 	cnt := make([]C.int32_t, R)
 	mean := make([]C.double, R)
-	st := C.muse_batch_run_many_in_window(hs, C.int32_t(R), &gid[0], C.int32_t(G), C.int32_t(r.MaxLag), C.int32_t(topN),
-		C.double(threshold), C.int32_t(sign), 1, &idx[0], &lag[0], &score[0], &cnt[0], &mean[0])
+	st := call(hs, C.int32_t(R), C.int32_t(G), C.int32_t(topN), &gid[0], C.double(threshold), C.int32_t(sign), &idx[0], &lag[0],
+		&score[0], &cnt[0], &mean[0])
 	if err := hipError(st); err != nil {
 		return err
 	}

@@ -1179,6 +1179,46 @@ public:
     {
         if (batches.empty())
             return;
+        const int32_t max_lag = (int32_t)batches[0]->Results_->MaxLag;
+        feed_many_in_window(
+            batches, groupByLabels, [&](Batch &b) { b.RunInWindow(groupByLabels); },
+            [&] {
+                if (max_lag < 0)
+                    throw Error(MUSE_ERR_INVALID, "RunManyInWindow: MaxLag < 0");
+            },
+            [&](muse_batch *const *hs, int32_t R, const int32_t *gid, int32_t G, int32_t top, double threshold, int32_t sign, int64_t *idx,
+                int32_t *lag, double *score, int32_t *cnt, double *mean) {
+                return muse_batch_run_many_in_window(hs, R, gid, G, max_lag, top, threshold, sign, 1, idx, lag, score, cnt, mean);
+            });
+    }
+
+    // RunMany inside the lags lagLo .. lagHi, lagLo <= 0 <= lagHi (muse_batch_run_many_in_lag_range): every batch receives what its
+    // own RunInLagRange gives, from one pass over the rows -- up to 48 lags with the references' table rows packed into one matrix
+    // product.  One device.  Results is fed as RunInWindow feeds it.  Batches that do not qualify for RunMany are RunInLagRange one
+    // by one.
+    static void RunManyInLagRange(const std::vector<std::shared_ptr<Batch>> &batches, const std::vector<std::string> &groupByLabels,
+                                  int lagLo, int lagHi)
+    {
+        if (lagLo > 0 || lagHi < 0)
+            throw Error(MUSE_ERR_INVALID, "RunManyInLagRange: lagLo <= 0 <= lagHi");
+        feed_many_in_window(
+            batches, groupByLabels, [&](Batch &b) { b.RunInLagRange(groupByLabels, lagLo, lagHi); }, [] {},
+            [&](muse_batch *const *hs, int32_t R, const int32_t *gid, int32_t G, int32_t top, double threshold, int32_t sign, int64_t *idx,
+                int32_t *lag, double *score, int32_t *cnt, double *mean) {
+                return muse_batch_run_many_in_lag_range(hs, R, gid, G, (int32_t)lagLo, (int32_t)lagHi, top, threshold, sign, 1, idx, lag,
+                                                        score, cnt, mean);
+            });
+    }
+
+    // what RunManyInWindow and RunManyInLagRange share: the batches that qualify (one Comparison, one engine, one device, the same
+    // Results settings; otherwise `each` batch by batch), `pre` (the form's own refusal once they do), the label groups, the call (one
+    // of the library's _run_many_in_ entry points) and the feed of every Results in group order
+    template <class Each, class Pre, class Call>
+    static void feed_many_in_window(const std::vector<std::shared_ptr<Batch>> &batches, const std::vector<std::string> &groupByLabels,
+                                    Each each, Pre pre, Call call)
+    {
+        if (batches.empty())
+            return;
         bool same = true;
         for (auto &b : batches) {
             same &= b->Comparison == batches[0]->Comparison && b->eng_ == batches[0]->eng_ && b->engines_.empty();
@@ -1187,12 +1227,11 @@ public:
         }
         if (!same) {
             for (auto &b : batches)
-                b->RunInWindow(groupByLabels);
+                each(*b);
             return;
         }
         Batch &b0 = *batches[0];
-        if (b0.Results_->MaxLag < 0)
-            throw Error(MUSE_ERR_INVALID, "RunManyInWindow: MaxLag < 0");
+        pre();
         std::vector<int32_t> gid;
         auto lvs = b0.Comparison->indexLabelValues(groupByLabels, &gid);
         if (lvs.empty())
@@ -1208,9 +1247,8 @@ public:
         std::vector<int64_t> idx((size_t)R * cap);
         std::vector<int32_t> lag((size_t)R * cap), cnt((size_t)R);
         std::vector<double> score((size_t)R * cap), mean((size_t)R);
-        check(muse_batch_run_many_in_window(hs.data(), R, gid.data(), (int32_t)lvs.size(), (int32_t)b0.Results_->MaxLag, top,
-                                            exact ? 0.0 : b0.Results_->Threshold, exact ? 0 : (int32_t)b0.Results_->Filter, 1,
-                                            idx.data(), lag.data(), score.data(), cnt.data(), mean.data()));
+        check(call(hs.data(), R, gid.data(), (int32_t)lvs.size(), top, exact ? 0.0 : b0.Results_->Threshold,
+                   exact ? 0 : (int32_t)b0.Results_->Filter, idx.data(), lag.data(), score.data(), cnt.data(), mean.data()));
         for (int r = 0; r < R; r++) {
             const size_t o = (size_t)r * std::max(top, 0);
             std::vector<int> order(cnt[r]);

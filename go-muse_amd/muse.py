@@ -792,7 +792,8 @@ def _scores_many(fn, batches, *window):
 
 
 def _run_many(fn, batches, group_id, G, max_lag, top_n, threshold, sign_filter, abs_scores):
-    """the C Run `fn` over the batches into R x top_n outputs: list of (series, lag, score, mean_abs), one per batch"""
+    """the C Run `fn` over the batches into R x top_n outputs: list of (series, lag, score, mean_abs), one per batch
+    (max_lag: the one int32 the entry point takes there, or the tuple (lag_lo, lag_hi) of the lag-range form)"""
     batches, arr = _batch_handles(batches)
     R = len(batches)
     cap = max(int(top_n), 1)
@@ -805,7 +806,8 @@ def _run_many(fn, batches, group_id, G, max_lag, top_n, threshold, sign_filter, 
     if group_id is not None:
         gid = np.ascontiguousarray(group_id, dtype=np.int32)
     B.check(getattr(B.load(), fn)(
-        arr, R, B.i32ptr(gid) if gid is not None else None, int(G), int(max_lag), int(top_n),
+        arr, R, B.i32ptr(gid) if gid is not None else None, int(G),
+        *([int(v) for v in max_lag] if isinstance(max_lag, tuple) else [int(max_lag)]), int(top_n),
         float(threshold), int(sign_filter), 1 if abs_scores else 0,
         B.i64ptr(o_s), B.i32ptr(o_l), B.dptr(o_v), B.i32ptr(cnt), B.dptr(mean)))
     tn = max(int(top_n), 0)
@@ -924,6 +926,48 @@ def many_in_window_plan(N, f32, max_lag, R):
     path = ctypes.c_int32(-1)
     B.check(B.load().muse_test_many_in_window_plan(int(N), 1 if f32 else 0, int(max_lag), int(R), ctypes.byref(path)))
     return int(path.value)
+
+
+def score_many_in_lag_range(batches, lag_lo, lag_hi):
+    """muse_batch_score_many_in_lag_range: R references against one resident group, each series' best match INSIDE the lags
+    lag_lo .. lag_hi (lag_lo <= 0 <= lag_hi, one range for every reference) from one pass over the rows -- up to 48 lags the
+    references' table rows packed into one matrix product per launch (asynchronous; results land in each DeviceBatch's own buffers,
+    bit-identical to score_in_lag_range per batch on the direct product; no batch's own window changes)."""
+    batches, arr = _batch_handles(batches)
+    B.check(B.load().muse_batch_score_many_in_lag_range(arr, len(batches), int(lag_lo), int(lag_hi)))
+
+
+def scores_many_in_lag_range(batches, lag_lo, lag_hi):
+    """score_many_in_lag_range + copy back: list of (lag, mv), one per batch"""
+    return _scores_many("muse_batch_score_many_in_lag_range", batches, int(lag_lo), int(lag_hi))
+
+
+def run_many_in_lag_range(batches, lag_lo, lag_hi, group_id=None, G=0, top_n=20, threshold=0.0, sign_filter=0, abs_scores=True):
+    """muse_batch_run_many_in_lag_range: Batch.RunInLagRange for every reference (Results.MaxLag = max(-lag_lo, lag_hi));
+    returns a list of (series, lag, score, mean_abs), one per batch"""
+    return _run_many("muse_batch_run_many_in_lag_range", batches, group_id, G, (lag_lo, lag_hi), top_n, threshold, sign_filter,
+                     abs_scores)
+
+
+def many_lag_range_plan(N, f32, lag_lo, lag_hi, R):
+    """muse_test_many_lag_range_plan (no device): MUSE_IN_WINDOW_* -- the pass score_many_in_lag_range takes for R references
+    against series of N samples (f32: float32 storage) and the lags lag_lo .. lag_hi"""
+    path = ctypes.c_int32(-1)
+    B.check(B.load().muse_test_many_lag_range_plan(int(N), 1 if f32 else 0, int(lag_lo), int(lag_hi), int(R), ctypes.byref(path)))
+    return int(path.value)
+
+
+def window_many_plan_rows(R, W):
+    """muse_test_window_many_plan_rows (no device): window_many_plan in the rows W of a reference's table (a window +-L: 2 L + 1,
+    a lag range: its lags) -- the same dict"""
+    R = int(R)
+    n, mx = ctypes.c_int32(0), ctypes.c_int32(0)
+    of, tiles, img, kc = (np.zeros(max(R, 1), dtype=np.int32) for _ in range(4))
+    B.check(B.load().muse_test_window_many_plan_rows(R, int(W), ctypes.byref(n), B.i32ptr(of), B.i32ptr(tiles), ctypes.byref(mx),
+                                                     B.i32ptr(img), B.i32ptr(kc)))
+    k = int(n.value)
+    return dict(launches=k, launch_of=of[:R].copy(), tiles_of=tiles[:k].copy(), max_refs=int(mx.value), img_of=img[:k].copy(),
+                kc_of=kc[:k].copy())
 
 
 def device_count():
@@ -1581,7 +1625,8 @@ def NewBatch(ref, comp, results, cc, engine=None, engines=None):
 def _run_many_labels(batches, groupByLabels, each, run, sharded_ok, exact_feed):
     """the label-level many-references Run: `run` (run_many*) over batches that share the Comparison, the engine and the Results
     settings, every Results fed in group order; batches that do not qualify (sharded ones too unless sharded_ok) take their own
-    `each` method one after the other.  exact_feed: MaxLag is a window (>= 0) and Results is fed as RunInWindow feeds it"""
+    `each` method (a name, or a callable of the batch) one after the other.  exact_feed: Results is fed as RunInWindow feeds it,
+    and (unless it is "range": `run` carries its own lags and ignores the MaxLag it is handed) MaxLag is a window (>= 0)"""
     batches = list(batches)
     if not batches:
         return None
@@ -1592,13 +1637,13 @@ def _run_many_labels(batches, groupByLabels, each, run, sharded_ok, exact_feed):
                (r0.MaxLag, r0.TopN, r0.Threshold, r0.SignFilter) for b in batches)
     if not same:
         for b in batches:
-            getattr(b, each)(groupByLabels)
+            each(b) if callable(each) else getattr(b, each)(groupByLabels)
         return None
     comp = b0.Comparison
     labelValuesSet = comp.indexLabelValues(groupByLabels)
     if not labelValuesSet:
         return None
-    if exact_feed and r0.MaxLag < 0:
+    if exact_feed and exact_feed != "range" and r0.MaxLag < 0:
         raise MuseError(B.MUSE_ERR_INVALID, "RunManyInWindow needs Results.MaxLag >= 0")
     series = comp._series_list()
     gid = comp._group_ids()
@@ -1635,6 +1680,18 @@ def RunManyInWindow(batches, groupByLabels):
     what its own RunInWindow(groupByLabels) gives, from one pass over the rows where the lengths have a masked many-references
     kernel.  One device.  Batches that do not qualify for RunMany are RunInWindow one after the other."""
     return _run_many_labels(batches, groupByLabels, "RunInWindow", run_many_in_window, False, True)
+
+
+def RunManyInLagRange(batches, groupByLabels, lagLo, lagHi):
+    """RunMany inside the lags lagLo .. lagHi, lagLo <= 0 <= lagHi (muse_batch_run_many_in_lag_range): every batch receives what its
+    own RunInLagRange(groupByLabels, lagLo, lagHi) gives, from one pass over the rows -- up to 48 lags with the references' table
+    rows packed into one matrix product.  One device.  Batches that do not qualify for RunMany take RunInLagRange one after the other."""
+    if lagLo > 0 or lagHi < 0:
+        raise MuseError(B.MUSE_ERR_INVALID, "RunManyInLagRange needs lagLo <= 0 <= lagHi")
+
+    def run(dbs, gid, G, _max_lag, top_n, threshold, sign_filter, abs_scores=True):
+        return run_many_in_lag_range(dbs, lagLo, lagHi, gid, G, top_n, threshold, sign_filter, abs_scores)
+    return _run_many_labels(batches, groupByLabels, lambda b: b.RunInLagRange(groupByLabels, lagLo, lagHi), run, False, "range")
 
 
 # ----------------------------------------------------------------- muse.go

@@ -404,7 +404,7 @@ int muse_batch_run_in_window(muse_batch *b, const int32_t *group_id, int32_t G, 
  * muse_batch_run_in_lag_range is that pass followed by Batch.Run's selection over the scores, outputs as muse_batch_run, with
  * Results.MaxLag = max(-lag_lo, lag_hi): every lag of the range passes the lag filter.  A sign_filter outside -1 .. 1 or a negative
  * G with group_id is refused before anything is scored.
- * Limits: ranges that exclude lag 0; the many-references, Muse.Run-rows (muse_batch_run_rows_windowed ...) and slide forms of a range;
+ * Limits: ranges that exclude lag 0; the Muse.Run-rows (muse_batch_run_rows_windowed ...) and slide forms of a range;
  * the multi-device layer; ranges of more than 127 lags, or float32 storage, outside FFT lengths 512 ... 4096; series longer than
  * 65536 samples (other than the whole range); narrow float64 ranges are never routed to the masked pass. */
 int muse_batch_score_in_lag_range(muse_batch *b, int32_t lag_lo, int32_t lag_hi);
@@ -588,6 +588,39 @@ int muse_batch_run_many_in_window(muse_batch *const *batches, int32_t R, const i
                                   int32_t max_lag, int32_t top_n, double threshold, int32_t sign_filter,
                                   int32_t abs_scores, int64_t *out_series, int32_t *out_lag, double *out_score,
                                   int32_t *out_count, double *out_mean_abs);
+/* Many references INSIDE A LAG RANGE in one pass over the rows: per batch and series the (lag, mv) of
+ * muse_batch_score_in_lag_range(b, lag_lo, lag_hi) -- its definition, clipping, scan order and (0, cc[0]), NaN and sigma == 0
+ * outcomes -- one range for every reference, lag_lo <= 0 <= lag_hi, no batch's own lag_window touched.  lag_lo == -lag_hi is by
+ * definition muse_batch_score_many_in_window(batches, R, lag_hi).  Which pass runs is decided from the length, the storage, R and
+ * the W = hi - lo + 1 lags of the clipped range:
+ *   the range is every lag                                           : muse_batch_score_many, bit for bit
+ *   float64 group, W <= 2 MUSE_LAG_WINDOW_MAX + 1, up to 65536 samples : the direct product.  Up to 48 lags the references' W table
+ *                                                                      rows are packed into the accumulator tiles of one launch
+ *                                                                      (at most 128 rows: sixteen references at -7 .. 0 where +-7
+ *                                                                      packs eight); wider ranges, and batches that do not share
+ *                                                                      one length, take one launch per reference.  Per batch BIT
+ *                                                                      FOR BIT muse_batch_score_in_lag_range, whose cached tables
+ *                                                                      the pass shares
+ *   FFT length 512 ... 4096 otherwise, R >= 2, and muse_batch_score_many's
+ *   own one-pass conditions (as at muse_batch_score_many_in_window)  : ONE pass of the many-references transform kernels with every
+ *                                                                      reference's argmax restricted to the range, the two bounds
+ *                                                                      set independently; listed pairs are redone with the range
+ *   the same lengths where those conditions do not hold              : muse_batch_score_in_lag_range(b, lag_lo, lag_hi) batch after batch
+ *   anything else                                                    : MUSE_ERR_UNSUPPORTED, nothing changed
+ * Exact fp64, never screened, the group's spectrum cache neither read nor built.  A kernel variant forced by a test hook that has no
+ * masked build is refused (MUSE_ERR_UNSUPPORTED), never run unmasked.
+ *   MUSE_ERR_INVALID: the list checks of muse_batch_score_many; lag_lo > 0 or lag_hi < 0; a batch whose own window is on (unless
+ *   lag_lo == -lag_hi equals it).  Everything is checked before anything is enqueued: a refusal leaves every batch's scores and
+ *   cached tables as they were.
+ * muse_batch_run_many_in_lag_range is that pass followed by Batch.Run's selection for every batch, outputs as muse_batch_run_many,
+ * with Results.MaxLag = max(-lag_lo, lag_hi).  A sign_filter outside -1 .. 1 or a negative G with group_id is refused before anything
+ * is scored.
+ * Limits: one range per reference; ranges that exclude lag 0; the multi-device layer. */
+int muse_batch_score_many_in_lag_range(muse_batch *const *batches, int32_t R, int32_t lag_lo, int32_t lag_hi);
+int muse_batch_run_many_in_lag_range(muse_batch *const *batches, int32_t R, const int32_t *group_id, int32_t G,
+                                     int32_t lag_lo, int32_t lag_hi, int32_t top_n, double threshold, int32_t sign_filter,
+                                     int32_t abs_scores, int64_t *out_series, int32_t *out_lag, double *out_score,
+                                     int32_t *out_count, double *out_mean_abs);
 int muse_batch_free(muse_batch *b);
 
 /* ------------------------------------------- single-pair entry points */

@@ -97,6 +97,10 @@ int muse_test_batch_redo_pairs(muse_batch *b, int64_t *pairs, int64_t cap, int64
  * single-reference kernel's (xcorr_window_mfma).  Any out pointer but launches may be NULL. */
 int muse_test_window_many_plan(int32_t R, int32_t L, int32_t *launches, int32_t *launch_of, int32_t *tiles_of, int32_t *max_refs,
                                int32_t *img_of, int32_t *kc_of);
+/* The same planner in the rows 1 <= W <= 2 MUSE_LAG_WINDOW_MAX + 1 of a reference's table: a window +-L has W = 2 L + 1 (the hook
+ * above), a lag range (muse_batch_score_many_in_lag_range) its W lags -- even W too.  Outputs as above. */
+int muse_test_window_many_plan_rows(int32_t R, int32_t W, int32_t *launches, int32_t *launch_of, int32_t *tiles_of, int32_t *max_refs,
+                                    int32_t *img_of, int32_t *kc_of);
 /* The planner of the windowed Muse.Run (muse_batch_run_rows_windowed; xcorr_window_split.hip), a pure host function (no device
  * needed): M >= 1 rows of N >= 2 samples on num_cus CUs are scored in *S slices of whole 1024-sample chunks, slice s = chunks
  * [s chunks / S, (s + 1) chunks / S) of chunks = ceil(N / 1024); *chunks_per_slice = the largest slice.  *S == 1: the unsplit kernel. */
@@ -143,6 +147,13 @@ int muse_test_lag_range_plan(int32_t N, int32_t f32_storage, int32_t lag_lo, int
  * table) turns _MASKED into _MASKED_EACH when the call runs.  MUSE_ERR_INVALID for N < 2, max_lag < 0, R < 1 or a NULL out pointer. */
 #define MUSE_IN_WINDOW_MASKED_EACH 4
 int muse_test_many_in_window_plan(int32_t N, int32_t f32_storage, int32_t max_lag, int32_t R, int32_t *path);
+/* muse_batch_score_many_in_lag_range's dispatch, a pure host function (no device needed): the pass that scores R >= 1 references
+ * against series of N >= 2 samples inside the lags lag_lo .. lag_hi -- *path = MUSE_IN_WINDOW_PLAIN (the clipped range is every lag:
+ * muse_batch_score_many), _MFMA (the direct product, packed where the planner packs: float64, at most 2 MUSE_LAG_WINDOW_MAX + 1 lags,
+ * up to 65536 samples), _MASKED, _MASKED_EACH (as above, with muse_batch_score_in_lag_range per batch) or _UNSUPPORTED.  For
+ * lag_lo == -lag_hi it is muse_test_many_in_window_plan(N, ., lag_hi, R).  MUSE_ERR_INVALID for N < 2, lag_lo > 0, lag_hi < 0, R < 1
+ * or a NULL out pointer. */
+int muse_test_many_lag_range_plan(int32_t N, int32_t f32_storage, int32_t lag_lo, int32_t lag_hi, int32_t R, int32_t *path);
 /* muse_batch_slide_score_in_window's dispatch, a pure host function (no device needed): how a group of series of N >= 2 samples
  * (f32_storage: a float32-storage group) is slid by 0 <= k <= N samples and scored inside +-max_lag >= 0 --
  *   _UNSUPPORTED : muse_test_in_window_plan says so (the call returns MUSE_ERR_UNSUPPORTED, nothing moves)
