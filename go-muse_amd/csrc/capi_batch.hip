@@ -595,27 +595,35 @@ extern "C" int muse_test_batch_redo_pairs(muse_batch *b, int64_t *pairs, int64_t
 
 extern "C" int muse_batch_score(muse_batch *b)
 {
-    return batch_score(b, true);
+    return batch_score(b, ScorePass{});
+}
+
+// the masked argmax is built into the default kernels of n = 512 ... 4096 and the rescaling kernel behind the n = 4096 one
+static int check_mask(const muse_batch *b, int variant, const LagRange &mask)
+{
+    if (!(variant == KERNEL_R16_FOLD || variant == KERNEL_R16_OCC3 || (variant == KERNEL_SMALL && b->logn <= 11)) || 2 * mask.hi > b->n)
+        return fail(MUSE_ERR_UNSUPPORTED, "the masked transform pass runs on the default kernels of FFT lengths 512 ... 4096");
+    if (2 * mask.lneg > b->n - 2)
+        return fail(MUSE_ERR_UNSUPPORTED, "the masked transform pass takes at most n / 2 - 1 lags below zero");
+    return MUSE_OK;
 }
 
 // (the refusals below in the order batch_score meets them)
-int batch_score_check(muse_batch *b, int win_L, int *variant)
+int batch_score_check(muse_batch *b, const LagRange *mask, int *variant)
 {
     *variant = -1;
-    if (win_L < 0 && b->windowed())
-        return MUSE_OK;
     if (b->n > GENERIC_MAX_N)
         return b->g->f32 ? fail(MUSE_ERR_UNSUPPORTED, "float32-storage groups run on the default kernels only (FFT lengths 512 ... 16384)") : MUSE_OK;
     const KernelChoice kc = choose_kernel(b, (b->g->M + 1) / 2);
     if (kc.error)
         return fail(MUSE_ERR_UNSUPPORTED, "%s", kc.error);
-    if (win_L >= 0 && (!(kc.variant == KERNEL_R16_FOLD || kc.variant == KERNEL_R16_OCC3 || (kc.variant == KERNEL_SMALL && b->logn <= 11)) || 2 * win_L > b->n))
-        return fail(MUSE_ERR_UNSUPPORTED, "the masked transform pass runs on the default kernels of FFT lengths 512 ... 4096");
+    if (mask && check_mask(b, kc.variant, *mask))
+        return MUSE_ERR_UNSUPPORTED;
     *variant = kc.variant;
     return MUSE_OK;
 }
 
-int batch_score(muse_batch *b, bool allow_spectrum_cache, int win_L, const SlideFuse *slide, int win_lneg)
+int batch_score(muse_batch *b, const ScorePass &pass)
 {
     if (!b)
         return fail(MUSE_ERR_INVALID, "NULL batch");
@@ -634,9 +642,9 @@ int batch_score(muse_batch *b, bool allow_spectrum_cache, int win_L, const Slide
     if (rc)
         return rc;
     b->origin = ScoreOrigin{};
-    if (win_L < 0 && b->windowed()) { // the best match inside +-MaxLag, directly (xcorr_window.hip): no transform, never screened
+    if (pass.window ? pass.direct() : b->windowed()) { // the best match inside the window, directly (xcorr_window.hip): no transform, never screened
         b->scores_exact = true;
-        return score_windowed(b);
+        return score_direct(b, pass.window ? *pass.window : lag_window_range(b->n, b->lag_window));
     }
     if (b->n > GENERIC_MAX_N) { // series longer than 65 536 samples: a sequence of chip-wide kernels per batch of pairs (xcorr_huge.hip)
         if (b->g->f32)
@@ -659,19 +667,16 @@ int batch_score(muse_batch *b, bool allow_spectrum_cache, int win_L, const Slide
     const int variant = kc.variant;
     if (kc.gsmall)
         p.gsmall = kc.gsmall;
-    if (win_L >= 0) { // the masked argmax: built into the default kernels of n = 512 ... 4096 and the rescaling kernel behind the n = 4096 one
-        if (!(variant == KERNEL_R16_FOLD || variant == KERNEL_R16_OCC3 || (variant == KERNEL_SMALL && b->logn <= 11)) || 2 * win_L > b->n)
-            return fail(MUSE_ERR_UNSUPPORTED, "the masked transform pass runs on the default kernels of FFT lengths 512 ... 4096");
-        if (win_lneg >= 0) { // a lag range: the two bounds as the caller clipped them
-            if (2 * win_lneg > b->n - 2)
-                return fail(MUSE_ERR_UNSUPPORTED, "the masked transform pass takes at most n / 2 - 1 lags below zero");
-            b->origin = ScoreOrigin::in_lag_range(MUSE_IN_WINDOW_MASKED, win_L, win_lneg, variant);
-            set_window(p, win_L, win_lneg);
-        } else {
-            b->origin = ScoreOrigin::in_window(MUSE_IN_WINDOW_MASKED, win_L, variant);
-            set_window(p, win_L);
-        }
+    const LagRange *mask = pass.mask();
+    if (mask) { // the two bounds as the caller clipped them
+        rc = check_mask(b, variant, *mask);
+        if (rc)
+            return rc;
+        b->origin = ScoreOrigin::in_window(MUSE_IN_WINDOW_MASKED, *mask, variant);
+        set_window(p, *mask);
     }
+    const bool allow_spectrum_cache = pass.allow_spectrum_cache;
+    const SlideFuse *slide = pass.slide;
     if (slide) { // (the rows are rewritten by the launch: only the kernel that was built for it may see the tails)
         if (variant != KERNEL_R16_FOLD || allow_spectrum_cache)
             return fail(MUSE_ERR_INVALID, "the fused slide runs in the default n = 4096 kernel, off the rows");
@@ -695,7 +700,7 @@ int batch_score(muse_batch *b, bool allow_spectrum_cache, int win_L, const Slide
         // two host threads one builds and the other one's reader sits behind that writer on the stream
         ZcPlan plan;
         std::unique_lock<std::mutex> zc_lock(b->g->ready_mu, std::defer_lock);
-        if (allow_spectrum_cache && win_L < 0 && spectrum_cache_candidate(b, variant)) { // (a masked pass always reads the rows)
+        if (allow_spectrum_cache && !mask && spectrum_cache_candidate(b, variant)) { // (a masked pass always reads the rows)
             zc_lock.lock();
             rc = plan_spectrum_cache(b, plan);
             if (rc)
@@ -826,8 +831,7 @@ extern "C" int muse_batch_kernel_name(muse_batch *b, char *name, int32_t cap)
     } else if (o.kind == ScoreOrigin::PACKED) {
         snprintf(k, sizeof(k), "xcorr_window_many_mfma<%d, %s>", o.tiles, window_wide(b->g->rows, b->g->stride) ? "true" : "false");
     } else if (b->windowed()) {
-        const int L = std::min(b->lag_window, b->n / 2);
-        snprintf(k, sizeof(k), "xcorr_window_mfma<%d, %s>", (2 * L + 1 + 15) / 16,
+        snprintf(k, sizeof(k), "xcorr_window_mfma<%d, %s>", (lag_window_range(b->n, b->lag_window).rows() + 15) / 16,
                  window_wide(b->g->rows, b->g->stride) ? "true" : "false");
     } else if (b->n > GENERIC_MAX_N) { // (the pass is a sequence of kernels: the one that moves the most bytes)
         snprintf(k, sizeof(k), "huge_rows<false>");

@@ -261,33 +261,49 @@ struct muse_spectrum {
     double xmax = -1.0;   // max |X[f]| (lazily, by the first screened Run): scales the fp32 error bound
 };
 
+// The lags a window +-L holds below zero at FFT length n: index n / 2 is lag +n/2 (xcorr.go:192-194), it is scanned once
+inline int window_lneg(int L, int n) { return 2 * L == n ? L - 1 : L; }
+// A window of lags as every pass takes it at FFT length n: lags -lneg .. hi (hi <= n / 2, lneg <= n / 2 - 1), and `origin`, the lags
+// below zero at which the direct product's table starts (row v of it is lag v - origin).  A table is determined by (origin, rows).
+struct LagRange {
+    int hi, lneg, origin;
+    int rows() const { return origin + hi + 1; }
+    bool every_lag(int64_t n) const { return 2 * (int64_t)hi == n && lneg == n / 2 - 1; }
+};
+// the window +-L (muse_batch_set_lag_window, muse_batch_score_in_window): the table starts L lags below zero, at L == n / 2 too
+// (where lag -n/2 is lag +n/2 and row 0 is not scanned)
+inline LagRange lag_window_range(int64_t n, int64_t L)
+{
+    const int hi = (int)std::min<int64_t>(L, n / 2);
+    return LagRange{hi, window_lneg(hi, (int)n), hi};
+}
+// the range lag_lo .. lag_hi (lag_lo <= 0 <= lag_hi; muse_batch_score_in_lag_range): the table starts at its lowest lag.  A range
+// -L .. L is the window +-L, so the two are one pass bit for bit
+inline LagRange clip_lag_range(int64_t n, int32_t lag_lo, int32_t lag_hi)
+{
+    if ((int64_t)lag_lo == -(int64_t)lag_hi)
+        return lag_window_range(n, lag_hi);
+    const int lneg = (int)std::min<int64_t>(-(int64_t)lag_lo, n / 2 - 1);
+    return LagRange{(int)std::min<int64_t>(lag_hi, n / 2), lneg, lneg};
+}
+
 // Which pass filled a batch's mv / lag.  The in-window kinds carry the MUSE_IN_WINDOW_* value (muse_hip_test.h) they report.
 struct ScoreOrigin {
     enum Kind : int32_t {
         PACKED = -1, // a packed launch of muse_batch_score_many_windowed (capi_window_many.hip) of `tiles` accumulator tiles
         OWN = 0,     // the batch's own setting: choose_kernel, or its own lag window (what the next muse_batch_score takes too)
-        PLAIN = MUSE_IN_WINDOW_PLAIN, MFMA = MUSE_IN_WINDOW_MFMA, MASKED = MUSE_IN_WINDOW_MASKED // muse_batch_score_in_window with `window`
+        PLAIN = MUSE_IN_WINDOW_PLAIN, MFMA = MUSE_IN_WINDOW_MFMA, MASKED = MUSE_IN_WINDOW_MASKED // a call's window (`window`)
     };
     static constexpr int32_t MANY = -1; // `variant` of muse_batch_score_many_in_window's one masked pass (no KERNEL_* is negative)
     Kind kind = OWN;
-    int32_t window = -1; // PLAIN / MFMA / MASKED: min(the call's window, n / 2)
+    LagRange window{0, 0, 0}; // PLAIN / MFMA / MASKED: the call's window, clipped
     int32_t variant = 0; // MASKED: the KERNEL_* the pass launched first, or MANY
     int32_t tiles = 0;   // PACKED
     int32_t slide = 0;   // the MUSE_SLIDE_IN_WINDOW_* path if the pass was muse_batch_slide_score_in_window's and moved the rows, 0 otherwise
-    // a lag range's two bounds (muse_batch_score_in_lag_range, lags -window_neg .. window): window_neg >= 0; -1: a symmetric window,
-    // whose negative bound is window_lneg(window, n)
-    int32_t window_neg = -1;
-    static ScoreOrigin packed(int32_t tiles) { return ScoreOrigin{PACKED, -1, 0, tiles}; }
-    static ScoreOrigin in_window(int32_t path, int32_t L, int32_t variant = 0) { return ScoreOrigin{(Kind)path, L, variant, 0}; }
-    static ScoreOrigin in_lag_range(int32_t path, int32_t lpos, int32_t lneg, int32_t variant = 0)
-    {
-        ScoreOrigin o{(Kind)path, lpos, variant, 0};
-        o.window_neg = lneg;
-        return o;
-    }
+    static ScoreOrigin packed(int32_t tiles) { return ScoreOrigin{PACKED, LagRange{0, 0, 0}, 0, tiles}; }
+    static ScoreOrigin in_window(int32_t path, const LagRange &w, int32_t variant = 0) { return ScoreOrigin{(Kind)path, w, variant}; }
     int32_t in_window_path() const { return kind > OWN ? (int32_t)kind : 0; }
-    // MFMA: the accumulator tiles of the direct product (rows 0 .. 2 window of a symmetric window's table, 0 .. window + window_neg of a range's)
-    int32_t mfma_tiles() const { return ((window_neg < 0 ? 2 * window : window + window_neg) + 1 + 15) / 16; }
+    int32_t mfma_tiles() const { return (window.rows() + 15) / 16; } // MFMA: the accumulator tiles of the direct product
 };
 
 struct muse_batch {
@@ -366,10 +382,10 @@ struct muse_batch {
     int64_t guard_trips = 0;            // Runs redone in fp64 because an estimate left its bound
     uint64_t guard_salt = 0;            // varies the guard's row sample from Run to Run
     // lag window (muse_batch_set_lag_window, capi_window.hip): < 0 = off; otherwise every scoring pass takes xcorr_window.hip
-    // with L = min(lag_window, n / 2).  win_e / win_pw: the shifted-reference image and its window sums for win_L (built by
-    // the first windowed pass; -1: none yet; window_range_key(): the tables of a lag range, muse_batch_score_in_lag_range)
+    // with L = min(lag_window, n / 2).  win_e / win_pw: the shifted-reference image and its window sums of the window or lag range
+    // win_key names (window_tables: built by the first pass that needs them; -1: none yet)
     int32_t lag_window = -1;
-    int32_t win_L = -1;
+    int32_t win_key = -1;
     PoolBuf<double> win_e, win_pw;
     bool windowed() const { return lag_window >= 0; }
     // which pass filled mv / lag (muse_batch_kernel_name names it, muse_test_last_in_window_path reports it): every scoring pass
@@ -456,9 +472,6 @@ int build_spectrum(muse_ctx *ctx, const double *ref_host, int N, int n, int norm
 hipError_t ensure_gscratch(muse_ctx *ctx, int64_t n, int slices_per_cu = muse::GSCRATCH_SLICES_PER_CU);
 hipError_t ensure_twl(muse_ctx *ctx, int64_t n);
 int ensure_scores(muse_batch *b);
-// capi_batch.hip: muse_batch_score (the many-references fallback passes false).  win_L >= 0: the MASKED pass of muse_batch_score_in_window --
-// the same launch sequence with the argmax of the transform kernels restricted to +-win_L (n = 512 ... 4096; the batch's own window and
-// the group's spectrum cache are neither read nor touched)
 // slide != nullptr: the slide of the group's rows fused into the pass (muse_batch_slide_score_in_window, FUSED): the n = 4096 kernel reads the
 // rows moved forward by slide->k samples (slide->tails: the group's device image of the tails) and stores them in place on the way; the
 // caller has made sure of the kernel (batch_score_check: KERNEL_R16_FOLD) and keeps the spectrum cache out (allow_spectrum_cache false)
@@ -466,63 +479,61 @@ struct SlideFuse {
     const void *tails;
     int32_t k;
 };
-// win_lneg >= 0 (with win_L >= 0): the masked pass over the lag range -win_lneg .. win_L, the two bounds independent of each other
-// (muse_batch_score_in_lag_range; win_L <= n / 2, win_lneg <= n / 2 - 1)
-int batch_score(muse_batch *b, bool allow_spectrum_cache, int win_L = -1, const SlideFuse *slide = nullptr, int win_lneg = -1);
-// what batch_score(b, ., win_L) would refuse for the batch as it stands (kernel selection, storage, length), without enqueueing
-// anything -- for a caller that moves rows before it scores; *variant = the KERNEL_* the pass would launch first (-1: none of them:
-// the batch's own window or a series longer than 65 536 samples)
-int batch_score_check(muse_batch *b, int win_L, int *variant);
+// What batch_score runs.  window == nullptr: the batch's own setting (its lag window if it has one, every lag otherwise).  Otherwise
+// the pass is a call's and the batch's own window is neither read nor touched: `window` scored as `path` says -- MUSE_IN_WINDOW_PLAIN
+// (it is every lag), _MFMA (the direct product) or _MASKED (the same launch sequence with the argmax of the transform kernels restricted
+// to it: n = 512 ... 4096, the spectrum cache neither read nor touched)
+struct ScorePass {
+    bool allow_spectrum_cache = true; // (the many-references fallback passes false)
+    const LagRange *window = nullptr;
+    int32_t path = MUSE_IN_WINDOW_PLAIN;
+    const SlideFuse *slide = nullptr;
+    const LagRange *mask() const { return window && path == MUSE_IN_WINDOW_MASKED ? window : nullptr; }
+    bool direct() const { return window && path == MUSE_IN_WINDOW_MFMA; }
+};
+int batch_score(muse_batch *b, const ScorePass &pass); // capi_batch.hip: muse_batch_score is batch_score(b, {})
+// what a call's pass through the transform kernels (every lag, or the argmax masked to *mask) would refuse for the batch as it stands
+// (kernel selection, storage, length), without enqueueing anything; *variant = the KERNEL_* the pass would launch first (-1: none of
+// them: a series longer than 65 536 samples)
+int batch_score_check(muse_batch *b, const LagRange *mask, int *variant);
 // the spectrum cache's policy, a pure host function: what a pass over `rows` rows of length N does about a cache
 // that does not exist yet -- nothing, build one of *bytes for *rows_cached rows, or decline for lack of memory
 enum { ZC_POLICY_NONE = 0, ZC_POLICY_BUILD = 1, ZC_POLICY_DECLINED = 2 };
 int spectrum_cache_policy(int64_t rows, int32_t N, bool f32, int mode, int64_t min_rows, int64_t free_bytes, int64_t budget,
                           int64_t *rows_cached, int64_t *bytes);
 void group_drop_spectrum_cache(muse_group *g);             // capi_batch.hip: frees the segments (ready_mu held, compute stream idle)
-int score_windowed(muse_batch *b);                     // capi_window.hip: the all-scores pass of a batch with a lag window (scores allocated)
 // capi_window.hip, what every caller of the lag-window kernels shares.  check_window_request: the refusals of a window of max_lag >= 0
 // over b's reference (f32: the rows are float32 storage); window_tables: the shifted-reference image and its window sums of b for
-// window L in e / pw, once per window (cached under *cached_L: -1 = none; the caller drops it when the reference changes);
-// window_params: the kernels' arguments for b's group and scores with those tables
+// the window w in e / pw, once per (origin, rows) (cached under *key: -1 = none, both at most 127; the caller drops it when the
+// reference changes); window_params: the kernels' arguments for b's group and scores with those tables
 int check_window_request(const muse_batch *b, int32_t max_lag, bool f32);
-int window_tables(muse_batch *b, int L, PoolBuf<double> &e, PoolBuf<double> &pw, int32_t *cached_L, hipStream_t st);
-// the key a lag range's tables (origin = its lags below zero, W rows) are cached under: no window +-L (L <= MUSE_LAG_WINDOW_MAX) has it,
-// so a symmetric pass never takes a range's tables or the other way round
-inline int32_t window_range_key(int origin, int W) { return 0x10000 + origin * 256 + W; }
-// a lag range lag_lo .. lag_hi (lag_lo <= 0 <= lag_hi) as the passes take it at FFT length n: hi = min(lag_hi, n / 2) lags above zero,
-// lneg = min(-lag_lo, n / 2 - 1) below
-struct LagRange {
-    int hi, lneg;
-    int W() const { return hi + lneg + 1; }
-};
-inline LagRange clip_lag_range(int64_t n, int32_t lag_lo, int32_t lag_hi)
-{
-    return LagRange{(int)std::min<int64_t>(lag_hi, n / 2), (int)std::min<int64_t>(-(int64_t)lag_lo, n / 2 - 1)};
-}
-// capi_window.hip: b's own tables (win_e / win_pw) of a lag range whose table has W rows and starts `origin` lags below zero, once
-// per range (cached under window_range_key)
-int window_range_tables(muse_batch *b, int origin, int W, hipStream_t st);
-// capi_window.hip: muse_batch_score_in_lag_range's dispatch (MUSE_IN_WINDOW_*), a pure host function
-int lag_range_plan(int32_t N, bool f32, int32_t lag_lo, int32_t lag_hi, bool force_transform);
-muse::WindowParams window_params(const muse_batch *b, int L, const double *e, const double *pw);
-// the lags a window +-L holds below zero at FFT length n: index n / 2 is lag +n/2 (xcorr.go:192-194), it is scanned once
-inline int window_lneg(int L, int n) { return 2 * L == n ? L - 1 : L; }
-// the masked argmax of the transform kernels (their WIN builds): the window +-L in the kernel's arguments
-inline void set_window(muse::FusedParams &p, int L)
+int window_tables(muse_batch *b, const LagRange &w, PoolBuf<double> &e, PoolBuf<double> &pw, int32_t *key, hipStream_t st);
+muse::WindowParams window_params(const muse_batch *b, const LagRange &w, const double *e, const double *pw);
+// the direct product over b's rows inside w, from b's own tables (device selected, rows uploaded, M > 0, mv / lag allocated); bracket:
+// the launch under a LaunchTimer of its own
+int score_direct(muse_batch *b, const LagRange &w, bool bracket = true);
+// The dispatch of every in-window entry point, a pure host function (MUSE_IN_WINDOW_*): which pass scores series of N samples (float32
+// storage or not) inside w, a window clipped at the FFT length of N
+int window_plan(int32_t N, bool f32, const LagRange &w, bool force_transform);
+// a call's window over one batch: plan_in_window fills *pass with what batch_score is to run, or refuses (nothing enqueued, the batch
+// unchanged); score_in_window plans, runs and names the pass
+int plan_in_window(muse_batch *b, const LagRange &w, ScorePass *pass);
+int score_in_window(muse_batch *b, const LagRange &w);
+// the masked argmax of the transform kernels (their WIN builds): cc indices 0 .. hi and n - lneg .. n - 1 in the kernel's arguments
+inline void set_window(muse::FusedParams &p, const LagRange &w)
 {
     p.win = 1;
-    p.win_lpos = L;
-    p.win_lneg = window_lneg(L, p.n);
+    p.win_lpos = w.hi;
+    p.win_lneg = w.lneg;
 }
-// the same for a lag range: cc indices 0 .. lpos and n - lneg .. n - 1
-inline void set_window(muse::FusedParams &p, int lpos, int lneg)
+// capi_window.hip: a call's lags lag_lo .. lag_hi against the batch's own window, which must be off or equal, i.e. L with -L .. L the
+// call's (r: the batch's index in a list, -1: a single batch)
+int check_own_window(const muse_batch *b, int32_t lag_lo, int32_t lag_hi, int r = -1);
+// Results.MaxLag of a Run inside lag_lo .. lag_hi: max(-lag_lo, lag_hi), every lag of the range passes the lag filter
+inline int32_t range_max_lag(int32_t lag_lo, int32_t lag_hi)
 {
-    p.win = 1;
-    p.win_lpos = lpos;
-    p.win_lneg = lneg;
+    return (int32_t)std::min<int64_t>(std::max<int64_t>(-(int64_t)lag_lo, lag_hi), INT32_MAX);
 }
-// capi_window.hip: a call's window against the batch's own, which must be off or equal (r: the batch's index in a list, -1: a single batch)
-int check_own_window(const muse_batch *b, int32_t max_lag, int r = -1);
 muse::FusedParams base_params(muse_batch *b);
 int ensure_select_ws(muse_batch *b, int64_t M, int64_t G, bool with_gid, int K, bool on_device);
 // the selection of a Run happens on the device (each chunk's best top_n) only beyond EXACT_FEED_MAX_GROUPS groups: capi_run.hip, run_select
@@ -539,6 +550,10 @@ int run_select(muse_batch *b, const int32_t *group_id, int32_t G_in, int64_t ser
                       std::vector<muse_record> &out, bool already_scored = false, bool prescreened = false);
 void emit(const std::vector<muse_record> &sel, int64_t *out_series, int32_t *out_lag, double *out_score,
                  int32_t *out_count, double *out_mean_abs);
+// the Run of a scored batch: run_select, then emit
+int run_scored(muse_batch *b, const int32_t *group_id, int32_t G, int32_t max_lag, int32_t top_n, double threshold, int32_t sign_filter,
+               int32_t abs_scores, int64_t *out_series, int32_t *out_lag, double *out_score, int32_t *out_count, double *out_mean_abs,
+               bool prescreened = false);
 // capi_run.hip: the selection's own argument checks (run_select applies them; a wrapper that moves or scores first applies them before)
 int check_select_args(const int32_t *group_id, int32_t G, int32_t sign_filter);
 // ---- capi_many.hip, what the many-references entry points share
@@ -548,12 +563,22 @@ int check_batch_list(muse_batch *const *bs, int32_t R);
 // which one-pass kernel family serves the list, a pure host decision (NONE: the batches are scored one after the other)
 enum ManyKind { MANY_NONE, MANY_SMALL, MANY_MULTI, MANY_LONG, MANY_REAL };
 ManyKind many_kind(muse_batch *const *bs, int32_t R);
-// ONE pass of the `kind` kernels over the rows for every batch of a checked list; win_L >= 0: the argmax masked to +-win_L (SMALL at
-// n <= 2048 and MULTI only), or with win_lneg >= 0 to the lag range -win_lneg .. win_L, the two bounds independent of each other
-int score_many_pass(muse_batch *const *bs, int32_t R, ManyKind kind, int win_L, int win_lneg = -1);
-// capi_window_many.hip: the direct product for a checked list of float64 batches with time-domain references, packed launches where
-// the planner packs; range == nullptr: the window +-max_lag, otherwise that (clipped) lag range for batches of one length
-int score_many_direct(muse_batch *const *bs, int32_t R, int32_t max_lag, const LagRange *range);
+// ONE pass of the `kind` kernels over the rows for every batch of a checked list; mask != nullptr: the argmax masked to it (SMALL at
+// n <= 2048 and MULTI only)
+int score_many_pass(muse_batch *const *bs, int32_t R, ManyKind kind, const LagRange *mask);
+// every lag for a checked list: that one pass where a kernel family serves the list, batch_score(., each) batch after batch otherwise
+int score_many_every_lag(muse_batch *const *bs, int32_t R, const ScorePass &each);
+// batches of one group share N, and with it (muse_batch_create) the FFT length; a list that does not is scored reference by reference
+inline bool one_length(muse_batch *const *bs, int32_t R)
+{
+    bool same = true;
+    for (int r = 1; r < R; r++)
+        same = same && bs[r]->N == bs[0]->N && bs[r]->n == bs[0]->n;
+    return same;
+}
+// capi_window_many.hip: the direct product inside w for a checked list of float64 batches of one length with time-domain references,
+// packed launches where the planner packs; alone: what names a reference that fills its launch alone
+int score_many_direct(muse_batch *const *bs, int32_t R, LagRange w, const ScoreOrigin &alone);
 // the Run of every batch of a scored list: run_select, then emit into row r of the caller's arrays
 int run_many_select(muse_batch *const *bs, int32_t R, const int32_t *group_id, int32_t G, int32_t max_lag, int32_t top_n,
                     double threshold, int32_t sign_filter, int32_t abs_scores, bool prescreened, int64_t *out_series,

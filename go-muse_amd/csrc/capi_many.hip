@@ -90,15 +90,14 @@ ManyKind many_kind(muse_batch *const *bs, int32_t R)
     return small_n ? MANY_SMALL : real_n ? MANY_REAL : long_n ? MANY_LONG : MANY_MULTI;
 }
 
-int score_many_pass(muse_batch *const *bs, int32_t R, ManyKind kind, int win_L, int win_lneg)
+int score_many_pass(muse_batch *const *bs, int32_t R, ManyKind kind, const LagRange *mask)
 {
     muse_batch *b0 = bs[0];
     muse_ctx *ctx = b0->ctx;
     const bool small_n = kind == MANY_SMALL, real_n = kind == MANY_REAL, long_n = kind == MANY_LONG;
-    const bool masked = win_L >= 0, range = masked && win_lneg >= 0; // (a lag range: the two bounds as the caller clipped them)
     // the unmasked pass is what each batch's own setting takes too: it says so from the start.  The masked pass is an argument of
     // its call: it names itself once its launches are enqueued (below)
-    for (int r = 0; r < R && !masked; r++)
+    for (int r = 0; r < R && !mask; r++)
         bs[r]->origin = ScoreOrigin{};
     int rc = use_device(ctx);
     if (rc)
@@ -139,10 +138,8 @@ int score_many_pass(muse_batch *const *bs, int32_t R, ManyKind kind, int win_L, 
     p.c1_many = (const double *const *)(t + 3 * R);
     p.zscratch = ctx->zscratch.p; // (read at n = 16384 only)
     p.zslots = (int)(ctx->zscratch.cap / 4096);
-    if (range)
-        set_window(p, win_L, win_lneg);
-    else if (masked)
-        set_window(p, win_L);
+    if (mask) // (the two bounds as the caller clipped them)
+        set_window(p, *mask);
     HIP_TRY(b0->ovf_list.ensure(ctx, 2 * p.npairs, b0->stream()));
     p.ovf_count = b0->ovf_count;
     p.work_counter = b0->ovf_count + 1;
@@ -177,10 +174,8 @@ int score_many_pass(muse_batch *const *bs, int32_t R, ManyKind kind, int win_L, 
         FusedParams q = base_params(bs[r]);
         q.pair_list = b0->ovf_list.p;
         q.pair_count = b0->ovf_count;
-        if (range) // the redone pairs keep their window (the WIN build of the redo kernel)
-            set_window(q, win_L, win_lneg);
-        else if (masked)
-            set_window(q, win_L);
+        if (mask) // the redone pairs keep their window (the WIN build of the redo kernel)
+            set_window(q, *mask);
         if (long_n) { // (the four-step kernel that isolates and rescales first, as behind a single long-series pass)
             q.npairs = std::min<long long>(q.npairs, (long long)ctx->num_cus * STOCKHAM_GLOBAL_WGS_PER_CU);
             HIP_TRY(launch_fused(q, KERNEL_STOCKHAM, ctx->num_cus, ctx->stream));
@@ -193,11 +188,10 @@ int score_many_pass(muse_batch *const *bs, int32_t R, ManyKind kind, int win_L, 
     for (int r = 0; r < R; r++) {
         muse_batch *b = bs[r];
         b->scores_exact = true; // mv / lag of every batch now hold fp64 results for every row
-        if (masked) { // as muse_batch_score_in_window leaves a batch; the unmasked pass, as muse_batch_score, leaves what the last Run did alone
+        if (mask) { // as muse_batch_score_in_window leaves a batch; the unmasked pass, as muse_batch_score, leaves what the last Run did alone
             b->last_path = MUSE_RUN_PATH_FP64;
             b->last_screened = false;
-            b->origin = range ? ScoreOrigin::in_lag_range(MUSE_IN_WINDOW_MASKED, win_L, win_lneg, ScoreOrigin::MANY)
-                              : ScoreOrigin::in_window(MUSE_IN_WINDOW_MASKED, win_L, ScoreOrigin::MANY);
+            b->origin = ScoreOrigin::in_window(MUSE_IN_WINDOW_MASKED, *mask, ScoreOrigin::MANY);
         }
     }
     return MUSE_OK;
@@ -211,16 +205,20 @@ extern "C" int muse_batch_score_many(muse_batch *const *bs, int32_t R)
     for (int r = 0; r < R; r++)
         if (bs[r]->windowed())
             return fail(MUSE_ERR_UNSUPPORTED, "a batch with a lag window cannot take part in a many-references pass");
+    return score_many_every_lag(bs, R, ScorePass{false}); // (a many-references pass never builds or reads the spectrum cache)
+}
+
+int score_many_every_lag(muse_batch *const *bs, int32_t R, const ScorePass &each)
+{
     const ManyKind kind = many_kind(bs, R);
-    if (kind == MANY_NONE) {
-        for (int r = 0; r < R; r++) {
-            rc = batch_score(bs[r], false); // (a many-references pass never builds or reads the spectrum cache)
-            if (rc)
-                return rc;
-        }
-        return MUSE_OK;
+    if (kind != MANY_NONE)
+        return score_many_pass(bs, R, kind, nullptr);
+    for (int r = 0; r < R; r++) {
+        const int rc = batch_score(bs[r], each);
+        if (rc)
+            return rc;
     }
-    return score_many_pass(bs, R, kind, -1);
+    return MUSE_OK;
 }
 
 int run_many_select(muse_batch *const *bs, int32_t R, const int32_t *group_id, int32_t G, int32_t max_lag, int32_t top_n,
@@ -229,13 +227,12 @@ int run_many_select(muse_batch *const *bs, int32_t R, const int32_t *group_id, i
 {
     const size_t cap = (size_t)std::max(top_n, 0);
     for (int r = 0; r < R; r++) {
-        std::vector<muse_record> sel;
-        const int rc = run_select(bs[r], group_id, G, 0, max_lag, top_n, threshold, sign_filter, abs_scores, sel, true, prescreened);
+        const int rc = run_scored(bs[r], group_id, G, max_lag, top_n, threshold, sign_filter, abs_scores,
+                                  out_series ? out_series + cap * r : nullptr, out_lag ? out_lag + cap * r : nullptr,
+                                  out_score ? out_score + cap * r : nullptr, out_count ? out_count + r : nullptr,
+                                  out_mean_abs ? out_mean_abs + r : nullptr, prescreened);
         if (rc)
             return rc;
-        emit(sel, out_series ? out_series + cap * r : nullptr, out_lag ? out_lag + cap * r : nullptr,
-             out_score ? out_score + cap * r : nullptr, out_count ? out_count + r : nullptr,
-             out_mean_abs ? out_mean_abs + r : nullptr);
     }
     return MUSE_OK;
 }

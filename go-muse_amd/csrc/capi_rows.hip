@@ -20,7 +20,7 @@
 // The WINDOWED forms (muse_batch_run_rows_windowed / _run_row_ptrs_windowed / _run_group_rows_windowed) are the same calls with the
 // per-row (lag, mv) of the lag window (muse_batch_set_lag_window) in place of the transform kernel's: the window is an argument of
 // the call, no batch's own setting is touched.  The slot keeps its own window tables (the e image and pw of launch_window_tables),
-// keyed by (the template spectrum's serial number, L) and rebuilt on the slot's stream when the key differs -- any number of host
+// keyed by (the template spectrum's serial number, window_tables' key) and rebuilt on the slot's stream when the key differs -- any number of host
 // threads share one template, so nothing is cached on it.  The window kernels need none of the context's shared scratch: every FFT
 // length runs on the slot's stream.  Few rows of long series take the split-K kernels (xcorr_window_split.hip) when
 // window_rows_plan says so; otherwise launch_window, the kernel of muse_batch_set_lag_window, untouched.
@@ -47,10 +47,10 @@ struct RowsSlot {
     SingleGroupOut *out = nullptr; // pinned: the winner record, written by the device
     hipEvent_t done = nullptr;
     hipStream_t stream = nullptr;  // the slot's own stream
-    // the windowed forms: the tables of launch_window_tables for (win_serial, win_L) (0: none), and the slabs of the split-K kernels
+    // the windowed forms: the tables of launch_window_tables for (win_serial, win_key) (0: none; window_tables' key), and the slabs of the split-K kernels
     PoolBuf<double> win_e, win_pw, win_slabs;
     uint64_t win_serial = 0;
-    int32_t win_L = -1;
+    int32_t win_key = -1;
 };
 
 // what a windowed call adds to slot_finish: the window, and (the test hook) where the slot's per-row results go before it is returned
@@ -230,19 +230,19 @@ static int slot_score_windowed(muse_ctx *ctx, RowsSlot *s, int32_t max_lag)
 {
     muse_batch *b = &s->b;
     const hipStream_t st = b->stream();
-    const int L = std::min(max_lag, b->n / 2);
+    const LagRange w = lag_window_range(b->n, max_lag);
     if (s->win_serial != b->sp->serial) // (another reference: whatever window the tables were built for)
-        s->win_L = -1;
-    const int rc = window_tables(b, L, s->win_e, s->win_pw, &s->win_L, st);
+        s->win_key = -1;
+    const int rc = window_tables(b, w, s->win_e, s->win_pw, &s->win_key, st);
     if (rc)
         return rc;
     s->win_serial = b->sp->serial;
-    const WindowParams p = window_params(b, L, s->win_e.p, s->win_pw.p);
+    const WindowParams p = window_params(b, w, s->win_e.p, s->win_pw.p);
     const int chunks = (b->N + WIN_KC - 1) / WIN_KC;
     const int forced = ctx->win_rows_slices.load(std::memory_order_relaxed);
     const int S = forced >= 1 ? std::min(forced, chunks) : window_rows_plan(p.M, p.N, ctx->num_cus, nullptr);
     if (S > 1)
-        HIP_TRY(s->win_slabs.ensure(ctx, (p.M + 15) / 16 * S * window_split_slab_doubles(L), st));
+        HIP_TRY(s->win_slabs.ensure(ctx, (p.M + 15) / 16 * S * window_split_slab_doubles(w.hi), st));
     LaunchTimer timer(ctx, false, st);
     HIP_TRY(timer.begin());
     if (S > 1)

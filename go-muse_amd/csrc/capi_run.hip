@@ -381,6 +381,17 @@ void emit(const std::vector<muse_record> &sel, int64_t *out_series, int32_t *out
         *out_mean_abs = sel.empty() ? std::numeric_limits<double>::quiet_NaN() : sum / (double)sel.size();
 }
 
+int run_scored(muse_batch *b, const int32_t *group_id, int32_t G, int32_t max_lag, int32_t top_n, double threshold, int32_t sign_filter,
+               int32_t abs_scores, int64_t *out_series, int32_t *out_lag, double *out_score, int32_t *out_count, double *out_mean_abs,
+               bool prescreened)
+{
+    std::vector<muse_record> sel;
+    const int rc = run_select(b, group_id, G, 0, max_lag, top_n, threshold, sign_filter, abs_scores, sel, true, prescreened);
+    if (!rc)
+        emit(sel, out_series, out_lag, out_score, out_count, out_mean_abs);
+    return rc;
+}
+
 extern "C" int muse_batch_run(muse_batch *b, const int32_t *group_id, int32_t G, int32_t max_lag, int32_t top_n,
                               double threshold, int32_t sign_filter, int32_t abs_scores, int64_t *out_series,
                               int32_t *out_lag, double *out_score, int32_t *out_count, double *out_mean_abs)

@@ -21,15 +21,15 @@ int check_window_request(const muse_batch *b, int32_t max_lag, bool f32)
     return MUSE_OK;
 }
 
-int check_own_window(const muse_batch *b, int32_t max_lag, int r)
+int check_own_window(const muse_batch *b, int32_t lag_lo, int32_t lag_hi, int r)
 {
-    if (!b->windowed() || b->lag_window == max_lag)
+    if (!b->windowed() || ((int64_t)lag_lo == -(int64_t)lag_hi && b->lag_window == lag_hi))
         return MUSE_OK;
-    if (r < 0)
-        return fail(MUSE_ERR_INVALID, "the batch has a lag window of %d of its own: it must be off or equal to the call's (%d)",
-                    b->lag_window, max_lag);
-    return fail(MUSE_ERR_INVALID, "batch %d has a lag window of %d of its own: it must be off or equal to the pass's (%d)", r,
-                b->lag_window, max_lag);
+    char who[32] = "the batch";
+    if (r >= 0)
+        snprintf(who, sizeof(who), "batch %d", r);
+    return fail(MUSE_ERR_INVALID, "%s has a lag window of %d of its own: it must be off or equal to the call's (lags %d .. %d)", who,
+                b->lag_window, lag_lo, lag_hi);
 }
 
 extern "C" int muse_batch_set_lag_window(muse_batch *b, int32_t max_lag)
@@ -55,31 +55,32 @@ extern "C" int muse_batch_lag_window(muse_batch *b, int32_t *max_lag)
     return MUSE_OK;
 }
 
-int window_tables(muse_batch *b, int L, PoolBuf<double> &e, PoolBuf<double> &pw, int32_t *cached_L, hipStream_t st)
+int window_tables(muse_batch *b, const LagRange &w, PoolBuf<double> &e, PoolBuf<double> &pw, int32_t *key, hipStream_t st)
 {
-    if (*cached_L == L)
+    const int32_t k = w.origin * 256 + w.rows();
+    if (*key == k)
         return MUSE_OK;
-    *cached_L = -1;
+    *key = -1;
     const long long e_len = window_e_len(b->N);
     HIP_TRY(e.ensure(b->ctx, e_len, st));
     HIP_TRY(pw.ensure(b->ctx, 2 * MUSE_LAG_WINDOW_MAX + 1, st));
-    HIP_TRY(launch_window_tables(b->xs, b->N, b->n, L, e.p, e_len, pw.p, st));
-    *cached_L = L;
+    HIP_TRY(launch_window_tables(b->xs, b->N, b->n, w.origin, w.rows(), e.p, e_len, pw.p, st));
+    *key = k;
     return MUSE_OK;
 }
 
-WindowParams window_params(const muse_batch *b, int L, const double *e, const double *pw)
+WindowParams window_params(const muse_batch *b, const LagRange &w, const double *e, const double *pw)
 {
     WindowParams p{};
     p.rows = b->g->rows;
     p.M = b->g->M;
     p.stride = b->g->stride;
     p.N = b->N;
-    p.L = L;
-    p.Lneg = window_lneg(L, b->n);
+    p.L = w.hi;
+    p.Lneg = w.lneg;
     p.invN = 1.0 / (double)b->N;
     p.invNm1 = 1.0 / (double)(b->N - 1);
-    p.origin = L;
+    p.origin = w.origin;
     p.e = e;
     p.pw = pw;
     p.mv = b->mv.p;
@@ -87,28 +88,17 @@ WindowParams window_params(const muse_batch *b, int L, const double *e, const do
     return p;
 }
 
-// a batch's own tables and arguments (win_e / win_pw under win_L)
-static int batch_window_params(muse_batch *b, int L, hipStream_t st, WindowParams *p)
+// the one direct-product pass: a batch's own window (muse_batch_score) and a call's (the MFMA path of every in-window entry point)
+int score_direct(muse_batch *b, const LagRange &w, bool bracket)
 {
-    const int rc = window_tables(b, L, b->win_e, b->win_pw, &b->win_L, st);
-    if (!rc)
-        *p = window_params(b, L, b->win_e.p, b->win_pw.p);
-    return rc;
-}
-
-// muse_batch_score of a batch with a window (device selected, rows uploaded, M > 0, mv / lag allocated)
-int score_windowed(muse_batch *b)
-{
-    muse_ctx *ctx = b->ctx;
     const hipStream_t st = b->stream();
-    const int L = std::min(b->lag_window, b->n / 2);
-    WindowParams p;
-    const int rc = batch_window_params(b, L, st, &p);
+    const int rc = window_tables(b, w, b->win_e, b->win_pw, &b->win_key, st);
     if (rc)
         return rc;
-    LaunchTimer timer(ctx, false, st);
-    HIP_TRY(timer.begin());
-    HIP_TRY(launch_window(p, st));
+    LaunchTimer timer(b->ctx, false, st);
+    if (bracket)
+        HIP_TRY(timer.begin());
+    HIP_TRY(launch_window(window_params(b, w, b->win_e.p, b->win_pw.p), st));
     HIP_TRY(timer.end());
     return MUSE_OK;
 }
@@ -143,7 +133,7 @@ extern "C" int muse_batch_slide_score_windowed(muse_batch *b, const double *tail
         return fail(MUSE_ERR_INVALID, "a windowed pass needs a lag window >= 0");
     rc = check_window_request(b, max_lag, g->f32);
     if (!rc)
-        rc = check_own_window(b, max_lag);
+        rc = check_own_window(b, -max_lag, max_lag);
     if (rc)
         return rc;
     if (M == 0) // nothing to move, nothing to score
@@ -161,18 +151,12 @@ extern "C" int muse_batch_slide_score_windowed(muse_batch *b, const double *tail
         return rc;
     b->origin = ScoreOrigin{};
     b->scores_exact = true;
-    const int L = std::min(max_lag, b->n / 2);
-    WindowParams p;
-    rc = batch_window_params(b, L, st, &p);
+    const LagRange w = lag_window_range(b->n, max_lag);
+    if (k == 0) // nothing moves and nothing is invalidated: the windowed pass alone
+        return score_direct(b, w);
+    rc = window_tables(b, w, b->win_e, b->win_pw, &b->win_key, st);
     if (rc)
         return rc;
-    if (k == 0) { // nothing moves and nothing is invalidated: the windowed pass alone
-        LaunchTimer timer(ctx, false, st);
-        HIP_TRY(timer.begin());
-        HIP_TRY(launch_window(p, st));
-        HIP_TRY(timer.end());
-        return MUSE_OK;
-    }
     rc = slide_upload_tails(g, M, tails, k, tail_stride);
     if (rc)
         return rc;
@@ -182,7 +166,7 @@ extern "C" int muse_batch_slide_score_windowed(muse_batch *b, const double *tail
     slide_invalidate(g, 0);
     LaunchTimer timer(ctx, false, st);
     HIP_TRY(timer.begin());
-    HIP_TRY(launch_window_slide(p, (const double *)g->slide_dev.p, k, st));
+    HIP_TRY(launch_window_slide(window_params(b, w, b->win_e.p, b->win_pw.p), (const double *)g->slide_dev.p, k, st));
     HIP_TRY(timer.end());
     HIP_TRY(hipStreamSynchronize(st));
     return MUSE_OK;
@@ -197,30 +181,24 @@ extern "C" int muse_batch_slide_run_windowed(muse_batch *b, const double *tails,
     int rc = check_select_args(group_id, G, sign_filter);
     if (!rc)
         rc = muse_batch_slide_score_windowed(b, tails, k, tail_stride, max_lag);
-    if (rc)
-        return rc;
-    std::vector<muse_record> sel;
-    rc = run_select(b, group_id, G, 0, max_lag, top_n, threshold, sign_filter, abs_scores, sel, true, false);
-    if (rc)
-        return rc;
-    emit(sel, out_series, out_lag, out_score, out_count, out_mean_abs);
-    return MUSE_OK;
+    return rc ? rc : run_scored(b, group_id, G, max_lag, top_n, threshold, sign_filter, abs_scores, out_series, out_lag, out_score, out_count, out_mean_abs);
 }
 
-// ---- the window as an argument, any width (muse_batch_score_in_window)
-// The dispatch, a pure host function: which pass scores series of N samples (float32 storage or not) inside +-max_lag.
-//   L == n / 2                                        : the window is every lag -- the plain pass of batch_score, any length, any storage
-//   float64, L <= MUSE_LAG_WINDOW_MAX, n <= 65536      : the direct product (score_windowed), unless `force_transform` and the length has masked kernels
-//   n in {512, 1024, 2048, 4096}, L > 63 or float32    : the transform kernels with a masked argmax (the WIN builds)
-//   anything else                                      : not built
-static int in_window_plan(int32_t N, bool f32, int32_t max_lag, bool force_transform)
+// ---- the window as an argument: any width (muse_batch_score_in_window), one-sided and asymmetric too (muse_batch_score_in_lag_range)
+// The dispatch of all of them, a pure host function: which pass scores series of N samples (float32 storage or not) inside w.
+//   w is every lag                                        : the plain pass of batch_score, any length, any storage
+//   float64, at most 2 MUSE_LAG_WINDOW_MAX + 1 table rows, n <= 65536 : the direct product (score_direct), its table starting at w.origin
+//                                                           (unless `force_transform` and the length has masked kernels)
+//   n in {512, 1024, 2048, 4096}, wider or float32        : the transform kernels with a masked argmax (the WIN builds), the two bounds
+//                                                           set independently
+//   anything else                                         : not built
+int window_plan(int32_t N, bool f32, const LagRange &w, bool force_transform)
 {
     const int64_t n = muse_next_pow2((double)N);
-    const int64_t L = std::min<int64_t>(max_lag, n / 2);
-    if (2 * L == n)
+    if (w.every_lag(n))
         return MUSE_IN_WINDOW_PLAIN;
     const bool masked_len = n == 512 || n == 1024 || n == 2048 || n == 4096;
-    if (!f32 && L <= MUSE_LAG_WINDOW_MAX && n <= GENERIC_MAX_N && !(force_transform && masked_len))
+    if (!f32 && w.rows() <= 2 * MUSE_LAG_WINDOW_MAX + 1 && n <= GENERIC_MAX_N && !(force_transform && masked_len))
         return MUSE_IN_WINDOW_MFMA;
     return masked_len ? MUSE_IN_WINDOW_MASKED : MUSE_IN_WINDOW_UNSUPPORTED;
 }
@@ -229,7 +207,15 @@ extern "C" int muse_test_in_window_plan(int32_t N, int32_t f32, int32_t max_lag,
 {
     if (!path || N < 2 || max_lag < 0)
         return fail(MUSE_ERR_INVALID, "bad in-window plan arguments (N >= 2, max_lag >= 0)");
-    *path = in_window_plan(N, f32 != 0, max_lag, false);
+    *path = window_plan(N, f32 != 0, lag_window_range(muse_next_pow2((double)N), max_lag), false);
+    return MUSE_OK;
+}
+
+extern "C" int muse_test_lag_range_plan(int32_t N, int32_t f32, int32_t lag_lo, int32_t lag_hi, int32_t *path)
+{
+    if (!path || N < 2 || lag_lo > 0 || lag_hi < 0)
+        return fail(MUSE_ERR_INVALID, "bad lag-range plan arguments (N >= 2, lag_lo <= 0 <= lag_hi)");
+    *path = window_plan(N, f32 != 0, clip_lag_range(muse_next_pow2((double)N), lag_lo, lag_hi), false);
     return MUSE_OK;
 }
 
@@ -249,6 +235,46 @@ extern "C" int muse_test_last_in_window_path(muse_batch *b, int32_t *path)
     return MUSE_OK;
 }
 
+static int fail_not_built(const muse_batch *b, const LagRange &w)
+{
+    return fail(MUSE_ERR_UNSUPPORTED, "the lags %d .. %d over series of %d samples%s are not built: more than %d table rows and float32 "
+                "storage take the masked argmax of the transform kernels of FFT lengths 512 ... 4096",
+                -w.lneg, w.hi, b->N, b->g->f32 ? " in float32 storage" : "", 2 * MUSE_LAG_WINDOW_MAX + 1);
+}
+
+int plan_in_window(muse_batch *b, const LagRange &w, ScorePass *pass)
+{
+    const int path = window_plan(b->N, b->g->f32, w, b->ctx->in_window_force.load());
+    if (path == MUSE_IN_WINDOW_UNSUPPORTED || (path == MUSE_IN_WINDOW_MFMA && !b->xs))
+        return fail_not_built(b, w);
+    *pass = ScorePass{path == MUSE_IN_WINDOW_PLAIN, &w, path}; // (a masked pass always reads the rows)
+    if (path == MUSE_IN_WINDOW_MFMA)
+        return MUSE_OK;
+    int variant = -1; // (what batch_score would refuse -- a forced kernel without a masked build -- before it touches the batch)
+    return batch_score_check(b, pass->mask(), &variant);
+}
+
+// as every in-window entry point leaves a batch it has scored
+static void scored_in_window(muse_batch *b, int path, const LagRange &w)
+{
+    b->scores_exact = true;
+    b->last_path = MUSE_RUN_PATH_FP64;
+    b->last_screened = false;
+    if (path != MUSE_IN_WINDOW_MASKED) // (batch_score records the masked origin: it knows the kernel it launches first)
+        b->origin = ScoreOrigin::in_window(path, w);
+}
+
+int score_in_window(muse_batch *b, const LagRange &w)
+{
+    ScorePass pass;
+    int rc = plan_in_window(b, w, &pass);
+    if (!rc)
+        rc = batch_score(b, pass);
+    if (!rc && b->g->M > 0)
+        scored_in_window(b, pass.path, w);
+    return rc;
+}
+
 extern "C" int muse_batch_score_in_window(muse_batch *b, int32_t max_lag)
 {
     // everything is checked before anything is enqueued: on a refusal the batch is unchanged
@@ -256,33 +282,8 @@ extern "C" int muse_batch_score_in_window(muse_batch *b, int32_t max_lag)
         return fail(MUSE_ERR_INVALID, "NULL batch");
     if (max_lag < 0)
         return fail(MUSE_ERR_INVALID, "a windowed pass needs a lag window >= 0");
-    int rc = check_own_window(b, max_lag);
-    if (rc)
-        return rc;
-    const int path = in_window_plan(b->N, b->g->f32, max_lag, b->ctx->in_window_force.load());
-    if (path == MUSE_IN_WINDOW_UNSUPPORTED || (path == MUSE_IN_WINDOW_MFMA && !b->xs))
-        return fail(MUSE_ERR_UNSUPPORTED, "a lag window of %d over series of %d samples%s is not built: wider than MUSE_LAG_WINDOW_MAX (%d) and for "
-                    "float32 storage the window is a masked argmax of the transform kernels of FFT lengths 512 ... 4096",
-                    max_lag, b->N, b->g->f32 ? " in float32 storage" : "", MUSE_LAG_WINDOW_MAX);
-    const int L = std::min(max_lag, b->n / 2);
-    const int32_t own = b->lag_window;
-    if (path == MUSE_IN_WINDOW_MASKED) { // (batch_score records the origin: it knows the kernel it launches first)
-        rc = batch_score(b, false, L);
-    } else { // the pass a batch with (MFMA) / without (PLAIN) a window of its own takes; the setting is put back, whatever the outcome
-        b->lag_window = path == MUSE_IN_WINDOW_MFMA ? max_lag : -1;
-        rc = batch_score(b, true);
-        b->lag_window = own;
-    }
-    if (rc)
-        return rc;
-    if (b->g->M == 0)
-        return MUSE_OK;
-    b->scores_exact = true;
-    b->last_path = MUSE_RUN_PATH_FP64;
-    b->last_screened = false;
-    if (path != MUSE_IN_WINDOW_MASKED)
-        b->origin = ScoreOrigin::in_window(path, L);
-    return MUSE_OK;
+    const int rc = check_own_window(b, -max_lag, max_lag);
+    return rc ? rc : score_in_window(b, lag_window_range(b->n, max_lag));
 }
 
 extern "C" int muse_batch_run_in_window(muse_batch *b, const int32_t *group_id, int32_t G, int32_t max_lag, int32_t top_n,
@@ -293,56 +294,7 @@ extern "C" int muse_batch_run_in_window(muse_batch *b, const int32_t *group_id, 
     int rc = check_select_args(group_id, G, sign_filter);
     if (!rc)
         rc = muse_batch_score_in_window(b, max_lag);
-    if (rc)
-        return rc;
-    std::vector<muse_record> sel;
-    rc = run_select(b, group_id, G, 0, max_lag, top_n, threshold, sign_filter, abs_scores, sel, true, false);
-    if (rc)
-        return rc;
-    emit(sel, out_series, out_lag, out_score, out_count, out_mean_abs);
-    return MUSE_OK;
-}
-
-// ---- one-sided and asymmetric windows: the best match inside lag_lo .. lag_hi, lag_lo <= 0 <= lag_hi (muse_batch_score_in_lag_range)
-// The range as the passes take it: clip_lag_range (capi_internal.h).  Its tables, the batch's own, start at its lowest lag:
-int window_range_tables(muse_batch *b, int origin, int W, hipStream_t st)
-{
-    const int32_t key = window_range_key(origin, W);
-    if (b->win_L == key)
-        return MUSE_OK;
-    b->win_L = -1;
-    const long long e_len = window_e_len(b->N);
-    HIP_TRY(b->win_e.ensure(b->ctx, e_len, st));
-    HIP_TRY(b->win_pw.ensure(b->ctx, 2 * MUSE_LAG_WINDOW_MAX + 1, st));
-    HIP_TRY(launch_window_tables(b->xs, b->N, b->n, origin, W, b->win_e.p, e_len, b->win_pw.p, st));
-    b->win_L = key;
-    return MUSE_OK;
-}
-// The dispatch, a pure host function: which pass scores series of N samples (float32 storage or not) inside lag_lo .. lag_hi; W = the
-// lags of the clipped range.  For lag_lo == -lag_hi it is in_window_plan's table row for row.
-//   the range is every lag                            : the plain pass of batch_score, any length, any storage
-//   float64, W <= 2 MUSE_LAG_WINDOW_MAX + 1, n <= 65536 : the direct product, its table starting at the lowest lag (unless `force_transform`
-//                                                       and the length has masked kernels)
-//   n in {512, 1024, 2048, 4096}, wider or float32    : the transform kernels with a masked argmax, the two bounds set independently
-//   anything else                                     : not built
-int lag_range_plan(int32_t N, bool f32, int32_t lag_lo, int32_t lag_hi, bool force_transform)
-{
-    const int64_t n = muse_next_pow2((double)N);
-    const LagRange r = clip_lag_range(n, lag_lo, lag_hi);
-    if (2 * (int64_t)r.hi == n && r.lneg == n / 2 - 1)
-        return MUSE_IN_WINDOW_PLAIN;
-    const bool masked_len = n == 512 || n == 1024 || n == 2048 || n == 4096;
-    if (!f32 && r.W() <= 2 * MUSE_LAG_WINDOW_MAX + 1 && n <= GENERIC_MAX_N && !(force_transform && masked_len))
-        return MUSE_IN_WINDOW_MFMA;
-    return masked_len ? MUSE_IN_WINDOW_MASKED : MUSE_IN_WINDOW_UNSUPPORTED;
-}
-
-extern "C" int muse_test_lag_range_plan(int32_t N, int32_t f32, int32_t lag_lo, int32_t lag_hi, int32_t *path)
-{
-    if (!path || N < 2 || lag_lo > 0 || lag_hi < 0)
-        return fail(MUSE_ERR_INVALID, "bad lag-range plan arguments (N >= 2, lag_lo <= 0 <= lag_hi)");
-    *path = lag_range_plan(N, f32 != 0, lag_lo, lag_hi, false);
-    return MUSE_OK;
+    return rc ? rc : run_scored(b, group_id, G, max_lag, top_n, threshold, sign_filter, abs_scores, out_series, out_lag, out_score, out_count, out_mean_abs);
 }
 
 extern "C" int muse_batch_score_in_lag_range(muse_batch *b, int32_t lag_lo, int32_t lag_hi)
@@ -352,62 +304,8 @@ extern "C" int muse_batch_score_in_lag_range(muse_batch *b, int32_t lag_lo, int3
         return fail(MUSE_ERR_INVALID, "NULL batch");
     if (lag_lo > 0 || lag_hi < 0)
         return fail(MUSE_ERR_INVALID, "the lag range %d .. %d does not hold lag 0 (lag_lo <= 0 <= lag_hi)", lag_lo, lag_hi);
-    if ((int64_t)lag_lo == -(int64_t)lag_hi) // by definition: the symmetric window's pass, bit for bit on every path
-        return muse_batch_score_in_window(b, lag_hi);
-    if (b->windowed())
-        return fail(MUSE_ERR_INVALID, "the batch has a lag window of %d of its own: it must be off, or equal to a range -L .. L", b->lag_window);
-    const int path = lag_range_plan(b->N, b->g->f32, lag_lo, lag_hi, b->ctx->in_window_force.load());
-    if (path == MUSE_IN_WINDOW_UNSUPPORTED || (path == MUSE_IN_WINDOW_MFMA && !b->xs))
-        return fail(MUSE_ERR_UNSUPPORTED, "the lag range %d .. %d over series of %d samples%s is not built: more than %d lags and float32 "
-                    "storage take the masked argmax of the transform kernels of FFT lengths 512 ... 4096",
-                    lag_lo, lag_hi, b->N, b->g->f32 ? " in float32 storage" : "", 2 * MUSE_LAG_WINDOW_MAX + 1);
-    const LagRange r = clip_lag_range(b->n, lag_lo, lag_hi);
-    int rc;
-    if (path != MUSE_IN_WINDOW_MFMA) { // (what batch_score would refuse -- a forced kernel without a masked build -- before it touches the batch)
-        int variant = -1;
-        rc = batch_score_check(b, path == MUSE_IN_WINDOW_MASKED ? r.hi : -1, &variant);
-        if (rc)
-            return rc;
-    }
-    if (path == MUSE_IN_WINDOW_MASKED) { // (batch_score records the origin: it knows the kernel it launches first)
-        rc = batch_score(b, false, r.hi, nullptr, r.lneg);
-    } else if (path == MUSE_IN_WINDOW_PLAIN) { // (the batch has no window of its own here)
-        rc = batch_score(b, true);
-    } else { // the direct product over a table whose row v is lag v - lneg: W rows, ceil(W / 16) accumulator tiles
-        muse_ctx *ctx = b->ctx;
-        rc = use_device(ctx);
-        if (rc)
-            return rc;
-        const hipStream_t st = b->stream();
-        rc = group_ready(b->g, st); // rows packed but not sent yet go first
-        if (rc)
-            return rc;
-        if (b->g->M == 0)
-            return MUSE_OK;
-        rc = ensure_scores(b);
-        if (rc)
-            return rc;
-        rc = window_range_tables(b, r.lneg, r.W(), st);
-        if (rc)
-            return rc;
-        WindowParams p = window_params(b, r.hi, b->win_e.p, b->win_pw.p);
-        p.Lneg = r.lneg;
-        p.origin = r.lneg;
-        LaunchTimer timer(ctx, false, st);
-        HIP_TRY(timer.begin());
-        HIP_TRY(launch_window(p, st));
-        HIP_TRY(timer.end());
-    }
-    if (rc)
-        return rc;
-    if (b->g->M == 0)
-        return MUSE_OK;
-    b->scores_exact = true;
-    b->last_path = MUSE_RUN_PATH_FP64;
-    b->last_screened = false;
-    if (path != MUSE_IN_WINDOW_MASKED)
-        b->origin = ScoreOrigin::in_lag_range(path, r.hi, r.lneg);
-    return MUSE_OK;
+    const int rc = check_own_window(b, lag_lo, lag_hi);
+    return rc ? rc : score_in_window(b, clip_lag_range(b->n, lag_lo, lag_hi));
 }
 
 extern "C" int muse_batch_run_in_lag_range(muse_batch *b, const int32_t *group_id, int32_t G, int32_t lag_lo, int32_t lag_hi,
@@ -419,42 +317,32 @@ extern "C" int muse_batch_run_in_lag_range(muse_batch *b, const int32_t *group_i
     int rc = check_select_args(group_id, G, sign_filter);
     if (!rc)
         rc = muse_batch_score_in_lag_range(b, lag_lo, lag_hi);
-    if (rc)
-        return rc;
-    // Results.MaxLag = max(-lag_lo, lag_hi): every lag of the range passes the lag filter
-    const int32_t max_lag = (int32_t)std::min<int64_t>(std::max<int64_t>(-(int64_t)lag_lo, lag_hi), INT32_MAX);
-    std::vector<muse_record> sel;
-    rc = run_select(b, group_id, G, 0, max_lag, top_n, threshold, sign_filter, abs_scores, sel, true, false);
-    if (rc)
-        return rc;
-    emit(sel, out_series, out_lag, out_score, out_count, out_mean_abs);
-    return MUSE_OK;
+    return rc ? rc : run_scored(b, group_id, G, range_max_lag(lag_lo, lag_hi), top_n, threshold, sign_filter, abs_scores, out_series, out_lag, out_score, out_count, out_mean_abs);
 }
 
 // ---- the slide and the pass of any window in one call (muse_batch_slide_score_in_window)
-// The dispatch, a pure host function: how series of N samples (float32 storage or not) are slid by k and scored inside +-max_lag.
-//   in_window_plan says UNSUPPORTED                    : not built
-//   in_window_plan says MFMA                           : muse_batch_slide_score_windowed (xcorr_window_slide.hip)
+// The dispatch, a pure host function: how series at FFT length n are slid and scored inside a window that window_plan sends to `pass`.
+//   window_plan says UNSUPPORTED                       : not built
+//   window_plan says MFMA                              : muse_batch_slide_score_windowed (xcorr_window_slide.hip)
 //   PLAIN or MASKED at FFT length 4096                 : the SLIDE builds of xcorr_fused_n4096_fold (one read and one write of the rows)
 //   anything else                                      : launch_row_slide and then the pass
 // Measured (tools/slide_in_window_bench.py, profiles/slide_in_window_bench.txt): the fused kernel against the two kernels
-// it replaces, per listed shape; no k is routed away from it.
-static int slide_in_window_plan(int32_t N, bool f32, int32_t max_lag, int32_t k, bool force_transform)
+// it replaces, per listed shape; no slide distance is routed away from it.
+static int slide_in_window_plan(int pass, int64_t n)
 {
-    (void)k;
-    const int pass = in_window_plan(N, f32, max_lag, force_transform);
     if (pass == MUSE_IN_WINDOW_UNSUPPORTED)
         return MUSE_SLIDE_IN_WINDOW_UNSUPPORTED;
     if (pass == MUSE_IN_WINDOW_MFMA)
         return MUSE_SLIDE_IN_WINDOW_MFMA;
-    return muse_next_pow2((double)N) == 4096 ? MUSE_SLIDE_IN_WINDOW_FUSED : MUSE_SLIDE_IN_WINDOW_TWO_STEP;
+    return n == 4096 ? MUSE_SLIDE_IN_WINDOW_FUSED : MUSE_SLIDE_IN_WINDOW_TWO_STEP;
 }
 
 extern "C" int muse_test_slide_in_window_plan(int32_t N, int32_t f32, int32_t max_lag, int32_t k, int32_t *path)
 {
     if (!path || N < 2 || max_lag < 0 || k < 0 || k > N)
         return fail(MUSE_ERR_INVALID, "bad slide-in-window plan arguments (N >= 2, max_lag >= 0, 0 <= k <= N)");
-    *path = slide_in_window_plan(N, f32 != 0, max_lag, k, false);
+    const int64_t n = muse_next_pow2((double)N);
+    *path = slide_in_window_plan(window_plan(N, f32 != 0, lag_window_range(n, max_lag), false), n);
     return MUSE_OK;
 }
 
@@ -485,39 +373,29 @@ extern "C" int muse_batch_slide_score_in_window(muse_batch *b, const double *tai
     const int64_t M = g->M;
     if (max_lag < 0)
         return fail(MUSE_ERR_INVALID, "a windowed pass needs a lag window >= 0");
-    rc = check_own_window(b, max_lag);
+    rc = check_own_window(b, -max_lag, max_lag);
     if (rc)
         return rc;
-    const bool force_transform = ctx->in_window_force.load();
-    const int pass = in_window_plan(b->N, g->f32, max_lag, force_transform);
-    int path = slide_in_window_plan(b->N, g->f32, max_lag, k, force_transform);
+    const LagRange w = lag_window_range(b->n, max_lag);
+    ScorePass pass{false, &w, window_plan(b->N, g->f32, w, ctx->in_window_force.load())}; // (the rows move: the spectrum cache stays out)
+    int path = slide_in_window_plan(pass.path, b->n);
     if (path == MUSE_SLIDE_IN_WINDOW_UNSUPPORTED || (path == MUSE_SLIDE_IN_WINDOW_MFMA && !b->xs))
-        return fail(MUSE_ERR_UNSUPPORTED, "a lag window of %d over series of %d samples%s is not built: wider than MUSE_LAG_WINDOW_MAX (%d) and for "
-                    "float32 storage the window is a masked argmax of the transform kernels of FFT lengths 512 ... 4096",
-                    max_lag, b->N, g->f32 ? " in float32 storage" : "", MUSE_LAG_WINDOW_MAX);
+        return fail_not_built(b, w);
     if (M == 0) // nothing to move, nothing to score
         return MUSE_OK;
     if (k == 0) // nothing moves and nothing is invalidated: the pass alone
         return muse_batch_score_in_window(b, max_lag);
-    const int L = std::min(max_lag, b->n / 2);
     if (path == MUSE_SLIDE_IN_WINDOW_MFMA) { // the direct product has a slide kernel of its own; the origin is muse_batch_score_in_window's
         rc = muse_batch_slide_score_windowed(b, tails, k, tail_stride, max_lag);
         if (rc)
             return rc;
-        b->last_path = MUSE_RUN_PATH_FP64;
-        b->last_screened = false;
-        b->origin = ScoreOrigin::in_window(MUSE_IN_WINDOW_MFMA, L);
+        scored_in_window(b, pass.path, w);
         b->origin.slide = path;
         return MUSE_OK;
     }
-    // the pass as muse_batch_score_in_window launches it: the masked one with the window in the kernel's arguments, the plain one
-    // with the batch's own setting (equal to the call's, or off) out of the way
-    const int win_L = pass == MUSE_IN_WINDOW_MASKED ? L : -1;
-    const int32_t own = b->lag_window;
-    b->lag_window = -1;
+    // the pass as muse_batch_score_in_window launches it, the plain one or the masked one: the call's, whatever the batch's own setting
     int variant = -1;
-    rc = batch_score_check(b, win_L, &variant);
-    b->lag_window = own;
+    rc = batch_score_check(b, pass.mask(), &variant);
     if (rc)
         return rc;
     // FUSED is the default n = 4096 kernel's build: a forced variant, a missing correction table or a hand-off learned from the rows
@@ -543,34 +421,24 @@ extern "C" int muse_batch_slide_score_in_window(muse_batch *b, const double *tai
     // tails have landed with it), and the call returns once they have finished
     HIP_TRY(hipDeviceSynchronize());
     slide_invalidate(g, 0);
-    b->lag_window = -1;
+    const SlideFuse fuse{g->slide_dev.p, k};
     if (path == MUSE_SLIDE_IN_WINDOW_FUSED) {
-        const SlideFuse fuse{g->slide_dev.p, k};
-        rc = batch_score(b, false, win_L, &fuse);
+        pass.slide = &fuse;
     } else {
-        rc = MUSE_OK;
-        {
-            LaunchTimer timer(ctx, false, st);
-            hipError_t e = timer.begin();
-            if (e == hipSuccess)
-                e = launch_row_slide(g->base(), g->f32, M, g->N, k, g->slide_dev.p, ctx->num_cus, st);
-            if (e == hipSuccess)
-                e = timer.end();
-            if (e != hipSuccess)
-                rc = fail(MUSE_ERR_HIP, "the row slide failed: %s", hipGetErrorString(e));
-        }
-        if (!rc)
-            rc = batch_score(b, false, win_L);
+        LaunchTimer timer(ctx, false, st);
+        hipError_t e = timer.begin();
+        if (e == hipSuccess)
+            e = launch_row_slide(g->base(), g->f32, M, g->N, k, g->slide_dev.p, ctx->num_cus, st);
+        if (e == hipSuccess)
+            e = timer.end();
+        if (e != hipSuccess)
+            return fail(MUSE_ERR_HIP, "the row slide failed: %s", hipGetErrorString(e));
     }
-    b->lag_window = own; // (put back, whatever the outcome)
+    rc = batch_score(b, pass);
     if (rc)
         return rc;
     HIP_TRY(hipStreamSynchronize(st));
-    b->scores_exact = true;
-    b->last_path = MUSE_RUN_PATH_FP64;
-    b->last_screened = false;
-    if (pass != MUSE_IN_WINDOW_MASKED) // (batch_score records the masked origin: it knows the kernel it launches first)
-        b->origin = ScoreOrigin::in_window(pass, L);
+    scored_in_window(b, pass.path, w);
     b->origin.slide = path;
     return MUSE_OK;
 }
@@ -584,14 +452,7 @@ extern "C" int muse_batch_slide_run_in_window(muse_batch *b, const double *tails
     int rc = check_select_args(group_id, G, sign_filter);
     if (!rc)
         rc = muse_batch_slide_score_in_window(b, tails, k, tail_stride, max_lag);
-    if (rc)
-        return rc;
-    std::vector<muse_record> sel;
-    rc = run_select(b, group_id, G, 0, max_lag, top_n, threshold, sign_filter, abs_scores, sel, true, false);
-    if (rc)
-        return rc;
-    emit(sel, out_series, out_lag, out_score, out_count, out_mean_abs);
-    return MUSE_OK;
+    return rc ? rc : run_scored(b, group_id, G, max_lag, top_n, threshold, sign_filter, abs_scores, out_series, out_lag, out_score, out_count, out_mean_abs);
 }
 
 // the reference's Run on the slid rows: the global argmax of every series, then the filter on Results.MaxLag
@@ -605,14 +466,7 @@ extern "C" int muse_batch_slide_run(muse_batch *b, const double *tails, int32_t 
         rc = fail(MUSE_ERR_INVALID, "the batch has a lag window of %d of its own: muse_batch_slide_run scores every lag", b->lag_window);
     if (!rc)
         rc = muse_batch_slide_score_in_window(b, tails, k, tail_stride, b ? b->n / 2 : 0);
-    if (rc)
-        return rc;
-    std::vector<muse_record> sel;
-    rc = run_select(b, group_id, G, 0, max_lag, top_n, threshold, sign_filter, abs_scores, sel, true, false);
-    if (rc)
-        return rc;
-    emit(sel, out_series, out_lag, out_score, out_count, out_mean_abs);
-    return MUSE_OK;
+    return rc ? rc : run_scored(b, group_id, G, max_lag, top_n, threshold, sign_filter, abs_scores, out_series, out_lag, out_score, out_count, out_mean_abs);
 }
 
 // test hook: the planner alone (xcorr_window_slide.hip), no device

@@ -61,21 +61,26 @@ extern "C" int muse_batch_score_many_windowed(muse_batch *const *bs, int32_t R, 
     for (int r = 0; r < R; r++) { // (the batches share the group and the window: behind r = 0 only the length check can still refuse)
         rc = check_window_request(bs[r], max_lag, bs[r]->g->f32);
         if (!rc)
-            rc = check_own_window(bs[r], max_lag, r);
+            rc = check_own_window(bs[r], -max_lag, max_lag, r);
         if (rc)
             return rc;
     }
-    return score_many_direct(bs, R, max_lag, nullptr);
+    // (a reference alone in its launch: the single-reference kernel, named as before the pass by the batch's own setting)
+    if (one_length(bs, R))
+        return score_many_direct(bs, R, lag_window_range(bs[0]->n, max_lag), ScoreOrigin{});
+    for (int r = 0; r < R && !rc; r++) // the clipping is per length: reference by reference
+        rc = score_many_direct(bs + r, 1, lag_window_range(bs[r]->n, max_lag), ScoreOrigin{});
+    return rc;
 }
 
-// The direct product for a checked list, in as few launches as the planner gives.  range == nullptr: the window +-max_lag, each
-// batch's tables under win_L = L as score_windowed caches them.  Otherwise the lag range -range->lneg .. range->hi, clipped to the
-// (shared) FFT length by the caller: tables whose row v is lag v - lneg, under window_range_key as muse_batch_score_in_lag_range
-// caches them -- the packed and the single pass serve each other's tables, and neither key is ever the other kind's.
-int score_many_direct(muse_batch *const *bs, int32_t R, int32_t max_lag, const LagRange *range)
+// The direct product inside w for a checked list of one length, in as few launches as the planner gives.  Each batch's tables are its
+// own, cached as score_direct caches them (window_tables): the packed and the single pass serve each other's tables.
+int score_many_direct(muse_batch *const *bs, int32_t R, LagRange w, const ScoreOrigin &alone)
 {
     muse_batch *b0 = bs[0];
     muse_ctx *ctx = b0->ctx;
+    if (!one_length(bs, R))
+        return fail(MUSE_ERR_INVALID, "a packed lag window needs batches of one length");
     int rc = use_device(ctx);
     if (rc)
         return rc;
@@ -88,33 +93,13 @@ int score_many_direct(muse_batch *const *bs, int32_t R, int32_t max_lag, const L
     const hipStream_t st = ctx->stream;
     for (int r = 0; r < R; r++) {
         rc = ensure_scores(bs[r]);
+        if (!rc)
+            rc = window_tables(bs[r], w, bs[r]->win_e, bs[r]->win_pw, &bs[r]->win_key, st);
         if (rc)
             return rc;
     }
-    // one window for the pass: batches of one group share N, and with it (muse_batch_create) the FFT length; a list that does
-    // not is scored reference by reference (a range's caller has sent such a list elsewhere: its clipping is per length)
-    bool same = true;
-    for (int r = 1; r < R; r++)
-        same = same && bs[r]->N == b0->N && bs[r]->n == b0->n;
-    if (range && !same)
-        return fail(MUSE_ERR_INVALID, "a packed lag range needs batches of one length");
-    const int L = range ? range->hi : std::min(max_lag, b0->n / 2);
-    const int W = range ? range->W() : 2 * L + 1;
     std::vector<int> launch_of((size_t)R), tiles_of((size_t)R);
-    int launches = R;
-    if (same) {
-        launches = window_many_plan(R, W, launch_of.data(), tiles_of.data());
-    } else {
-        for (int r = 0; r < R; r++)
-            launch_of[(size_t)r] = r;
-    }
-    // each batch's tables, cached under win_L exactly as the single form caches them: the same buffers serve both forms
-    for (int r = 0; r < R; r++) {
-        muse_batch *b = bs[r];
-        rc = range ? window_range_tables(b, range->lneg, W, st) : window_tables(b, std::min(max_lag, b->n / 2), b->win_e, b->win_pw, &b->win_L, st);
-        if (rc)
-            return rc;
-    }
+    window_many_plan(R, w.rows(), launch_of.data(), tiles_of.data());
     bool packed = false;
     for (int r = 0; r + 1 < R; r++)
         packed = packed || launch_of[(size_t)r] == launch_of[(size_t)r + 1];
@@ -138,17 +123,13 @@ int score_many_direct(muse_batch *const *bs, int32_t R, int32_t max_lag, const L
         int r1 = r0 + 1;
         while (r1 < R && launch_of[(size_t)r1] == launch_of[(size_t)r0])
             r1++;
-        muse_batch *b = bs[r0];
-        WindowParams p1 = window_params(b, range ? L : std::min(max_lag, b->n / 2), b->win_e.p, b->win_pw.p);
-        if (range) { // (muse_batch_score_in_lag_range's shape)
-            p1.Lneg = range->lneg;
-            p1.origin = range->lneg;
-        }
         if (r1 - r0 == 1) { // a reference that fills its launch alone: the single-reference kernel
-            HIP_TRY(launch_window(p1, st));
+            rc = score_direct(bs[r0], w, false);
+            if (rc)
+                return rc;
         } else {
             WindowManyParams p{};
-            static_cast<WindowShape &>(p) = p1;
+            static_cast<WindowShape &>(p) = window_params(bs[r0], w, nullptr, nullptr);
             p.R = r1 - r0;
             p.e = (const double *const *)(tab_dev + r0);
             p.pw = (const double *const *)(tab_dev + R + r0);
@@ -160,11 +141,7 @@ int score_many_direct(muse_batch *const *bs, int32_t R, int32_t max_lag, const L
             bs[r]->scores_exact = true;
             bs[r]->last_path = MUSE_RUN_PATH_FP64;
             bs[r]->last_screened = false;
-            // (a reference alone in its launch: the single-reference kernel, named as before the pass by the batch's own setting, or as
-            // the single range pass names it)
-            bs[r]->origin = r1 - r0 > 1 ? ScoreOrigin::packed(tiles_of[(size_t)launch_of[(size_t)r0]])
-                            : range     ? ScoreOrigin::in_lag_range(MUSE_IN_WINDOW_MFMA, range->hi, range->lneg)
-                                        : ScoreOrigin{};
+            bs[r]->origin = r1 - r0 > 1 ? ScoreOrigin::packed(tiles_of[(size_t)launch_of[(size_t)r0]]) : alone;
         }
         r0 = r1;
     }

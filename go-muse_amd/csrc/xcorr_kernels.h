@@ -198,10 +198,6 @@ inline bool window_wide(const double *rows, long long stride) { return stride % 
 inline long long window_e_len(int N) { return (long long)((N + WIN_KC - 1) / WIN_KC) * WIN_KC + WIN_E_TAIL; }
 // the tables of a window whose row v is lag v - origin, rows 0 .. W - 1 (a symmetric window +-L: origin = L, W = 2 L + 1)
 hipError_t launch_window_tables(const double *xs, int N, int n, int origin, int W, double *e, long long e_len, double *pw, hipStream_t stream);
-inline hipError_t launch_window_tables(const double *xs, int N, int n, int L, double *e, long long e_len, double *pw, hipStream_t stream)
-{
-    return launch_window_tables(xs, N, n, L, 2 * L + 1, e, e_len, pw, stream);
-}
 hipError_t launch_window(const WindowParams &p, hipStream_t stream);
 // ---- the same while the rows slide (xcorr_window_slide.hip; muse_batch_slide_score_windowed): xcorr_window_mfma over the NEW rows
 // -- old row[k .. N) followed by tails[r * k + 0 .. k), a dense M x k device buffer, 16-byte aligned -- which are stored in place on

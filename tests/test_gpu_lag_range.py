@@ -213,6 +213,52 @@ def test_rows_won_inside_the_range_keep_their_bits(muse, eng):
         h.close()
 
 
+def test_one_window_type_own_window_at_half_the_length_and_every_table_shape(muse, eng, oracle):
+    """the window +-L and the lag range are one description (origin, rows) of a table, cached under one key.
+    (a) a batch's own window at L = n / 2 keeps the symmetric form's table: origin 32, 31 lags below zero, 65 rows in five tiles
+    (N = n = 64, M = 33: two full 16-row tiles and one row; seed chosen on the CPU: the oracle flags no tie, row 32 wins at lag +32 and
+    row 11 at lag -31, the two ends of the scan).
+    (b) one batch walks every table shape in turn; after every step its bytes are a fresh batch's for the same call."""
+    B = muse.binding
+    # (a)
+    ref, rows = W.make_case(64, 33, seed=6478)
+    exp, _, _, n = LR.expect(oracle, ref, rows, (), Ls=(32,))
+    assert n == 64 and not exp[32][2].any() and exp[32][0][32] == 32 and exp[32][0][11] == -31
+    dg = muse.DeviceGroup.from_rows(eng, rows)
+    db = muse.DeviceBatch(eng, dg, ref)
+    db.set_lag_window(63)
+    lag, mv = db.scores()
+    check(lag, mv, *exp[32], tag="own window 63 at n = 64")
+    assert db.lag_window() == 63 and db.last_in_window_path() == 0
+    assert eng.kernel_name(db).startswith("xcorr_window_mfma<5, "), eng.kernel_name(db)
+    db.close()
+    dg.close()
+    # (b)
+    ref, rows = W.make_case(1024, 33, seed=6478)
+    dg = muse.DeviceGroup.from_rows(eng, rows)
+    db = muse.DeviceBatch(eng, dg, ref)
+    win = lambda L: (lambda b: b.scores_in_window(L))
+    rng = lambda lo, hi: (lambda b: b.scores_in_lag_range(lo, hi))
+    own7 = lambda b: (b.set_lag_window(7), b.scores())[1]
+    off = lambda b: (b.set_lag_window(-1), b.scores_in_lag_range(-3, 40))[1]
+    steps = (("window 7", win(7), -1, B.MUSE_IN_WINDOW_MFMA), ("range -7 .. 0", rng(-7, 0), -1, B.MUSE_IN_WINDOW_MFMA),
+             ("range 0 .. 7", rng(0, 7), -1, B.MUSE_IN_WINDOW_MFMA), ("range -7 .. 7", rng(-7, 7), -1, B.MUSE_IN_WINDOW_MFMA),
+             ("window 7 again", win(7), -1, B.MUSE_IN_WINDOW_MFMA), ("own window 7", own7, 7, 0),
+             ("range -7 .. 7 under the own window", rng(-7, 7), 7, B.MUSE_IN_WINDOW_MFMA),
+             ("window off, range -3 .. 40", off, -1, B.MUSE_IN_WINDOW_MFMA), ("window 40", win(40), -1, B.MUSE_IN_WINDOW_MFMA))
+    for tag, call, own, path in steps:
+        got = call(db)
+        fresh = muse.DeviceBatch(eng, dg, ref)
+        want = call(fresh)
+        assert got[0].tobytes() == want[0].tobytes() and got[1].tobytes() == want[1].tobytes(), tag
+        assert db.lag_window() == own, (tag, db.lag_window())                # (what was last set: no call touches it)
+        assert db.last_in_window_path() == fresh.last_in_window_path() == path, (tag, db.last_in_window_path())
+        assert eng.kernel_name(db) == eng.kernel_name(fresh), tag
+        fresh.close()
+    db.close()
+    dg.close()
+
+
 # ------------------------------------------------------------------ 5. refusals
 def test_refusals_leave_everything_as_it_was(muse, eng):
     B = muse.binding

@@ -130,6 +130,36 @@ def test_plan_pinned_rows(muse):
         assert P(4096, f32, -2046, 2048) == P(4096, f32, -2047, 2047) == B.MUSE_IN_WINDOW_MASKED
 
 
+def test_five_plan_hooks_are_one_planner(muse):
+    """the identities the five plan hooks share now that each is a call of one function: range(-L, L) is window(L); many(R) is
+    the single plan with MASKED read as MASKED_EACH at R = 1 and as MASKED at R >= 2 unless float32 at n <= 2048; the slide plan is
+    UNSUPPORTED / MFMA exactly where the window plan is"""
+    B = muse.binding
+    for N in (2, 63, 64, 65, 480, 512, 1000, 2048, 3000, 4096, 5000, 8192, 65536, 70000):
+        n = muse.next_pow2(float(N))
+        h = n // 2
+        ends = sorted(e for e in {0, 1, 7, 62, 63, 64, 126, 127, 128, h - 1, h, h + 1} if e >= 0)
+        for f32 in (False, True):
+            def many_of(single, R):
+                if single != B.MUSE_IN_WINDOW_MASKED:
+                    return single
+                return B.MUSE_IN_WINDOW_MASKED if R >= 2 and not (f32 and n <= 2048) else B.MUSE_IN_WINDOW_MASKED_EACH
+            for L in ends:
+                win = muse.in_window_plan(N, f32, L)
+                assert muse.lag_range_plan(N, f32, -L, L) == win, (N, f32, L)
+                for R in (1, 2, 8):
+                    assert muse.many_in_window_plan(N, f32, L, R) == muse.many_lag_range_plan(N, f32, -L, L, R) == many_of(win, R), (N, f32, L, R)
+                for k in (0, 1, N):
+                    slide = muse.slide_in_window_plan(N, f32, L, k)
+                    assert (slide == B.MUSE_SLIDE_IN_WINDOW_UNSUPPORTED) == (win == B.MUSE_IN_WINDOW_UNSUPPORTED), (N, f32, L, k)
+                    assert (slide == B.MUSE_SLIDE_IN_WINDOW_MFMA) == (win == B.MUSE_IN_WINDOW_MFMA), (N, f32, L, k)
+            for a in ends:
+                for b in ends:
+                    single = muse.lag_range_plan(N, f32, -a, b)
+                    for R in (1, 2, 8):
+                        assert muse.many_lag_range_plan(N, f32, -a, b, R) == many_of(single, R), (N, f32, -a, b, R)
+
+
 # ------------------------------------------------------------------ 3. the helper is the definition
 def _brute(cc, n, lo, hi):
     """the definition, spelled out index by index"""
