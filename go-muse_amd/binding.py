@@ -31,6 +31,9 @@ MUSE_ERR_EMPTY = -8
 MUSE_LAG_WINDOW_MAX = 63
 MUSE_IN_WINDOW_UNSUPPORTED, MUSE_IN_WINDOW_PLAIN, MUSE_IN_WINDOW_MFMA, MUSE_IN_WINDOW_MASKED = 0, 1, 2, 3   # muse_hip_test.h
 MUSE_IN_WINDOW_MASKED_EACH = 4   # (muse_test_many_in_window_plan only)
+MUSE_RUN_ROWS_LAG_RANGE_MAX = 2048
+(MUSE_ROWS_LAG_RANGE_UNSUPPORTED, MUSE_ROWS_LAG_RANGE_PLAIN, MUSE_ROWS_LAG_RANGE_WINDOW, MUSE_ROWS_LAG_RANGE_SPLIT,
+ MUSE_ROWS_LAG_RANGE_PANELS) = 0, 1, 2, 3, 4   # muse_hip_test.h (muse_test_rows_lag_range_plan)
 MUSE_SLIDE_IN_WINDOW_UNSUPPORTED, MUSE_SLIDE_IN_WINDOW_MFMA, MUSE_SLIDE_IN_WINDOW_FUSED, MUSE_SLIDE_IN_WINDOW_TWO_STEP = 0, 1, 2, 3   # muse_hip_test.h
 
 
@@ -96,6 +99,11 @@ SIGNATURES = {
     "muse_batch_run_rows_windowed": (ctypes.c_int, [_vp, _dp, _i64, _i64, _i32, _i32, _recp, ctypes.POINTER(ctypes.c_uint8)]),
     "muse_batch_run_row_ptrs_windowed": (ctypes.c_int, [_vp, ctypes.POINTER(_dp), _i64, _i32, _i32, _recp, ctypes.POINTER(ctypes.c_uint8)]),
     "muse_batch_run_group_rows_windowed": (ctypes.c_int, [_vp, _vp, _i64p, _i64, _i32, _i32, _recp, ctypes.POINTER(ctypes.c_uint8)]),
+    "muse_batch_run_rows_in_lag_range": (ctypes.c_int, [_vp, _dp, _i64, _i64, _i32, _i32, _i32, _recp, ctypes.POINTER(ctypes.c_uint8)]),
+    "muse_batch_run_row_ptrs_in_lag_range": (ctypes.c_int, [_vp, ctypes.POINTER(_dp), _i64, _i32, _i32, _i32, _recp, ctypes.POINTER(ctypes.c_uint8)]),
+    "muse_batch_run_group_rows_in_lag_range": (ctypes.c_int, [_vp, _vp, _i64p, _i64, _i32, _i32, _i32, _recp, ctypes.POINTER(ctypes.c_uint8)]),
+    "muse_test_rows_lag_range_plan": (ctypes.c_int, [_i64, _i32, _i32, _i32, _i32, _i32p, _i32p, _i32p]),
+    "muse_test_run_rows_in_lag_range_scores": (ctypes.c_int, [_vp, _dp, _i64, _i64, _i32, _i32, _i32p, _dp]),
     "muse_test_window_rows_plan": (ctypes.c_int, [_i64, _i32, _i32, _i32p, _i32p]),
     "muse_test_window_rows_slices": (ctypes.c_int, [_vp, _i32]),
     "muse_test_run_rows_windowed_scores": (ctypes.c_int, [_vp, _dp, _i64, _i64, _i32, _i32p, _dp]),

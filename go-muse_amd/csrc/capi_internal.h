@@ -554,6 +554,9 @@ void emit(const std::vector<muse_record> &sel, int64_t *out_series, int32_t *out
 int run_scored(muse_batch *b, const int32_t *group_id, int32_t G, int32_t max_lag, int32_t top_n, double threshold, int32_t sign_filter,
                int32_t abs_scores, int64_t *out_series, int32_t *out_lag, double *out_score, int32_t *out_count, double *out_mean_abs,
                bool prescreened = false);
+// muse_batch_run_groups with `score(b, score_arg)` filling mv / lag in place of muse_batch_score (nullptr: muse_batch_score)
+int run_groups(muse_batch *b, const int32_t *group_id, int32_t G, int64_t series_offset, int32_t abs_scores,
+               muse_record *out_records, uint8_t *out_state, int (*score)(muse_batch *, const void *), const void *score_arg);
 // capi_run.hip: the selection's own argument checks (run_select applies them; a wrapper that moves or scores first applies them before)
 int check_select_args(const int32_t *group_id, int32_t G, int32_t sign_filter);
 // ---- capi_many.hip, what the many-references entry points share

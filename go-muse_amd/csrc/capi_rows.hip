@@ -24,6 +24,12 @@
 // threads share one template, so nothing is cached on it.  The window kernels need none of the context's shared scratch: every FFT
 // length runs on the slot's stream.  Few rows of long series take the split-K kernels (xcorr_window_split.hip) when
 // window_rows_plan says so; otherwise launch_window, the kernel of muse_batch_set_lag_window, untouched.
+//
+// The LAG-RANGE forms (muse_batch_run_rows_in_lag_range / _run_row_ptrs_in_lag_range / _run_group_rows_in_lag_range) are the windowed
+// calls with the lags lag_lo .. lag_hi of muse_batch_score_in_lag_range in place of +-max_lag (WindowCall carries a LagRange; the
+// _windowed forms are its symmetric constructor).  rows_lag_range_plan, a pure host function, picks the pass: every lag -- the
+// unwindowed call; up to 127 lags -- the kernels above over a table that starts at lag_lo; up to 2048 lags -- the panel kernels
+// (xcorr_window_panels.hip), which split the lags over workgroups too; the slot's table cache keys the wide tables apart.
 #include "capi_internal.h"
 
 using namespace muse;
@@ -53,11 +59,27 @@ struct RowsSlot {
     int32_t win_key = -1;
 };
 
-// what a windowed call adds to slot_finish: the window, and (the test hook) where the slot's per-row results go before it is returned
+// what a windowed call adds to a Muse.Run: its lags, and (the test hooks) where the per-row results go before the slot is returned.
+// The _windowed forms are the symmetric constructor (lags -max_lag .. max_lag, at most MUSE_LAG_WINDOW_MAX either way, always the window
+// kernels); the _in_lag_range forms take the dispatch table of muse_batch_run_rows_in_lag_range (rows_lag_range_plan).
 struct WindowCall {
-    int32_t max_lag;
+    int32_t lo, hi;
+    bool ranged;   // an _in_lag_range form
     int32_t *lag_out;
     double *mv_out;
+    // filled in by check_window_call: the lags clipped at the template's FFT length, and the pass
+    LagRange w{0, 0, 0};
+    bool plain = false; // every lag: the unwindowed namesake's pass
+    bool wide = false;  // more than 2 MUSE_LAG_WINDOW_MAX + 1 table rows: the panel kernels
+    static WindowCall window(int32_t max_lag, int32_t *lag_out = nullptr, double *mv_out = nullptr)
+    {
+        return WindowCall{max_lag < 0 ? max_lag : -max_lag, max_lag, false, lag_out, mv_out};
+    }
+    static WindowCall range(int32_t lo, int32_t hi, int32_t *lag_out = nullptr, double *mv_out = nullptr)
+    {
+        return WindowCall{lo, hi, true, lag_out, mv_out};
+    }
+    bool direct() const { return !plain; } // the window kernels score it: every FFT length on the slot's stream
 };
 
 static void slot_destroy(RowsSlot *s)
@@ -224,15 +246,78 @@ static int slot_take(muse_batch *tmpl, int64_t M, size_t elems, RowsSlot **out, 
     return MUSE_OK;
 }
 
+// The dispatch of the _in_lag_range forms, a pure host function of (M, N, CUs, the clipped range): MUSE_ROWS_LAG_RANGE_*
+//   w is every lag                              : PLAIN, the unwindowed namesake's pass
+//   at most 2 MUSE_LAG_WINDOW_MAX + 1 table rows, n <= 65536 : the existing kernels -- WINDOW (launch_window), or SPLIT
+//                                                 (launch_window_split) when window_rows_plan says S > 1
+//   up to WIN_PANEL_MAX_ROWS rows, n <= 65536   : PANELS (xcorr_window_panels.hip), S by window_panels_plan
+//   anything else                               : not built
+static int rows_lag_range_plan(int64_t M, int32_t N, int num_cus, const LagRange &w, int *panels, int *S)
+{
+    const int64_t n = muse_next_pow2((double)N);
+    *panels = 0;
+    *S = 0;
+    if (w.every_lag(n))
+        return MUSE_ROWS_LAG_RANGE_PLAIN;
+    if (n > GENERIC_MAX_N || w.rows() > WIN_PANEL_MAX_ROWS)
+        return MUSE_ROWS_LAG_RANGE_UNSUPPORTED;
+    if (w.rows() <= 2 * MUSE_LAG_WINDOW_MAX + 1) {
+        *panels = 1;
+        *S = window_rows_plan(M, N, num_cus, nullptr);
+        return *S > 1 ? MUSE_ROWS_LAG_RANGE_SPLIT : MUSE_ROWS_LAG_RANGE_WINDOW;
+    }
+    *S = window_panels_plan(M, N, num_cus, w.rows(), panels);
+    return MUSE_ROWS_LAG_RANGE_PANELS;
+}
+
+// the panel pass over b's rows inside w (device selected, rows in place, M > 0, mv / lag allocated): the wide tables in e / pw, cached
+// under *key -- (origin, rows) of up to 2048 each above bit 30, where no key of window_tables (origin 256 + rows, both <= 127) lies --
+// then launch_window_panels into `slabs`, all on b's stream
+static int score_panels(muse_batch *b, const LagRange &w, PoolBuf<double> &e, PoolBuf<double> &pw, PoolBuf<double> &slabs, int32_t *key)
+{
+    muse_ctx *ctx = b->ctx;
+    const hipStream_t st = b->stream();
+    const int W = w.rows();
+    const int32_t k = 0x40000000 + w.origin * 4096 + W;
+    if (*key != k) {
+        *key = -1;
+        const long long e_len = window_panels_e_len(b->N, W);
+        HIP_TRY(e.ensure(ctx, e_len, st));
+        HIP_TRY(pw.ensure(ctx, W, st));
+        HIP_TRY(launch_window_tables_wide(b->xs, b->N, b->n, w.origin, W, e.p, e_len, pw.p, st));
+        *key = k;
+    }
+    const WindowParams p = window_params(b, w, e.p, pw.p);
+    const int chunks = (b->N + WIN_KC - 1) / WIN_KC;
+    const int forced = ctx->win_rows_slices.load(std::memory_order_relaxed);
+    int panels = 0;
+    int S = window_panels_plan(p.M, p.N, ctx->num_cus, W, &panels);
+    if (forced >= 1)
+        S = std::min(forced, chunks);
+    HIP_TRY(slabs.ensure(ctx, (p.M + 15) / 16 * panels * S * window_panels_slab_doubles(), st));
+    LaunchTimer timer(ctx, false, st);
+    HIP_TRY(timer.begin());
+    HIP_TRY(launch_window_panels(p, S, slabs.p, st));
+    HIP_TRY(timer.end());
+    return MUSE_OK;
+}
+
 // the windowed per-row pass of a slot (rows in place or their copy enqueued, mv / lag allocated): the slot's tables for
-// (spectrum, L), then launch_window or -- few rows of long series -- the split-K kernels, all on the slot's stream
-static int slot_score_windowed(muse_ctx *ctx, RowsSlot *s, int32_t max_lag)
+// (spectrum, origin, rows), then launch_window or -- few rows of long series -- the split-K kernels, or -- more than 127 table rows --
+// the panel kernels, all on the slot's stream
+static int slot_score_windowed(muse_ctx *ctx, RowsSlot *s, const WindowCall &wc)
 {
     muse_batch *b = &s->b;
     const hipStream_t st = b->stream();
-    const LagRange w = lag_window_range(b->n, max_lag);
+    const LagRange w = wc.w;
     if (s->win_serial != b->sp->serial) // (another reference: whatever window the tables were built for)
         s->win_key = -1;
+    if (wc.wide) {
+        const int prc = score_panels(b, w, s->win_e, s->win_pw, s->win_slabs, &s->win_key);
+        if (!prc)
+            s->win_serial = b->sp->serial;
+        return prc;
+    }
     const int rc = window_tables(b, w, s->win_e, s->win_pw, &s->win_key, st);
     if (rc)
         return rc;
@@ -242,7 +327,7 @@ static int slot_score_windowed(muse_ctx *ctx, RowsSlot *s, int32_t max_lag)
     const int forced = ctx->win_rows_slices.load(std::memory_order_relaxed);
     const int S = forced >= 1 ? std::min(forced, chunks) : window_rows_plan(p.M, p.N, ctx->num_cus, nullptr);
     if (S > 1)
-        HIP_TRY(s->win_slabs.ensure(ctx, (p.M + 15) / 16 * S * window_split_slab_doubles(w.hi), st));
+        HIP_TRY(s->win_slabs.ensure(ctx, (p.M + 15) / 16 * S * window_split_slab_doubles(p), st));
     LaunchTimer timer(ctx, false, st);
     HIP_TRY(timer.begin());
     if (S > 1)
@@ -262,7 +347,7 @@ static int slot_finish(muse_ctx *ctx, RowsSlot *s, int64_t M, int32_t abs_scores
     int rc = MUSE_OK;
     if (e == hipSuccess) {
         // the fused kernel automatic selection takes for this length (and its redo launch, if any), or the window kernels
-        rc = wc ? slot_score_windowed(ctx, s, wc->max_lag) : muse_batch_score(&s->b);
+        rc = wc && wc->direct() ? slot_score_windowed(ctx, s, *wc) : muse_batch_score(&s->b);
         if (!rc)
             e = launch_single_group(s->b.mv.p, s->b.lag.p, M, abs_scores ? 1 : 0, 0, s->out, st);
     }
@@ -318,15 +403,63 @@ static int slot_finish(muse_ctx *ctx, RowsSlot *s, int64_t M, int32_t abs_scores
     return MUSE_OK;
 }
 
-// the refusals of the windowed forms (nothing is changed before the last of them has passed)
-static int check_window_call(const muse_batch *tmpl, int32_t max_lag)
+// the refusals of the windowed forms (nothing is changed before the last of them has passed), and the call's pass
+static int check_window_call(const muse_batch *tmpl, WindowCall *wc)
 {
-    if (max_lag < 0)
-        return fail(MUSE_ERR_INVALID, "a windowed Muse.Run needs a lag window >= 0");
-    if (tmpl->windowed() && tmpl->lag_window != max_lag)
-        return fail(MUSE_ERR_INVALID, "the template has a lag window of %d of its own: it must be off or equal to the call's (%d)",
-                    tmpl->lag_window, max_lag);
-    return check_window_request(tmpl, max_lag, false); // (the rows are the call's own float64: the template's group is not read)
+    if (!wc->ranged) {
+        const int32_t max_lag = wc->hi;
+        if (max_lag < 0)
+            return fail(MUSE_ERR_INVALID, "a windowed Muse.Run needs a lag window >= 0");
+        if (tmpl->windowed() && tmpl->lag_window != max_lag)
+            return fail(MUSE_ERR_INVALID, "the template has a lag window of %d of its own: it must be off or equal to the call's (%d)",
+                        tmpl->lag_window, max_lag);
+        wc->w = lag_window_range(tmpl->n, max_lag);
+        return check_window_request(tmpl, max_lag, false); // (the rows are the call's own float64: the template's group is not read)
+    }
+    if (wc->lo > 0 || wc->hi < 0)
+        return fail(MUSE_ERR_INVALID, "the lag range %d .. %d does not hold lag 0 (lag_lo <= 0 <= lag_hi)", wc->lo, wc->hi);
+    const int rc = check_own_window(tmpl, wc->lo, wc->hi);
+    if (rc)
+        return rc;
+    wc->w = clip_lag_range(tmpl->n, wc->lo, wc->hi);
+    int panels = 0, S = 0;
+    const int path = rows_lag_range_plan(1, tmpl->N, 1, wc->w, &panels, &S); // (which pass: M and the CUs choose S only)
+    wc->plain = path == MUSE_ROWS_LAG_RANGE_PLAIN;
+    wc->wide = path == MUSE_ROWS_LAG_RANGE_PANELS;
+    if (path == MUSE_ROWS_LAG_RANGE_UNSUPPORTED || (!wc->plain && !tmpl->xs))
+        return fail(MUSE_ERR_UNSUPPORTED, "a Muse.Run inside the lags %d .. %d over series of %d samples is not built: up to %d lags of "
+                    "series of up to %d samples, or every lag", -wc->w.lneg, wc->w.hi, tmpl->N, WIN_PANEL_MAX_ROWS, GENERIC_MAX_N);
+    return MUSE_OK;
+}
+
+// the pass of a general path's private batch inside the call's lags: the direct product of batch_score up to 127 table rows, the
+// panel pass beyond (its slabs: the caller's, released behind the Run)
+struct GeneralPass {
+    const WindowCall *wc;
+    PoolBuf<double> *slabs;
+};
+static int general_score(muse_batch *b, const void *arg)
+{
+    const GeneralPass *gp = (const GeneralPass *)arg;
+    const WindowCall *wc = gp->wc;
+    if (!wc->wide) {
+        ScorePass pass;
+        pass.window = &wc->w;
+        pass.path = MUSE_IN_WINDOW_MFMA;
+        return batch_score(b, pass);
+    }
+    // as batch_score prepares a pass
+    int rc = use_device(b->ctx);
+    if (!rc)
+        rc = group_ready(b->g, b->stream());
+    if (rc || b->g->M == 0)
+        return rc;
+    rc = ensure_scores(b);
+    if (rc)
+        return rc;
+    b->origin = ScoreOrigin{};
+    b->scores_exact = true;
+    return score_panels(b, wc->w, b->win_e, b->win_pw, *gp->slabs, &b->win_key);
 }
 
 // the private batch of a general path: like tmpl over g, with the call's window (if any); Run with G = 1; the test hook's scores
@@ -335,14 +468,19 @@ static int run_general_batch(muse_batch *tmpl, muse_group *g, int64_t M, int32_t
 {
     muse_batch *b = nullptr;
     int rc = muse_batch_create_like(tmpl, g, &b);
-    if (!rc && wc)
-        rc = muse_batch_set_lag_window(b, wc->max_lag);
+    PoolBuf<double> slabs;
     if (!rc) {
         std::vector<int32_t> gid((size_t)M, 0);
-        rc = muse_batch_run_groups(b, gid.data(), 1, 0, abs_scores, out_winner, out_state);
+        const GeneralPass gp{wc, &slabs};
+        const bool direct = wc && wc->direct();
+        rc = run_groups(b, gid.data(), 1, 0, abs_scores, out_winner, out_state, direct ? general_score : nullptr, &gp);
     }
     if (!rc && wc && wc->lag_out && wc->mv_out)
         rc = muse_batch_read_scores(b, wc->lag_out, wc->mv_out);
+    if (slabs.p) {
+        (void)hipStreamSynchronize(b->stream()); // nothing of this call may still be using the slabs
+        slabs.release(tmpl->ctx);
+    }
     muse_batch_free(b);
     return rc;
 }
@@ -372,14 +510,14 @@ static int run_rows_general(muse_batch *tmpl, const double *rows, const double *
 // rows: M x N with stride row_stride, or (rows == NULL) row_ptrs[r] -> the N samples of row r
 // wc: the windowed forms (NULL: the transform kernels)
 static int run_rows(muse_batch *tmpl, const double *rows, const double *const *row_ptrs, int64_t M, int64_t row_stride,
-                    int32_t abs_scores, muse_record *out_winner, uint8_t *out_state, const WindowCall *wc = nullptr)
+                    int32_t abs_scores, muse_record *out_winner, uint8_t *out_state, WindowCall *wc = nullptr)
 {
     if (!tmpl || !out_winner || !out_state || M < 0 || (M > 0 && !rows && !row_ptrs))
         return fail(MUSE_ERR_INVALID, "bad arguments");
     *out_winner = muse_record{-1, 0.0, 0, 0};
     *out_state = 0;
     if (wc) {
-        const int wrc = check_window_call(tmpl, wc->max_lag);
+        const int wrc = check_window_call(tmpl, wc);
         if (wrc)
             return wrc;
     } else if (tmpl->windowed()) {
@@ -403,7 +541,7 @@ static int run_rows(muse_batch *tmpl, const double *rows, const double *const *r
     if (elems > ROWS_SLOT_MAX_ELEMS)
         return run_rows_general(tmpl, rows, row_ptrs, M, row_stride, abs_scores, out_winner, out_state, wc);
     RowsSlot *s = nullptr;
-    rc = slot_take(tmpl, M, elems, &s, wc != nullptr);
+    rc = slot_take(tmpl, M, elems, &s, wc && wc->direct());
     if (rc)
         return rc;
     const hipStream_t st = s->b.stream();
@@ -460,14 +598,14 @@ static int run_group_rows_general(muse_batch *tmpl, muse_group *src, const int64
 }
 
 static int run_group_rows(muse_batch *tmpl, muse_group *src, const int64_t *rows, int64_t M, int32_t abs_scores,
-                          muse_record *out_winner, uint8_t *out_state, const WindowCall *wc)
+                          muse_record *out_winner, uint8_t *out_state, WindowCall *wc)
 {
     if (!tmpl || !src || !out_winner || !out_state || M < 0 || (M > 0 && !rows))
         return fail(MUSE_ERR_INVALID, "bad arguments");
     *out_winner = muse_record{-1, 0.0, 0, 0};
     *out_state = 0;
     if (wc) {
-        const int wrc = check_window_call(tmpl, wc->max_lag);
+        const int wrc = check_window_call(tmpl, wc);
         if (wrc)
             return wrc;
     } else if (tmpl->windowed()) {
@@ -497,7 +635,7 @@ static int run_group_rows(muse_batch *tmpl, muse_group *src, const int64_t *rows
         contiguous = rows[i] == rows[0] + i;
     // the index list rides at the end of the slot's device buffer (behind the M x N gathered rows)
     RowsSlot *s = nullptr;
-    rc = slot_take(tmpl, M, contiguous ? elems : elems + (size_t)M, &s, wc != nullptr);
+    rc = slot_take(tmpl, M, contiguous ? elems : elems + (size_t)M, &s, wc && wc->direct());
     if (rc)
         return rc;
     const hipStream_t st = s->b.stream();
@@ -542,7 +680,7 @@ extern "C" int muse_batch_run_rows_windowed(muse_batch *tmpl, const double *rows
 {
     if (M > 0 && !rows)
         return fail(MUSE_ERR_INVALID, "bad arguments");
-    const WindowCall wc{max_lag, nullptr, nullptr};
+    WindowCall wc = WindowCall::window(max_lag);
     return run_rows(tmpl, rows, nullptr, M, row_stride, abs_scores, out_winner, out_state, &wc);
 }
 
@@ -551,18 +689,70 @@ extern "C" int muse_batch_run_row_ptrs_windowed(muse_batch *tmpl, const double *
 {
     if (M > 0 && !rows)
         return fail(MUSE_ERR_INVALID, "bad arguments");
-    const WindowCall wc{max_lag, nullptr, nullptr};
+    WindowCall wc = WindowCall::window(max_lag);
     return run_rows(tmpl, nullptr, rows, M, 0, abs_scores, out_winner, out_state, &wc);
 }
 
 extern "C" int muse_batch_run_group_rows_windowed(muse_batch *tmpl, muse_group *src, const int64_t *rows, int64_t M, int32_t max_lag,
                                                   int32_t abs_scores, muse_record *out_winner, uint8_t *out_state)
 {
-    const WindowCall wc{max_lag, nullptr, nullptr};
+    WindowCall wc = WindowCall::window(max_lag);
+    return run_group_rows(tmpl, src, rows, M, abs_scores, out_winner, out_state, &wc);
+}
+
+// ---- the same inside the lags lag_lo .. lag_hi (lag_lo <= 0 <= lag_hi): the per-row (lag, mv) is muse_batch_score_in_lag_range's,
+// for up to MUSE_RUN_ROWS_LAG_RANGE_MAX lags (rows_lag_range_plan), everything behind it unchanged
+extern "C" int muse_batch_run_rows_in_lag_range(muse_batch *tmpl, const double *rows, int64_t M, int64_t row_stride, int32_t lag_lo,
+                                                int32_t lag_hi, int32_t abs_scores, muse_record *out_winner, uint8_t *out_state)
+{
+    if (M > 0 && !rows)
+        return fail(MUSE_ERR_INVALID, "bad arguments");
+    WindowCall wc = WindowCall::range(lag_lo, lag_hi);
+    return run_rows(tmpl, rows, nullptr, M, row_stride, abs_scores, out_winner, out_state, &wc);
+}
+
+extern "C" int muse_batch_run_row_ptrs_in_lag_range(muse_batch *tmpl, const double *const *rows, int64_t M, int32_t lag_lo,
+                                                    int32_t lag_hi, int32_t abs_scores, muse_record *out_winner, uint8_t *out_state)
+{
+    if (M > 0 && !rows)
+        return fail(MUSE_ERR_INVALID, "bad arguments");
+    WindowCall wc = WindowCall::range(lag_lo, lag_hi);
+    return run_rows(tmpl, nullptr, rows, M, 0, abs_scores, out_winner, out_state, &wc);
+}
+
+extern "C" int muse_batch_run_group_rows_in_lag_range(muse_batch *tmpl, muse_group *src, const int64_t *rows, int64_t M, int32_t lag_lo,
+                                                      int32_t lag_hi, int32_t abs_scores, muse_record *out_winner, uint8_t *out_state)
+{
+    WindowCall wc = WindowCall::range(lag_lo, lag_hi);
     return run_group_rows(tmpl, src, rows, M, abs_scores, out_winner, out_state, &wc);
 }
 
 // ---- test hooks of the windowed forms (include/muse_hip_test.h)
+extern "C" int muse_test_rows_lag_range_plan(int64_t M, int32_t N, int32_t num_cus, int32_t lag_lo, int32_t lag_hi, int32_t *path,
+                                             int32_t *panels, int32_t *S)
+{
+    if (M < 1 || N < 2 || num_cus < 1 || lag_lo > 0 || lag_hi < 0 || !path)
+        return fail(MUSE_ERR_INVALID, "rows lag-range plan: M >= 1, N >= 2, num_cus >= 1, lag_lo <= 0 <= lag_hi");
+    int pn = 0, s = 0;
+    *path = rows_lag_range_plan(M, N, num_cus, clip_lag_range(muse_next_pow2((double)N), lag_lo, lag_hi), &pn, &s);
+    if (panels)
+        *panels = pn;
+    if (S)
+        *S = s;
+    return MUSE_OK;
+}
+
+extern "C" int muse_test_run_rows_in_lag_range_scores(muse_batch *tmpl, const double *rows, int64_t M, int64_t row_stride,
+                                                      int32_t lag_lo, int32_t lag_hi, int32_t *lag_out, double *mv_out)
+{
+    if (M > 0 && (!rows || !lag_out || !mv_out))
+        return fail(MUSE_ERR_INVALID, "bad arguments");
+    muse_record win;
+    uint8_t state = 0;
+    WindowCall wc = WindowCall::range(lag_lo, lag_hi, lag_out, mv_out);
+    return run_rows(tmpl, rows, nullptr, M, row_stride, 0, &win, &state, &wc);
+}
+
 extern "C" int muse_test_window_rows_plan(int64_t M, int32_t N, int32_t num_cus, int32_t *S, int32_t *chunks_per_slice)
 {
     if (M < 1 || N < 2 || num_cus < 1 || !S)
@@ -589,7 +779,7 @@ extern "C" int muse_test_run_rows_windowed_scores(muse_batch *tmpl, const double
         return fail(MUSE_ERR_INVALID, "bad arguments");
     muse_record win;
     uint8_t state = 0;
-    const WindowCall wc{max_lag, lag_out, mv_out};
+    WindowCall wc = WindowCall::window(max_lag, lag_out, mv_out);
     return run_rows(tmpl, rows, nullptr, M, row_stride, 0, &win, &state, &wc);
 }
 

@@ -427,12 +427,19 @@ extern "C" int muse_batch_run_shard(muse_batch *b, const int32_t *group_id, int3
 extern "C" int muse_batch_run_groups(muse_batch *b, const int32_t *group_id, int32_t G, int64_t series_offset,
                                      int32_t abs_scores, muse_record *out_records, uint8_t *out_state)
 {
+    return run_groups(b, group_id, G, series_offset, abs_scores, out_records, out_state, nullptr, nullptr);
+}
+
+// score: the pass that fills b's mv / lag in place of muse_batch_score (a call's lag range: capi_rows.hip), nullptr = muse_batch_score
+int run_groups(muse_batch *b, const int32_t *group_id, int32_t G, int64_t series_offset, int32_t abs_scores,
+               muse_record *out_records, uint8_t *out_state, int (*score)(muse_batch *, const void *), const void *score_arg)
+{
     if (!b || !group_id || G < 0 || (G > 0 && (!out_records || !out_state)))
         return fail(MUSE_ERR_INVALID, "bad arguments (label groups are required: ungrouped Runs shard with muse_batch_run_shard)");
     muse_ctx *ctx = b->ctx;
     b->last_path = MUSE_RUN_PATH_FP64;
     b->last_screened = false;
-    int rc = muse_batch_score(b);
+    int rc = score ? score(b, score_arg) : muse_batch_score(b);
     if (rc)
         return rc;
     const int64_t M = b->g->M;

@@ -218,9 +218,34 @@ constexpr int WIN_ROWS_FULL_SPLIT = 16;        // up to this many slices a slice
 constexpr int WIN_ROWS_MIN_CHUNKS = 2;         // beyond: chunks per slice at least
 constexpr bool WIN_ROWS_SPLIT_ENABLED = true;  // false: the planner returns 1 everywhere
 int window_rows_plan(long long M, int N, int num_cus, int *chunks_per_slice);
-long long window_split_slab_doubles(int L);    // doubles of one (block, slice) slab for window L: tiles x 256 + 32
-// S >= 2 slices (<= chunks) into slabs[blocks x S x window_split_slab_doubles(L)], summed in slice order, scanned into p.mv / p.lag
+long long window_split_slab_doubles(const WindowShape &p); // doubles of one (block, slice) slab: tiles x 256 + 32, tiles = ceil((origin + L + 1) / 16)
+// S >= 2 slices (<= chunks) into slabs[blocks x S x window_split_slab_doubles(p)], summed in slice order, scanned into p.mv / p.lag
 hipError_t launch_window_split(const WindowParams &p, int S, double *slabs, hipStream_t stream);
+// ---- the same for few rows and MANY lags (xcorr_window_panels.hip; muse_batch_run_rows_in_lag_range): a table of W = origin + L + 1
+// rows, 128 < W <= WIN_PANEL_MAX_ROWS, cut into panels of WIN_PANEL_ROWS rows (one workgroup's eight accumulator tiles); a grid of
+// blocks x S x panels workgroups, then one finish kernel that merges the panels.
+constexpr int WIN_PANEL_ROWS = 128;        // table rows of a panel: eight accumulator tiles, the most one workgroup holds
+constexpr int WIN_PANEL_MAX_ROWS = 2048;   // = MUSE_RUN_ROWS_LAG_RANGE_MAX: at most 16 panels
+static_assert(WIN_PANEL_MAX_ROWS == MUSE_RUN_ROWS_LAG_RANGE_MAX && WIN_PANEL_ROWS + 2 <= WIN_E_TAIL + 2, "a panel's image is a chunk's");
+int window_panels(int W);                  // ceil(W / WIN_PANEL_ROWS)
+// the tables of such a window: e[window_panels_e_len(N, W)] (a chunk's image per panel runs on 128 (panels - 1) entries behind the
+// narrow table's; zero from N + W - 1 on) and pw[W], each entry summed in window_table_p's order
+long long window_panels_e_len(int N, int W);
+hipError_t launch_window_tables_wide(const double *xs, int N, int n, int origin, int W, double *e, long long e_len, double *pw, hipStream_t stream);
+// window_panels_plan (pure host function): the slice count S for M rows of N samples and W table rows on num_cus CUs; *panels =
+// ceil(W / WIN_PANEL_ROWS).  Lags supply parallelism here, and the finish kernel adds a block's panels x S slabs one after the other
+// while the partial kernel's time falls as chunks / S: S = the largest S <= chunks with (2 S - 1)^2 panels <= 4 WIN_PANEL_BALANCE
+// chunks (sqrt(WIN_PANEL_BALANCE chunks / panels), rounded), at most CUs / (blocks x panels), at least 1 (S = 1 whenever
+// blocks x panels >= CUs).
+// Measured (tools/rows_lag_range_bench.py part (b), profiles/rows_lag_range_bench.txt, one box): over 16 / 100 rows x 4096,
+// 16384, 40000, 65536 samples x 255, 1025, 2048 lags the fastest S hardly depends on the blocks and follows that square root with a
+// constant of 8 ... 10; window_rows_plan's own rule with blocks x panels workgroups (where this planner started) picked 2 ... 8 x
+// too many slices for one block of long series (16 x 65536, 1025 lags: 603 us at S = 28 against 309 us at S = 8).
+constexpr int WIN_PANEL_BALANCE = 10;
+int window_panels_plan(long long M, int N, int num_cus, int W, int *panels);
+long long window_panels_slab_doubles();    // doubles of one (block, panel, slice) slab: 8 x 256 + 32
+// 1 <= S <= chunks slices into slabs[blocks x panels x S x window_panels_slab_doubles()]; p.e / p.pw: launch_window_tables_wide's
+hipError_t launch_window_panels(const WindowParams &p, int S, double *slabs, hipStream_t stream);
 // ---- the same for many references in one pass (xcorr_window_many.hip): the references' windows packed into the tiles of one product
 constexpr int WINM_MAX_TILES = 8;       // accumulator tiles of a launch: 128 packed (reference, lag) rows
 constexpr int WINM_PACK_MAX_ROWS = 48;   // wider windows (four tiles per reference) are not packed: one launch per reference

@@ -16,6 +16,9 @@
 // At S > 1 the k-summation tree differs from xcorr_window_mfma's (partial sums per slice, then the slices), so a row's (lag, mv)
 // equals the definition at the project's tolerance (1e-6 relative), not xcorr_window_mfma's result bit for bit.
 //
+// The table may start at any lag (WindowShape::origin: a symmetric window's L, or the lowest lag of a lag range --
+// muse_batch_run_rows_in_lag_range): the slabs are sized and TILES picked by window_tiles(const WindowShape &).
+//
 // The planner (window_rows_plan, a pure host function) chooses S: see there.
 #include "window_device.h"
 
@@ -117,7 +120,7 @@ __global__ __launch_bounds__(WIN_THREADS) void window_split_finish(const WindowP
     window_scan_write<TILES>(lds, CAND, lds[STAT + 2 * c], lds[STAT + 2 * c + 1], p, (long long)blockIdx.x * 16, t);
 }
 
-long long window_split_slab_doubles(int L) { return (long long)window_tiles(L) * 256 + 32; }
+long long window_split_slab_doubles(const WindowShape &p) { return (long long)window_tiles(p) * 256 + 32; }
 
 hipError_t launch_window_split(const WindowParams &p, int S, double *slabs, hipStream_t stream)
 {
@@ -125,12 +128,12 @@ hipError_t launch_window_split(const WindowParams &p, int S, double *slabs, hipS
         return hipSuccess;
     const int chunks = (p.N + WIN_KC - 1) / WIN_KC;
     long long blocks;
-    // (its callers' windows are symmetric, and the slabs are sized by window_split_slab_doubles(L))
-    if (window_launch_check(p, &blocks) != hipSuccess || p.origin != p.L || p.Lneg > p.L || S < 2 || S > chunks || !slabs)
+    // (a table of any origin: the slabs are sized by window_split_slab_doubles(p), the tiles of rows 0 .. origin + L)
+    if (window_launch_check(p, &blocks) != hipSuccess || S < 2 || S > chunks || !slabs)
         return hipErrorInvalidValue;
     const dim3 grid((unsigned)blocks, (unsigned)S), fgrid((unsigned)blocks), block(WIN_THREADS);
     const bool wide = window_wide(p.rows, p.stride);
-    window_with_tiles(window_tiles(p.L), [&](auto tiles) {
+    window_with_tiles(window_tiles(p), [&](auto tiles) {
         if (wide)
             xcorr_window_split_partial<tiles(), true><<<grid, block, 0, stream>>>(p, chunks, slabs);
         else

@@ -1197,7 +1197,7 @@ func New(ref *Series, results *Results) (*Muse, error) {
 // goroutines (muse_test.go:203-214): every call owns its group and batch, the
 // spectrum is shared read-only, Results has its mutex.
 func (m *Muse) Run(compGraphs []*Series) error {
-	return m.run(compGraphs, -1)
+	return m.run(compGraphs, -1, nil)
 }
 
 // RunWindowed is Run with Results.MaxLag as a LAG WINDOW (muse_batch_run_rows_windowed): every series contributes its best
@@ -1207,11 +1207,22 @@ func (m *Muse) RunWindowed(compGraphs []*Series) error {
 	if m.Results.MaxLag < 0 || m.Results.MaxLag > C.MUSE_LAG_WINDOW_MAX {
 		return fmt.Errorf("RunWindowed: MaxLag outside 0 .. %d", int(C.MUSE_LAG_WINDOW_MAX))
 	}
-	return m.run(compGraphs, m.Results.MaxLag)
+	return m.run(compGraphs, m.Results.MaxLag, nil)
 }
 
-// window < 0: Run; otherwise RunWindowed with that window
-func (m *Muse) run(compGraphs []*Series, window int) error {
+// RunInLagRange is Run inside the lags lagLo .. lagHi, lagLo <= 0 <= lagHi (muse_batch_run_rows_in_lag_range): every series
+// contributes its best match inside the range -- up to MUSE_RUN_ROWS_LAG_RANGE_MAX lags, one-sided ranges too ("which of these
+// series trails the reference by up to k samples?").  Results is fed as Batch.RunInLagRange feeds it: the group's Score through
+// Results.Update, which applies the Results' own filters unchanged.  The range is an argument of the call: Run itself never changes.
+func (m *Muse) RunInLagRange(compGraphs []*Series, lagLo, lagHi int) error {
+	if lagLo > 0 || lagHi < 0 {
+		return fmt.Errorf("RunInLagRange: lagLo <= 0 <= lagHi")
+	}
+	return m.run(compGraphs, -1, &[2]int{lagLo, lagHi})
+}
+
+// lagRange != nil: RunInLagRange with those lags; else window < 0: Run; otherwise RunWindowed with that window
+func (m *Muse) run(compGraphs []*Series, window int, lagRange *[2]int) error {
 	if len(compGraphs) == 0 {
 		return nil
 	}
@@ -1233,7 +1244,9 @@ func (m *Muse) run(compGraphs []*Series, window int) error {
 	var win C.muse_record
 	var state C.uint8_t
 	var st C.int
-	if window >= 0 {
+	if lagRange != nil {
+		st = C.muse_batch_run_rows_in_lag_range(m.template, (*C.double)(unsafe.Pointer(&rows[0])), C.int64_t(len(compGraphs)), C.int64_t(N), C.int32_t(lagRange[0]), C.int32_t(lagRange[1]), 0, &win, &state)
+	} else if window >= 0 {
 		st = C.muse_batch_run_rows_windowed(m.template, (*C.double)(unsafe.Pointer(&rows[0])), C.int64_t(len(compGraphs)), C.int64_t(N), C.int32_t(window), 0, &win, &state)
 	} else {
 		st = C.muse_batch_run_rows(m.template, (*C.double)(unsafe.Pointer(&rows[0])), C.int64_t(len(compGraphs)), C.int64_t(N), 0, &win, &state)

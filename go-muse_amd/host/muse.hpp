@@ -1517,7 +1517,7 @@ public:
     Muse(const Muse &) = delete;
     Muse &operator=(const Muse &) = delete;
     ResultsPtr Results_;
-    void Run(const std::vector<SeriesPtr> &compGraphs) { run(compGraphs, -1); } // muse.go:46-92
+    void Run(const std::vector<SeriesPtr> &compGraphs) { run(compGraphs, -1, nullptr); } // muse.go:46-92
     // Run with Results.MaxLag as a LAG WINDOW (muse_batch_run_row_ptrs_windowed / _run_group_rows_windowed): every series
     // contributes its best match inside +-MaxLag, where Run takes its best match over all lags and Update drops the group when
     // that lies outside.  Same length check, same resident-row reuse, same Update; Run itself never changes.
@@ -1525,12 +1525,24 @@ public:
     {
         if (Results_->MaxLag < 0 || Results_->MaxLag > MUSE_LAG_WINDOW_MAX)
             throw Error(MUSE_ERR_UNSUPPORTED, "RunWindowed: MaxLag outside 0 .. MUSE_LAG_WINDOW_MAX");
-        run(compGraphs, (int32_t)Results_->MaxLag);
+        run(compGraphs, (int32_t)Results_->MaxLag, nullptr);
+    }
+    // Run inside the lags lagLo .. lagHi, lagLo <= 0 <= lagHi (muse_batch_run_row_ptrs_in_lag_range / _run_group_rows_in_lag_range):
+    // every series contributes its best match inside the range -- up to MUSE_RUN_ROWS_LAG_RANGE_MAX lags, one-sided ranges too
+    // ("which of these series trails the reference by up to k samples?").  Same length check, same resident-row reuse as
+    // RunWindowed; Results is fed as Batch::RunInLagRange feeds it: the group's Score through Update, the Results' own filters
+    // unchanged.  Run itself never changes.
+    void RunInLagRange(const std::vector<SeriesPtr> &compGraphs, int lagLo, int lagHi)
+    {
+        if (lagLo > 0 || lagHi < 0)
+            throw Error(MUSE_ERR_INVALID, "RunInLagRange: lagLo <= 0 <= lagHi");
+        const int32_t range[2] = {(int32_t)lagLo, (int32_t)lagHi};
+        run(compGraphs, -1, range);
     }
 
 private:
-    // window < 0: Run; otherwise RunWindowed with that window
-    void run(const std::vector<SeriesPtr> &compGraphs, int32_t window)
+    // range != nullptr: RunInLagRange with those lags; else window < 0: Run; otherwise RunWindowed with that window
+    void run(const std::vector<SeriesPtr> &compGraphs, int32_t window, const int32_t *range)
     {
         if (compGraphs.empty())
             return;
@@ -1551,8 +1563,10 @@ private:
         }
         muse_record win{};
         uint8_t state = 0;
-        if (!run_resident(compGraphs, window, &win, &state)) {
-            if (window >= 0)
+        if (!run_resident(compGraphs, window, range, &win, &state)) {
+            if (range)
+                check(muse_batch_run_row_ptrs_in_lag_range(template_, rows, (int64_t)compGraphs.size(), range[0], range[1], 0, &win, &state));
+            else if (window >= 0)
                 check(muse_batch_run_row_ptrs_windowed(template_, rows, (int64_t)compGraphs.size(), window, 0, &win, &state));
             else
                 check(muse_batch_run_row_ptrs(template_, rows, (int64_t)compGraphs.size(), 0, &win, &state));
@@ -1562,7 +1576,7 @@ private:
     }
 
     // every series lives in ONE live home on this engine: scored where it lies (muse_batch_run_group_rows), nothing crosses PCIe
-    bool run_resident(const std::vector<SeriesPtr> &compGraphs, int32_t window, muse_record *win, uint8_t *state)
+    bool run_resident(const std::vector<SeriesPtr> &compGraphs, int32_t window, const int32_t *range, muse_record *win, uint8_t *state)
     {
         if (!Group::ReuseResidentRows)
             return false;
@@ -1577,7 +1591,9 @@ private:
         std::shared_lock<std::shared_mutex> lock(src->mu);
         if (!src->alive)
             return false;
-        if (window >= 0)
+        if (range)
+            check(muse_batch_run_group_rows_in_lag_range(template_, src->dev, at.data(), (int64_t)at.size(), range[0], range[1], 0, win, state));
+        else if (window >= 0)
             check(muse_batch_run_group_rows_windowed(template_, src->dev, at.data(), (int64_t)at.size(), window, 0, win, state));
         else
             check(muse_batch_run_group_rows(template_, src->dev, at.data(), (int64_t)at.size(), 0, win, state));

@@ -654,6 +654,48 @@ class DeviceBatch:
                                                             B.i32ptr(lag), B.dptr(mv)))
         return lag, mv
 
+    # ---- the same inside a lag range lag_lo .. lag_hi (lag_lo <= 0 <= lag_hi) of up to MUSE_RUN_ROWS_LAG_RANGE_MAX lags
+    def run_rows_in_lag_range(self, rows, lag_lo, lag_hi, abs_scores=False):
+        """muse_batch_run_rows_in_lag_range: run_rows with every row's best match INSIDE the lags lag_lo .. lag_hi (the definition of
+        score_in_lag_range); (-L, L) is run_rows_windowed(L)"""
+        rows, stride = self._rows2d(rows)
+        rec = np.zeros(1, dtype=B.RECORD_DTYPE)
+        state = ctypes.c_uint8(0)
+        B.check(B.load().muse_batch_run_rows_in_lag_range(self._h, rows.ctypes.data_as(B._dp), rows.shape[0], stride, int(lag_lo),
+                                                          int(lag_hi), 1 if abs_scores else 0, B.recptr(rec), ctypes.byref(state)))
+        return rec[0], int(state.value)
+
+    def run_row_ptrs_in_lag_range(self, series, lag_lo, lag_hi, abs_scores=False):
+        """muse_batch_run_row_ptrs_in_lag_range: run_row_ptrs inside the lag range"""
+        arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in series]
+        for a in arrs:
+            if a.ndim != 1 or a.shape[0] != self.dgroup.N:
+                raise MuseError(B.MUSE_ERR_LENGTH, "Encountered a comparison graph with differing length than the reference")
+        ptrs = (B._dp * max(len(arrs), 1))(*[a.ctypes.data_as(B._dp) for a in arrs])
+        rec = np.zeros(1, dtype=B.RECORD_DTYPE)
+        state = ctypes.c_uint8(0)
+        B.check(B.load().muse_batch_run_row_ptrs_in_lag_range(self._h, ptrs, len(arrs), int(lag_lo), int(lag_hi),
+                                                              1 if abs_scores else 0, B.recptr(rec), ctypes.byref(state)))
+        return rec[0], int(state.value)
+
+    def run_group_rows_in_lag_range(self, src, rows, lag_lo, lag_hi, abs_scores=False):
+        """muse_batch_run_group_rows_in_lag_range: run_group_rows inside the lag range (a float32-storage src is accepted)"""
+        idx = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        rec = np.zeros(1, dtype=B.RECORD_DTYPE)
+        state = ctypes.c_uint8(0)
+        B.check(B.load().muse_batch_run_group_rows_in_lag_range(self._h, src._h, B.i64ptr(idx), idx.shape[0], int(lag_lo), int(lag_hi),
+                                                                1 if abs_scores else 0, B.recptr(rec), ctypes.byref(state)))
+        return rec[0], int(state.value)
+
+    def run_rows_in_lag_range_scores(self, rows, lag_lo, lag_hi):
+        """test hook: the per-row (lag, mv) of run_rows_in_lag_range's path (muse_test_run_rows_in_lag_range_scores)"""
+        rows, stride = self._rows2d(rows)
+        lag = np.zeros(rows.shape[0], dtype=np.int32)
+        mv = np.zeros(rows.shape[0])
+        B.check(B.load().muse_test_run_rows_in_lag_range_scores(self._h, rows.ctypes.data_as(B._dp), rows.shape[0], stride,
+                                                                int(lag_lo), int(lag_hi), B.i32ptr(lag), B.dptr(mv)))
+        return lag, mv
+
     # ---- the slide of the group's rows and the windowed pass over the new rows in one kernel
     def _tails2d(self, tails):
         """tails (M, k) as DeviceGroup.slide prepares them -> (array, k, stride, moved)"""
@@ -875,6 +917,15 @@ def window_rows_plan(M, N, num_cus):
     S, cps = ctypes.c_int32(0), ctypes.c_int32(0)
     B.check(B.load().muse_test_window_rows_plan(int(M), int(N), int(num_cus), ctypes.byref(S), ctypes.byref(cps)))
     return int(S.value), int(cps.value)
+
+
+def rows_lag_range_plan(M, N, num_cus, lag_lo, lag_hi):
+    """muse_test_rows_lag_range_plan (no device): (MUSE_ROWS_LAG_RANGE_*, panels, S) -- the pass run_rows_in_lag_range takes for M
+    rows of N samples on num_cus CUs inside the lags lag_lo .. lag_hi"""
+    path, panels, S = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0)
+    B.check(B.load().muse_test_rows_lag_range_plan(int(M), int(N), int(num_cus), int(lag_lo), int(lag_hi), ctypes.byref(path),
+                                                   ctypes.byref(panels), ctypes.byref(S)))
+    return path.value, panels.value, S.value
 
 
 def in_window_plan(N, f32, max_lag):
@@ -1751,6 +1802,31 @@ class Muse:
         else:
             rows = np.stack([s.y for s in compGraphs])
             win, state = self._template.run_rows_windowed(rows, window, abs_scores=False)
+        if state == 1 and win["series"] >= 0:
+            self.Results.Update(Score(compGraphs[int(win["series"])].Labels(), int(win["lag"]), float(win["score"])))
+        return None
+
+    def RunInLagRange(self, compGraphs, lagLo, lagHi):
+        """Run inside the lags lagLo .. lagHi, lagLo <= 0 <= lagHi (muse_batch_run_rows_in_lag_range / _run_group_rows_in_lag_range):
+        every series contributes its best match inside the range -- up to MUSE_RUN_ROWS_LAG_RANGE_MAX lags, one-sided ranges too: "which
+        of these series trails the reference by up to k samples?".  Same length check, same resident-row reuse, same Update as
+        RunWindowed; Results is fed as Batch.RunInLagRange feeds it: the group's Score through Results.Update, which applies the
+        Results' own filters unchanged.  Run itself never changes."""
+        if len(compGraphs) == 0:
+            return None
+        lagLo, lagHi = int(lagLo), int(lagHi)
+        if lagLo > 0 or lagHi < 0:
+            raise MuseError(B.MUSE_ERR_INVALID, "RunInLagRange needs lagLo <= 0 <= lagHi")
+        for s in compGraphs:                      # muse.go:68-70
+            if s.Length() != self.refN:
+                raise MuseError(B.MUSE_ERR_LENGTH, "Encountered a comparison graph with differing length "
+                                "than the reference, %r" % (s.Labels(),))
+        home = self._resident(compGraphs)
+        if home is not None:
+            win, state = self._template.run_group_rows_in_lag_range(home[0], home[1], lagLo, lagHi, abs_scores=False)
+        else:
+            rows = np.stack([s.y for s in compGraphs])
+            win, state = self._template.run_rows_in_lag_range(rows, lagLo, lagHi, abs_scores=False)
         if state == 1 and win["series"] >= 0:
             self.Results.Update(Score(compGraphs[int(win["series"])].Labels(), int(win["lag"]), float(win["score"])))
         return None

@@ -404,13 +404,45 @@ int muse_batch_run_in_window(muse_batch *b, const int32_t *group_id, int32_t G, 
  * muse_batch_run_in_lag_range is that pass followed by Batch.Run's selection over the scores, outputs as muse_batch_run, with
  * Results.MaxLag = max(-lag_lo, lag_hi): every lag of the range passes the lag filter.  A sign_filter outside -1 .. 1 or a negative
  * G with group_id is refused before anything is scored.
- * Limits: ranges that exclude lag 0; the Muse.Run-rows (muse_batch_run_rows_windowed ...) and slide forms of a range;
+ * Limits: ranges that exclude lag 0; the slide forms of a range (the Muse.Run-rows forms: muse_batch_run_rows_in_lag_range below);
  * the multi-device layer; ranges of more than 127 lags, or float32 storage, outside FFT lengths 512 ... 4096; series longer than
  * 65536 samples (other than the whole range); narrow float64 ranges are never routed to the masked pass. */
 int muse_batch_score_in_lag_range(muse_batch *b, int32_t lag_lo, int32_t lag_hi);
 int muse_batch_run_in_lag_range(muse_batch *b, const int32_t *group_id, int32_t G, int32_t lag_lo, int32_t lag_hi,
                                 int32_t top_n, double threshold, int32_t sign_filter, int32_t abs_scores,
                                 int64_t *out_series, int32_t *out_lag, double *out_score, int32_t *out_count, double *out_mean_abs);
+/* Muse.Run (muse.go:46-92) INSIDE A LAG RANGE of up to MUSE_RUN_ROWS_LAG_RANGE_MAX lags, in one call.  Each behaves as its _windowed
+ * namesake (muse_batch_run_rows_windowed, _run_row_ptrs_windowed, _run_group_rows_windowed): same validation, same out_winner /
+ * out_state rules, same abs_scores, M == 0 gives state 0, the same pool of slots, any number of host threads on one tmpl; a
+ * float32-storage src is accepted by the _group_rows_ form, and groups too large for a slot take the same general path.  The only
+ * difference is the per-row (lag, mv): the one defined at muse_batch_score_in_lag_range -- its clipping (hi = min(lag_hi, n/2),
+ * lo = max(lag_lo, -(n/2 - 1))), its scan order (0 .. hi, then n + lo .. n - 1), its start values, strict '>' and outcome rules.  The
+ * range is an argument of the call: the template's own lag_window must be off, or on with lag_lo == -lag_hi equal to it, and is not
+ * touched.  Which pass runs is decided from M, N, the CUs of the device and the W = hi - lo + 1 lags of the clipped range:
+ *   the range is every lag                     : the unwindowed namesake's pass, bit for bit (this row comes first: the _windowed
+ *                                                forms keep the window kernels where +-max_lag covers every lag, n <= 126)
+ *   W <= 127, up to 65536 samples              : the kernels of the _windowed forms over a table that starts at lag lo (unsplit, or
+ *                                                split over the samples for few rows of long series); lag_lo == -lag_hi IS the
+ *                                                _windowed call, bit for bit.  Unsplit, the value at a lag has the bits of
+ *                                                muse_batch_score_in_lag_range's direct product over the same rows
+ *   128 <= W <= 2048, up to 65536 samples      : the panel kernels (xcorr_window_panels.hip): the table cut into ceil(W / 128) panels
+ *                                                of 128 lags, one workgroup per (16 rows, slice of the samples, panel), the panels
+ *                                                merged by scan position.  2 M N W flops: few rows are what makes it cheap.  In one
+ *                                                slice the value at a lag has the bits the direct product gives there; in several,
+ *                                                the definition at the project's tolerance (1e-6 relative).  Two calls give the
+ *                                                same bits
+ *   anything else                              : MUSE_ERR_UNSUPPORTED, nothing changed
+ * MUSE_ERR_INVALID, every handle left as it was (everything is checked before anything is enqueued): lag_lo > 0 or lag_hi < 0, a
+ * template whose own window is on and is not this range, and the namesakes' own argument errors.
+ * Limits: the slide form of a range; more than 2048 lags; ranges that exclude lag 0; series longer than 65536 samples (other than
+ * every lag); float32 host rows; the multi-device layer. */
+#define MUSE_RUN_ROWS_LAG_RANGE_MAX 2048   /* the most lags (hi - lo + 1, after clipping) a Muse.Run range may hold */
+int muse_batch_run_rows_in_lag_range(muse_batch *tmpl, const double *rows, int64_t M, int64_t row_stride,
+                                     int32_t lag_lo, int32_t lag_hi, int32_t abs_scores, muse_record *out_winner, uint8_t *out_state);
+int muse_batch_run_row_ptrs_in_lag_range(muse_batch *tmpl, const double *const *rows, int64_t M,
+                                         int32_t lag_lo, int32_t lag_hi, int32_t abs_scores, muse_record *out_winner, uint8_t *out_state);
+int muse_batch_run_group_rows_in_lag_range(muse_batch *tmpl, muse_group *src, const int64_t *rows, int64_t M,
+                                           int32_t lag_lo, int32_t lag_hi, int32_t abs_scores, muse_record *out_winner, uint8_t *out_state);
 /* THE SLIDE AND THE PASS OF ANY WINDOW IN ONE CALL.  muse_batch_slide_score_in_window is equivalent to
  *   muse_group_slide(the batch's group, 0, M, tails, k, tail_stride)  followed by  muse_batch_score_in_window(b, max_lag):
  * afterwards the group holds the slid rows -- BIT FOR BIT those of muse_group_slide -- and muse_batch_read_scores returns, BIT FOR

@@ -112,6 +112,24 @@ int muse_test_window_rows_slices(muse_ctx *ctx, int32_t S);
  * back before the slot is returned: without it only the winner is observable. */
 int muse_test_run_rows_windowed_scores(muse_batch *tmpl, const double *rows, int64_t M, int64_t row_stride, int32_t max_lag,
                                        int32_t *lag_out, double *mv_out);
+/* The dispatch of muse_batch_run_rows_in_lag_range and its siblings, a pure host function (no device needed) of M >= 1 rows of
+ * N >= 2 samples on num_cus CUs and the lags lag_lo .. lag_hi (lag_lo <= 0 <= lag_hi, clipped at the FFT length of N as
+ * muse_batch_score_in_lag_range clips them; W = the lags that remain): *path = MUSE_ROWS_LAG_RANGE_PLAIN (every lag: the unwindowed
+ * namesake's pass; *panels = *S = 0), _WINDOW / _SPLIT (W <= 127: the kernels of muse_batch_run_rows_windowed, unsplit / in the *S > 1
+ * slices muse_test_window_rows_plan gives; *panels = 1), _PANELS (128 <= W <= MUSE_RUN_ROWS_LAG_RANGE_MAX: xcorr_window_panels.hip,
+ * *panels = ceil(W / 128) panels in *S >= 1 slices) or _UNSUPPORTED (more lags, or series longer than 65536 samples).  panels and S
+ * may be NULL. */
+#define MUSE_ROWS_LAG_RANGE_UNSUPPORTED 0
+#define MUSE_ROWS_LAG_RANGE_PLAIN 1
+#define MUSE_ROWS_LAG_RANGE_WINDOW 2
+#define MUSE_ROWS_LAG_RANGE_SPLIT 3
+#define MUSE_ROWS_LAG_RANGE_PANELS 4
+int muse_test_rows_lag_range_plan(int64_t M, int32_t N, int32_t num_cus, int32_t lag_lo, int32_t lag_hi, int32_t *path,
+                                  int32_t *panels, int32_t *S);
+/* muse_batch_run_rows_in_lag_range's path (same checks, same slot, same kernels; muse_test_window_rows_slices forces its slice count
+ * too), and the slot's per-row (lag_out[M], mv_out[M]) copied back before the slot is returned. */
+int muse_test_run_rows_in_lag_range_scores(muse_batch *tmpl, const double *rows, int64_t M, int64_t row_stride, int32_t lag_lo,
+                                           int32_t lag_hi, int32_t *lag_out, double *mv_out);
 /* The load / store widths of muse_batch_slide_score_windowed's kernel (xcorr_window_slide.hip), a pure host function (no device
  * needed): for rows of N samples slid by k, `wide` = the rows are 16-byte aligned (even N: the kernel's WIDE mapping) -- *load_bytes
  * = 16 iff wide and k is even (8 otherwise: the same samples from two loads), *store_bytes = 16 iff wide.  MUSE_ERR_INVALID for
