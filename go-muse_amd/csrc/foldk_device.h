@@ -267,49 +267,91 @@ __device__ __forceinline__ void gdft16_nr_l2(double2 (&v)[16], F fetch)
 // LDS record of one pair (one per parity): as in xcorr_r16_fast.hip
 constexpr int REC = 36;
 
-// cross-wave argmax combine + variance + store (lanes 0 / 1, one series each);
-// returns true when the series' statistics are NaN/Inf or the pair's sigmas are too far apart (the pair is redone)
-__device__ __forceinline__ bool finalize(const double *r, const int series, const double invN, const double invNm1,
-                                         double *mv_out, int *lag_out)
+// A pair's results come from two parts.  The VERDICT depends on the group's rows alone: per series 1 / sigma and whether
+// sigma is zero or the statistics are NaN / Inf, per pair whether the two sigmas are too far apart for one shared transform.
+// The COMBINE depends on the reference: the best of the four wave records times 1 / sigma, with the verdict's overrides.
+// The kernels that read rows form both from the record (finalize); the spectrum cache keeps the verdict beside the
+// spectrum (xcorr_kernels.h, ZC_STAT) and its readers combine alone.
+constexpr unsigned VERDICT_ZERO_A = 1u, VERDICT_NAN_A = 2u, VERDICT_SPREAD = 4u, VERDICT_ZERO_B = 8u, VERDICT_NAN_B = 16u;
+// the bits of one series in the pair's word, and the bits for which that series' lane lists the pair for the redo
+__device__ __forceinline__ unsigned verdict_zero(const int series) { return series == 0 ? VERDICT_ZERO_A : VERDICT_ZERO_B; }
+__device__ __forceinline__ unsigned verdict_nan(const int series) { return series == 0 ? VERDICT_NAN_A : VERDICT_NAN_B; }
+__device__ __forceinline__ unsigned verdict_redo(const int series) { return series == 0 ? VERDICT_NAN_A | VERDICT_SPREAD : VERDICT_NAN_B; }
+
+// the variance of a record's series from its sums (the partial sums of d^2 in the plain kernel's order)
+__device__ __forceinline__ double record_variance(const double *r, const int series, const double invN, const double invNm1, bool &zero, bool &nan)
 {
-    double m[4], s[4], ix[4];
-#pragma unroll
-    for (int w = 0; w < 4; w++) {
-        m[w] = r[6 * w + 3 * series];
-        s[w] = r[6 * w + 3 * series + 1];
-        ix[w] = r[6 * w + 3 * series + 2];
-    }
     const double s2 = (r[24 + series] + r[26 + series]) + (r[28 + series] + r[30 + series]);
     const Stat st{r[32 + series], s2};
-    double best = m[0], bsv = s[0], bidx = ix[0];
-#pragma unroll
-    for (int w = 1; w < 4; w++) {
-        if (m[w] > best || (m[w] == best && ix[w] < bidx)) {
-            best = m[w];
-            bsv = s[w];
-            bidx = ix[w];
-        }
-    }
-    bool zero, nan;
-    const double var = variance(st, invN, invNm1, zero, nan);
-    const int idx = (best > 0.0) ? (int)bidx : 0; // nothing above 0: index 0, mv = cc[0]
+    return variance(st, invN, invNm1, zero, nan);
+}
+// 1 / sigma: rsq and two Newton steps (garbage where the variance is zero or not finite: the verdict's overrides)
+__device__ __forceinline__ double inv_sigma(const double var)
+{
     double y = __builtin_amdgcn_rsq(var);
     y = y * fma(-0.5 * var * y, y, 1.5);
     y = y * fma(-0.5 * var * y, y, 1.5);
-    double mv = ((best > 0.0) ? bsv : s[0]) * y;
+    return y;
+}
+// the four wave records of a series ...
+struct WaveRecords {
+    double m[4], s[4], ix[4];
+};
+__device__ __forceinline__ WaveRecords load_wave_records(const double *r, const int series)
+{
+    WaveRecords w;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        w.m[k] = r[6 * k + 3 * series];
+        w.s[k] = r[6 * k + 3 * series + 1];
+        w.ix[k] = r[6 * k + 3 * series + 2];
+    }
+    return w;
+}
+// ... and the series' result from them: cross-wave argmax combine, 1 / sigma, the lag unwrap and the verdict's overrides
+__device__ __forceinline__ void combine(const WaveRecords &w, const double y, const bool zero, const bool nan, double *mv_out, int *lag_out)
+{
+    double best = w.m[0], bsv = w.s[0], bidx = w.ix[0];
+#pragma unroll
+    for (int k = 1; k < 4; k++) {
+        if (w.m[k] > best || (w.m[k] == best && w.ix[k] < bidx)) {
+            best = w.m[k];
+            bsv = w.s[k];
+            bidx = w.ix[k];
+        }
+    }
+    const int idx = (best > 0.0) ? (int)bidx : 0; // nothing above 0: index 0, mv = cc[0]
+    double mv = ((best > 0.0) ? bsv : w.s[0]) * y;
     int lag = idx > 2048 ? idx - 4096 : idx;
     if (zero) { mv = 0.0; lag = 0; }              // xcorr.go:166-167
     if (nan) { mv = __builtin_nan(""); lag = 0; } // placeholder: the pair is redone
     *mv_out = mv;
     *lag_out = lag;
+}
+
+// verdict + combine + store from a complete record (lanes 0 / 1, one series each); returns true when the pair is redone: the
+// series' statistics are NaN / Inf, or the pair's sigmas are too far apart.  keep(y, bits) takes the series' verdict: 1 / sigma
+// and the pair's word as far as this series' lane knows it -- its own bits, and series 0 of a full pair (r[35]) the other
+// series' and the spread test as well: the whole word.
+template <typename Keep>
+__device__ __forceinline__ bool finalize(const double *r, const int series, const double invN, const double invNm1,
+                                         double *mv_out, int *lag_out, const Keep keep)
+{
+    const WaveRecords w = load_wave_records(r, series);
+    bool zero, nan;
+    const double var = record_variance(r, series, invN, invNm1, zero, nan);
+    const double y = inv_sigma(var);
+    combine(w, y, zero, nan, mv_out, lag_out);
     bool redo = nan;
+    unsigned bits = (zero ? verdict_zero(series) : 0u) | (nan ? verdict_nan(series) : 0u);
     if (series == 0 && r[35] != 0.0) { // the pair's other series: sigmas too far apart for one shared transform?
-        const double s2b = (r[25] + r[27]) + (r[29] + r[31]);
-        const Stat sb{r[33], s2b};
         bool zb, nb;
-        const double varb = variance(sb, invN, invNm1, zb, nb);
-        redo = redo || (!nb && sigma_spread_too_wide(var, varb));
+        const double varb = record_variance(r, 1, invN, invNm1, zb, nb);
+        const bool spread = !nb && sigma_spread_too_wide(var, varb);
+        redo = redo || spread;
+        bits |= (zb ? VERDICT_ZERO_B : 0u) | (nb ? VERDICT_NAN_B : 0u) | (spread ? VERDICT_SPREAD : 0u);
     }
+    keep(y, bits);
     return redo;
 }
 

@@ -135,12 +135,15 @@ __device__ __forceinline__ void take_dc(double2 (&v)[16], const int t, double &s
 // A pair's results from its complete record: among the threads with `writer` set, those with series 0 / 1 write one series
 // each.  In a pair loop the previous pair's (lane 0 of waves 0 / 1, behind the first barriers of the current pair); behind the
 // loop and an lds_barrier the last pair's (threads 0 / 1).
+// tap.verdict(pair, series, y, bits) takes the series' verdict (foldk_device.h) where the kernel keeps it.
+template <typename Tap>
 __device__ __forceinline__ void finalize_pair(const double *prec, const int series, const bool writer, const double invN,
-                                              const double invNm1, const FusedParams &p)
+                                              const double invNm1, const FusedParams &p, const Tap &tap)
 {
     if (writer && series < 2 && prec[34] >= 0.0 && (series == 0 || prec[35] != 0.0)) {
         const long long row = (long long)prec[34] + series;
-        if (finalize(prec, series, invN, invNm1, p.mv + row, p.lag + row)) {
+        if (finalize(prec, series, invN, invNm1, p.mv + row, p.lag + row,
+                     [&](const double y, const unsigned bits) __attribute__((always_inline)) { tap.verdict(row >> 1, series, y, bits); })) {
             const int slot = atomicAdd(p.ovf_count, 1);
             p.ovf_list[slot] = row >> 1;
         }
@@ -181,25 +184,78 @@ __device__ __forceinline__ void request_z(d2v (&zn)[16], const SpectrumCacheArgs
     for (int i = 0; i < 16; i++)
         zn[i] = __builtin_nontemporal_load((gptr<d2v>)lane_entry(c.zc, (pr - c.pair0) * 4096, i, t));
 }
-// the statistics of the segment's pair `rel` (a wave-uniform address: the scalar cache) ...
-__device__ __forceinline__ void load_pair_stats(double (&st)[10], const double *zstat, const long long rel)
+// The verdict of the segment's pair `rel` as the writer stored it (ZC_VERDICT; a wave-uniform address: the scalar cache), and
+// with SUMS the two sums of d that N < 4096 takes the means from.  A reader requests it a pair ahead, behind the pair in hand's
+// publish: it travels in scalar registers beside the pair in hand, and no wait of a pair is for a request of that pair.
+struct PairVerdict {
+    double yA, yB, s1a, s1b;
+    unsigned bits;
+};
+// Scalar loads return out of order, so every wait for LDS behind the request is one for the request as well: IN_LOOP, the
+// request stands behind the pair's last read of LDS (the waves' exchanges are complete behind their barrier, which the compiler
+// cannot see: the explicit wait, for thread 0's two stores at the most, tells it), and the next wait is the first exchange of
+// the next pair.
+template <bool SUMS, bool IN_LOOP>
+__device__ __forceinline__ PairVerdict load_pair_verdict(const double *zstat, const long long rel_)
 {
+    PairVerdict q = {};
 #if defined(__HIP_DEVICE_COMPILE__)
+    long long rel = rel_;
+    if (IN_LOOP) {
+        fence();
+        __builtin_amdgcn_s_waitcnt(0xc07f); // lgkmcnt(0)
+        asm volatile("" : "+s"(rel));       // (the address is formed, and the request issued, behind the wait)
+    }
     const zstat_in_ptr sp = (zstat_in_ptr)(unsigned long long)(zstat + rel * ZC_STAT);
-#pragma unroll
-    for (int k = 0; k < 10; k++)
-        st[k] = sp[k];
+    if (SUMS) {
+        q.s1a = sp[8];
+        q.s1b = sp[9];
+    }
+    q.yA = sp[ZC_VERDICT];
+    q.yB = sp[ZC_VERDICT + 1];
+    q.bits = ((const unsigned __attribute__((address_space(4))) *)sp)[2 * (ZC_VERDICT + 2)]; // (one word: a register of the request that nobody reads is one the compiler reuses, behind a wait for the request)
+    if (IN_LOOP)
+        fence();
 #endif
+    return q;
 }
-// ... and their way into the pair's record, where consume_rows and the end of a pair put them in the kernels that read rows
-__device__ __forceinline__ void publish_pair_stats(double *rec, const double (&st)[10], const int t, const long long rA, const bool hasB)
+// The readers' record of a pair: the four wave records at [0, 24) as everywhere, yA and yB at [24], [25], and in the four
+// words of [26], [27] the verdict's bits, the pair's first row (-1: no pair yet) and whether it has a second one.
+struct ReaderHead {
+    unsigned bits;
+    int row, hasB, unused;
+};
+__device__ __forceinline__ void reader_prologue(double *red, const int t)
+{
+    if (t < 2)
+        *(ReaderHead *)(red + REC * t + 26) = ReaderHead{0u, -1, 0, 0};
+}
+// thread 0 publishes the pair in hand (two 16-byte stores) ...
+__device__ __forceinline__ void publish_pair_verdict(double *rec, const PairVerdict &q, const int t, const long long rA, const bool hasB)
 {
     if (t == 0) {
-#pragma unroll
-        for (int k = 0; k < 10; k++)
-            rec[24 + k] = st[k];
-        rec[34] = (double)rA;
-        rec[35] = hasB ? 1.0 : 0.0;
+        *(double2 *)(rec + 24) = make_double2(q.yA, q.yB);
+        *(ReaderHead *)(rec + 26) = ReaderHead{q.bits, (int)rA, hasB ? 1 : 0, 0};
+    }
+}
+// ... and a pair behind, among the threads with `writer` set, those with series 0 / 1 combine one series each from the complete
+// record, as finalize_pair does in the kernels that read rows: everything is read in one batch, then three compare-selects and
+// one multiply; the redo list gets what the plain kernel's verdict would give it (verdict_redo).
+__device__ __forceinline__ void finalize_pair_cached(const double *prec, const int series, const bool writer, const FusedParams &p)
+{
+    if (writer && series < 2) {
+        const WaveRecords w = load_wave_records(prec, series);
+        const double y = prec[24 + series];
+        const ReaderHead h = *(const ReaderHead *)(prec + 26);
+        fence(); // (one round trip to LDS: none of the reads behind the branch)
+        if (h.row >= 0 && (series == 0 || h.hasB != 0)) {
+            const long long row = (long long)h.row + series;
+            combine(w, y, (h.bits & verdict_zero(series)) != 0u, (h.bits & verdict_nan(series)) != 0u, p.mv + row, p.lag + row);
+            if (h.bits & verdict_redo(series)) {
+                const int slot = atomicAdd(p.ovf_count, 1);
+                p.ovf_list[slot] = row >> 1;
+            }
+        }
     }
 }
 
@@ -208,6 +264,7 @@ __device__ __forceinline__ void publish_pair_stats(double *rec, const double (&s
 struct NoTap {
     static constexpr long long first = 0;
     __device__ __forceinline__ void operator()(const double2 (&)[16], const double *, double, double, long long, int) const {}
+    __device__ __forceinline__ void verdict(long long, int, double, unsigned) const {}
 };
 
 // The pair loop of the kernels that score from the ROWS, four workgroups per CU: pairs [tap.first, tap.first + p.npairs), handed
@@ -268,7 +325,7 @@ __device__ __forceinline__ void pair_loop_from_rows(const FusedParams &p, const 
         // wave-local transpose below while the waves are still in step
         exchange_cross<0, 1, true>(v, xbuf, wave, t, WIDE ? wide_column(t) : -1);
         // the previous pair's record is complete and visible
-        finalize_pair(prec, wave, lane == 0, invN, invNm1, p);
+        finalize_pair(prec, wave, lane == 0, invN, invNm1, p, tap);
         clk.template stamp<3>();
         // pass 2: generalised DFT over b, delta = k1 / 16 (carries W_256^(b k1))
         gdft16_nr(v, G2Fetch{g2s, t >> 4});
@@ -330,7 +387,7 @@ __device__ __forceinline__ void pair_loop_from_rows(const FusedParams &p, const 
         clk.template stamp<12>();
     }
     lds_barrier();
-    finalize_pair(red + REC * (parity ^ 1), t, true, invN, invNm1, p);
+    finalize_pair(red + REC * (parity ^ 1), t, true, invN, invNm1, p, tap);
     if (TIMING && p.dbg && lane == 0) {
 #pragma unroll
         for (int i = 0; i < NPHASE; i++)

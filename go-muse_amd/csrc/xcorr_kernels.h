@@ -132,7 +132,8 @@ hipError_t launch_fused_multi(const FusedParams &p, int num_cus, hipStream_t str
 // xcorr_r16_cached.hip: a resident float64 group's spectrum cache at n = 4096.  One segment covers the pairs [pair0, pair0 + zpairs)
 // of the group: zc[(pair - pair0)][16][256] double2, zstat[(pair - pair0)][ZC_STAT] double.  Both launchers process the pairs
 // [pair0, pair0 + p.npairs) (p.M, p.mv, p.lag, p.ovf_list: the whole group's), ADD to *p.ovf_count and want *p.work_counter zero.
-constexpr int ZC_STAT = 16;                                       // doubles per pair: 8 sum-of-squares partials, 2 sums, 6 unused
+constexpr int ZC_STAT = 16;                                       // doubles per pair: 8 sum-of-squares partials, 2 sums, the verdict, 3 unused
+constexpr int ZC_VERDICT = 10;                                    // the pair's verdict (foldk_device.h): 1 / sigma of series A and of B, then one word of bits (the low word of the slot)
 constexpr long long ZC_PAIR_BYTES = 4096 * 16 + ZC_STAT * 8;      // 64 KB + 128 B
 struct SpectrumCacheArgs {
     double2 *zc;

@@ -8,13 +8,15 @@
 //
 //   zc[pair][i][t]   (double2) the value thread t holds in register v[i] right behind pass 3 of the first transform and its
 //                    DC handling: register i of a workgroup is 4 KB contiguous, every access a full-width 16-byte one
-//   zstat[pair][16]  (double)  [0, 8) the eight per-wave partial sums of d^2 (2 * wave + series), kept as partials and summed by
-//                    finalize in the plain kernel's order; [8], [9] sum d of the two series (the DC bin)
+//   zstat[pair][16]  (double)  [0, 8) the eight per-wave partial sums of d^2 (2 * wave + series), kept as partials and summed in
+//                    the plain kernel's order; [8], [9] sum d of the two series (the DC bin); [10], [11] 1 / sigma of the two
+//                    series and [12] one word of bits -- the pair's VERDICT (foldk_device.h), which depends on the rows alone:
+//                    the writer's finalize stores what it computed, the readers' finalize is the combine alone
 //
 // xcorr_cache_fill_n4096: the plain kernel plus the stores (results unchanged) over pairs [pair0, pair0 + npairs); the first
 //                         `zpairs` of them are cached (0: none -- the plain arithmetic on a tail of the group).
-// xcorr_cached_n4096:     per pair sixteen 16-byte loads of Z, requested a whole pair ahead, the statistics through the scalar
-//                         cache, then the plain kernel's second half, function by function: the same operations on the same
+// xcorr_cached_n4096:     per pair sixteen 16-byte loads of Z and the verdict through the scalar cache, both requested a whole
+//                         pair ahead, then the plain kernel's second half, function by function: the same operations on the same
 //                         doubles, so mv and lag come out bit for bit as from the rows.  Two workgroups per CU: the reference's
 //                         table stays in registers for the whole launch; pairs are claimed two per atomic add.
 // xcorr_cached_n4096_occ4: the reader at four workgroups per CU that one replaced (table from L2 in every pair, Z requested at
@@ -48,6 +50,20 @@ struct CacheTap {
                 const foldk::zstat_out_ptr so = (foldk::zstat_out_ptr)(unsigned long long)(c.zstat + rel * ZC_STAT);
                 so[t] = t < 8 ? rec[24 + t] : (t == 8 ? s1a : s1b);
             }
+        }
+#endif
+    }
+    // finalize runs a pair behind the tap (and once behind the loop), in one lane per series: the pair comes from the record's row.
+    // Series 0 of a full pair knows the whole word, and only full pairs are cached.
+    __device__ __forceinline__ void verdict(const long long pair, const int series, const double y, const unsigned bits) const
+    {
+#if defined(__HIP_DEVICE_COMPILE__)
+        const long long rel = pair - first;
+        if (rel < c.zpairs) {
+            const foldk::zstat_out_ptr so = (foldk::zstat_out_ptr)(unsigned long long)(c.zstat + rel * ZC_STAT);
+            so[ZC_VERDICT + series] = y;
+            if (series == 0)
+                so[ZC_VERDICT + 2] = __hiloint2double(0, (int)bits);
         }
 #endif
     }
@@ -98,11 +114,12 @@ __global__ __launch_bounds__(OCC_THREADS, 2) void xcorr_cached_n4096(const Fused
     using namespace foldk;
     __shared__ double2 xbuf[OCC_XBUF_FULL];
     __shared__ double2 g2s[128];
-    __shared__ double red[2 * REC];
+    __shared__ alignas(16) double red[2 * REC];
     __shared__ int next_s[2];
     const PairThread th = pair_prologue<PADDED>(p, g2s, red + 34, REC);
     const int t = th.t, lane = th.lane, wave = th.wave;
-    const double invN = th.invN, invNm1 = th.invNm1;
+    const double invN = th.invN;
+    reader_prologue(red, t);
     double2 *const xw = xbuf + 1088 * wave;
     const long long first = c.pair0, total = c.pair0 + p.npairs;
     // N < 4096 has the -m c1 correction's registers on top and would spill with the request at the top of the pair: it requests
@@ -114,6 +131,7 @@ __global__ __launch_bounds__(OCC_THREADS, 2) void xcorr_cached_n4096(const Fused
         next_s[1] = (int)gridDim.x + atomicAdd(p.work_counter, 1);
     d2v zn[16]; // the next pair's spectrum, in flight
     request_z(zn, c, first + (long long)ch * blockIdx.x, t); // (the grid has at most ceil(npairs / ch) workgroups)
+    PairVerdict qn = load_pair_verdict<PADDED, false>(c.zstat, (long long)ch * blockIdx.x); // the next pair's verdict, in flight
     // launch-invariant: the reference's factors of this thread (xc for k3 = j) and pass 3's table entries of planes 2 and 4
     double2 xf[16];
 #pragma unroll
@@ -133,8 +151,7 @@ __global__ __launch_bounds__(OCC_THREADS, 2) void xcorr_cached_n4096(const Fused
         const bool hasB = rA + 1 < p.M;
         double *const rec = red + REC * parity;
         const double *const prec = red + REC * (parity ^ 1);
-        double st[10]; // the pair's statistics, used behind the workgroup transpose below
-        load_pair_stats(st, c.zstat, pair - first);
+        const PairVerdict q = qn; // requested a pair ago, published behind the workgroup transpose below
         // ================= ccA + i ccB = FFT(Z conj(X)/n) (unscaled by 1/sigma) =================
         double2 v[16];
 #pragma unroll
@@ -175,15 +192,16 @@ __global__ __launch_bounds__(OCC_THREADS, 2) void xcorr_cached_n4096(const Fused
         lds_barrier(); // the reads are done: the next pair's wave-local transpose writes without a barrier of its own
         // behind the barriers: the previous pair's record is complete and visible, and nobody reads this parity's record any more
         // (its last reader was the finalize of the pair before the previous one, in front of these barriers)
-        finalize_pair(prec, wave, lane == 0, invN, invNm1, p);
-        publish_pair_stats(rec, st, t, rA, hasB);
+        finalize_pair_cached(prec, wave, lane == 0, p);
+        publish_pair_verdict(rec, q, t, rA, hasB);
         if (claiming) {
             after = first + (long long)ch * __builtin_amdgcn_readfirstlane(next_s[cpar]);
             cpar ^= 1;
         }
+        qn = load_pair_verdict<PADDED, true>(c.zstat, nxt - first); // behind the pair's last read of LDS
         gdft16_nr_l2(v, g3);
         if (PADDED) // all sixteen c1 values in front of the request: loads return in order, one behind it would wait for the spectrum
-            correct_padded<16>(v, p.c1, t, st[8] * invN, st[9] * invN, [&]() __attribute__((always_inline)) {
+            correct_padded<16>(v, p.c1, t, q.s1a * invN, q.s1b * invN, [&]() __attribute__((always_inline)) {
                 request_z(zn, c, nxt, t);
                 fence();
             });
@@ -198,7 +216,7 @@ __global__ __launch_bounds__(OCC_THREADS, 2) void xcorr_cached_n4096(const Fused
         }
     }
     lds_barrier();
-    finalize_pair(red + REC * (parity ^ 1), t, true, invN, invNm1, p);
+    finalize_pair_cached(red + REC * (parity ^ 1), t, true, p);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- the reader at four workgroups per CU (test hook: muse_test_spectrum_cache_reader)
@@ -210,11 +228,12 @@ __global__ __launch_bounds__(OCC_THREADS, 4) void xcorr_cached_n4096_occ4(const 
     using namespace foldk;
     __shared__ double2 xbuf[OCC_XBUF];
     __shared__ double2 g2s[128];
-    __shared__ double red[2 * REC];
+    __shared__ alignas(16) double red[2 * REC];
     __shared__ int next_s[2];
     const PairThread th = pair_prologue<PADDED>(p, g2s, red + 34, REC);
     const int t = th.t, lane = th.lane, wave = th.wave;
-    const double invN = th.invN, invNm1 = th.invNm1;
+    const double invN = th.invN;
+    reader_prologue(red, t);
     double2 *const xw = xbuf + XW * wave;
     __syncthreads();
 
@@ -222,6 +241,7 @@ __global__ __launch_bounds__(OCC_THREADS, 4) void xcorr_cached_n4096_occ4(const 
     const long long first = c.pair0, total = c.pair0 + p.npairs;
     d2v zn[16]; // the next pair's spectrum, in flight
     request_z(zn, c, first + blockIdx.x < total ? first + (long long)blockIdx.x : first, t);
+    PairVerdict qn = load_pair_verdict<PADDED, false>(c.zstat, first + blockIdx.x < total ? (long long)blockIdx.x : 0); // the next pair's verdict, in flight
 
     long long nextpair = 0;
     for (long long pair = first + blockIdx.x; pair < total; pair = nextpair) {
@@ -231,8 +251,7 @@ __global__ __launch_bounds__(OCC_THREADS, 4) void xcorr_cached_n4096_occ4(const 
         const double *const prec = red + REC * (parity ^ 1);
         if (t == 0)
             next_s[parity] = (int)gridDim.x + atomicAdd(p.work_counter, 1);
-        double st[10]; // the pair's statistics, used behind the workgroup transpose below
-        load_pair_stats(st, c.zstat, pair - first);
+        const PairVerdict q = qn; // requested a pair ago, published behind the workgroup transpose below
         double2 v[16];
 #pragma unroll
         for (int i = 0; i < 16; i++)
@@ -246,14 +265,15 @@ __global__ __launch_bounds__(OCC_THREADS, 4) void xcorr_cached_n4096_occ4(const 
         // the first transform's workgroup transpose, which begins with a barrier, in between)
         exchange_cross<1, 1, true>(v, xbuf, wave, t);
         // behind the barriers: as in xcorr_cached_n4096
-        finalize_pair(prec, wave, lane == 0, invN, invNm1, p);
-        publish_pair_stats(rec, st, t, rA, hasB);
+        finalize_pair_cached(prec, wave, lane == 0, p);
+        publish_pair_verdict(rec, q, t, rA, hasB);
         nextpair = first + __builtin_amdgcn_readfirstlane(next_s[parity]);
         long long nxt = nextpair;
         nxt = nxt < total ? nxt : first; // last iteration: a dummy request
+        qn = load_pair_verdict<PADDED, true>(c.zstat, nxt - first); // behind the pair's last read of LDS
         gdft16_nr_l2(v, G3Derived(p.g3b, t));
         if (PADDED)
-            correct_padded<8>(v, p.c1, t, st[8] * invN, st[9] * invN);
+            correct_padded<8>(v, p.c1, t, q.s1a * invN, q.s1b * invN);
         wave_argmax_store(v, wave, lane, rec + 6 * wave);
         // (requesting half of the next spectrum in front of the argmax fits the registers and changes nothing: 7.08 ms either
         // way at 1 M x 4096; all of it there, or any of it in front of pass 3, spills)
@@ -263,7 +283,7 @@ __global__ __launch_bounds__(OCC_THREADS, 4) void xcorr_cached_n4096_occ4(const 
         parity ^= 1;
     }
     lds_barrier();
-    finalize_pair(red + REC * (parity ^ 1), t, true, invN, invNm1, p);
+    finalize_pair_cached(red + REC * (parity ^ 1), t, true, p);
 }
 
 static bool cache_launch_ok(const FusedParams &p, const SpectrumCacheArgs &c)
@@ -291,7 +311,8 @@ hipError_t launch_cache_fill(const FusedParams &p_in, const SpectrumCacheArgs &c
 hipError_t launch_cached(const FusedParams &p_in, const SpectrumCacheArgs &c, int num_cus, hipStream_t stream, bool occ4)
 {
     const FusedParams p = with_reciprocals(p_in);
-    if (!cache_launch_ok(p, c) || !c.zc || !c.zstat || c.zpairs < p.npairs || 2 * (c.pair0 + p.npairs) > p.M)
+    if (!cache_launch_ok(p, c) || !c.zc || !c.zstat || c.zpairs < p.npairs || 2 * (c.pair0 + p.npairs) > p.M ||
+        p.M > 0x7fffffffLL) // (the readers' record carries the row as an int)
         return hipErrorInvalidValue;
     const dim3 g((unsigned)(occ4 ? std::min<long long>(p.npairs, (long long)num_cus * 4)
                                  : std::min<long long>((p.npairs + ZC_CLAIM - 1) / ZC_CLAIM, (long long)num_cus * 2))), b(OCC_THREADS);
