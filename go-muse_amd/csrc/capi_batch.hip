@@ -644,7 +644,7 @@ int batch_score(muse_batch *b, const ScorePass &pass)
     b->origin = ScoreOrigin{};
     if (pass.window ? pass.direct() : b->windowed()) { // the best match inside the window, directly (xcorr_window.hip): no transform, never screened
         b->scores_exact = true;
-        return score_direct(b, pass.window ? *pass.window : lag_window_range(b->n, b->lag_window));
+        return score_direct(b, pass.window ? *pass.window : lag_window_range(b->n, b->lag_window), true, pass.window ? pass.sign : 0);
     }
     if (b->n > GENERIC_MAX_N) { // series longer than 65 536 samples: a sequence of chip-wide kernels per batch of pairs (xcorr_huge.hip)
         if (b->g->f32)
@@ -674,6 +674,8 @@ int batch_score(muse_batch *b, const ScorePass &pass)
             return rc;
         b->origin = ScoreOrigin::in_window(MUSE_IN_WINDOW_MASKED, *mask, variant);
         set_window(p, *mask);
+        p.win_sign = pass.sign; // (+-1: the signed builds of the same kernels, the rescaling kernel behind the n = 4096 one included)
+        b->origin.sign = pass.sign;
     }
     const bool allow_spectrum_cache = pass.allow_spectrum_cache;
     const SlideFuse *slide = pass.slide;
@@ -814,6 +816,14 @@ extern "C" int muse_batch_kernel_name(muse_batch *b, char *name, int32_t cap)
     const ScoreOrigin &o = b->origin; // (the in-window and packed kinds: an argument of a call, not a setting the next pass takes)
     if (o.slide == MUSE_SLIDE_IN_WINDOW_FUSED) { // (muse_batch_slide_score_in_window's one kernel: plain or masked argmax)
         snprintf(k, sizeof(k), "xcorr_fused_n4096_fold<false, %s, %s, %s, true>", padded, f32, o.kind == ScoreOrigin::MASKED ? "true" : "false");
+    } else if (o.kind == ScoreOrigin::MASKED && o.sign != 0) { // (muse_batch_score_signed_in_lag_range: the signed builds)
+        const char *neg = o.sign < 0 ? "true" : "false";
+        if (b->n == 4096)
+            snprintf(k, sizeof(k), "xcorr_fused_n4096_%s_signed<%s, %s, %s>", o.variant == KERNEL_R16_OCC3 ? "occ4" : "fold", padded, f32, neg);
+        else
+            snprintf(k, sizeof(k), "xcorr_fused_small_signed<%d, %s, %s, %s>", b->logn, padded, f32, neg);
+    } else if (o.kind == ScoreOrigin::MFMA && o.sign != 0) {
+        snprintf(k, sizeof(k), "xcorr_window_signed_mfma<%d, %s, %d>", o.mfma_tiles(), window_wide(b->g->rows, b->g->stride) ? "true" : "false", o.sign);
     } else if (o.kind == ScoreOrigin::MASKED) {
         if (o.variant == ScoreOrigin::MANY && b->n == 4096) // (muse_batch_score_many_in_window's one pass)
             snprintf(k, sizeof(k), "xcorr_fused_n4096_fold_multi<%s, %s, true>", padded, f32);

@@ -300,6 +300,7 @@ struct ScoreOrigin {
     int32_t variant = 0; // MASKED: the KERNEL_* the pass launched first, or MANY
     int32_t tiles = 0;   // PACKED
     int32_t slide = 0;   // the MUSE_SLIDE_IN_WINDOW_* path if the pass was muse_batch_slide_score_in_window's and moved the rows, 0 otherwise
+    int32_t sign = 0;    // MFMA / MASKED: +-1 if the pass was muse_batch_score_signed_in_lag_range's signed best match, 0 otherwise
     static ScoreOrigin packed(int32_t tiles) { return ScoreOrigin{PACKED, LagRange{0, 0, 0}, 0, tiles}; }
     static ScoreOrigin in_window(int32_t path, const LagRange &w, int32_t variant = 0) { return ScoreOrigin{(Kind)path, w, variant}; }
     int32_t in_window_path() const { return kind > OWN ? (int32_t)kind : 0; }
@@ -488,6 +489,7 @@ struct ScorePass {
     const LagRange *window = nullptr;
     int32_t path = MUSE_IN_WINDOW_PLAIN;
     const SlideFuse *slide = nullptr;
+    int32_t sign = 0; // MFMA / MASKED: +-1 = the signed best match inside the window (muse_batch_score_signed_in_lag_range), 0 = the best by magnitude
     const LagRange *mask() const { return window && path == MUSE_IN_WINDOW_MASKED ? window : nullptr; }
     bool direct() const { return window && path == MUSE_IN_WINDOW_MFMA; }
 };
@@ -511,14 +513,18 @@ int window_tables(muse_batch *b, const LagRange &w, PoolBuf<double> &e, PoolBuf<
 muse::WindowParams window_params(const muse_batch *b, const LagRange &w, const double *e, const double *pw);
 // the direct product over b's rows inside w, from b's own tables (device selected, rows uploaded, M > 0, mv / lag allocated); bracket:
 // the launch under a LaunchTimer of its own
-int score_direct(muse_batch *b, const LagRange &w, bool bracket = true);
+// sign: +-1 = the signed scan (launch_window_signed), 0 = the scan by magnitude
+int score_direct(muse_batch *b, const LagRange &w, bool bracket = true, int sign = 0);
 // The dispatch of every in-window entry point, a pure host function (MUSE_IN_WINDOW_*): which pass scores series of N samples (float32
 // storage or not) inside w, a window clipped at the FFT length of N
 int window_plan(int32_t N, bool f32, const LagRange &w, bool force_transform);
+// the same for the signed best match (muse_batch_score_signed_in_lag_range): sign == 0 is window_plan; otherwise its MFMA and MASKED
+// stand, and every lag (its PLAIN) is the masked pass with both bounds at their widest where the length has masked kernels
+int signed_window_plan(int32_t N, bool f32, const LagRange &w, int sign, bool force_transform);
 // a call's window over one batch: plan_in_window fills *pass with what batch_score is to run, or refuses (nothing enqueued, the batch
 // unchanged); score_in_window plans, runs and names the pass
-int plan_in_window(muse_batch *b, const LagRange &w, ScorePass *pass);
-int score_in_window(muse_batch *b, const LagRange &w);
+int plan_in_window(muse_batch *b, const LagRange &w, ScorePass *pass, int sign = 0);
+int score_in_window(muse_batch *b, const LagRange &w, int sign = 0);
 // the masked argmax of the transform kernels (their WIN builds): cc indices 0 .. hi and n - lneg .. n - 1 in the kernel's arguments
 inline void set_window(muse::FusedParams &p, const LagRange &w)
 {

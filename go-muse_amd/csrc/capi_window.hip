@@ -89,7 +89,7 @@ WindowParams window_params(const muse_batch *b, const LagRange &w, const double 
 }
 
 // the one direct-product pass: a batch's own window (muse_batch_score) and a call's (the MFMA path of every in-window entry point)
-int score_direct(muse_batch *b, const LagRange &w, bool bracket)
+int score_direct(muse_batch *b, const LagRange &w, bool bracket, int sign)
 {
     const hipStream_t st = b->stream();
     const int rc = window_tables(b, w, b->win_e, b->win_pw, &b->win_key, st);
@@ -98,7 +98,7 @@ int score_direct(muse_batch *b, const LagRange &w, bool bracket)
     LaunchTimer timer(b->ctx, false, st);
     if (bracket)
         HIP_TRY(timer.begin());
-    HIP_TRY(launch_window(window_params(b, w, b->win_e.p, b->win_pw.p), st));
+    HIP_TRY(launch_window_signed(window_params(b, w, b->win_e.p, b->win_pw.p), sign, st)); // (sign 0: launch_window)
     HIP_TRY(timer.end());
     return MUSE_OK;
 }
@@ -203,6 +203,28 @@ int window_plan(int32_t N, bool f32, const LagRange &w, bool force_transform)
     return masked_len ? MUSE_IN_WINDOW_MASKED : MUSE_IN_WINDOW_UNSUPPORTED;
 }
 
+// The dispatch of the signed best match (muse_batch_score_signed_in_lag_range), a pure host function; sign == 0: window_plan.
+//   window_plan says MFMA                                  : the direct product with the signed scan (xcorr_window_signed_mfma)
+//   window_plan says MASKED                                : the transform kernels' WIN builds with the signed mask, both storages
+//   window_plan says PLAIN, n in {512, 1024, 2048, 4096}   : the same masked kernels with both bounds at their widest (off the rows)
+//   anything else                                          : not built
+int signed_window_plan(int32_t N, bool f32, const LagRange &w, int sign, bool force_transform)
+{
+    const int path = window_plan(N, f32, w, force_transform);
+    if (sign == 0 || path != MUSE_IN_WINDOW_PLAIN)
+        return path;
+    const int64_t n = muse_next_pow2((double)N);
+    return n == 512 || n == 1024 || n == 2048 || n == 4096 ? MUSE_IN_WINDOW_MASKED : MUSE_IN_WINDOW_UNSUPPORTED;
+}
+
+extern "C" int muse_test_signed_lag_range_plan(int32_t N, int32_t f32, int32_t lag_lo, int32_t lag_hi, int32_t sign, int32_t *path)
+{
+    if (!path || N < 2 || lag_lo > 0 || lag_hi < 0 || sign < -1 || sign > 1)
+        return fail(MUSE_ERR_INVALID, "bad signed lag-range plan arguments (N >= 2, lag_lo <= 0 <= lag_hi, sign -1 .. 1)");
+    *path = signed_window_plan(N, f32 != 0, clip_lag_range(muse_next_pow2((double)N), lag_lo, lag_hi), sign, false);
+    return MUSE_OK;
+}
+
 extern "C" int muse_test_in_window_plan(int32_t N, int32_t f32, int32_t max_lag, int32_t *path)
 {
     if (!path || N < 2 || max_lag < 0)
@@ -242,12 +264,15 @@ static int fail_not_built(const muse_batch *b, const LagRange &w)
                 -w.lneg, w.hi, b->N, b->g->f32 ? " in float32 storage" : "", 2 * MUSE_LAG_WINDOW_MAX + 1);
 }
 
-int plan_in_window(muse_batch *b, const LagRange &w, ScorePass *pass)
+int plan_in_window(muse_batch *b, const LagRange &w, ScorePass *pass, int sign)
 {
-    const int path = window_plan(b->N, b->g->f32, w, b->ctx->in_window_force.load());
+    const int path = signed_window_plan(b->N, b->g->f32, w, sign, b->ctx->in_window_force.load());
     if (path == MUSE_IN_WINDOW_UNSUPPORTED || (path == MUSE_IN_WINDOW_MFMA && !b->xs))
-        return fail_not_built(b, w);
+        return sign && w.every_lag(b->n) ? fail(MUSE_ERR_UNSUPPORTED, "the signed best match at every lag over series of %d samples is not built: "
+                                                "it takes the masked argmax of the transform kernels of FFT lengths 512 ... 4096", b->N)
+                                         : fail_not_built(b, w);
     *pass = ScorePass{path == MUSE_IN_WINDOW_PLAIN, &w, path}; // (a masked pass always reads the rows)
+    pass->sign = sign;
     if (path == MUSE_IN_WINDOW_MFMA)
         return MUSE_OK;
     int variant = -1; // (what batch_score would refuse -- a forced kernel without a masked build -- before it touches the batch)
@@ -255,23 +280,24 @@ int plan_in_window(muse_batch *b, const LagRange &w, ScorePass *pass)
 }
 
 // as every in-window entry point leaves a batch it has scored
-static void scored_in_window(muse_batch *b, int path, const LagRange &w)
+static void scored_in_window(muse_batch *b, int path, const LagRange &w, int sign = 0)
 {
     b->scores_exact = true;
     b->last_path = MUSE_RUN_PATH_FP64;
     b->last_screened = false;
     if (path != MUSE_IN_WINDOW_MASKED) // (batch_score records the masked origin: it knows the kernel it launches first)
         b->origin = ScoreOrigin::in_window(path, w);
+    b->origin.sign = sign;
 }
 
-int score_in_window(muse_batch *b, const LagRange &w)
+int score_in_window(muse_batch *b, const LagRange &w, int sign)
 {
     ScorePass pass;
-    int rc = plan_in_window(b, w, &pass);
+    int rc = plan_in_window(b, w, &pass, sign);
     if (!rc)
         rc = batch_score(b, pass);
     if (!rc && b->g->M > 0)
-        scored_in_window(b, pass.path, w);
+        scored_in_window(b, pass.path, w, sign);
     return rc;
 }
 
@@ -317,6 +343,34 @@ extern "C" int muse_batch_run_in_lag_range(muse_batch *b, const int32_t *group_i
     int rc = check_select_args(group_id, G, sign_filter);
     if (!rc)
         rc = muse_batch_score_in_lag_range(b, lag_lo, lag_hi);
+    return rc ? rc : run_scored(b, group_id, G, range_max_lag(lag_lo, lag_hi), top_n, threshold, sign_filter, abs_scores, out_series, out_lag, out_score, out_count, out_mean_abs);
+}
+
+// ---- the signed best match inside a lag range: the argmax restricted to the values of one sign, not its answer filtered
+extern "C" int muse_batch_score_signed_in_lag_range(muse_batch *b, int32_t lag_lo, int32_t lag_hi, int32_t sign)
+{
+    // everything is checked before anything is enqueued: on a refusal the batch is unchanged
+    if (sign == MUSE_SIGN_ANY)
+        return muse_batch_score_in_lag_range(b, lag_lo, lag_hi);
+    if (!b)
+        return fail(MUSE_ERR_INVALID, "NULL batch");
+    if (sign != MUSE_SIGN_POS && sign != MUSE_SIGN_NEG)
+        return fail(MUSE_ERR_INVALID, "sign %d: one of MUSE_SIGN_ANY (0), MUSE_SIGN_POS (1), MUSE_SIGN_NEG (-1)", sign);
+    if (lag_lo > 0 || lag_hi < 0)
+        return fail(MUSE_ERR_INVALID, "the lag range %d .. %d does not hold lag 0 (lag_lo <= 0 <= lag_hi)", lag_lo, lag_hi);
+    const int rc = check_own_window(b, lag_lo, lag_hi);
+    return rc ? rc : score_in_window(b, clip_lag_range(b->n, lag_lo, lag_hi), sign);
+}
+
+extern "C" int muse_batch_run_signed_in_lag_range(muse_batch *b, const int32_t *group_id, int32_t G, int32_t lag_lo, int32_t lag_hi,
+                                                  int32_t top_n, double threshold, int32_t sign_filter, int32_t abs_scores,
+                                                  int64_t *out_series, int32_t *out_lag, double *out_score, int32_t *out_count,
+                                                  double *out_mean_abs)
+{
+    // (the selection's own argument checks come first, as in muse_batch_run_in_lag_range: they refuse a sign_filter outside -1 .. 1)
+    int rc = check_select_args(group_id, G, sign_filter);
+    if (!rc)
+        rc = muse_batch_score_signed_in_lag_range(b, lag_lo, lag_hi, sign_filter);
     return rc ? rc : run_scored(b, group_id, G, range_max_lag(lag_lo, lag_hi), top_n, threshold, sign_filter, abs_scores, out_series, out_lag, out_score, out_count, out_mean_abs);
 }
 

@@ -102,7 +102,16 @@ __device__ __forceinline__ double2 ldg2u(gptr<double2> p, unsigned i)
 // becomes +0.0 in front of maxAbsIndex.  A select, not a multiply: a NaN outside the window goes with the rest.  The two bounds
 // are taken relative to the thread's base once (two registers, formed here and not hoisted out of the pair loop), so that each
 // register costs two compares against a literal and four selects, and no scalar register holds a bound per register.
-template <bool BITREV, int STEP>
+// SGN (muse_batch_score_signed_in_lag_range; a compile-time argument: 0 is the mask above, instruction for instruction): +1 / -1 keeps
+// a value inside the window only if it is > 0 / < 0 -- per component, one more compare against the literal 0.0 and'ed into the
+// window's condition, no register -- so that the unchanged maxAbsIndex behind it finds the largest positive / the most negative
+// value, the first index winning ties, and (index 0, +0.0) where there is none.  A NaN and a zero of either sign become +0.0.
+// Everything the kernels apply behind the mask is a positive factor (1 / sigma).
+template <int SGN> __device__ __forceinline__ bool mask_keeps(const bool in, const double x)
+{
+    return SGN == 0 ? in : SGN > 0 ? (in && x > 0.0) : (in && x < 0.0);
+}
+template <bool BITREV, int STEP, int SGN = 0>
 __device__ __forceinline__ void mask_window(double2 (&v)[16], const int base, const int lpos, const int nl)
 {
     int a = lpos - base, b = nl - base;
@@ -111,8 +120,8 @@ __device__ __forceinline__ void mask_window(double2 (&v)[16], const int base, co
     for (int m = 0; m < 16; m++) {
         const int k = BITREV ? ((m & 1) << 3) | ((m & 2) << 1) | ((m & 4) >> 1) | ((m & 8) >> 3) : m;
         const bool in = STEP * m <= a || STEP * m >= b;
-        v[k].x = in ? v[k].x : 0.0;
-        v[k].y = in ? v[k].y : 0.0;
+        v[k].x = mask_keeps<SGN>(in, v[k].x) ? v[k].x : 0.0;
+        v[k].y = mask_keeps<SGN>(in, v[k].y) ? v[k].y : 0.0;
     }
 }
 // The same mask with the register number compared against the two QUOTIENTS floor(a / STEP) and ceil(b / STEP) (STEP a power of two:

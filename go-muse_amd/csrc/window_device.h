@@ -170,14 +170,19 @@ __device__ __forceinline__ double window_score(const double *lds, const int row0
 struct WindowBest { // (pos as a double: the candidates lie in LDS as three doubles)
     double abs = 0.0, val = 0.0, pos = -1.0;
 };
+// SGN (muse_batch_score_signed_in_lag_range; xcorr_window_signed_mfma alone): the key of the scan is |val| (0, what every other
+// kernel takes), val (+1: the best positive value) or -val (-1: the best negative one).  A key is compared with strict '>' against
+// 0.0 first, so a value of the other sign, a zero and a NaN never win; the candidates' merge compares keys as they are.
+template <int SGN> __device__ __forceinline__ double window_key(const double val) { return SGN == 0 ? fabs(val) : SGN > 0 ? val : -val; }
+template <int SGN = 0>
 __device__ __forceinline__ void window_scan_pos(WindowBest &best, const double *lds, const int row0, const int pos, const int c, const int L,
                                                 const int Lneg, const int origin, const WindowStats &st, const double *__restrict__ pw)
 {
     if (pos < L + 1 + Lneg) {
         const int v = (pos <= L ? pos : pos - 1 - Lneg - L) + origin; // lag + origin
         const double val = window_score(lds, row0, v, c, st, pw);
-        if (fabs(val) > best.abs) {
-            best.abs = fabs(val);
+        if (window_key<SGN>(val) > best.abs) {
+            best.abs = window_key<SGN>(val);
             best.val = val;
             best.pos = (double)pos;
         }
@@ -190,6 +195,8 @@ __device__ __forceinline__ void window_put_best(double *cand, const WindowBest &
     cand[2] = best.pos;
 }
 // parts slot0 .. slot0 + parts - 1 of series c merged in their order, and the outcome: the value, and through *lag its lag
+// (SGN != 0: no value of the sign in the window is (lag 0, +0.0), not cc[0], which would have the other sign)
+template <int SGN = 0>
 __device__ __forceinline__ double window_outcome(const double *lds, const int CAND, const int slot0, const int parts, const int row0,
                                                  const int c, const int L, const int Lneg, const int origin, const WindowStats &st,
                                                  const double *__restrict__ pw, int *lag)
@@ -211,14 +218,14 @@ __device__ __forceinline__ double window_outcome(const double *lds, const int CA
     if (st.zero)
         return 0.0; // sigma == 0: (nil, 0, 0), xcorr.go:165-168
     if (bp < 0) // only zeros or NaN in the window: index 0 stands
-        return window_score(lds, row0, origin, c, st, pw);
+        return SGN != 0 ? 0.0 : window_score(lds, row0, origin, c, st, pw);
     *lag = bp <= L ? bp : bp - 1 - Lneg - L;
     return bv;
 }
 
 // ---- the scan and the write-out of the single-reference kernels: the summed tiles in lds[0 .. TILES 256), (t1, t2) = series (t & 15)'s
 // sum d and sum d^2; 16 parts of TILES positions per series, candidates in lds[CAND ..).  Every thread of the workgroup calls it.
-template <int TILES>
+template <int TILES, int SGN = 0>
 __device__ __forceinline__ void window_scan_write(double *lds, const int CAND, const double t1, const double t2, const WindowParams &p,
                                                   const long long row0, const int t)
 {
@@ -227,26 +234,26 @@ __device__ __forceinline__ void window_scan_write(double *lds, const int CAND, c
     WindowBest best;
 #pragma unroll
     for (int k = 0; k < TILES; k++)
-        window_scan_pos(best, lds, 0, part * TILES + k, c, p.L, p.Lneg, p.origin, st, p.pw);
+        window_scan_pos<SGN>(best, lds, 0, part * TILES + k, c, p.L, p.Lneg, p.origin, st, p.pw);
     window_put_best(lds + CAND + (part * 16 + c) * 3, best);
     __syncthreads();
     if (t < 16 && row0 + t < p.M) {
         int lag;
-        p.mv[row0 + t] = window_outcome(lds, CAND, 0, 16, 0, c, p.L, p.Lneg, p.origin, st, p.pw, &lag);
+        p.mv[row0 + t] = window_outcome<SGN>(lds, CAND, 0, 16, 0, c, p.L, p.Lneg, p.origin, st, p.pw, &lag);
         p.lag[row0 + t] = lag;
     }
 }
 
 // acc: the wave's share of S (its pieces of every chunk); s1 / s2: the lane's share of sum d and sum d^2.  Every thread of the
 // workgroup calls it, behind its last piece; row0: the workgroup's first series
-template <int TILES>
+template <int TILES, int SGN = 0>
 __device__ __forceinline__ void window_finish(double *lds, const v4d (&acc)[TILES], const double s1, const double s2, const WindowParams &p,
                                               const long long row0, const int t, const int wave, const int r, const int q)
 {
     constexpr int STAT = WindowLds<TILES>::STAT;
     window_sum_tiles<TILES>(lds, STAT, acc, s1, s2, wave, r, q);
     const int c = t & 15;
-    window_scan_write<TILES>(lds, WindowLds<TILES>::CAND, window_wave_sum(lds, STAT, 2 * c), window_wave_sum(lds, STAT, 2 * c + 1), p, row0, t);
+    window_scan_write<TILES, SGN>(lds, WindowLds<TILES>::CAND, window_wave_sum(lds, STAT, 2 * c), window_wave_sum(lds, STAT, 2 * c + 1), p, row0, t);
 }
 
 // ---- the launch side: the checks every launch makes on a window's shape, and the tile count as a compile-time constant

@@ -92,6 +92,10 @@ struct FusedParams {
     // rows32 are written).  Behind everything else, for the same reason as the window.
     const void *slide_tails;
     int slide_k;
+    // the signed masked argmax (muse_batch_score_signed_in_lag_range; the SIGNED kernels of xcorr_r16_fold.hip, xcorr_r16_occ4.hip and
+    // xcorr_small.hip): win != 0 and win_sign = +1 / -1 -> a value inside the window that is not > 0 / < 0 becomes +0.0 as well.  Read
+    // by the launchers alone (the sign is a template argument of those kernels); 0: the kernels above.  Behind everything else again.
+    int win_sign;
 };
 inline FusedParams with_reciprocals(FusedParams p)
 {
@@ -200,6 +204,9 @@ inline long long window_e_len(int N) { return (long long)((N + WIN_KC - 1) / WIN
 // the tables of a window whose row v is lag v - origin, rows 0 .. W - 1 (a symmetric window +-L: origin = L, W = 2 L + 1)
 hipError_t launch_window_tables(const double *xs, int N, int n, int origin, int W, double *e, long long e_len, double *pw, hipStream_t stream);
 hipError_t launch_window(const WindowParams &p, hipStream_t stream);
+// the signed best match (muse_batch_score_signed_in_lag_range): sign = +1 / -1 the largest positive / the most negative value inside
+// the window, (lag 0, +0.0) where there is none (xcorr_window_signed_mfma); sign = 0 is launch_window
+hipError_t launch_window_signed(const WindowParams &p, int sign, hipStream_t stream);
 // ---- the same while the rows slide (xcorr_window_slide.hip; muse_batch_slide_score_windowed): xcorr_window_mfma over the NEW rows
 // -- old row[k .. N) followed by tails[r * k + 0 .. k), a dense M x k device buffer, 16-byte aligned -- which are stored in place on
 // the way: one read and one write of the rows instead of launch_row_slide's pair plus launch_window's read, the same bits as the two.

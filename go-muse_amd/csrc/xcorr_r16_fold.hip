@@ -56,6 +56,13 @@ __global__ __launch_bounds__(OCC_THREADS, 4) void xcorr_fused_n4096_fold(const F
 {
     foldk::pair_loop_from_rows<TIMING, PADDED, F32, WIN, SLIDE>(p, foldk::NoTap{});
 }
+// The WIN build with the signed mask (muse_batch_score_signed_in_lag_range; FusedParams::win_sign): NEG false / true = the largest
+// positive / the most negative value inside the window.  A kernel of its own, so that the ones above keep their symbols.
+template <bool PADDED, bool F32, bool NEG>
+__global__ __launch_bounds__(OCC_THREADS, 4) void xcorr_fused_n4096_fold_signed(const FusedParams p)
+{
+    foldk::pair_loop_from_rows<false, PADDED, F32, true, false, foldk::NoTap, NEG ? -1 : 1>(p, foldk::NoTap{});
+}
 
 // ============================================================================
 // Many references against one resident group in ONE pass over the rows
@@ -340,7 +347,7 @@ hipError_t launch_fused_multi(const FusedParams &p_in, int num_cus, hipStream_t 
     if (!p.work_counter || p.R < 1 || !p.g2 || !p.g3a || !p.g3b || !p.xcp_many || !p.mv_many || !p.lag_many)
         return hipErrorInvalidValue;
     const dim3 g((unsigned)grid), b(OCC_THREADS);
-    if ((p.N < 4096 && !p.c1_many) || !window_bounds_ok(p)) // (one window for every reference: muse_batch_score_many_in_window)
+    if ((p.N < 4096 && !p.c1_many) || !window_bounds_ok(p) || p.win_sign) // (one window for every reference: muse_batch_score_many_in_window; no signed build)
         return hipErrorInvalidValue;
     with_bools([&](auto padded, auto f32, auto win) {
         hipLaunchKernelGGL((xcorr_fused_n4096_fold_multi<decltype(padded)::value, decltype(f32)::value, decltype(win)::value>), g, b, 0, stream, p);
@@ -367,6 +374,14 @@ hipError_t launch_fused_fold(const FusedParams &p_in, int num_cus, hipStream_t s
     if (p.slide_tails && (p.slide_k < 1 || p.slide_k > p.N || p.N <= 2048 || p.N > 4096 || p.stride < p.N || p.pair_list || p.npairs != (p.M + 1) / 2 ||
                           (p.N == 4096 && !p.rows32 && !window_wide(p.rows, p.stride))))
         return hipErrorInvalidValue;
+    if (p.win_sign) { // the signed masked argmax: a window, a sign of +-1, no slide
+        if (!p.win || (p.win_sign != 1 && p.win_sign != -1) || p.slide_tails)
+            return hipErrorInvalidValue;
+        with_bools([&](auto padded, auto f32, auto neg) {
+            hipLaunchKernelGGL((xcorr_fused_n4096_fold_signed<decltype(padded)::value, decltype(f32)::value, decltype(neg)::value>), g, b, 0, stream, p);
+        }, p.N < 4096, p.rows32 != nullptr, p.win_sign < 0);
+        return hipGetLastError();
+    }
     with_bools([&](auto padded, auto f32, auto win, auto slide) {
         hipLaunchKernelGGL((xcorr_fused_n4096_fold<false, decltype(padded)::value, decltype(f32)::value, decltype(win)::value, decltype(slide)::value>), g, b, 0, stream, p);
     }, p.N < 4096, p.rows32 != nullptr, p.win != 0, p.slide_tails != nullptr);

@@ -140,8 +140,11 @@ __device__ __forceinline__ void finalize(const double *r, const Stat &st, double
 
 // WIN: masked argmax (muse_batch_score_in_window; r16_device.h, mask_window): the pairs the default kernel's WIN build hands over, and
 // whole groups after a dense hand-off, keep their lag window
-template <bool PADDED, int WPS, bool TIMING = false, bool F32 = false, bool WIN = false>
-__global__ __launch_bounds__(OCC_THREADS, WPS) void xcorr_fused_n4096_occ4(const FusedParams p)
+// SGN != 0 (WIN builds): the signed mask (muse_batch_score_signed_in_lag_range; xcorr_fused_n4096_occ4_signed below).  The body of
+// both kernels: inlined into each, so that xcorr_fused_n4096_occ4 keeps its symbols and its code (the arguments by value, as the
+// kernel takes them: by reference two of its builds' scalar spill counts moved; profiles/signed_lag_range_resources.txt).
+template <bool PADDED, bool TIMING, bool F32, bool WIN, int SGN>
+__device__ __forceinline__ void occ4_body(const FusedParams p)
 {
     using namespace occ4;
     __shared__ double2 xbuf[OCC_XBUF];
@@ -298,7 +301,7 @@ __global__ __launch_bounds__(OCC_THREADS, WPS) void xcorr_fused_n4096_occ4(const
         // its sign come from ballots (scalar unit).  Lowest k first, then lowest lane
         // == lowest index, because t < 256.
         if (WIN)
-            mask_window<false, 256>(v, t, p.win_lpos, 4096 - p.win_lneg);
+            mask_window<false, 256, SGN>(v, t, p.win_lpos, 4096 - p.win_lneg);
         double ma = 0.0, mb = 0.0;
 #pragma unroll
         for (int k = 0; k < 16; k++) {
@@ -366,6 +369,18 @@ __global__ __launch_bounds__(OCC_THREADS, WPS) void xcorr_fused_n4096_occ4(const
     }
 }
 
+template <bool PADDED, int WPS, bool TIMING = false, bool F32 = false, bool WIN = false>
+__global__ __launch_bounds__(OCC_THREADS, WPS) void xcorr_fused_n4096_occ4(const FusedParams p)
+{
+    occ4_body<PADDED, TIMING, F32, WIN, 0>(p);
+}
+// the WIN build with the signed mask (FusedParams::win_sign): the pairs xcorr_fused_n4096_fold_signed hands over, and whole groups
+template <bool PADDED, bool F32, bool NEG>
+__global__ __launch_bounds__(OCC_THREADS, 3) void xcorr_fused_n4096_occ4_signed(const FusedParams p)
+{
+    occ4_body<PADDED, false, F32, true, NEG ? -1 : 1>(p);
+}
+
 hipError_t launch_fused_occ4(const FusedParams &p_in, int num_cus, hipStream_t stream)
 {
     const FusedParams p = with_reciprocals(p_in);
@@ -380,6 +395,14 @@ hipError_t launch_fused_occ4(const FusedParams &p_in, int num_cus, hipStream_t s
     const dim3 g((unsigned)grid), b(OCC_THREADS);
     if (!window_bounds_ok(p)) // (the masked argmax: muse_batch_score_in_window)
         return hipErrorInvalidValue;
+    if (p.win_sign) { // the signed masked argmax: a window and a sign of +-1
+        if (!p.win || (p.win_sign != 1 && p.win_sign != -1))
+            return hipErrorInvalidValue;
+        with_bools([&](auto padded, auto f32, auto neg) {
+            hipLaunchKernelGGL((xcorr_fused_n4096_occ4_signed<decltype(padded)::value, decltype(f32)::value, decltype(neg)::value>), g, b, 0, stream, p);
+        }, p.N < 4096, p.rows32 != nullptr, p.win_sign < 0);
+        return hipGetLastError();
+    }
     with_bools([&](auto padded, auto f32, auto win) {
         hipLaunchKernelGGL((xcorr_fused_n4096_occ4<decltype(padded)::value, 3, false, decltype(f32)::value, decltype(win)::value>), g, b, 0, stream, p);
     }, p.N < 4096, p.rows32 != nullptr, p.win != 0);

@@ -158,4 +158,68 @@ hipError_t launch_window(const WindowParams &p, hipStream_t stream)
     return hipGetLastError();
 }
 
+// The signed best match (muse_batch_score_signed_in_lag_range): the product of xcorr_window_mfma -- the same pieces on the same waves
+// in the same order, from the functions of window_device.h, so S, the statistics and every cc are its bits -- with the scan's key val
+// (SGN = +1) or -val (SGN = -1) in place of |val| (window_key).  A kernel of its own: xcorr_window_mfma and its symbols stay as they are.
+template <int TILES, bool WIDE, int SGN>
+__global__ __launch_bounds__(WIN_THREADS) void xcorr_window_signed_mfma(const WindowParams p)
+{
+    static_assert(SGN == 1 || SGN == -1, "the unsigned scan is xcorr_window_mfma's");
+    __shared__ double lds[WindowLds<TILES>::SIZE];
+
+    const int t = threadIdx.x;
+    const int lane = t & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int r = lane & 15, q = lane >> 4;
+    const int N = p.N;
+    const long long row0 = (long long)blockIdx.x * 16;
+    long long row = row0 + r;
+    if (row >= p.M) // masked tail rows read the last row (valid memory); nothing of them is written
+        row = p.M - 1;
+    const double *__restrict__ y = p.rows + row * p.stride;
+    const double y0 = y[0];
+
+    v4d acc[TILES];
+#pragma unroll
+    for (int i = 0; i < TILES; i++)
+        acc[i] = v4d{0.0, 0.0, 0.0, 0.0};
+    double s1 = 0.0, s2 = 0.0;
+
+    for (int T0 = 0; T0 < N; T0 += WIN_KC) {
+        if (T0 > 0)
+            __syncthreads();
+        window_stage_e(lds, p.e + T0, t);
+        __syncthreads();
+        for (int s = wave; s < WIN_KC / 64; s += 4) {
+            const int T = T0 + 64 * s;
+            if (T >= N)
+                break;
+            double d[16];
+            window_load_piece<WIDE>(d, y, y0, T, N, q);
+            window_mac_piece<TILES, WIDE>(acc, s1, s2, [&](int m) { return d[m]; }, lds, s, r, q);
+        }
+    }
+    window_finish<TILES, SGN>(lds, acc, s1, s2, p, row0, t, wave, r, q);
+}
+
+hipError_t launch_window_signed(const WindowParams &p, int sign, hipStream_t stream)
+{
+    if (sign == 0)
+        return launch_window(p, stream);
+    if (sign != 1 && sign != -1)
+        return hipErrorInvalidValue;
+    if (p.M <= 0)
+        return hipSuccess;
+    long long blocks;
+    if (window_launch_check(p, &blocks) != hipSuccess)
+        return hipErrorInvalidValue;
+    const dim3 grid((unsigned)blocks), block(WIN_THREADS);
+    window_with_tiles(window_tiles(p), [&](auto tiles) {
+        with_bools([&](auto wide, auto neg) {
+            xcorr_window_signed_mfma<decltype(tiles)::value, decltype(wide)::value, decltype(neg)::value ? -1 : 1><<<grid, block, 0, stream>>>(p);
+        }, window_wide(p.rows, p.stride), sign < 0);
+    });
+    return hipGetLastError();
+}
+
 } // namespace muse

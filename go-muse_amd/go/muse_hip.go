@@ -540,7 +540,7 @@ func (b *Batch) RunInWindow(groupByLabels []string) error {
 	if es := shardEngines(); es != nil {
 		return fmt.Errorf("RunInWindow runs on one device")
 	}
-	return b.feedInWindow(groupByLabels, false, 0, 0)
+	return b.feedInWindow(groupByLabels, false, 0, 0, false)
 }
 
 // RunInLagRange is RunInWindow for a one-sided or asymmetric window (muse_batch_run_in_lag_range): every series contributes its
@@ -553,12 +553,38 @@ func (b *Batch) RunInLagRange(groupByLabels []string, lagLo, lagHi int) error {
 	if es := shardEngines(); es != nil {
 		return fmt.Errorf("RunInLagRange runs on one device")
 	}
-	return b.feedInWindow(groupByLabels, true, lagLo, lagHi)
+	return b.feedInWindow(groupByLabels, true, lagLo, lagHi, false)
 }
 
-// feedInWindow is what RunInWindow and RunInLagRange share: the label groups, the resident rows, the call (ranged: the lag range
-// lagLo .. lagHi, otherwise the window Results.MaxLag) and the feed of Results in group order.
-func (b *Batch) feedInWindow(groupByLabels []string, ranged bool, lagLo, lagHi int) error {
+// RunSignedInLagRange is RunInLagRange with Results.SignFilter restricting the ARGMAX, not only filtering its answer
+// (muse_batch_run_signed_in_lag_range): under SignFilter_POS every series contributes its largest positive value inside the lags
+// lagLo .. lagHi (SignFilter_NEG: its most negative one), so a series whose peak of the other sign is the larger one by magnitude
+// is not lost, and a label group's maximum is taken over its members' values of the sign.  SignFilter_ANY is RunInLagRange.  One
+// device.  Results is fed as RunInLagRange feeds it -- the sign always goes to the device, where it selects the argmax; a series
+// with no value of the sign comes back as (0, +0.0), which no sign filter passes.  Under a sign the Scores carry the SIGNED value,
+// clamped to +-1 as Muse.Run's are (muse.go:72-76): Batch.Run reports magnitudes (muse_batch.go:74), which SignFilter_NEG never passes.
+func (b *Batch) RunSignedInLagRange(groupByLabels []string, lagLo, lagHi int) error {
+	if lagLo > 0 || lagHi < 0 {
+		return fmt.Errorf("RunSignedInLagRange: lagLo <= 0 <= lagHi")
+	}
+	if es := shardEngines(); es != nil {
+		return fmt.Errorf("RunSignedInLagRange runs on one device")
+	}
+	return b.feedInWindow(groupByLabels, true, lagLo, lagHi, true)
+}
+
+// RunSigned is RunSignedInLagRange(-MaxLag, MaxLag): RunInWindow with Results.SignFilter restricting the argmax.
+func (b *Batch) RunSigned(groupByLabels []string) error {
+	if b.Results.MaxLag < 0 {
+		return fmt.Errorf("RunSigned: MaxLag < 0")
+	}
+	return b.RunSignedInLagRange(groupByLabels, -b.Results.MaxLag, b.Results.MaxLag)
+}
+
+// feedInWindow is what RunInWindow, RunInLagRange and RunSignedInLagRange share: the label groups, the resident rows, the call (ranged:
+// the lag range lagLo .. lagHi, otherwise the window Results.MaxLag; signed: the ranged call whose argmax takes Results.SignFilter) and
+// the feed of Results in group order.
+func (b *Batch) feedInWindow(groupByLabels []string, ranged bool, lagLo, lagHi int, signed bool) error {
 	labelValuesSet := b.Comparison.indexLabelValues(groupByLabels)
 	if len(labelValuesSet) == 0 {
 		return nil
@@ -615,7 +641,14 @@ func (b *Batch) feedInWindow(groupByLabels []string, ranged bool, lagLo, lagHi i
 	var cnt C.int32_t
 	var mean C.double
 	var st C.int
-	if ranged {
+	if signed {
+		absScores := 1
+		if int(r.SignFilter) != 0 { // (not SignFilter_ANY)
+			absScores = 0
+		}
+		st = C.muse_batch_run_signed_in_lag_range(b.batch, &gid[0], C.int32_t(G), C.int32_t(lagLo), C.int32_t(lagHi), C.int32_t(topN),
+			C.double(threshold), C.int32_t(r.SignFilter), C.int32_t(absScores), &idx[0], &lag[0], &score[0], &cnt, &mean)
+	} else if ranged {
 		st = C.muse_batch_run_in_lag_range(b.batch, &gid[0], C.int32_t(G), C.int32_t(lagLo), C.int32_t(lagHi), C.int32_t(topN),
 			C.double(threshold), C.int32_t(sign), 1, &idx[0], &lag[0], &score[0], &cnt, &mean)
 	} else {

@@ -1124,6 +1124,36 @@ public:
         });
     }
 
+    // RunInLagRange with Results.SignFilter restricting the ARGMAX, not only filtering its answer (muse_batch_run_signed_in_lag_range):
+    // under SignFilter_POS every series contributes its largest positive value inside the lags lagLo .. lagHi (SignFilter_NEG: its
+    // most negative one), so a series whose peak of the other sign is the larger one by magnitude is not lost, and a label group's
+    // maximum is taken over its members' values of the sign.  SignFilter_ANY is RunInLagRange.  One device.  Results is fed as
+    // RunInLagRange feeds it -- the sign always goes to the device, where it selects the argmax; a series with no value of the sign
+    // comes back as (0, +0.0), which no sign filter passes -- and Results.Update applies the Results' own filters unchanged.  Under a
+    // sign the Scores carry the SIGNED value, clamped to +-1 as Muse::Run's are (muse.go:72-76): Batch::Run reports magnitudes
+    // (muse_batch.go:74), which SignFilter_NEG never passes.
+    void RunSignedInLagRange(const std::vector<std::string> &groupByLabels, int lagLo, int lagHi)
+    {
+        if (lagLo > 0 || lagHi < 0)
+            throw Error(MUSE_ERR_INVALID, "RunSignedInLagRange: lagLo <= 0 <= lagHi");
+        if (!engines_.empty())
+            throw Error(MUSE_ERR_UNSUPPORTED, "RunSignedInLagRange runs on one device");
+        const int32_t filter = (int32_t)Results_->Filter;
+        feed_in_window(groupByLabels, [&](const int32_t *gid, int32_t G, int32_t top, double threshold, int32_t, int64_t *idx,
+                                          int32_t *lag, double *score, int32_t *cnt, double *mean) {
+            return muse_batch_run_signed_in_lag_range(batch_, gid, G, (int32_t)lagLo, (int32_t)lagHi, top, threshold, filter,
+                                                      filter == 0 ? 1 : 0, idx, lag, score, cnt, mean);
+        });
+    }
+
+    // RunSignedInLagRange(-MaxLag, MaxLag): RunInWindow with Results.SignFilter restricting the argmax
+    void RunSigned(const std::vector<std::string> &groupByLabels)
+    {
+        if (Results_->MaxLag < 0)
+            throw Error(MUSE_ERR_INVALID, "RunSigned: MaxLag < 0");
+        RunSignedInLagRange(groupByLabels, -Results_->MaxLag, Results_->MaxLag);
+    }
+
     // what RunInWindow and RunInLagRange share: the label groups, the resident rows, the call (one of the library's _run_in_ entry
     // points) and the feed of Results in group order
     template <class Call> void feed_in_window(const std::vector<std::string> &groupByLabels, Call call)

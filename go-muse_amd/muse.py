@@ -489,9 +489,41 @@ class DeviceBatch:
         c = cnt.value
         return o_s[:c].copy(), o_l[:c].copy(), o_v[:c].copy(), float(mean.value)
 
+    def score_signed_in_lag_range(self, lag_lo, lag_hi, sign):
+        """muse_batch_score_signed_in_lag_range: score_in_lag_range with the argmax restricted to the values of one sign -- sign = +1
+        every series' largest positive value inside the lags lag_lo .. lag_hi, -1 its most negative one, (lag 0, +0.0) where the
+        range holds no value of the sign; sign = 0 is score_in_lag_range, bit for bit.  Up to 127 lags on float64 groups: the direct
+        product with a signed scan; wider, float32 storage, or every lag: the transform kernels' masked argmax with the sign in the
+        mask (FFT lengths 512 ... 4096 only).  Results: read_scores()."""
+        B.check(B.load().muse_batch_score_signed_in_lag_range(self._h, int(lag_lo), int(lag_hi), int(sign)))
+
+    def scores_signed_in_lag_range(self, lag_lo, lag_hi, sign):
+        """score_signed_in_lag_range + copy back: (lag, mv)"""
+        self.score_signed_in_lag_range(lag_lo, lag_hi, sign)
+        return self.read_scores()
+
+    def run_signed_in_lag_range(self, lag_lo, lag_hi, group_id=None, G=0, top_n=20, threshold=0.0, sign_filter=0, abs_scores=True):
+        """muse_batch_run_signed_in_lag_range: score_signed_in_lag_range(lag_lo, lag_hi, sign_filter) followed by Batch.Run's
+        selection with Results.MaxLag = max(-lag_lo, lag_hi) and Results.SignFilter = sign_filter: the sign restricts the argmax
+        and filters the selection; -> (series, lag, score, mean_abs) as run().  sign_filter = 0 is run_in_lag_range."""
+        cap = max(int(top_n), 1)
+        o_s = np.zeros(cap, dtype=np.int64)
+        o_l = np.zeros(cap, dtype=np.int32)
+        o_v = np.zeros(cap)
+        cnt, mean = ctypes.c_int32(0), ctypes.c_double(0)
+        gid = None
+        if group_id is not None:
+            gid = np.ascontiguousarray(group_id, dtype=np.int32)
+        B.check(B.load().muse_batch_run_signed_in_lag_range(
+            self._h, B.i32ptr(gid) if gid is not None else None, int(G), int(lag_lo), int(lag_hi), int(top_n), float(threshold),
+            int(sign_filter), 1 if abs_scores else 0, B.i64ptr(o_s), B.i32ptr(o_l), B.dptr(o_v), ctypes.byref(cnt),
+            ctypes.byref(mean)))
+        c = cnt.value
+        return o_s[:c].copy(), o_l[:c].copy(), o_v[:c].copy(), float(mean.value)
+
     def last_in_window_path(self):
-        """test hook: MUSE_IN_WINDOW_* of the last score_in_window / run_in_window / score_in_lag_range / run_in_lag_range, 0 after
-        any other scoring pass"""
+        """test hook: MUSE_IN_WINDOW_* of the last score_in_window / run_in_window / score_in_lag_range / run_in_lag_range or of
+        their signed forms, 0 after any other scoring pass"""
         w = ctypes.c_int32(0)
         B.check(B.load().muse_test_last_in_window_path(self._h, ctypes.byref(w)))
         return int(w.value)
@@ -998,6 +1030,14 @@ def run_many_in_lag_range(batches, lag_lo, lag_hi, group_id=None, G=0, top_n=20,
     returns a list of (series, lag, score, mean_abs), one per batch"""
     return _run_many("muse_batch_run_many_in_lag_range", batches, group_id, G, (lag_lo, lag_hi), top_n, threshold, sign_filter,
                      abs_scores)
+
+
+def signed_lag_range_plan(N, f32, lag_lo, lag_hi, sign):
+    """muse_test_signed_lag_range_plan (no device): MUSE_IN_WINDOW_* -- the pass score_signed_in_lag_range takes for series of N
+    samples (f32: float32 storage) inside the lags lag_lo .. lag_hi with the sign; sign = 0 is lag_range_plan"""
+    path = ctypes.c_int32(0)
+    B.check(B.load().muse_test_signed_lag_range_plan(int(N), 1 if f32 else 0, int(lag_lo), int(lag_hi), int(sign), ctypes.byref(path)))
+    return int(path.value)
 
 
 def many_lag_range_plan(N, f32, lag_lo, lag_hi, R):
@@ -1590,6 +1630,43 @@ class Batch:
         for k in order:
             r.Update(Score(series[int(idx[k])].Labels(), int(lag[k]), float(score[k])))
         return None
+
+    def RunSignedInLagRange(self, groupByLabels, lagLo, lagHi):
+        """RunInLagRange with Results.SignFilter restricting the ARGMAX, not only filtering its answer
+        (muse_batch_run_signed_in_lag_range): under SignFilter_POS every series contributes its largest positive value inside the
+        lags lagLo .. lagHi (SignFilter_NEG: its most negative one), so a series whose peak of the other sign is the larger one by
+        magnitude is not lost, and a label group's maximum is taken over its members' values of the sign.  SignFilter_ANY is
+        RunInLagRange.  One device; Results is fed as RunInLagRange feeds it (a series with no value of the sign comes back as
+        (0, +0.0), which no sign filter passes), and Results.Update applies the Results' own filters unchanged.  Under a sign
+        the Scores carry the SIGNED value, clamped to +-1 as Muse.Run's are (muse.go:72-76): Batch.Run reports magnitudes
+        (muse_batch.go:74), which SignFilter_NEG never passes."""
+        comp = self.Comparison
+        labelValuesSet = comp.indexLabelValues(groupByLabels)
+        if not labelValuesSet:
+            return None
+        if self._engines:
+            raise MuseError(B.MUSE_ERR_UNSUPPORTED, "RunSignedInLagRange runs on one device")
+        r = self.Results
+        if lagLo > 0 or lagHi < 0:
+            raise MuseError(B.MUSE_ERR_INVALID, "RunSignedInLagRange needs lagLo <= 0 <= lagHi")
+        series = comp._series_list()
+        gid = comp._group_ids()
+        G = len(labelValuesSet)
+        mag = r.SignFilter == SignFilter_ANY
+        if G <= EXACT_FEED_MAX_GROUPS:
+            idx, lag, score, _ = self._batch().run_signed_in_lag_range(lagLo, lagHi, gid, G, G, 0.0, r.SignFilter, abs_scores=mag)
+        else:
+            idx, lag, score, _ = self._batch().run_signed_in_lag_range(lagLo, lagHi, gid, G, r.TopN, r.Threshold, r.SignFilter, abs_scores=mag)
+        order = np.argsort(gid[idx], kind="stable")
+        for k in order:
+            r.Update(Score(series[int(idx[k])].Labels(), int(lag[k]), float(score[k])))
+        return None
+
+    def RunSigned(self, groupByLabels):
+        """RunSignedInLagRange(-MaxLag, MaxLag): RunInWindow with Results.SignFilter restricting the argmax"""
+        if self.Results.MaxLag < 0:
+            raise MuseError(B.MUSE_ERR_INVALID, "RunSigned needs Results.MaxLag >= 0")
+        return self.RunSignedInLagRange(groupByLabels, -self.Results.MaxLag, self.Results.MaxLag)
 
     def _shard_batches(self):
         shards = self.Comparison._device_shards(self._engines)

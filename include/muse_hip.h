@@ -411,6 +411,46 @@ int muse_batch_score_in_lag_range(muse_batch *b, int32_t lag_lo, int32_t lag_hi)
 int muse_batch_run_in_lag_range(muse_batch *b, const int32_t *group_id, int32_t G, int32_t lag_lo, int32_t lag_hi,
                                 int32_t top_n, double threshold, int32_t sign_filter, int32_t abs_scores,
                                 int64_t *out_series, int32_t *out_lag, double *out_score, int32_t *out_count, double *out_mean_abs);
+/* THE SIGNED BEST MATCH.  muse_batch_score_signed_in_lag_range is muse_batch_score_in_lag_range with the argmax restricted to the
+ * values of one sign: sign = MUSE_SIGN_POS "where does the series move WITH the reference most", MUSE_SIGN_NEG "where AGAINST it".
+ * The reference takes each series' argmax of |cc| and drops the series when the winner has the wrong sign (results.go:46-52): a
+ * series whose anti-correlated peak is the larger one by magnitude is lost to a SignFilter_POS caller, because its positive peak
+ * was never reported -- no filter brings it back.  Here the argmax is restricted instead of its answer filtered.  Definition, per
+ * series, with n, lo, hi, cc[0 .. n-1] and the scan order exactly as at muse_batch_score_in_lag_range (indices 0 .. hi, then
+ * n + lo .. n - 1):
+ *   sign == MUSE_SIGN_ANY : by definition muse_batch_score_in_lag_range(b, lag_lo, lag_hi), bit for bit on every path, its
+ *                           every-lag and MUSE_ERR_UNSUPPORTED outcomes included
+ *   sign == MUSE_SIGN_POS : the scan starts from (0, 0.0) and takes index i when cc[i] > best (strict): the first index wins ties,
+ *                           only values > 0 can win, a NaN never wins
+ *   sign == MUSE_SIGN_NEG : takes i when -cc[i] > -best
+ *   no value of the requested sign inside the range : (lag 0, mv +0.0) -- not cc[0], which would have the wrong sign; the selection's
+ *                           sign filter (score > 0, score < 0) then drops the series, as it drops sigma == 0 rows
+ *   a series with sigma == 0 : (0, 0.0);  a NaN / Inf series : (0, NaN), as the unsigned pass gives
+ * Invariant: whenever the unsigned in-range winner has the requested sign, the signed result is that same (lag, value).
+ * Which pass runs, for sign != 0 (W = hi - lo + 1 the lags of the clipped range):
+ *   float64 group, W <= 2 MUSE_LAG_WINDOW_MAX + 1, up to 65536 samples : the direct product of muse_batch_score_in_lag_range with the
+ *                                                                      signed scan (key cc or -cc in place of |cc|): the same cc bits
+ *   FFT length 512, 1024, 2048 or 4096, W wider or float32 storage   : the transform kernels' masked argmax with the sign in the mask
+ *                                                                      (a value inside the range that has not the sign becomes +0.0
+ *                                                                      in front of the unchanged maxAbsIndex), both storages
+ *   the range is every lag, FFT length 512, 1024, 2048 or 4096       : the same masked kernels with both bounds at their widest
+ *                                                                      ("the best positive match at any lag"); reads the rows
+ *   anything else                                                    : MUSE_ERR_UNSUPPORTED, nothing changed
+ * Results land in the batch's score buffers; the pass is exact fp64, never screened, and never uses, builds or counts towards the
+ * group's spectrum cache; the batch's own lag_window rule is muse_batch_score_in_lag_range's.  MUSE_ERR_INVALID, nothing changed:
+ * that call's cases, and a sign outside -1 .. 1.
+ * muse_batch_run_signed_in_lag_range is that pass followed by Batch.Run's selection, outputs as muse_batch_run_in_lag_range:
+ * sign_filter is both the argmax's sign and the selection's Results.SignFilter (as max_lag is both the window and Results.MaxLag of
+ * muse_batch_run_in_window), Results.MaxLag = max(-lag_lo, lag_hi).  A label group's maximum is then taken over its members' best
+ * values OF THE SIGN: a group whose first-by-magnitude member has the wrong sign is no longer dropped whole.  sign_filter == 0 is
+ * muse_batch_run_in_lag_range.
+ * Limits: the many-references forms, the slide forms, the Muse.Run rows forms, the muse_batch_set_lag_window setting (a batch's own
+ * window is unsigned), the multi-device and dist.py layers; signed passes where the table above says MUSE_ERR_UNSUPPORTED (every
+ * lag, more than 127 lags or float32 storage outside FFT lengths 512 ... 4096). */
+int muse_batch_score_signed_in_lag_range(muse_batch *b, int32_t lag_lo, int32_t lag_hi, int32_t sign);
+int muse_batch_run_signed_in_lag_range(muse_batch *b, const int32_t *group_id, int32_t G, int32_t lag_lo, int32_t lag_hi,
+                                       int32_t top_n, double threshold, int32_t sign_filter, int32_t abs_scores,
+                                       int64_t *out_series, int32_t *out_lag, double *out_score, int32_t *out_count, double *out_mean_abs);
 /* Muse.Run (muse.go:46-92) INSIDE A LAG RANGE of up to MUSE_RUN_ROWS_LAG_RANGE_MAX lags, in one call.  Each behaves as its _windowed
  * namesake (muse_batch_run_rows_windowed, _run_row_ptrs_windowed, _run_group_rows_windowed): same validation, same out_winner /
  * out_state rules, same abs_scores, M == 0 gives state 0, the same pool of slots, any number of host threads on one tmpl; a

@@ -157,6 +157,12 @@ int muse_test_last_in_window_path(muse_batch *b, int32_t *path);
  * transform kernels with a masked argmax) or _UNSUPPORTED.  For lag_lo == -lag_hi it is muse_test_in_window_plan(N, ., lag_hi).
  * MUSE_ERR_INVALID for N < 2, lag_lo > 0, lag_hi < 0 or a NULL out pointer. */
 int muse_test_lag_range_plan(int32_t N, int32_t f32_storage, int32_t lag_lo, int32_t lag_hi, int32_t *path);
+/* muse_batch_score_signed_in_lag_range's dispatch, a pure host function (no device needed).  sign == 0: muse_test_lag_range_plan.
+ * sign == +-1: its _MFMA and _MASKED stand (the signed scan, the signed mask); where it says _PLAIN (the clipped range is every lag)
+ * *path = MUSE_IN_WINDOW_MASKED at FFT lengths 512, 1024, 2048 and 4096 (the masked kernels with both bounds at their widest) and
+ * _UNSUPPORTED elsewhere.  MUSE_ERR_INVALID for N < 2, lag_lo > 0, lag_hi < 0, a sign outside -1 .. 1 or a NULL out pointer.
+ * muse_test_last_in_window_path reports the signed calls' passes too. */
+int muse_test_signed_lag_range_plan(int32_t N, int32_t f32_storage, int32_t lag_lo, int32_t lag_hi, int32_t sign, int32_t *path);
 /* muse_batch_score_many_in_window's dispatch, a pure host function (no device needed): the pass that scores R >= 1 references against
  * series of N >= 2 samples (f32_storage: a float32-storage group) inside +-max_lag >= 0 -- *path = MUSE_IN_WINDOW_PLAIN
  * (muse_batch_score_many), _MFMA (muse_batch_score_many_windowed), _MASKED (ONE many-references pass of the transform kernels with a
