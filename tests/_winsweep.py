@@ -77,11 +77,12 @@ class Case:
     """ref / refs, rows, the planted lag of every row (for refs[0]; refs[i]: + offsets[i], folded), the outlier mask"""
 
 
-def make_case(N, seed=0, lags=None, offsets=(0,)):
+def make_case(N, seed=0, lags=None, offsets=(0,), p=None):
     """the case of length N.  lags: the planted lags instead of planted_lags() (the outlier copies are appended either way);
-    offsets: one reference per entry, the code at p + offset over noise of its own"""
+    offsets: one reference per entry, the code at p + offset over noise of its own; p: the reference's code position instead of
+    the middle of the row"""
     w = code_len(N)
-    n, p = LS.fft_len(N), (N - w) // 2
+    n, p = LS.fft_len(N), ((N - w) // 2 if p is None else int(p))
     lags = planted_lags(N, w) if lags is None else np.asarray(lags, dtype=np.int64)
     lags = lags[np.random.default_rng([seed, 7]).permutation(len(lags))]
     ref, rows, n2 = LS.make_case(N, -lags, p, w, seed)
@@ -117,17 +118,24 @@ def _g(k):
 
 
 class Table:
-    """cc[M, 2 Lc + 1] (long double) and B[M, 2 Lc + 1] (float64) for lags -Lc .. Lc"""
+    """cc[M, 2 Lc + 1] (long double) and B[M, 2 Lc + 1] (float64) for lags -Lc .. Lc (column c: lag lags[c] = c - Lc)"""
 
 
 class Image:
     """the matrix of shifted references of one reference, [lag][t] contiguous: E[lag + Lc, t] = the (normalised, zero-padded)
     reference under sample t at that lag, in long double; computed once per reference"""
 
-    def __init__(self, ref, n):
+    def __init__(self, ref, n, lags=None):
+        """lags: a contiguous ascending lag list in place of -Lc .. Lc (tests/_rangesweep.py); Lc is then the column of lag 0"""
         N = len(ref)
         self.N, self.n, self.Lc = N, n, min(LMAX, n // 2)
-        lags = np.arange(-self.Lc, self.Lc + 1)
+        if lags is None:
+            lags = np.arange(-self.Lc, self.Lc + 1)
+        else:
+            lags = np.asarray(lags, dtype=np.int64)
+            assert lags[0] <= 0 <= lags[-1] and np.array_equal(lags, np.arange(lags[0], lags[-1] + 1))
+            self.Lc = -int(lags[0])
+        self.lags = lags
         xs_pad = LS.ld_ref(ref, n)
         self.E = np.ascontiguousarray(xs_pad[(n - N + lags[:, None] + np.arange(N)[None, :]) % n])
         self.Eabs = np.abs(self.E)
@@ -135,19 +143,19 @@ class Image:
         self.Pabs = self.Eabs.sum(axis=1)[None, :]
 
 
-def tables(ref, rows, n, image=None):
-    """the Table of `rows` against `ref` (image: its Image, when the caller keeps one)"""
+def tables(ref, rows, n, image=None, lags=None):
+    """the Table of `rows` against `ref` (image: its Image, when the caller keeps one; lags: Image's, for a table of other columns)"""
     ld = np.longdouble
     rows = np.asarray(rows, dtype=np.float64)
     M, N = rows.shape
-    im = Image(ref, n) if image is None else image
+    im = Image(ref, n, lags) if image is None else image
     assert im.N == N and im.n == n
     Y = rows.astype(ld)
     mean = Y.sum(axis=1) / N
     Dm = Y - mean[:, None]
     sigma = np.sqrt((Dm * Dm).sum(axis=1) / (N - 1))
     t = Table()
-    t.n, t.N, t.Lc = n, N, im.Lc
+    t.n, t.N, t.Lc, t.lags = n, N, im.Lc, im.lags
     Sm = np.dot(Dm, im.E.T)                                               # one long-double dot per (row, lag)
     t.cc = Sm / sigma[:, None]
     # the bound, from the kernel's quantities
