@@ -18,7 +18,7 @@ from .muse import (Batch, DefaultLabel, DeviceBatch, DeviceGroup, Engine, Group,
                    RunMany, run_many, score_many, scores_many, xcorr_groups, device_count,
                    RunManyWindowed, run_many_windowed, score_many_windowed, scores_many_windowed, window_many_plan, window_rows_plan, in_window_plan,
                    RunManyInWindow, run_many_in_window, score_many_in_window, scores_many_in_window, many_in_window_plan,
-                   slide_in_window_plan, lag_range_plan, signed_lag_range_plan, rows_lag_range_plan,
+                   slide_in_window_plan, lag_range_plan, signed_lag_range_plan, lag_band_plan, rows_lag_range_plan,
                    RunManyInLagRange, run_many_in_lag_range, score_many_in_lag_range, scores_many_in_lag_range, many_lag_range_plan,
                    window_many_plan_rows,
                    merge_group_records, merge_group_winners)

@@ -118,6 +118,10 @@ SIGNATURES = {
     "muse_batch_run_signed_in_lag_range": (ctypes.c_int, [_vp, _i32p, _i32, _i32, _i32, _i32, _f64, _i32, _i32,
                                                           _i64p, _i32p, _dp, _i32p, _dp]),
     "muse_test_signed_lag_range_plan": (ctypes.c_int, [_i32, _i32, _i32, _i32, _i32, _i32p]),
+    "muse_batch_score_in_lag_band": (ctypes.c_int, [_vp, _i32, _i32, _i32]),
+    "muse_batch_run_in_lag_band": (ctypes.c_int, [_vp, _i32p, _i32, _i32, _i32, _i32, _f64, _i32, _i32,
+                                                  _i64p, _i32p, _dp, _i32p, _dp]),
+    "muse_test_lag_band_plan": (ctypes.c_int, [_i32, _i32, _i32, _i32, _i32, _i32p]),
     "muse_test_in_window_plan": (ctypes.c_int, [_i32, _i32, _i32, _i32p]),
     "muse_test_in_window_force_transform": (ctypes.c_int, [_vp, _i32]),
     "muse_test_last_in_window_path": (ctypes.c_int, [_vp, _i32p]),

@@ -673,7 +673,7 @@ int batch_score(muse_batch *b, const ScorePass &pass)
         if (rc)
             return rc;
         b->origin = ScoreOrigin::in_window(MUSE_IN_WINDOW_MASKED, *mask, variant);
-        set_window(p, *mask);
+        set_window(p, *mask); // (a band: the band builds of the same kernels, the rescaling kernel behind the n = 4096 one included)
         p.win_sign = pass.sign; // (+-1: the signed builds of the same kernels, the rescaling kernel behind the n = 4096 one included)
         b->origin.sign = pass.sign;
     }
@@ -816,6 +816,13 @@ extern "C" int muse_batch_kernel_name(muse_batch *b, char *name, int32_t cap)
     const ScoreOrigin &o = b->origin; // (the in-window and packed kinds: an argument of a call, not a setting the next pass takes)
     if (o.slide == MUSE_SLIDE_IN_WINDOW_FUSED) { // (muse_batch_slide_score_in_window's one kernel: plain or masked argmax)
         snprintf(k, sizeof(k), "xcorr_fused_n4096_fold<false, %s, %s, %s, true>", padded, f32, o.kind == ScoreOrigin::MASKED ? "true" : "false");
+    } else if (o.kind == ScoreOrigin::MASKED && o.window.band()) { // (muse_batch_score_in_lag_band: the band builds, any sign)
+        if (b->n == 4096)
+            snprintf(k, sizeof(k), "xcorr_fused_n4096_%s_band<%s, %s, %d>", o.variant == KERNEL_R16_OCC3 ? "occ4" : "fold", padded, f32, o.sign);
+        else
+            snprintf(k, sizeof(k), "xcorr_fused_small_band<%d, %s, %s, %d>", b->logn, padded, f32, o.sign);
+    } else if (o.kind == ScoreOrigin::MFMA && o.window.band()) {
+        snprintf(k, sizeof(k), "xcorr_window_band_mfma<%d, %s, %d>", o.mfma_tiles(), window_wide(b->g->rows, b->g->stride) ? "true" : "false", o.sign);
     } else if (o.kind == ScoreOrigin::MASKED && o.sign != 0) { // (muse_batch_score_signed_in_lag_range: the signed builds)
         const char *neg = o.sign < 0 ? "true" : "false";
         if (b->n == 4096)

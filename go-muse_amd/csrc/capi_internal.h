@@ -265,10 +265,14 @@ struct muse_spectrum {
 inline int window_lneg(int L, int n) { return 2 * L == n ? L - 1 : L; }
 // A window of lags as every pass takes it at FFT length n: lags -lneg .. hi (hi <= n / 2, lneg <= n / 2 - 1), and `origin`, the lags
 // below zero at which the direct product's table starts (row v of it is lag v - origin).  A table is determined by (origin, rows).
+// A BAND (muse_batch_score_in_lag_band) is the same three numbers with lag 0 outside: lags lo .. hi with 0 < lo (lneg = -lo < 0) or
+// hi < 0, origin = lneg = -lo, so rows() is its W = hi - lo + 1 and it is never every lag; what differs per pass asks band()
 struct LagRange {
     int hi, lneg, origin;
     int rows() const { return origin + hi + 1; }
     bool every_lag(int64_t n) const { return 2 * (int64_t)hi == n && lneg == n / 2 - 1; }
+    bool band() const { return hi < 0 || lneg < 0; }
+    int lo() const { return -lneg; }
 };
 // the window +-L (muse_batch_set_lag_window, muse_batch_score_in_window): the table starts L lags below zero, at L == n / 2 too
 // (where lag -n/2 is lag +n/2 and row 0 is not scanned)
@@ -285,6 +289,16 @@ inline LagRange clip_lag_range(int64_t n, int32_t lag_lo, int32_t lag_hi)
         return lag_window_range(n, lag_hi);
     const int lneg = (int)std::min<int64_t>(-(int64_t)lag_lo, n / 2 - 1);
     return LagRange{(int)std::min<int64_t>(lag_hi, n / 2), lneg, lneg};
+}
+
+// the band lag_lo .. lag_hi (lag_lo <= lag_hi, lag 0 outside) clipped to -(n / 2 - 1) .. n / 2; false: nothing of it is left
+inline bool clip_lag_band(int64_t n, int32_t lag_lo, int32_t lag_hi, LagRange *w)
+{
+    const int64_t hi = std::min<int64_t>(lag_hi, n / 2), lo = std::max<int64_t>(lag_lo, -(n / 2 - 1));
+    if (lo > hi)
+        return false;
+    *w = LagRange{(int)hi, (int)-lo, (int)-lo};
+    return true;
 }
 
 // Which pass filled a batch's mv / lag.  The in-window kinds carry the MUSE_IN_WINDOW_* value (muse_hip_test.h) they report.
@@ -506,7 +520,8 @@ int spectrum_cache_policy(int64_t rows, int32_t N, bool f32, int mode, int64_t m
 void group_drop_spectrum_cache(muse_group *g);             // capi_batch.hip: frees the segments (ready_mu held, compute stream idle)
 // capi_window.hip, what every caller of the lag-window kernels shares.  check_window_request: the refusals of a window of max_lag >= 0
 // over b's reference (f32: the rows are float32 storage); window_tables: the shifted-reference image and its window sums of b for
-// the window w in e / pw, once per (origin, rows) (cached under *key: -1 = none, both at most 127; the caller drops it when the
+// the window w in e / pw, once per (origin, rows) (cached under *key: -1 = none, both at most 127; a band's key carries bit 29 and its origin offset by 32768, so no
+// two tables share a key; the caller drops it when the
 // reference changes); window_params: the kernels' arguments for b's group and scores with those tables
 int check_window_request(const muse_batch *b, int32_t max_lag, bool f32);
 int window_tables(muse_batch *b, const LagRange &w, PoolBuf<double> &e, PoolBuf<double> &pw, int32_t *key, hipStream_t st);
@@ -525,10 +540,17 @@ int signed_window_plan(int32_t N, bool f32, const LagRange &w, int sign, bool fo
 // unchanged); score_in_window plans, runs and names the pass
 int plan_in_window(muse_batch *b, const LagRange &w, ScorePass *pass, int sign = 0);
 int score_in_window(muse_batch *b, const LagRange &w, int sign = 0);
-// the masked argmax of the transform kernels (their WIN builds): cc indices 0 .. hi and n - lneg .. n - 1 in the kernel's arguments
+// the masked argmax of the transform kernels (their WIN builds): cc indices 0 .. hi and n - lneg .. n - 1 in the kernel's arguments;
+// a band: the one interval lo .. hi, or n + lo .. n + hi below zero (their BAND builds; p.n is set)
 inline void set_window(muse::FusedParams &p, const LagRange &w)
 {
     p.win = 1;
+    if (w.band()) {
+        p.win_band = 1;
+        p.win_a = w.hi < 0 ? p.n + w.lo() : w.lo();
+        p.win_b = w.hi < 0 ? p.n + w.hi : w.hi;
+        return;
+    }
     p.win_lpos = w.hi;
     p.win_lneg = w.lneg;
 }

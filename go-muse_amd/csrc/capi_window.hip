@@ -1,7 +1,8 @@
 // capi_window.hip -- the lag window of a batch (muse_batch_set_lag_window): the setting, its tables, the windowed all-scores pass,
 // that pass fused with the slide of the group's rows (muse_batch_slide_score_windowed / _slide_run_windowed), and the window of any
 // width as an argument (muse_batch_score_in_window / _run_in_window: the direct product or the masked transform kernels), one-sided
-// and asymmetric too (muse_batch_score_in_lag_range / _run_in_lag_range)
+// and asymmetric too (muse_batch_score_in_lag_range / _run_in_lag_range), and lag bands that need not hold lag 0
+// (muse_batch_score_in_lag_band / _run_in_lag_band)
 // Part of the implementation of the C ABI declared in include/muse_hip.h (capi_internal.h: the handles and the helpers the
 // parts share).  Host-side orchestration only; there is no CPU compute fallback anywhere: without a gfx950 device every
 // compute entry point returns MUSE_ERR_NO_DEVICE.
@@ -57,14 +58,18 @@ extern "C" int muse_batch_lag_window(muse_batch *b, int32_t *max_lag)
 
 int window_tables(muse_batch *b, const LagRange &w, PoolBuf<double> &e, PoolBuf<double> &pw, int32_t *key, hipStream_t st)
 {
-    const int32_t k = w.origin * 256 + w.rows();
+    // (a band's origin is -lo, anywhere in -32768 .. 32767: its keys have a bit of their own, 29, as the panel tables' have bit 30)
+    const int32_t k = w.band() ? (1 << 29) | ((w.origin + 32768) * 256 + w.rows()) : w.origin * 256 + w.rows();
     if (*key == k)
         return MUSE_OK;
     *key = -1;
     const long long e_len = window_e_len(b->N);
     HIP_TRY(e.ensure(b->ctx, e_len, st));
     HIP_TRY(pw.ensure(b->ctx, 2 * MUSE_LAG_WINDOW_MAX + 1, st));
-    HIP_TRY(launch_window_tables(b->xs, b->N, b->n, w.origin, w.rows(), e.p, e_len, pw.p, st));
+    if (w.band())
+        HIP_TRY(launch_window_tables_band(b->xs, b->N, b->n, w.lo(), w.rows(), e.p, e_len, pw.p, st));
+    else
+        HIP_TRY(launch_window_tables(b->xs, b->N, b->n, w.origin, w.rows(), e.p, e_len, pw.p, st));
     *key = k;
     return MUSE_OK;
 }
@@ -98,7 +103,10 @@ int score_direct(muse_batch *b, const LagRange &w, bool bracket, int sign)
     LaunchTimer timer(b->ctx, false, st);
     if (bracket)
         HIP_TRY(timer.begin());
-    HIP_TRY(launch_window_signed(window_params(b, w, b->win_e.p, b->win_pw.p), sign, st)); // (sign 0: launch_window)
+    if (w.band())
+        HIP_TRY(launch_window_band(window_params(b, w, b->win_e.p, b->win_pw.p), sign, st));
+    else
+        HIP_TRY(launch_window_signed(window_params(b, w, b->win_e.p, b->win_pw.p), sign, st)); // (sign 0: launch_window)
     HIP_TRY(timer.end());
     return MUSE_OK;
 }
@@ -261,7 +269,7 @@ static int fail_not_built(const muse_batch *b, const LagRange &w)
 {
     return fail(MUSE_ERR_UNSUPPORTED, "the lags %d .. %d over series of %d samples%s are not built: more than %d table rows and float32 "
                 "storage take the masked argmax of the transform kernels of FFT lengths 512 ... 4096",
-                -w.lneg, w.hi, b->N, b->g->f32 ? " in float32 storage" : "", 2 * MUSE_LAG_WINDOW_MAX + 1);
+                w.lo(), w.hi, b->N, b->g->f32 ? " in float32 storage" : "", 2 * MUSE_LAG_WINDOW_MAX + 1);
 }
 
 int plan_in_window(muse_batch *b, const LagRange &w, ScorePass *pass, int sign)
@@ -372,6 +380,71 @@ extern "C" int muse_batch_run_signed_in_lag_range(muse_batch *b, const int32_t *
     if (!rc)
         rc = muse_batch_score_signed_in_lag_range(b, lag_lo, lag_hi, sign_filter);
     return rc ? rc : run_scored(b, group_id, G, range_max_lag(lag_lo, lag_hi), top_n, threshold, sign_filter, abs_scores, out_series, out_lag, out_score, out_count, out_mean_abs);
+}
+
+// ---- lag bands: the best match inside lags lag_lo .. lag_hi that need not hold lag 0 (muse_batch_score_in_lag_band).  A band that
+// holds lag 0 IS the signed range call; one that does not is a LagRange with lag 0 outside (capi_internal.h: band()), which
+// window_plan / signed_window_plan dispatch by its rows as they are -- never every lag -- and score_direct / batch_score send to the
+// band builds of the kernels (xcorr_window_band_mfma; the BAND builds of the masked transform kernels)
+static int check_band_args(int32_t lag_lo, int32_t lag_hi, int32_t sign)
+{
+    if (sign != MUSE_SIGN_ANY && sign != MUSE_SIGN_POS && sign != MUSE_SIGN_NEG)
+        return fail(MUSE_ERR_INVALID, "sign %d: one of MUSE_SIGN_ANY (0), MUSE_SIGN_POS (1), MUSE_SIGN_NEG (-1)", sign);
+    if (lag_lo > lag_hi)
+        return fail(MUSE_ERR_INVALID, "the lag band %d .. %d is empty (lag_lo <= lag_hi)", lag_lo, lag_hi);
+    return MUSE_OK;
+}
+
+static int fail_empty_band(int32_t lag_lo, int32_t lag_hi, int64_t n)
+{
+    return fail(MUSE_ERR_INVALID, "nothing of the lag band %d .. %d is left inside the lags %lld .. %lld of FFT length %lld", lag_lo, lag_hi,
+                -(long long)(n / 2 - 1), (long long)(n / 2), (long long)n);
+}
+
+extern "C" int muse_test_lag_band_plan(int32_t N, int32_t f32, int32_t lag_lo, int32_t lag_hi, int32_t sign, int32_t *path)
+{
+    if (!path || N < 2)
+        return fail(MUSE_ERR_INVALID, "bad lag-band plan arguments (N >= 2, a path to fill)");
+    const int rc = check_band_args(lag_lo, lag_hi, sign);
+    if (rc)
+        return rc;
+    if (lag_lo <= 0 && lag_hi >= 0)
+        return muse_test_signed_lag_range_plan(N, f32, lag_lo, lag_hi, sign, path);
+    const int64_t n = muse_next_pow2((double)N);
+    LagRange w;
+    if (!clip_lag_band(n, lag_lo, lag_hi, &w))
+        return fail_empty_band(lag_lo, lag_hi, n);
+    *path = signed_window_plan(N, f32 != 0, w, sign, false);
+    return MUSE_OK;
+}
+
+extern "C" int muse_batch_score_in_lag_band(muse_batch *b, int32_t lag_lo, int32_t lag_hi, int32_t sign)
+{
+    // everything is checked before anything is enqueued: on a refusal the batch is unchanged
+    if (!b)
+        return fail(MUSE_ERR_INVALID, "NULL batch");
+    int rc = check_band_args(lag_lo, lag_hi, sign);
+    if (rc)
+        return rc;
+    if (lag_lo <= 0 && lag_hi >= 0) // (clipping moves neither bound across lag 0)
+        return muse_batch_score_signed_in_lag_range(b, lag_lo, lag_hi, sign);
+    LagRange w;
+    if (!clip_lag_band(b->n, lag_lo, lag_hi, &w))
+        return fail_empty_band(lag_lo, lag_hi, b->n);
+    rc = check_own_window(b, lag_lo, lag_hi); // (no band is a symmetric window: any window of the batch's own refuses it)
+    return rc ? rc : score_in_window(b, w, sign);
+}
+
+extern "C" int muse_batch_run_in_lag_band(muse_batch *b, const int32_t *group_id, int32_t G, int32_t lag_lo, int32_t lag_hi,
+                                          int32_t top_n, double threshold, int32_t sign_filter, int32_t abs_scores, int64_t *out_series,
+                                          int32_t *out_lag, double *out_score, int32_t *out_count, double *out_mean_abs)
+{
+    // (the selection's own argument checks come first, as in muse_batch_run_signed_in_lag_range: they refuse a sign_filter outside -1 .. 1)
+    int rc = check_select_args(group_id, G, sign_filter);
+    if (!rc)
+        rc = muse_batch_score_in_lag_band(b, lag_lo, lag_hi, sign_filter);
+    const int32_t max_lag = (int32_t)std::min<int64_t>(std::max<int64_t>(std::llabs((long long)lag_lo), std::llabs((long long)lag_hi)), INT32_MAX);
+    return rc ? rc : run_scored(b, group_id, G, max_lag, top_n, threshold, sign_filter, abs_scores, out_series, out_lag, out_score, out_count, out_mean_abs);
 }
 
 // ---- the slide and the pass of any window in one call (muse_batch_slide_score_in_window)

@@ -271,7 +271,8 @@ struct NoTap {
 // out by the atomic counter (relative to tap.first); tap(v, rec, s1a, s1b, pair - tap.first, t) runs right behind the first
 // transform.  The flags are xcorr_fused_n4096_fold's (xcorr_r16_fold.hip).
 // SGN != 0 (WIN builds, named with Tap spelled out): the signed mask of r16_device.h (xcorr_fused_n4096_fold_signed).
-template <bool TIMING, bool PADDED, bool F32, bool WIN, bool SLIDE, typename Tap, int SGN = 0>
+// BAND (WIN builds, any SGN): the mask is the one index interval p.win_a .. p.win_b (xcorr_fused_n4096_fold_band).
+template <bool TIMING, bool PADDED, bool F32, bool WIN, bool SLIDE, typename Tap, int SGN = 0, bool BAND = false>
 __device__ __forceinline__ void pair_loop_from_rows(const FusedParams &p, const Tap tap)
 {
     __shared__ double2 xbuf[OCC_XBUF];
@@ -365,7 +366,7 @@ __device__ __forceinline__ void pair_loop_from_rows(const FusedParams &p, const 
         if (PADDED)
             correct_padded<8>(v, p.c1, t, rec[32] * invN, rec[33] * invN);
         if (WIN) // cc index t + 256 m3 at v[BR16(m3)]
-            mask_window<true, 256, SGN>(v, tl<PADDED>(t), p.win_lpos, 4096 - p.win_lneg);
+            mask_window<true, 256, SGN, BAND>(v, tl<PADDED>(t), BAND ? p.win_b : p.win_lpos, BAND ? p.win_a : 4096 - p.win_lneg);
         clk.template stamp<11>();
         // float32 rows take 34 registers instead of 66: room to request them BEFORE the argmax, which then runs under
         // the HBM latency (float64 rows: behind it, there is no register left to land them in)

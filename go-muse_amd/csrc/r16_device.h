@@ -107,11 +107,14 @@ __device__ __forceinline__ double2 ldg2u(gptr<double2> p, unsigned i)
 // window's condition, no register -- so that the unchanged maxAbsIndex behind it finds the largest positive / the most negative
 // value, the first index winning ties, and (index 0, +0.0) where there is none.  A NaN and a zero of either sign become +0.0.
 // Everything the kernels apply behind the mask is a positive factor (1 / sigma).
+// BAND (muse_batch_score_in_lag_band; a compile-time argument: false is the mask above, instruction for instruction): the window is ONE
+// index interval nl <= index <= lpos that does not hold index 0 (FusedParams::win_a / ::win_b) -- the same two registers and the same
+// two compares per register, and'ed instead of or'ed.  Index 0 is masked then, so "nothing left" is maxAbsIndex's (index 0, +0.0).
 template <int SGN> __device__ __forceinline__ bool mask_keeps(const bool in, const double x)
 {
     return SGN == 0 ? in : SGN > 0 ? (in && x > 0.0) : (in && x < 0.0);
 }
-template <bool BITREV, int STEP, int SGN = 0>
+template <bool BITREV, int STEP, int SGN = 0, bool BAND = false>
 __device__ __forceinline__ void mask_window(double2 (&v)[16], const int base, const int lpos, const int nl)
 {
     int a = lpos - base, b = nl - base;
@@ -119,7 +122,7 @@ __device__ __forceinline__ void mask_window(double2 (&v)[16], const int base, co
 #pragma unroll
     for (int m = 0; m < 16; m++) {
         const int k = BITREV ? ((m & 1) << 3) | ((m & 2) << 1) | ((m & 4) >> 1) | ((m & 8) >> 3) : m;
-        const bool in = STEP * m <= a || STEP * m >= b;
+        const bool in = BAND ? (STEP * m <= a && STEP * m >= b) : (STEP * m <= a || STEP * m >= b);
         v[k].x = mask_keeps<SGN>(in, v[k].x) ? v[k].x : 0.0;
         v[k].y = mask_keeps<SGN>(in, v[k].y) ? v[k].y : 0.0;
     }

@@ -174,12 +174,16 @@ struct WindowBest { // (pos as a double: the candidates lie in LDS as three doub
 // kernel takes), val (+1: the best positive value) or -val (-1: the best negative one).  A key is compared with strict '>' against
 // 0.0 first, so a value of the other sign, a zero and a NaN never win; the candidates' merge compares keys as they are.
 template <int SGN> __device__ __forceinline__ double window_key(const double val) { return SGN == 0 ? fabs(val) : SGN > 0 ? val : -val; }
-template <int SGN = 0>
+// BAND (muse_batch_score_in_lag_band; xcorr_window_band_mfma alone): the lags lo .. hi do not hold lag 0, origin = Lneg = -lo, L = hi
+// (one of L, Lneg is negative; W = L + 1 + Lneg as ever).  The scan runs over the cc indices of the band in ascending order, which is
+// the table's own: position pos is row pos, lag pos - origin -- no zig-zag -- and with nothing above 0.0 the outcome is (lag 0, +0.0)
+// for every SGN: index 0 is not in the band, so there is no row `origin` to read.
+template <int SGN = 0, bool BAND = false>
 __device__ __forceinline__ void window_scan_pos(WindowBest &best, const double *lds, const int row0, const int pos, const int c, const int L,
                                                 const int Lneg, const int origin, const WindowStats &st, const double *__restrict__ pw)
 {
     if (pos < L + 1 + Lneg) {
-        const int v = (pos <= L ? pos : pos - 1 - Lneg - L) + origin; // lag + origin
+        const int v = BAND ? pos : (pos <= L ? pos : pos - 1 - Lneg - L) + origin; // lag + origin
         const double val = window_score(lds, row0, v, c, st, pw);
         if (window_key<SGN>(val) > best.abs) {
             best.abs = window_key<SGN>(val);
@@ -196,7 +200,7 @@ __device__ __forceinline__ void window_put_best(double *cand, const WindowBest &
 }
 // parts slot0 .. slot0 + parts - 1 of series c merged in their order, and the outcome: the value, and through *lag its lag
 // (SGN != 0: no value of the sign in the window is (lag 0, +0.0), not cc[0], which would have the other sign)
-template <int SGN = 0>
+template <int SGN = 0, bool BAND = false>
 __device__ __forceinline__ double window_outcome(const double *lds, const int CAND, const int slot0, const int parts, const int row0,
                                                  const int c, const int L, const int Lneg, const int origin, const WindowStats &st,
                                                  const double *__restrict__ pw, int *lag)
@@ -218,14 +222,14 @@ __device__ __forceinline__ double window_outcome(const double *lds, const int CA
     if (st.zero)
         return 0.0; // sigma == 0: (nil, 0, 0), xcorr.go:165-168
     if (bp < 0) // only zeros or NaN in the window: index 0 stands
-        return SGN != 0 ? 0.0 : window_score(lds, row0, origin, c, st, pw);
-    *lag = bp <= L ? bp : bp - 1 - Lneg - L;
+        return SGN != 0 || BAND ? 0.0 : window_score(lds, row0, origin, c, st, pw);
+    *lag = BAND ? bp - origin : bp <= L ? bp : bp - 1 - Lneg - L;
     return bv;
 }
 
 // ---- the scan and the write-out of the single-reference kernels: the summed tiles in lds[0 .. TILES 256), (t1, t2) = series (t & 15)'s
 // sum d and sum d^2; 16 parts of TILES positions per series, candidates in lds[CAND ..).  Every thread of the workgroup calls it.
-template <int TILES, int SGN = 0>
+template <int TILES, int SGN = 0, bool BAND = false>
 __device__ __forceinline__ void window_scan_write(double *lds, const int CAND, const double t1, const double t2, const WindowParams &p,
                                                   const long long row0, const int t)
 {
@@ -234,26 +238,26 @@ __device__ __forceinline__ void window_scan_write(double *lds, const int CAND, c
     WindowBest best;
 #pragma unroll
     for (int k = 0; k < TILES; k++)
-        window_scan_pos<SGN>(best, lds, 0, part * TILES + k, c, p.L, p.Lneg, p.origin, st, p.pw);
+        window_scan_pos<SGN, BAND>(best, lds, 0, part * TILES + k, c, p.L, p.Lneg, p.origin, st, p.pw);
     window_put_best(lds + CAND + (part * 16 + c) * 3, best);
     __syncthreads();
     if (t < 16 && row0 + t < p.M) {
         int lag;
-        p.mv[row0 + t] = window_outcome<SGN>(lds, CAND, 0, 16, 0, c, p.L, p.Lneg, p.origin, st, p.pw, &lag);
+        p.mv[row0 + t] = window_outcome<SGN, BAND>(lds, CAND, 0, 16, 0, c, p.L, p.Lneg, p.origin, st, p.pw, &lag);
         p.lag[row0 + t] = lag;
     }
 }
 
 // acc: the wave's share of S (its pieces of every chunk); s1 / s2: the lane's share of sum d and sum d^2.  Every thread of the
 // workgroup calls it, behind its last piece; row0: the workgroup's first series
-template <int TILES, int SGN = 0>
+template <int TILES, int SGN = 0, bool BAND = false>
 __device__ __forceinline__ void window_finish(double *lds, const v4d (&acc)[TILES], const double s1, const double s2, const WindowParams &p,
                                               const long long row0, const int t, const int wave, const int r, const int q)
 {
     constexpr int STAT = WindowLds<TILES>::STAT;
     window_sum_tiles<TILES>(lds, STAT, acc, s1, s2, wave, r, q);
     const int c = t & 15;
-    window_scan_write<TILES, SGN>(lds, WindowLds<TILES>::CAND, window_wave_sum(lds, STAT, 2 * c), window_wave_sum(lds, STAT, 2 * c + 1), p, row0, t);
+    window_scan_write<TILES, SGN, BAND>(lds, WindowLds<TILES>::CAND, window_wave_sum(lds, STAT, 2 * c), window_wave_sum(lds, STAT, 2 * c + 1), p, row0, t);
 }
 
 // ---- the launch side: the checks every launch makes on a window's shape, and the tile count as a compile-time constant
@@ -261,6 +265,14 @@ inline hipError_t window_launch_check(const WindowShape &p, long long *blocks)
 {
     // rows origin - Lneg .. origin + L of the table: inside the eight tiles, pw and the staged image's tail (2 MUSE_LAG_WINDOW_MAX + 1 rows)
     if (p.L < 0 || p.Lneg < 0 || p.L + p.Lneg > 2 * MUSE_LAG_WINDOW_MAX || p.origin < p.Lneg || p.origin + p.L > 2 * MUSE_LAG_WINDOW_MAX || p.N < 2)
+        return hipErrorInvalidValue;
+    *blocks = (p.M + 15) / 16;
+    return *blocks > 0x7fffffffLL ? hipErrorInvalidValue : hipSuccess;
+}
+// the same for a band (WindowShape: origin = Lneg = -lo, L = hi, lag 0 outside): rows 0 .. W - 1 = L + Lneg of the table
+inline hipError_t window_launch_check_band(const WindowShape &p, long long *blocks)
+{
+    if ((p.L >= 0 && p.Lneg >= 0) || p.origin != p.Lneg || p.L + p.Lneg < 0 || p.L + p.Lneg > 2 * MUSE_LAG_WINDOW_MAX || p.N < 2)
         return hipErrorInvalidValue;
     *blocks = (p.M + 15) / 16;
     return *blocks > 0x7fffffffLL ? hipErrorInvalidValue : hipSuccess;

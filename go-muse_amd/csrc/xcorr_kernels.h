@@ -96,6 +96,11 @@ struct FusedParams {
     // xcorr_small.hip): win != 0 and win_sign = +1 / -1 -> a value inside the window that is not > 0 / < 0 becomes +0.0 as well.  Read
     // by the launchers alone (the sign is a template argument of those kernels); 0: the kernels above.  Behind everything else again.
     int win_sign;
+    // the band mask (muse_batch_score_in_lag_band; the BAND kernels of the same three files): win != 0 and win_band != 0 -> index i of cc
+    // takes part iff win_a <= i <= win_b, one interval on one side of lag 0 (1 <= win_a <= win_b <= n / 2, or n / 2 + 1 <= win_a <= win_b
+    // <= n - 1); win_lpos / win_lneg are not read, win_sign is as above and may be 0.  win_band is read by the launchers alone.  Behind
+    // everything else again.
+    int win_band, win_a, win_b;
 };
 inline FusedParams with_reciprocals(FusedParams p)
 {
@@ -103,10 +108,15 @@ inline FusedParams with_reciprocals(FusedParams p)
     p.invNm1 = 1.0 / (double)(p.N - 1);
     return p;
 }
+// the band mask's interval at FFT length n: on one side of lag 0, index 0 outside
+inline bool band_bounds_ok(const FusedParams &p, int n)
+{
+    return p.win && p.win_a >= 1 && p.win_a <= p.win_b && p.win_b <= n - 1 && (p.win_b <= n / 2 || p.win_a > n / 2);
+}
 // the masked argmax's window as the n = 4096 launchers accept it (no window: nothing to check)
 inline bool window_bounds_ok(const FusedParams &p)
 {
-    return !p.win || (p.win_lpos >= 0 && p.win_lneg >= 0 && p.win_lpos <= 2048 && p.win_lneg <= 2047);
+    return (!p.win || (p.win_lpos >= 0 && p.win_lneg >= 0 && p.win_lpos <= 2048 && p.win_lneg <= 2047)) && (!p.win_band || band_bounds_ok(p, 4096));
 }
 // run-time booleans -> template arguments: with_bools(f, b0, b1, ...) calls f(std::bool_constant<b0>{}, std::bool_constant<b1>{}, ...),
 // so a launcher names its kernel once, with decltype(flag)::value for each flag, and every combination is instantiated
@@ -114,6 +124,17 @@ template <typename F>
 inline void with_bools(F f)
 {
     f();
+}
+// the same for a sign of -1 .. 1: f(std::integral_constant<int, sign>{})
+template <typename F>
+inline void with_sign(int sign, F f)
+{
+    if (sign > 0)
+        f(std::integral_constant<int, 1>{});
+    else if (sign < 0)
+        f(std::integral_constant<int, -1>{});
+    else
+        f(std::integral_constant<int, 0>{});
 }
 template <typename F, typename... Rest>
 inline void with_bools(F f, bool b, Rest... rest)
@@ -191,7 +212,8 @@ struct WindowShape {    // what every lag-window kernel takes: the rows and the 
     int L, Lneg;        // lags -Lneg .. L (a symmetric window: Lneg = L, or L - 1 when L == n / 2: index n / 2 is lag +n/2 only)
     double invN, invNm1;
     int origin;         // row v of the product table is lag v - origin, Lneg <= origin: L for a symmetric window (rows L - Lneg .. 2 L),
-                        // Lneg for a lag range (muse_batch_score_in_lag_range: rows 0 .. L + Lneg).  Last: the offsets above are what they were
+                        // Lneg for a lag range (muse_batch_score_in_lag_range: rows 0 .. L + Lneg).  Last: the offsets above are what they were.
+                        // A band (launch_window_band alone): lags lo .. hi without lag 0 as L = hi, Lneg = origin = -lo, one of them negative
 };
 struct WindowParams : WindowShape {
     const double *e;    // [window_e_len(N)] e[v] = xs[(n - N + v - origin) mod n], zero from N + origin + L on
@@ -207,6 +229,13 @@ hipError_t launch_window(const WindowParams &p, hipStream_t stream);
 // the signed best match (muse_batch_score_signed_in_lag_range): sign = +1 / -1 the largest positive / the most negative value inside
 // the window, (lag 0, +0.0) where there is none (xcorr_window_signed_mfma); sign = 0 is launch_window
 hipError_t launch_window_signed(const WindowParams &p, int sign, hipStream_t stream);
+// ---- the same over a lag band lo .. hi that does not hold lag 0 (xcorr_window_band.hip; muse_batch_score_in_lag_band): a table whose
+// row v is lag lo + v, W = hi - lo + 1 <= 2 MUSE_LAG_WINDOW_MAX + 1 rows (launch_window_tables_band: -(n / 2 - 1) <= lo, hi <= n / 2),
+// and the shape L = hi, Lneg = origin = -lo (one of L, Lneg negative).  sign = 0 / +1 / -1: the best by magnitude / the largest positive
+// / the most negative value of the band, (lag 0, +0.0) where nothing wins (xcorr_window_band_mfma)
+hipError_t launch_window_tables_at(const double *xs, int N, int n, int origin, int W, double *e, long long e_len, double *pw, hipStream_t stream);
+hipError_t launch_window_tables_band(const double *xs, int N, int n, int lo, int W, double *e, long long e_len, double *pw, hipStream_t stream);
+hipError_t launch_window_band(const WindowParams &p, int sign, hipStream_t stream);
 // ---- the same while the rows slide (xcorr_window_slide.hip; muse_batch_slide_score_windowed): xcorr_window_mfma over the NEW rows
 // -- old row[k .. N) followed by tails[r * k + 0 .. k), a dense M x k device buffer, 16-byte aligned -- which are stored in place on
 // the way: one read and one write of the rows instead of launch_row_slide's pair plus launch_window's read, the same bits as the two.

@@ -63,6 +63,13 @@ __global__ __launch_bounds__(OCC_THREADS, 4) void xcorr_fused_n4096_fold_signed(
 {
     foldk::pair_loop_from_rows<false, PADDED, F32, true, false, foldk::NoTap, NEG ? -1 : 1>(p, foldk::NoTap{});
 }
+// The WIN build with the band mask (muse_batch_score_in_lag_band; FusedParams::win_band): the argmax over the one index interval
+// p.win_a .. p.win_b, by magnitude (SGN = 0) or over the values of one sign (+-1).  A kernel of its own again.
+template <bool PADDED, bool F32, int SGN>
+__global__ __launch_bounds__(OCC_THREADS, 4) void xcorr_fused_n4096_fold_band(const FusedParams p)
+{
+    foldk::pair_loop_from_rows<false, PADDED, F32, true, false, foldk::NoTap, SGN, true>(p, foldk::NoTap{});
+}
 
 // ============================================================================
 // Many references against one resident group in ONE pass over the rows
@@ -347,7 +354,7 @@ hipError_t launch_fused_multi(const FusedParams &p_in, int num_cus, hipStream_t 
     if (!p.work_counter || p.R < 1 || !p.g2 || !p.g3a || !p.g3b || !p.xcp_many || !p.mv_many || !p.lag_many)
         return hipErrorInvalidValue;
     const dim3 g((unsigned)grid), b(OCC_THREADS);
-    if ((p.N < 4096 && !p.c1_many) || !window_bounds_ok(p) || p.win_sign) // (one window for every reference: muse_batch_score_many_in_window; no signed build)
+    if ((p.N < 4096 && !p.c1_many) || !window_bounds_ok(p) || p.win_sign || p.win_band) // (one window for every reference: muse_batch_score_many_in_window; no signed build, no band build)
         return hipErrorInvalidValue;
     with_bools([&](auto padded, auto f32, auto win) {
         hipLaunchKernelGGL((xcorr_fused_n4096_fold_multi<decltype(padded)::value, decltype(f32)::value, decltype(win)::value>), g, b, 0, stream, p);
@@ -374,6 +381,16 @@ hipError_t launch_fused_fold(const FusedParams &p_in, int num_cus, hipStream_t s
     if (p.slide_tails && (p.slide_k < 1 || p.slide_k > p.N || p.N <= 2048 || p.N > 4096 || p.stride < p.N || p.pair_list || p.npairs != (p.M + 1) / 2 ||
                           (p.N == 4096 && !p.rows32 && !window_wide(p.rows, p.stride))))
         return hipErrorInvalidValue;
+    if (p.win_band) { // the band mask: a window, a sign of -1 .. 1, no slide
+        if (!p.win || p.win_sign < -1 || p.win_sign > 1 || p.slide_tails)
+            return hipErrorInvalidValue;
+        with_bools([&](auto padded, auto f32) {
+            with_sign(p.win_sign, [&](auto sgn) {
+                hipLaunchKernelGGL((xcorr_fused_n4096_fold_band<decltype(padded)::value, decltype(f32)::value, decltype(sgn)::value>), g, b, 0, stream, p);
+            });
+        }, p.N < 4096, p.rows32 != nullptr);
+        return hipGetLastError();
+    }
     if (p.win_sign) { // the signed masked argmax: a window, a sign of +-1, no slide
         if (!p.win || (p.win_sign != 1 && p.win_sign != -1) || p.slide_tails)
             return hipErrorInvalidValue;

@@ -143,7 +143,9 @@ __device__ __forceinline__ void finalize(const double *r, const Stat &st, double
 // SGN != 0 (WIN builds): the signed mask (muse_batch_score_signed_in_lag_range; xcorr_fused_n4096_occ4_signed below).  The body of
 // both kernels: inlined into each, so that xcorr_fused_n4096_occ4 keeps its symbols and its code (the arguments by value, as the
 // kernel takes them: by reference two of its builds' scalar spill counts moved; profiles/signed_lag_range_resources.txt).
-template <bool PADDED, bool TIMING, bool F32, bool WIN, int SGN>
+// BAND (WIN builds, any SGN): the mask is the one index interval p.win_a .. p.win_b (muse_batch_score_in_lag_band;
+// xcorr_fused_n4096_occ4_band below).
+template <bool PADDED, bool TIMING, bool F32, bool WIN, int SGN, bool BAND = false>
 __device__ __forceinline__ void occ4_body(const FusedParams p)
 {
     using namespace occ4;
@@ -301,7 +303,7 @@ __device__ __forceinline__ void occ4_body(const FusedParams p)
         // its sign come from ballots (scalar unit).  Lowest k first, then lowest lane
         // == lowest index, because t < 256.
         if (WIN)
-            mask_window<false, 256, SGN>(v, t, p.win_lpos, 4096 - p.win_lneg);
+            mask_window<false, 256, SGN, BAND>(v, t, BAND ? p.win_b : p.win_lpos, BAND ? p.win_a : 4096 - p.win_lneg);
         double ma = 0.0, mb = 0.0;
 #pragma unroll
         for (int k = 0; k < 16; k++) {
@@ -380,6 +382,12 @@ __global__ __launch_bounds__(OCC_THREADS, 3) void xcorr_fused_n4096_occ4_signed(
 {
     occ4_body<PADDED, false, F32, true, NEG ? -1 : 1>(p);
 }
+// the WIN build with the band mask (FusedParams::win_band): the pairs xcorr_fused_n4096_fold_band hands over, and whole groups
+template <bool PADDED, bool F32, int SGN>
+__global__ __launch_bounds__(OCC_THREADS, 3) void xcorr_fused_n4096_occ4_band(const FusedParams p)
+{
+    occ4_body<PADDED, false, F32, true, SGN, true>(p);
+}
 
 hipError_t launch_fused_occ4(const FusedParams &p_in, int num_cus, hipStream_t stream)
 {
@@ -395,6 +403,16 @@ hipError_t launch_fused_occ4(const FusedParams &p_in, int num_cus, hipStream_t s
     const dim3 g((unsigned)grid), b(OCC_THREADS);
     if (!window_bounds_ok(p)) // (the masked argmax: muse_batch_score_in_window)
         return hipErrorInvalidValue;
+    if (p.win_band) { // the band mask: a window and a sign of -1 .. 1
+        if (!p.win || p.win_sign < -1 || p.win_sign > 1)
+            return hipErrorInvalidValue;
+        with_bools([&](auto padded, auto f32) {
+            with_sign(p.win_sign, [&](auto sgn) {
+                hipLaunchKernelGGL((xcorr_fused_n4096_occ4_band<decltype(padded)::value, decltype(f32)::value, decltype(sgn)::value>), g, b, 0, stream, p);
+            });
+        }, p.N < 4096, p.rows32 != nullptr);
+        return hipGetLastError();
+    }
     if (p.win_sign) { // the signed masked argmax: a window and a sign of +-1
         if (!p.win || (p.win_sign != 1 && p.win_sign != -1))
             return hipErrorInvalidValue;

@@ -61,6 +61,7 @@ template <int LOGN, bool PADDED, bool MULTI, bool F32 = false, bool WIN = false>
 __global__ __launch_bounds__((LOGN >= 11 ? (1 << LOGN) / 16 : 256), ((MULTI && LOGN <= 13) ? 2 : 4)) void xcorr_fused_small(const FusedParams p)
 {
     constexpr int SGN = 0;
+    constexpr bool BAND = false;
 #include "xcorr_small_body.h"
 }
 // the WIN build with the signed mask (FusedParams::win_sign), one reference: NEG false / true = the largest positive / the most
@@ -70,6 +71,15 @@ __global__ __launch_bounds__((LOGN >= 11 ? (1 << LOGN) / 16 : 256), 4) void xcor
 {
     constexpr bool MULTI = false, WIN = true;
     constexpr int SGN = NEG ? -1 : 1;
+    constexpr bool BAND = false;
+#include "xcorr_small_body.h"
+}
+// the WIN build with the band mask (muse_batch_score_in_lag_band; FusedParams::win_band), one reference: the argmax over the one index
+// interval p.win_a .. p.win_b, by magnitude (SGN = 0) or over the values of one sign (+-1)
+template <int LOGN, bool PADDED, bool F32, int SGN>
+__global__ __launch_bounds__((LOGN >= 11 ? (1 << LOGN) / 16 : 256), 4) void xcorr_fused_small_band(const FusedParams p)
+{
+    constexpr bool MULTI = false, WIN = true, BAND = true;
 #include "xcorr_small_body.h"
 }
 
@@ -264,6 +274,8 @@ static hipError_t launch_small_n(const FusedParams &p, int num_cus, hipStream_t 
         return hipErrorInvalidValue; // (the masked argmax is built for n = 512, 1024, 2048)
     if (p.win_sign && (p.R > 1 || !p.win || (p.win_sign != 1 && p.win_sign != -1)))
         return hipErrorInvalidValue; // (the signed mask: one reference, a window, a sign of +-1)
+    if (p.win_band && (p.R > 1 || !p.win || LOGN > 11 || !band_bounds_ok(p, 1 << LOGN)))
+        return hipErrorInvalidValue; // (the band mask: one reference, a window, one index interval on one side of lag 0)
     if (p.R > 1) { // one pass for R references: exactly the resident workgroups (n = 16384: each with its slice of the spectrum scratch)
         constexpr bool ZREG = LOGN <= 13;
         if (!p.xcp_many || !p.mv_many || !p.lag_many || (!ZREG && !p.zscratch))
@@ -293,6 +305,15 @@ static hipError_t launch_small_n(const FusedParams &p, int num_cus, hipStream_t 
         if constexpr (LOGN <= 11) {
             if (p.pair_list || p.win_lpos < 0 || p.win_lneg < 0 || p.win_lpos > (1 << LOGN) / 2 || p.win_lneg > (1 << LOGN) / 2 - 1)
                 return hipErrorInvalidValue;
+            if (p.win_band) { // (muse_batch_score_in_lag_band)
+                with_bools([&](auto padded, auto f32) {
+                    with_sign(p.win_sign, [&](auto sgn) {
+                        hipLaunchKernelGGL((xcorr_fused_small_band<LOGN, decltype(padded)::value, decltype(f32)::value, decltype(sgn)::value>),
+                                           dim3((unsigned)grid), dim3(TPB), 0, stream, p);
+                    });
+                }, p.N < (1 << LOGN), p.rows32 != nullptr);
+                return hipGetLastError();
+            }
             if (p.win_sign) { // (muse_batch_score_signed_in_lag_range)
                 with_bools([&](auto padded, auto f32, auto neg) {
                     hipLaunchKernelGGL((xcorr_fused_small_signed<LOGN, decltype(padded)::value, decltype(f32)::value, decltype(neg)::value>),

@@ -1,8 +1,8 @@
-// xcorr_small_body.h -- the body of xcorr_fused_small and of xcorr_fused_small_signed (xcorr_small.hip), included inside each kernel's
-// braces: no include guard, nothing but statements.  The including kernel provides p (const FusedParams) and the compile-time
-// constants LOGN, PADDED, MULTI, F32, WIN (the flags xcorr_small.hip describes) and SGN (0: the argmax by magnitude; +-1 with WIN: the
-// signed mask, r16_device.h).  Kept as text so that the two kernels are one source under two names and xcorr_fused_small compiles to
-// the code it had as a kernel with the body written out.
+// xcorr_small_body.h -- the body of xcorr_fused_small, xcorr_fused_small_signed and xcorr_fused_small_band (xcorr_small.hip), included
+// inside each kernel's braces: no include guard, nothing but statements.  The including kernel provides p (const FusedParams) and the
+// compile-time constants LOGN, PADDED, MULTI, F32, WIN (the flags xcorr_small.hip describes), SGN (0: the argmax by magnitude; +-1 with
+// WIN: the signed mask, r16_device.h) and BAND (with WIN: the mask is the one index interval p.win_a .. p.win_b).  Kept as text so that
+// the kernels are one source under three names and xcorr_fused_small compiles to the code it had as a kernel with the body written out.
     using namespace occ4;
     using namespace fold;
     using namespace small;
@@ -268,7 +268,7 @@
             int jw = j;
             asm volatile("" : "+v"(jw)); // (derived here, not hoisted)
             jw &= S - 1;
-            mask_window<true, S, SGN>(v, jw, p.win_lpos, n - p.win_lneg);
+            mask_window<true, S, SGN, BAND>(v, jw, BAND ? p.win_b : p.win_lpos, BAND ? p.win_a : n - p.win_lneg);
         }
         // ---- maxAbsIndex (xcorr.go:39-50) per series: ascending r = ascending index for this thread
         double sa = 0.0, sb = 0.0; // signed value of the lane's first maximum of |cc|, and its register index

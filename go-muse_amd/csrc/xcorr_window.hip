@@ -59,13 +59,22 @@ __global__ __launch_bounds__(256) void window_table_p(const double *__restrict__
         pw[v] = part[0];
 }
 
-hipError_t launch_window_tables(const double *xs, int N, int n, int origin, int W, double *e, long long e_len, double *pw, hipStream_t stream)
+// the two launches for a table of 1 <= W <= 2 MUSE_LAG_WINDOW_MAX + 1 rows at ANY integer origin (window_table_e takes the index mod n):
+// the callers below and launch_window_tables_band (xcorr_window_band.hip: a negative origin or one beyond the rows) check theirs
+hipError_t launch_window_tables_at(const double *xs, int N, int n, int origin, int W, double *e, long long e_len, double *pw, hipStream_t stream)
 {
-    if (origin < 0 || W < origin + 1 || W > 2 * MUSE_LAG_WINDOW_MAX + 1) // (pw holds 2 MUSE_LAG_WINDOW_MAX + 1 sums, a chunk's image WIN_E_TAIL more samples)
+    if (W < 1 || W > 2 * MUSE_LAG_WINDOW_MAX + 1) // (pw holds 2 MUSE_LAG_WINDOW_MAX + 1 sums, a chunk's image WIN_E_TAIL more samples)
         return hipErrorInvalidValue;
     window_table_e<<<dim3((unsigned)((e_len + 255) / 256)), dim3(256), 0, stream>>>(xs, N, n, origin, W, e_len, e);
     window_table_p<<<dim3((unsigned)W), dim3(256), 0, stream>>>(e, N, pw);
     return hipGetLastError();
+}
+
+hipError_t launch_window_tables(const double *xs, int N, int n, int origin, int W, double *e, long long e_len, double *pw, hipStream_t stream)
+{
+    if (origin < 0 || W < origin + 1) // (a table that holds lag 0: a band's is launch_window_tables_band's)
+        return hipErrorInvalidValue;
+    return launch_window_tables_at(xs, N, n, origin, W, e, e_len, pw, stream);
 }
 
 template <int TILES, bool WIDE>

@@ -540,7 +540,7 @@ func (b *Batch) RunInWindow(groupByLabels []string) error {
 	if es := shardEngines(); es != nil {
 		return fmt.Errorf("RunInWindow runs on one device")
 	}
-	return b.feedInWindow(groupByLabels, false, 0, 0, false)
+	return b.feedInWindow(groupByLabels, false, 0, 0, false, false)
 }
 
 // RunInLagRange is RunInWindow for a one-sided or asymmetric window (muse_batch_run_in_lag_range): every series contributes its
@@ -553,7 +553,7 @@ func (b *Batch) RunInLagRange(groupByLabels []string, lagLo, lagHi int) error {
 	if es := shardEngines(); es != nil {
 		return fmt.Errorf("RunInLagRange runs on one device")
 	}
-	return b.feedInWindow(groupByLabels, true, lagLo, lagHi, false)
+	return b.feedInWindow(groupByLabels, true, lagLo, lagHi, false, false)
 }
 
 // RunSignedInLagRange is RunInLagRange with Results.SignFilter restricting the ARGMAX, not only filtering its answer
@@ -570,7 +570,34 @@ func (b *Batch) RunSignedInLagRange(groupByLabels []string, lagLo, lagHi int) er
 	if es := shardEngines(); es != nil {
 		return fmt.Errorf("RunSignedInLagRange runs on one device")
 	}
-	return b.feedInWindow(groupByLabels, true, lagLo, lagHi, true)
+	return b.feedInWindow(groupByLabels, true, lagLo, lagHi, true, false)
+}
+
+// RunInLagBand is RunInLagRange for a lag band that need not hold lag 0 (muse_batch_run_in_lag_band): every series contributes its best
+// match by magnitude inside the lags lagLo .. lagHi -- (1, k): the series that lead the reference by 1 .. k samples, where
+// RunInLagRange(0, k) reports lag 0 for every co-moving series.  A series with nothing in the band comes back as (0, +0.0).  One
+// device.  Results is fed as RunInLagRange feeds it; Results.Update applies the Results' own filters unchanged, its MaxLag included.
+func (b *Batch) RunInLagBand(groupByLabels []string, lagLo, lagHi int) error {
+	if lagLo > lagHi {
+		return fmt.Errorf("RunInLagBand: lagLo <= lagHi")
+	}
+	if es := shardEngines(); es != nil {
+		return fmt.Errorf("RunInLagBand runs on one device")
+	}
+	return b.feedInWindow(groupByLabels, true, lagLo, lagHi, false, true)
+}
+
+// RunSignedInLagBand is RunInLagBand with Results.SignFilter restricting the ARGMAX: under SignFilter_POS every series contributes its
+// largest positive value inside the band, under SignFilter_NEG its most negative one; SignFilter_ANY is RunInLagBand.  Fed as
+// RunSignedInLagRange feeds it: under a sign the Scores carry the signed value.
+func (b *Batch) RunSignedInLagBand(groupByLabels []string, lagLo, lagHi int) error {
+	if lagLo > lagHi {
+		return fmt.Errorf("RunSignedInLagBand: lagLo <= lagHi")
+	}
+	if es := shardEngines(); es != nil {
+		return fmt.Errorf("RunSignedInLagBand runs on one device")
+	}
+	return b.feedInWindow(groupByLabels, true, lagLo, lagHi, true, true)
 }
 
 // RunSigned is RunSignedInLagRange(-MaxLag, MaxLag): RunInWindow with Results.SignFilter restricting the argmax.
@@ -583,8 +610,9 @@ func (b *Batch) RunSigned(groupByLabels []string) error {
 
 // feedInWindow is what RunInWindow, RunInLagRange and RunSignedInLagRange share: the label groups, the resident rows, the call (ranged:
 // the lag range lagLo .. lagHi, otherwise the window Results.MaxLag; signed: the ranged call whose argmax takes Results.SignFilter) and
-// the feed of Results in group order.
-func (b *Batch) feedInWindow(groupByLabels []string, ranged bool, lagLo, lagHi int, signed bool) error {
+// the feed of Results in group order.  band: the lag band lagLo .. lagHi, which need not hold lag 0 (muse_batch_run_in_lag_band; signed as
+// above, unsigned: the device always gets SignFilter_ANY, because the call's sign is the argmax's too).
+func (b *Batch) feedInWindow(groupByLabels []string, ranged bool, lagLo, lagHi int, signed bool, band bool) error {
 	labelValuesSet := b.Comparison.indexLabelValues(groupByLabels)
 	if len(labelValuesSet) == 0 {
 		return nil
@@ -641,7 +669,14 @@ func (b *Batch) feedInWindow(groupByLabels []string, ranged bool, lagLo, lagHi i
 	var cnt C.int32_t
 	var mean C.double
 	var st C.int
-	if signed {
+	if band {
+		bandSign, absScores := 0, 1
+		if signed && int(r.SignFilter) != 0 { // (not SignFilter_ANY)
+			bandSign, absScores = int(r.SignFilter), 0
+		}
+		st = C.muse_batch_run_in_lag_band(b.batch, &gid[0], C.int32_t(G), C.int32_t(lagLo), C.int32_t(lagHi), C.int32_t(topN),
+			C.double(threshold), C.int32_t(bandSign), C.int32_t(absScores), &idx[0], &lag[0], &score[0], &cnt, &mean)
+	} else if signed {
 		absScores := 1
 		if int(r.SignFilter) != 0 { // (not SignFilter_ANY)
 			absScores = 0

@@ -1146,6 +1146,41 @@ public:
         });
     }
 
+    // RunInLagRange for a lag band that need not hold lag 0 (muse_batch_run_in_lag_band): every series contributes its best match by
+    // magnitude inside the lags lagLo .. lagHi -- (1, k): the series that lead the reference by 1 .. k samples, where
+    // RunInLagRange(0, k) reports lag 0 for every co-moving series.  A series with nothing in the band comes back as (0, +0.0).  One
+    // device.  Results is fed as RunInLagRange feeds it (the call's sign is the argmax's too, so the device always gets
+    // SignFilter_ANY here) and Results.Update applies the Results' own filters unchanged, its MaxLag included.
+    void RunInLagBand(const std::vector<std::string> &groupByLabels, int lagLo, int lagHi)
+    {
+        if (lagLo > lagHi)
+            throw Error(MUSE_ERR_INVALID, "RunInLagBand: lagLo <= lagHi");
+        if (!engines_.empty())
+            throw Error(MUSE_ERR_UNSUPPORTED, "RunInLagBand runs on one device");
+        feed_in_window(groupByLabels, [&](const int32_t *gid, int32_t G, int32_t top, double threshold, int32_t, int64_t *idx,
+                                          int32_t *lag, double *score, int32_t *cnt, double *mean) {
+            return muse_batch_run_in_lag_band(batch_, gid, G, (int32_t)lagLo, (int32_t)lagHi, top, threshold, 0, 1, idx, lag, score,
+                                              cnt, mean);
+        });
+    }
+
+    // RunInLagBand with Results.SignFilter restricting the ARGMAX (muse_batch_run_in_lag_band with the sign): under SignFilter_POS every
+    // series contributes its largest positive value inside the band, under SignFilter_NEG its most negative one; SignFilter_ANY is
+    // RunInLagBand.  Fed as RunSignedInLagRange feeds it: under a sign the Scores carry the signed value.
+    void RunSignedInLagBand(const std::vector<std::string> &groupByLabels, int lagLo, int lagHi)
+    {
+        if (lagLo > lagHi)
+            throw Error(MUSE_ERR_INVALID, "RunSignedInLagBand: lagLo <= lagHi");
+        if (!engines_.empty())
+            throw Error(MUSE_ERR_UNSUPPORTED, "RunSignedInLagBand runs on one device");
+        const int32_t filter = (int32_t)Results_->Filter;
+        feed_in_window(groupByLabels, [&](const int32_t *gid, int32_t G, int32_t top, double threshold, int32_t, int64_t *idx,
+                                          int32_t *lag, double *score, int32_t *cnt, double *mean) {
+            return muse_batch_run_in_lag_band(batch_, gid, G, (int32_t)lagLo, (int32_t)lagHi, top, threshold, filter, filter == 0 ? 1 : 0,
+                                              idx, lag, score, cnt, mean);
+        });
+    }
+
     // RunSignedInLagRange(-MaxLag, MaxLag): RunInWindow with Results.SignFilter restricting the argmax
     void RunSigned(const std::vector<std::string> &groupByLabels)
     {

@@ -521,9 +521,41 @@ class DeviceBatch:
         c = cnt.value
         return o_s[:c].copy(), o_l[:c].copy(), o_v[:c].copy(), float(mean.value)
 
+    def score_in_lag_band(self, lag_lo, lag_hi, sign=0):
+        """muse_batch_score_in_lag_band: every series' best match inside the lags lag_lo .. lag_hi, which need not hold lag 0 --
+        (1, k): "which series lead the reference by 1 .. k samples".  sign = 0 the best by magnitude, +1 the largest positive value,
+        -1 the most negative one; (lag 0, +0.0) where nothing in the band wins.  A band that holds lag 0 is
+        score_signed_in_lag_range, bit for bit.  Up to 127 lags on float64 groups: the direct product over a table of just those
+        lags, wherever the band lies; wider, or float32 storage: the transform kernels with the argmax masked to the one index
+        interval (FFT lengths 512 ... 4096).  Results: read_scores()."""
+        B.check(B.load().muse_batch_score_in_lag_band(self._h, int(lag_lo), int(lag_hi), int(sign)))
+
+    def scores_in_lag_band(self, lag_lo, lag_hi, sign=0):
+        """score_in_lag_band + copy back: (lag, mv)"""
+        self.score_in_lag_band(lag_lo, lag_hi, sign)
+        return self.read_scores()
+
+    def run_in_lag_band(self, lag_lo, lag_hi, group_id=None, G=0, top_n=20, threshold=0.0, sign_filter=0, abs_scores=True):
+        """muse_batch_run_in_lag_band: score_in_lag_band(lag_lo, lag_hi, sign_filter) followed by Batch.Run's selection with
+        Results.MaxLag = max(|lag_lo|, |lag_hi|) and Results.SignFilter = sign_filter; -> (series, lag, score, mean_abs) as run()"""
+        cap = max(int(top_n), 1)
+        o_s = np.zeros(cap, dtype=np.int64)
+        o_l = np.zeros(cap, dtype=np.int32)
+        o_v = np.zeros(cap)
+        cnt, mean = ctypes.c_int32(0), ctypes.c_double(0)
+        gid = None
+        if group_id is not None:
+            gid = np.ascontiguousarray(group_id, dtype=np.int32)
+        B.check(B.load().muse_batch_run_in_lag_band(
+            self._h, B.i32ptr(gid) if gid is not None else None, int(G), int(lag_lo), int(lag_hi), int(top_n), float(threshold),
+            int(sign_filter), 1 if abs_scores else 0, B.i64ptr(o_s), B.i32ptr(o_l), B.dptr(o_v), ctypes.byref(cnt),
+            ctypes.byref(mean)))
+        c = cnt.value
+        return o_s[:c].copy(), o_l[:c].copy(), o_v[:c].copy(), float(mean.value)
+
     def last_in_window_path(self):
-        """test hook: MUSE_IN_WINDOW_* of the last score_in_window / run_in_window / score_in_lag_range / run_in_lag_range or of
-        their signed forms, 0 after any other scoring pass"""
+        """test hook: MUSE_IN_WINDOW_* of the last score_in_window / run_in_window / score_in_lag_range / run_in_lag_range, of
+        their signed forms or of score_in_lag_band / run_in_lag_band, 0 after any other scoring pass"""
         w = ctypes.c_int32(0)
         B.check(B.load().muse_test_last_in_window_path(self._h, ctypes.byref(w)))
         return int(w.value)
@@ -1030,6 +1062,14 @@ def run_many_in_lag_range(batches, lag_lo, lag_hi, group_id=None, G=0, top_n=20,
     returns a list of (series, lag, score, mean_abs), one per batch"""
     return _run_many("muse_batch_run_many_in_lag_range", batches, group_id, G, (lag_lo, lag_hi), top_n, threshold, sign_filter,
                      abs_scores)
+
+
+def lag_band_plan(N, f32, lag_lo, lag_hi, sign=0):
+    """muse_test_lag_band_plan (no device): MUSE_IN_WINDOW_* -- the pass score_in_lag_band takes for series of N samples inside the
+    lags lag_lo .. lag_hi (a band that holds lag 0: signed_lag_range_plan)"""
+    path = ctypes.c_int32(0)
+    B.check(B.load().muse_test_lag_band_plan(int(N), 1 if f32 else 0, int(lag_lo), int(lag_hi), int(sign), ctypes.byref(path)))
+    return int(path.value)
 
 
 def signed_lag_range_plan(N, f32, lag_lo, lag_hi, sign):
@@ -1657,6 +1697,49 @@ class Batch:
             idx, lag, score, _ = self._batch().run_signed_in_lag_range(lagLo, lagHi, gid, G, G, 0.0, r.SignFilter, abs_scores=mag)
         else:
             idx, lag, score, _ = self._batch().run_signed_in_lag_range(lagLo, lagHi, gid, G, r.TopN, r.Threshold, r.SignFilter, abs_scores=mag)
+        order = np.argsort(gid[idx], kind="stable")
+        for k in order:
+            r.Update(Score(series[int(idx[k])].Labels(), int(lag[k]), float(score[k])))
+        return None
+
+    def RunInLagBand(self, groupByLabels, lagLo, lagHi):
+        """RunInLagRange for a lag band that need not hold lag 0 (muse_batch_run_in_lag_band): every series contributes its best
+        match by magnitude inside the lags lagLo .. lagHi -- (1, k): the series that lead the reference by 1 .. k samples, where
+        RunInLagRange(0, k) reports lag 0 for every co-moving series.  A series with nothing in the band comes back as (0, +0.0).
+        One device.  Results is fed exactly as RunInLagRange feeds it, and Results.Update applies the Results' own filters
+        unchanged (its MaxLag included: set it to max(|lagLo|, |lagHi|) or wider to keep every lag of the band)."""
+        return self._run_in_lag_band(groupByLabels, lagLo, lagHi, False, "RunInLagBand")
+
+    def RunSignedInLagBand(self, groupByLabels, lagLo, lagHi):
+        """RunInLagBand with Results.SignFilter restricting the ARGMAX (muse_batch_run_in_lag_band with the sign): under
+        SignFilter_POS every series contributes its largest positive value inside the band, under SignFilter_NEG its most negative
+        one; SignFilter_ANY is RunInLagBand.  Fed as RunSignedInLagRange feeds it: under a sign the Scores carry the signed
+        value."""
+        return self._run_in_lag_band(groupByLabels, lagLo, lagHi, True, "RunSignedInLagBand")
+
+    def _run_in_lag_band(self, groupByLabels, lagLo, lagHi, signed, who):
+        comp = self.Comparison
+        labelValuesSet = comp.indexLabelValues(groupByLabels)
+        if not labelValuesSet:
+            return None
+        if self._engines:
+            raise MuseError(B.MUSE_ERR_UNSUPPORTED, who + " runs on one device")
+        r = self.Results
+        if lagLo > lagHi:
+            raise MuseError(B.MUSE_ERR_INVALID, who + " needs lagLo <= lagHi")
+        series = comp._series_list()
+        gid = comp._group_ids()
+        G = len(labelValuesSet)
+        sign = r.SignFilter if signed else SignFilter_ANY
+        mag = sign == SignFilter_ANY
+        if G <= EXACT_FEED_MAX_GROUPS:
+            idx, lag, score, _ = self._batch().run_in_lag_band(lagLo, lagHi, gid, G, G, 0.0, sign, abs_scores=mag)
+        elif signed:
+            idx, lag, score, _ = self._batch().run_in_lag_band(lagLo, lagHi, gid, G, r.TopN, r.Threshold, sign, abs_scores=mag)
+        else:
+            # (the call's sign_filter is the argmax's sign too: the unsigned form pre-selects on the device without a sign and leaves
+            # Results.SignFilter to Results.Update -- up to TopN of either sign reach it)
+            idx, lag, score, _ = self._batch().run_in_lag_band(lagLo, lagHi, gid, G, r.TopN, r.Threshold, SignFilter_ANY, abs_scores=True)
         order = np.argsort(gid[idx], kind="stable")
         for k in order:
             r.Update(Score(series[int(idx[k])].Labels(), int(lag[k]), float(score[k])))

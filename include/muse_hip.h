@@ -404,7 +404,8 @@ int muse_batch_run_in_window(muse_batch *b, const int32_t *group_id, int32_t G, 
  * muse_batch_run_in_lag_range is that pass followed by Batch.Run's selection over the scores, outputs as muse_batch_run, with
  * Results.MaxLag = max(-lag_lo, lag_hi): every lag of the range passes the lag filter.  A sign_filter outside -1 .. 1 or a negative
  * G with group_id is refused before anything is scored.
- * Limits: ranges that exclude lag 0; the slide forms of a range (the Muse.Run-rows forms: muse_batch_run_rows_in_lag_range below);
+ * Limits: ranges that exclude lag 0 (muse_batch_score_in_lag_band below scores them); the slide forms of a range (the Muse.Run-rows
+ * forms: muse_batch_run_rows_in_lag_range below);
  * the multi-device layer; ranges of more than 127 lags, or float32 storage, outside FFT lengths 512 ... 4096; series longer than
  * 65536 samples (other than the whole range); narrow float64 ranges are never routed to the masked pass. */
 int muse_batch_score_in_lag_range(muse_batch *b, int32_t lag_lo, int32_t lag_hi);
@@ -451,6 +452,42 @@ int muse_batch_score_signed_in_lag_range(muse_batch *b, int32_t lag_lo, int32_t 
 int muse_batch_run_signed_in_lag_range(muse_batch *b, const int32_t *group_id, int32_t G, int32_t lag_lo, int32_t lag_hi,
                                        int32_t top_n, double threshold, int32_t sign_filter, int32_t abs_scores,
                                        int64_t *out_series, int32_t *out_lag, double *out_score, int32_t *out_count, double *out_mean_abs);
+/* LAG BANDS: the best match inside lags lag_lo .. lag_hi that NEED NOT HOLD LAG 0 -- "which series lead the reference by 1 .. k
+ * samples", "between 200 and 230 samples behind".  A range [0, k] answers another question: every co-moving series peaks at lag 0 or
+ * next to it, lag 0 wins the argmax, and no later filter recovers the best lag inside 1 .. k.  Definition, per series, with n,
+ * cc[0 .. n-1] and lag(i) as at muse_batch_score_in_lag_range; the band is clipped to hi = min(lag_hi, n/2),
+ * lo = max(lag_lo, -(n/2 - 1)):
+ *   lo <= 0 <= hi : by definition muse_batch_score_signed_in_lag_range(b, lag_lo, lag_hi, sign), bit for bit on every path, its
+ *                   every-lag and MUSE_ERR_UNSUPPORTED outcomes included; no kernel of the bands runs
+ *   0 < lo <= hi  : the scan runs over the indices lo .. hi in ascending order
+ *   lo <= hi < 0  : the scan runs over the indices n + lo .. n + hi in ascending order
+ * On both one-sided bands the scan starts from (0, 0.0) and uses strict '>', so the first index wins: sign == MUSE_SIGN_ANY compares
+ * |cc[i]|, MUSE_SIGN_POS compares cc[i] (only values > 0 can win), MUSE_SIGN_NEG compares -cc[i] (only values < 0); a NaN never wins.
+ *   nothing wins (the band holds only zeros or NaN, or no value of the sign) : (lag 0, mv +0.0) for every sign -- index 0 is not in the
+ *                   band, so cc[0] is not an answer: the signed pass's "none" outcome
+ *   a series with sigma == 0 : (0, 0.0);  a NaN / Inf series : (0, NaN), as everywhere else
+ * Which pass runs for a band that excludes lag 0 (W = hi - lo + 1; such a band is never "every lag"):
+ *   float64 group, W <= 2 MUSE_LAG_WINDOW_MAX + 1, up to 65536 samples : the direct product over a table whose row v is lag lo + v:
+ *                                                                      W rows, ceil(W / 16) accumulator tiles wherever the band lies
+ *                                                                      (xcorr_window_band_mfma); the value at a lag has the bits
+ *                                                                      muse_batch_score_in_lag_range's direct product gives there
+ *   FFT length 512, 1024, 2048 or 4096, W wider or float32 storage   : the transform kernels with the argmax masked to the one index
+ *                                                                      interval, the sign in the mask (their band builds)
+ *   anything else                                                    : MUSE_ERR_UNSUPPORTED, nothing changed
+ * Results land in the batch's score buffers; the pass is exact fp64, never screened, and never uses, builds or counts towards the
+ * group's spectrum cache.  MUSE_ERR_INVALID, nothing changed (everything is checked before anything is enqueued): a NULL batch,
+ * lag_lo > lag_hi, a band that is empty after clipping ((100, 226) at n = 64), a sign outside -1 .. 1, a batch whose own lag window
+ * is on (unless the band is the symmetric range equal to it, as the range call allows).
+ * muse_batch_run_in_lag_band is that pass followed by Batch.Run's selection, outputs as muse_batch_run_in_lag_range, with
+ * Results.MaxLag = max(|lag_lo|, |lag_hi|); sign_filter is both the argmax's sign and the selection's filter, as in
+ * muse_batch_run_signed_in_lag_range; the selection's own argument checks come first.
+ * Limits: the many-references form, the Muse.Run rows and panels forms, the slide forms, the muse_batch_set_lag_window setting, the
+ * multi-device and dist.py layers; bands where the table above says MUSE_ERR_UNSUPPORTED (more than 127 lags or float32 storage
+ * outside FFT lengths 512 ... 4096, series longer than 65536 samples). */
+int muse_batch_score_in_lag_band(muse_batch *b, int32_t lag_lo, int32_t lag_hi, int32_t sign);
+int muse_batch_run_in_lag_band(muse_batch *b, const int32_t *group_id, int32_t G, int32_t lag_lo, int32_t lag_hi,
+                               int32_t top_n, double threshold, int32_t sign_filter, int32_t abs_scores,
+                               int64_t *out_series, int32_t *out_lag, double *out_score, int32_t *out_count, double *out_mean_abs);
 /* Muse.Run (muse.go:46-92) INSIDE A LAG RANGE of up to MUSE_RUN_ROWS_LAG_RANGE_MAX lags, in one call.  Each behaves as its _windowed
  * namesake (muse_batch_run_rows_windowed, _run_row_ptrs_windowed, _run_group_rows_windowed): same validation, same out_winner /
  * out_state rules, same abs_scores, M == 0 gives state 0, the same pool of slots, any number of host threads on one tmpl; a
@@ -474,7 +511,8 @@ int muse_batch_run_signed_in_lag_range(muse_batch *b, const int32_t *group_id, i
  *   anything else                              : MUSE_ERR_UNSUPPORTED, nothing changed
  * MUSE_ERR_INVALID, every handle left as it was (everything is checked before anything is enqueued): lag_lo > 0 or lag_hi < 0, a
  * template whose own window is on and is not this range, and the namesakes' own argument errors.
- * Limits: the slide form of a range; more than 2048 lags; ranges that exclude lag 0; series longer than 65536 samples (other than
+ * Limits: the slide form of a range; more than 2048 lags; ranges that exclude lag 0 (a resident group: muse_batch_score_in_lag_band);
+ * series longer than 65536 samples (other than
  * every lag); float32 host rows; the multi-device layer. */
 #define MUSE_RUN_ROWS_LAG_RANGE_MAX 2048   /* the most lags (hi - lo + 1, after clipping) a Muse.Run range may hold */
 int muse_batch_run_rows_in_lag_range(muse_batch *tmpl, const double *rows, int64_t M, int64_t row_stride,
@@ -687,7 +725,7 @@ int muse_batch_run_many_in_window(muse_batch *const *batches, int32_t R, const i
  * muse_batch_run_many_in_lag_range is that pass followed by Batch.Run's selection for every batch, outputs as muse_batch_run_many,
  * with Results.MaxLag = max(-lag_lo, lag_hi).  A sign_filter outside -1 .. 1 or a negative G with group_id is refused before anything
  * is scored.
- * Limits: one range per reference; ranges that exclude lag 0; the multi-device layer. */
+ * Limits: one range per reference; ranges that exclude lag 0 (one reference: muse_batch_score_in_lag_band); the multi-device layer. */
 int muse_batch_score_many_in_lag_range(muse_batch *const *batches, int32_t R, int32_t lag_lo, int32_t lag_hi);
 int muse_batch_run_many_in_lag_range(muse_batch *const *batches, int32_t R, const int32_t *group_id, int32_t G,
                                      int32_t lag_lo, int32_t lag_hi, int32_t top_n, double threshold, int32_t sign_filter,

@@ -163,6 +163,13 @@ int muse_test_lag_range_plan(int32_t N, int32_t f32_storage, int32_t lag_lo, int
  * _UNSUPPORTED elsewhere.  MUSE_ERR_INVALID for N < 2, lag_lo > 0, lag_hi < 0, a sign outside -1 .. 1 or a NULL out pointer.
  * muse_test_last_in_window_path reports the signed calls' passes too. */
 int muse_test_signed_lag_range_plan(int32_t N, int32_t f32_storage, int32_t lag_lo, int32_t lag_hi, int32_t sign, int32_t *path);
+/* muse_batch_score_in_lag_band's dispatch, a pure host function (no device needed).  A band that holds lag 0:
+ * muse_test_signed_lag_range_plan.  Otherwise, with W the lags of the clipped band: *path = MUSE_IN_WINDOW_MFMA (float64, W <= 2
+ * MUSE_LAG_WINDOW_MAX + 1, up to 65536 samples: the direct product over W table rows), _MASKED (FFT lengths 512 ... 4096, W wider or
+ * float32 storage: the transform kernels masked to the one index interval) or _UNSUPPORTED; never _PLAIN.  MUSE_ERR_INVALID for
+ * N < 2, lag_lo > lag_hi, a band that is empty after clipping, a sign outside -1 .. 1 or a NULL out pointer.
+ * muse_test_in_window_force_transform applies to bands as to ranges, muse_test_last_in_window_path reports the band pass. */
+int muse_test_lag_band_plan(int32_t N, int32_t f32_storage, int32_t lag_lo, int32_t lag_hi, int32_t sign, int32_t *path);
 /* muse_batch_score_many_in_window's dispatch, a pure host function (no device needed): the pass that scores R >= 1 references against
  * series of N >= 2 samples (f32_storage: a float32-storage group) inside +-max_lag >= 0 -- *path = MUSE_IN_WINDOW_PLAIN
  * (muse_batch_score_many), _MFMA (muse_batch_score_many_windowed), _MASKED (ONE many-references pass of the transform kernels with a
