@@ -382,6 +382,15 @@ class DeviceGroup:
             pass
 
 
+def _gid_ptr(group_id):
+    """a Run's group_id argument for the C call: (the int32 array to keep alive across it, its pointer); None (every series its own
+    group) -> (None, NULL)"""
+    if group_id is None:
+        return None, None
+    gid = np.ascontiguousarray(group_id, dtype=np.int32)
+    return gid, B.i32ptr(gid)
+
+
 class DeviceBatch:
     """muse_batch: resident reference spectrum + per-series result buffers."""
 
@@ -401,6 +410,81 @@ class DeviceBatch:
     def like(cls, template, dgroup):
         """a batch for `dgroup` against the template's reference (no transform, two small allocations)"""
         return cls(template.engine, dgroup, None, like=template)
+
+    # ---- the C call shapes, each spelled once (the C function goes in by name, as muse.hpp's cores take theirs by pointer)
+    def _select(self, fn, lead, group_id, G, window, top_n, threshold, sign_filter, abs_scores):
+        """the run-selection shape: fn(handle, *lead, gid | NULL, G, *window, top_n, threshold, sign_filter, abs, o_s, o_l, o_v, &cnt,
+        &mean) -> (series, lag, score, mean_abs).  lead: () or the slide forms' (tails, k, stride); window: (max_lag,) or (lag_lo, lag_hi)"""
+        cap = max(int(top_n), 1)
+        o_s = np.zeros(cap, dtype=np.int64)
+        o_l = np.zeros(cap, dtype=np.int32)
+        o_v = np.zeros(cap)
+        cnt, mean = ctypes.c_int32(0), ctypes.c_double(0)
+        gid, gptr = _gid_ptr(group_id)
+        B.check(getattr(B.load(), fn)(
+            self._h, *lead, gptr, int(G), *[int(w) for w in window], int(top_n), float(threshold), int(sign_filter),
+            1 if abs_scores else 0, B.i64ptr(o_s), B.i32ptr(o_l), B.dptr(o_v), ctypes.byref(cnt), ctypes.byref(mean)))
+        c = cnt.value
+        return o_s[:c].copy(), o_l[:c].copy(), o_v[:c].copy(), float(mean.value)
+
+    def _slide_select(self, fn, tails, *selection):
+        """_select behind a slide of the whole group: lead = the prepared tails; the group has slid once the call has passed"""
+        tails, k, stride, moved = self._tails2d(tails)
+        out = self._select(fn, (tails.ctypes.data_as(B._dp), k, stride), *selection)
+        if moved:
+            self.dgroup.slides += 1
+        return out
+
+    def _winner(self, fn, rows, window, abs_scores):
+        """the winner shape: fn(handle, *rows, *window, abs, rec, &state) -> (winner record, state).  rows: where the label group's rows
+        are, as _run_rows / _run_row_ptrs / _run_group_rows spell it; window: (), (max_lag,) or (lag_lo, lag_hi)"""
+        rec = np.zeros(1, dtype=B.RECORD_DTYPE)
+        state = ctypes.c_uint8(0)
+        B.check(getattr(B.load(), fn)(self._h, *rows, *[int(w) for w in window], 1 if abs_scores else 0,
+                                      B.recptr(rec), ctypes.byref(state)))
+        return rec[0], int(state.value)
+
+    def _run_rows(self, fn, rows, window, abs_scores):
+        """_winner over host rows (M x N)"""
+        rows, stride = self._rows2d(rows)
+        return self._winner(fn, (rows.ctypes.data_as(B._dp), rows.shape[0], stride), window, abs_scores)
+
+    def _run_row_ptrs(self, fn, series, window, abs_scores):
+        """_winner over one pointer per series"""
+        arrs, ptrs = self._row_ptrs(series)
+        return self._winner(fn, (ptrs, len(arrs)), window, abs_scores)
+
+    def _run_group_rows(self, fn, src, rows, window, abs_scores):
+        """_winner over the rows `rows` of the DeviceGroup src"""
+        idx = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        return self._winner(fn, (src._h, B.i64ptr(idx), idx.shape[0]), window, abs_scores)
+
+    def _row_scores(self, fn, rows, window):
+        """the per-row scores shape (test hooks): fn(handle, rows, M, stride, *window, lag, mv) -> (lag, mv)"""
+        rows, stride = self._rows2d(rows)
+        lag = np.zeros(rows.shape[0], dtype=np.int32)
+        mv = np.zeros(rows.shape[0])
+        B.check(getattr(B.load(), fn)(self._h, rows.ctypes.data_as(B._dp), rows.shape[0], stride, *[int(w) for w in window],
+                                      B.i32ptr(lag), B.dptr(mv)))
+        return lag, mv
+
+    @staticmethod
+    def _rows2d(rows):
+        """host rows (M x N) as the C calls take them -> (float64 array with unit column stride, row stride in samples)"""
+        rows = np.asarray(rows, dtype=np.float64)
+        if rows.ndim != 2:
+            raise ValueError("rows must be 2-D")
+        if rows.shape[0] and rows.strides[1] != 8:
+            rows = np.ascontiguousarray(rows)
+        return rows, (rows.strides[0] // 8 if rows.shape[0] > 1 else rows.shape[1])
+
+    def _row_ptrs(self, series):
+        """separate per-series arrays -> (the contiguous float64 arrays to keep alive, the C array of their pointers)"""
+        arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in series]
+        for a in arrs:
+            if a.ndim != 1 or a.shape[0] != self.dgroup.N:
+                raise MuseError(B.MUSE_ERR_LENGTH, "Encountered a comparison graph with differing length than the reference")
+        return arrs, (B._dp * max(len(arrs), 1))(*[a.ctypes.data_as(B._dp) for a in arrs])
 
     def spectrum(self):
         out = np.zeros(2 * (self.n // 2 + 1))
@@ -443,20 +527,7 @@ class DeviceBatch:
     def run_in_window(self, max_lag, group_id=None, G=0, top_n=20, threshold=0.0, sign_filter=0, abs_scores=True):
         """muse_batch_run_in_window: score_in_window followed by Batch.Run's selection (max_lag is the window and the
         Results.MaxLag); -> (series, lag, score, mean_abs) as run()"""
-        cap = max(int(top_n), 1)
-        o_s = np.zeros(cap, dtype=np.int64)
-        o_l = np.zeros(cap, dtype=np.int32)
-        o_v = np.zeros(cap)
-        cnt, mean = ctypes.c_int32(0), ctypes.c_double(0)
-        gid = None
-        if group_id is not None:
-            gid = np.ascontiguousarray(group_id, dtype=np.int32)
-        B.check(B.load().muse_batch_run_in_window(
-            self._h, B.i32ptr(gid) if gid is not None else None, int(G), int(max_lag), int(top_n), float(threshold),
-            int(sign_filter), 1 if abs_scores else 0, B.i64ptr(o_s), B.i32ptr(o_l), B.dptr(o_v), ctypes.byref(cnt),
-            ctypes.byref(mean)))
-        c = cnt.value
-        return o_s[:c].copy(), o_l[:c].copy(), o_v[:c].copy(), float(mean.value)
+        return self._select("muse_batch_run_in_window", (), group_id, G, (max_lag,), top_n, threshold, sign_filter, abs_scores)
 
     def score_in_lag_range(self, lag_lo, lag_hi):
         """muse_batch_score_in_lag_range: an all-scores pass with every series' best match inside the lags lag_lo .. lag_hi
@@ -474,20 +545,7 @@ class DeviceBatch:
     def run_in_lag_range(self, lag_lo, lag_hi, group_id=None, G=0, top_n=20, threshold=0.0, sign_filter=0, abs_scores=True):
         """muse_batch_run_in_lag_range: score_in_lag_range followed by Batch.Run's selection with Results.MaxLag =
         max(-lag_lo, lag_hi); -> (series, lag, score, mean_abs) as run()"""
-        cap = max(int(top_n), 1)
-        o_s = np.zeros(cap, dtype=np.int64)
-        o_l = np.zeros(cap, dtype=np.int32)
-        o_v = np.zeros(cap)
-        cnt, mean = ctypes.c_int32(0), ctypes.c_double(0)
-        gid = None
-        if group_id is not None:
-            gid = np.ascontiguousarray(group_id, dtype=np.int32)
-        B.check(B.load().muse_batch_run_in_lag_range(
-            self._h, B.i32ptr(gid) if gid is not None else None, int(G), int(lag_lo), int(lag_hi), int(top_n), float(threshold),
-            int(sign_filter), 1 if abs_scores else 0, B.i64ptr(o_s), B.i32ptr(o_l), B.dptr(o_v), ctypes.byref(cnt),
-            ctypes.byref(mean)))
-        c = cnt.value
-        return o_s[:c].copy(), o_l[:c].copy(), o_v[:c].copy(), float(mean.value)
+        return self._select("muse_batch_run_in_lag_range", (), group_id, G, (lag_lo, lag_hi), top_n, threshold, sign_filter, abs_scores)
 
     def score_signed_in_lag_range(self, lag_lo, lag_hi, sign):
         """muse_batch_score_signed_in_lag_range: score_in_lag_range with the argmax restricted to the values of one sign -- sign = +1
@@ -506,20 +564,8 @@ class DeviceBatch:
         """muse_batch_run_signed_in_lag_range: score_signed_in_lag_range(lag_lo, lag_hi, sign_filter) followed by Batch.Run's
         selection with Results.MaxLag = max(-lag_lo, lag_hi) and Results.SignFilter = sign_filter: the sign restricts the argmax
         and filters the selection; -> (series, lag, score, mean_abs) as run().  sign_filter = 0 is run_in_lag_range."""
-        cap = max(int(top_n), 1)
-        o_s = np.zeros(cap, dtype=np.int64)
-        o_l = np.zeros(cap, dtype=np.int32)
-        o_v = np.zeros(cap)
-        cnt, mean = ctypes.c_int32(0), ctypes.c_double(0)
-        gid = None
-        if group_id is not None:
-            gid = np.ascontiguousarray(group_id, dtype=np.int32)
-        B.check(B.load().muse_batch_run_signed_in_lag_range(
-            self._h, B.i32ptr(gid) if gid is not None else None, int(G), int(lag_lo), int(lag_hi), int(top_n), float(threshold),
-            int(sign_filter), 1 if abs_scores else 0, B.i64ptr(o_s), B.i32ptr(o_l), B.dptr(o_v), ctypes.byref(cnt),
-            ctypes.byref(mean)))
-        c = cnt.value
-        return o_s[:c].copy(), o_l[:c].copy(), o_v[:c].copy(), float(mean.value)
+        return self._select("muse_batch_run_signed_in_lag_range", (), group_id, G, (lag_lo, lag_hi), top_n, threshold, sign_filter,
+                            abs_scores)
 
     def score_in_lag_band(self, lag_lo, lag_hi, sign=0):
         """muse_batch_score_in_lag_band: every series' best match inside the lags lag_lo .. lag_hi, which need not hold lag 0 --
@@ -538,20 +584,7 @@ class DeviceBatch:
     def run_in_lag_band(self, lag_lo, lag_hi, group_id=None, G=0, top_n=20, threshold=0.0, sign_filter=0, abs_scores=True):
         """muse_batch_run_in_lag_band: score_in_lag_band(lag_lo, lag_hi, sign_filter) followed by Batch.Run's selection with
         Results.MaxLag = max(|lag_lo|, |lag_hi|) and Results.SignFilter = sign_filter; -> (series, lag, score, mean_abs) as run()"""
-        cap = max(int(top_n), 1)
-        o_s = np.zeros(cap, dtype=np.int64)
-        o_l = np.zeros(cap, dtype=np.int32)
-        o_v = np.zeros(cap)
-        cnt, mean = ctypes.c_int32(0), ctypes.c_double(0)
-        gid = None
-        if group_id is not None:
-            gid = np.ascontiguousarray(group_id, dtype=np.int32)
-        B.check(B.load().muse_batch_run_in_lag_band(
-            self._h, B.i32ptr(gid) if gid is not None else None, int(G), int(lag_lo), int(lag_hi), int(top_n), float(threshold),
-            int(sign_filter), 1 if abs_scores else 0, B.i64ptr(o_s), B.i32ptr(o_l), B.dptr(o_v), ctypes.byref(cnt),
-            ctypes.byref(mean)))
-        c = cnt.value
-        return o_s[:c].copy(), o_l[:c].copy(), o_v[:c].copy(), float(mean.value)
+        return self._select("muse_batch_run_in_lag_band", (), group_id, G, (lag_lo, lag_hi), top_n, threshold, sign_filter, abs_scores)
 
     def last_in_window_path(self):
         """test hook: MUSE_IN_WINDOW_* of the last score_in_window / run_in_window / score_in_lag_range / run_in_lag_range, of
@@ -601,164 +634,68 @@ class DeviceBatch:
         return est, flags, float(E.value)
 
     def run(self, group_id=None, G=0, max_lag=10, top_n=20, threshold=0.0, sign_filter=0, abs_scores=True):
-        cap = max(int(top_n), 1)
-        o_s = np.zeros(cap, dtype=np.int64)
-        o_l = np.zeros(cap, dtype=np.int32)
-        o_v = np.zeros(cap)
-        cnt, mean = ctypes.c_int32(0), ctypes.c_double(0)
-        gid = None
-        if group_id is not None:
-            gid = np.ascontiguousarray(group_id, dtype=np.int32)
-        B.check(B.load().muse_batch_run(
-            self._h, B.i32ptr(gid) if gid is not None else None, int(G), int(max_lag), int(top_n),
-            float(threshold), int(sign_filter), 1 if abs_scores else 0,
-            B.i64ptr(o_s), B.i32ptr(o_l), B.dptr(o_v), ctypes.byref(cnt), ctypes.byref(mean)))
-        c = cnt.value
-        return o_s[:c].copy(), o_l[:c].copy(), o_v[:c].copy(), float(mean.value)
+        return self._select("muse_batch_run", (), group_id, G, (max_lag,), top_n, threshold, sign_filter, abs_scores)
 
     def run_shard(self, group_id=None, G=0, series_offset=0, max_lag=10, top_n=20, threshold=0.0,
                   sign_filter=0, abs_scores=True):
         """this shard's top-N candidates as a RECORD_DTYPE array (<= top_n)"""
         rec = np.zeros(max(int(top_n), 1), dtype=B.RECORD_DTYPE)
         cnt = ctypes.c_int32(0)
-        gid = None
-        if group_id is not None:
-            gid = np.ascontiguousarray(group_id, dtype=np.int32)
+        gid, gptr = _gid_ptr(group_id)
         B.check(B.load().muse_batch_run_shard(
-            self._h, B.i32ptr(gid) if gid is not None else None, int(G), int(series_offset), int(max_lag),
-            int(top_n), float(threshold), int(sign_filter), 1 if abs_scores else 0,
-            B.recptr(rec), ctypes.byref(cnt)))
+            self._h, gptr, int(G), int(series_offset), int(max_lag), int(top_n), float(threshold), int(sign_filter),
+            1 if abs_scores else 0, B.recptr(rec), ctypes.byref(cnt)))
         return rec[:cnt.value].copy()
 
     def run_rows(self, rows, abs_scores=False):
         """muse_batch_run_rows: Muse.Run (muse.go:46-92) in one call -- `rows` (M x N, host) form ONE label group scored against
         this batch's reference (the batch's own group is not touched); -> (winner record, state) as run_groups reports them"""
-        rows = np.asarray(rows, dtype=np.float64)
-        if rows.ndim != 2:
-            raise ValueError("rows must be 2-D")
-        if rows.shape[0] and rows.strides[1] != 8:
-            rows = np.ascontiguousarray(rows)
-        stride = rows.strides[0] // 8 if rows.shape[0] > 1 else rows.shape[1]
-        rec = np.zeros(1, dtype=B.RECORD_DTYPE)
-        state = ctypes.c_uint8(0)
-        B.check(B.load().muse_batch_run_rows(self._h, rows.ctypes.data_as(B._dp), rows.shape[0], stride,
-                                             1 if abs_scores else 0, B.recptr(rec), ctypes.byref(state)))
-        return rec[0], int(state.value)
+        return self._run_rows("muse_batch_run_rows", rows, (), abs_scores)
 
     def run_row_ptrs(self, series, abs_scores=False):
         """muse_batch_run_row_ptrs: the same with one pointer per series (a list of separate contiguous float64 arrays of the
         reference's length): gathered straight into the call's pinned buffer"""
-        arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in series]
-        for a in arrs:
-            if a.ndim != 1 or a.shape[0] != self.dgroup.N:
-                raise MuseError(B.MUSE_ERR_LENGTH, "Encountered a comparison graph with differing length than the reference")
-        ptrs = (B._dp * max(len(arrs), 1))(*[a.ctypes.data_as(B._dp) for a in arrs])
-        rec = np.zeros(1, dtype=B.RECORD_DTYPE)
-        state = ctypes.c_uint8(0)
-        B.check(B.load().muse_batch_run_row_ptrs(self._h, ptrs, len(arrs), 1 if abs_scores else 0, B.recptr(rec), ctypes.byref(state)))
-        return rec[0], int(state.value)
+        return self._run_row_ptrs("muse_batch_run_row_ptrs", series, (), abs_scores)
 
     def run_group_rows(self, src, rows, abs_scores=False):
         """muse_batch_run_group_rows: run_rows over rows that already live in the DeviceGroup `src` (row i of the label group =
         src row rows[i]); -> (winner record, state), the winner's series being its position in `rows`"""
-        idx = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
-        rec = np.zeros(1, dtype=B.RECORD_DTYPE)
-        state = ctypes.c_uint8(0)
-        B.check(B.load().muse_batch_run_group_rows(self._h, src._h, B.i64ptr(idx), idx.shape[0], 1 if abs_scores else 0,
-                                                   B.recptr(rec), ctypes.byref(state)))
-        return rec[0], int(state.value)
+        return self._run_group_rows("muse_batch_run_group_rows", src, rows, (), abs_scores)
 
     # ---- the same inside a lag window: the window is an argument of the call, this batch's own setting is not touched
-    @staticmethod
-    def _rows2d(rows):
-        rows = np.asarray(rows, dtype=np.float64)
-        if rows.ndim != 2:
-            raise ValueError("rows must be 2-D")
-        if rows.shape[0] and rows.strides[1] != 8:
-            rows = np.ascontiguousarray(rows)
-        return rows, (rows.strides[0] // 8 if rows.shape[0] > 1 else rows.shape[1])
-
     def run_rows_windowed(self, rows, max_lag, abs_scores=False):
         """muse_batch_run_rows_windowed: run_rows with every row's best match INSIDE +-max_lag (the lag window of set_lag_window)"""
-        rows, stride = self._rows2d(rows)
-        rec = np.zeros(1, dtype=B.RECORD_DTYPE)
-        state = ctypes.c_uint8(0)
-        B.check(B.load().muse_batch_run_rows_windowed(self._h, rows.ctypes.data_as(B._dp), rows.shape[0], stride, int(max_lag),
-                                                      1 if abs_scores else 0, B.recptr(rec), ctypes.byref(state)))
-        return rec[0], int(state.value)
+        return self._run_rows("muse_batch_run_rows_windowed", rows, (max_lag,), abs_scores)
 
     def run_row_ptrs_windowed(self, series, max_lag, abs_scores=False):
         """muse_batch_run_row_ptrs_windowed: run_row_ptrs inside the lag window"""
-        arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in series]
-        for a in arrs:
-            if a.ndim != 1 or a.shape[0] != self.dgroup.N:
-                raise MuseError(B.MUSE_ERR_LENGTH, "Encountered a comparison graph with differing length than the reference")
-        ptrs = (B._dp * max(len(arrs), 1))(*[a.ctypes.data_as(B._dp) for a in arrs])
-        rec = np.zeros(1, dtype=B.RECORD_DTYPE)
-        state = ctypes.c_uint8(0)
-        B.check(B.load().muse_batch_run_row_ptrs_windowed(self._h, ptrs, len(arrs), int(max_lag), 1 if abs_scores else 0,
-                                                          B.recptr(rec), ctypes.byref(state)))
-        return rec[0], int(state.value)
+        return self._run_row_ptrs("muse_batch_run_row_ptrs_windowed", series, (max_lag,), abs_scores)
 
     def run_group_rows_windowed(self, src, rows, max_lag, abs_scores=False):
         """muse_batch_run_group_rows_windowed: run_group_rows inside the lag window (a float32-storage src is accepted)"""
-        idx = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
-        rec = np.zeros(1, dtype=B.RECORD_DTYPE)
-        state = ctypes.c_uint8(0)
-        B.check(B.load().muse_batch_run_group_rows_windowed(self._h, src._h, B.i64ptr(idx), idx.shape[0], int(max_lag),
-                                                            1 if abs_scores else 0, B.recptr(rec), ctypes.byref(state)))
-        return rec[0], int(state.value)
+        return self._run_group_rows("muse_batch_run_group_rows_windowed", src, rows, (max_lag,), abs_scores)
 
     def run_rows_windowed_scores(self, rows, max_lag):
         """test hook: the per-row (lag, mv) of run_rows_windowed's path (muse_test_run_rows_windowed_scores)"""
-        rows, stride = self._rows2d(rows)
-        lag = np.zeros(rows.shape[0], dtype=np.int32)
-        mv = np.zeros(rows.shape[0])
-        B.check(B.load().muse_test_run_rows_windowed_scores(self._h, rows.ctypes.data_as(B._dp), rows.shape[0], stride, int(max_lag),
-                                                            B.i32ptr(lag), B.dptr(mv)))
-        return lag, mv
+        return self._row_scores("muse_test_run_rows_windowed_scores", rows, (max_lag,))
 
     # ---- the same inside a lag range lag_lo .. lag_hi (lag_lo <= 0 <= lag_hi) of up to MUSE_RUN_ROWS_LAG_RANGE_MAX lags
     def run_rows_in_lag_range(self, rows, lag_lo, lag_hi, abs_scores=False):
         """muse_batch_run_rows_in_lag_range: run_rows with every row's best match INSIDE the lags lag_lo .. lag_hi (the definition of
         score_in_lag_range); (-L, L) is run_rows_windowed(L)"""
-        rows, stride = self._rows2d(rows)
-        rec = np.zeros(1, dtype=B.RECORD_DTYPE)
-        state = ctypes.c_uint8(0)
-        B.check(B.load().muse_batch_run_rows_in_lag_range(self._h, rows.ctypes.data_as(B._dp), rows.shape[0], stride, int(lag_lo),
-                                                          int(lag_hi), 1 if abs_scores else 0, B.recptr(rec), ctypes.byref(state)))
-        return rec[0], int(state.value)
+        return self._run_rows("muse_batch_run_rows_in_lag_range", rows, (lag_lo, lag_hi), abs_scores)
 
     def run_row_ptrs_in_lag_range(self, series, lag_lo, lag_hi, abs_scores=False):
         """muse_batch_run_row_ptrs_in_lag_range: run_row_ptrs inside the lag range"""
-        arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in series]
-        for a in arrs:
-            if a.ndim != 1 or a.shape[0] != self.dgroup.N:
-                raise MuseError(B.MUSE_ERR_LENGTH, "Encountered a comparison graph with differing length than the reference")
-        ptrs = (B._dp * max(len(arrs), 1))(*[a.ctypes.data_as(B._dp) for a in arrs])
-        rec = np.zeros(1, dtype=B.RECORD_DTYPE)
-        state = ctypes.c_uint8(0)
-        B.check(B.load().muse_batch_run_row_ptrs_in_lag_range(self._h, ptrs, len(arrs), int(lag_lo), int(lag_hi),
-                                                              1 if abs_scores else 0, B.recptr(rec), ctypes.byref(state)))
-        return rec[0], int(state.value)
+        return self._run_row_ptrs("muse_batch_run_row_ptrs_in_lag_range", series, (lag_lo, lag_hi), abs_scores)
 
     def run_group_rows_in_lag_range(self, src, rows, lag_lo, lag_hi, abs_scores=False):
         """muse_batch_run_group_rows_in_lag_range: run_group_rows inside the lag range (a float32-storage src is accepted)"""
-        idx = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
-        rec = np.zeros(1, dtype=B.RECORD_DTYPE)
-        state = ctypes.c_uint8(0)
-        B.check(B.load().muse_batch_run_group_rows_in_lag_range(self._h, src._h, B.i64ptr(idx), idx.shape[0], int(lag_lo), int(lag_hi),
-                                                                1 if abs_scores else 0, B.recptr(rec), ctypes.byref(state)))
-        return rec[0], int(state.value)
+        return self._run_group_rows("muse_batch_run_group_rows_in_lag_range", src, rows, (lag_lo, lag_hi), abs_scores)
 
     def run_rows_in_lag_range_scores(self, rows, lag_lo, lag_hi):
         """test hook: the per-row (lag, mv) of run_rows_in_lag_range's path (muse_test_run_rows_in_lag_range_scores)"""
-        rows, stride = self._rows2d(rows)
-        lag = np.zeros(rows.shape[0], dtype=np.int32)
-        mv = np.zeros(rows.shape[0])
-        B.check(B.load().muse_test_run_rows_in_lag_range_scores(self._h, rows.ctypes.data_as(B._dp), rows.shape[0], stride,
-                                                                int(lag_lo), int(lag_hi), B.i32ptr(lag), B.dptr(mv)))
-        return lag, mv
+        return self._row_scores("muse_test_run_rows_in_lag_range_scores", rows, (lag_lo, lag_hi))
 
     # ---- the slide of the group's rows and the windowed pass over the new rows in one kernel
     def _tails2d(self, tails):
@@ -786,23 +723,7 @@ class DeviceBatch:
     def slide_run_windowed(self, tails, max_lag, group_id=None, G=0, top_n=20, threshold=0.0, sign_filter=0, abs_scores=True):
         """muse_batch_slide_run_windowed: slide_score_windowed followed by Batch.Run's selection (max_lag is the window and the
         Results.MaxLag); -> (series, lag, score, mean_abs) as run()"""
-        tails, k, stride, moved = self._tails2d(tails)
-        cap = max(int(top_n), 1)
-        o_s = np.zeros(cap, dtype=np.int64)
-        o_l = np.zeros(cap, dtype=np.int32)
-        o_v = np.zeros(cap)
-        cnt, mean = ctypes.c_int32(0), ctypes.c_double(0)
-        gid = None
-        if group_id is not None:
-            gid = np.ascontiguousarray(group_id, dtype=np.int32)
-        B.check(B.load().muse_batch_slide_run_windowed(
-            self._h, tails.ctypes.data_as(B._dp), k, stride, B.i32ptr(gid) if gid is not None else None, int(G), int(max_lag),
-            int(top_n), float(threshold), int(sign_filter), 1 if abs_scores else 0,
-            B.i64ptr(o_s), B.i32ptr(o_l), B.dptr(o_v), ctypes.byref(cnt), ctypes.byref(mean)))
-        if moved:
-            self.dgroup.slides += 1
-        c = cnt.value
-        return o_s[:c].copy(), o_l[:c].copy(), o_v[:c].copy(), float(mean.value)
+        return self._slide_select("muse_batch_slide_run_windowed", tails, group_id, G, (max_lag,), top_n, threshold, sign_filter, abs_scores)
 
     # ---- the same for a window of any width and both storage types (row level only, as slide_score_windowed: DESIGN 8.10)
     def slide_score_in_window(self, tails, max_lag):
@@ -815,34 +736,15 @@ class DeviceBatch:
         if moved:
             self.dgroup.slides += 1
 
-    def _slide_run(self, fn, tails, max_lag, group_id, G, top_n, threshold, sign_filter, abs_scores):
-        tails, k, stride, moved = self._tails2d(tails)
-        cap = max(int(top_n), 1)
-        o_s = np.zeros(cap, dtype=np.int64)
-        o_l = np.zeros(cap, dtype=np.int32)
-        o_v = np.zeros(cap)
-        cnt, mean = ctypes.c_int32(0), ctypes.c_double(0)
-        gid = None
-        if group_id is not None:
-            gid = np.ascontiguousarray(group_id, dtype=np.int32)
-        B.check(getattr(B.load(), fn)(
-            self._h, tails.ctypes.data_as(B._dp), k, stride, B.i32ptr(gid) if gid is not None else None, int(G), int(max_lag),
-            int(top_n), float(threshold), int(sign_filter), 1 if abs_scores else 0,
-            B.i64ptr(o_s), B.i32ptr(o_l), B.dptr(o_v), ctypes.byref(cnt), ctypes.byref(mean)))
-        if moved:
-            self.dgroup.slides += 1
-        c = cnt.value
-        return o_s[:c].copy(), o_l[:c].copy(), o_v[:c].copy(), float(mean.value)
-
     def slide_run_in_window(self, tails, max_lag, group_id=None, G=0, top_n=20, threshold=0.0, sign_filter=0, abs_scores=True):
         """muse_batch_slide_run_in_window: slide_score_in_window followed by Batch.Run's selection (max_lag is the window and the
         Results.MaxLag); -> (series, lag, score, mean_abs) as run()"""
-        return self._slide_run("muse_batch_slide_run_in_window", tails, max_lag, group_id, G, top_n, threshold, sign_filter, abs_scores)
+        return self._slide_select("muse_batch_slide_run_in_window", tails, group_id, G, (max_lag,), top_n, threshold, sign_filter, abs_scores)
 
     def slide_run(self, tails, group_id=None, G=0, max_lag=10, top_n=20, threshold=0.0, sign_filter=0, abs_scores=True):
         """muse_batch_slide_run: the reference's Run on the slid rows -- DeviceGroup.slide(tails) + run(...): the unwindowed pass, then
         the selection with Results.MaxLag = max_lag; -> (series, lag, score, mean_abs) as run()"""
-        return self._slide_run("muse_batch_slide_run", tails, max_lag, group_id, G, top_n, threshold, sign_filter, abs_scores)
+        return self._slide_select("muse_batch_slide_run", tails, group_id, G, (max_lag,), top_n, threshold, sign_filter, abs_scores)
 
     def last_slide_path(self):
         """test hook: MUSE_SLIDE_IN_WINDOW_* of the last slide_score_in_window / slide_run_in_window / slide_run that moved rows, 0
@@ -855,8 +757,8 @@ class DeviceBatch:
         """this shard's winner per label group, unfiltered (muse_batch_run_groups): (records[G], state[G])"""
         rec = np.zeros(max(int(G), 1), dtype=B.RECORD_DTYPE)
         state = np.zeros(max(int(G), 1), dtype=np.uint8)
-        gid = np.ascontiguousarray(group_id, dtype=np.int32)
-        B.check(B.load().muse_batch_run_groups(self._h, B.i32ptr(gid), int(G), int(series_offset), 1 if abs_scores else 0,
+        gid, gptr = _gid_ptr(group_id)
+        B.check(B.load().muse_batch_run_groups(self._h, gptr, int(G), int(series_offset), 1 if abs_scores else 0,
                                                B.recptr(rec), state.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))))
         return rec[:int(G)], state[:int(G)]
 
@@ -908,11 +810,9 @@ def _run_many(fn, batches, group_id, G, max_lag, top_n, threshold, sign_filter, 
     o_v = np.zeros(R * cap)
     cnt = np.zeros(R, dtype=np.int32)
     mean = np.zeros(R)
-    gid = None
-    if group_id is not None:
-        gid = np.ascontiguousarray(group_id, dtype=np.int32)
+    gid, gptr = _gid_ptr(group_id)
     B.check(getattr(B.load(), fn)(
-        arr, R, B.i32ptr(gid) if gid is not None else None, int(G),
+        arr, R, gptr, int(G),
         *([int(v) for v in max_lag] if isinstance(max_lag, tuple) else [int(max_lag)]), int(top_n),
         float(threshold), int(sign_filter), 1 if abs_scores else 0,
         B.i64ptr(o_s), B.i32ptr(o_l), B.dptr(o_v), B.i32ptr(cnt), B.dptr(mean)))
@@ -962,17 +862,29 @@ def run_many_windowed(batches, group_id=None, G=0, max_lag=10, top_n=20, thresho
     return _run_many("muse_batch_run_many_windowed", batches, group_id, G, max_lag, top_n, threshold, sign_filter, abs_scores)
 
 
-def window_many_plan(R, L):
-    """muse_test_window_many_plan (no device): how score_many_windowed cuts R references with window L into launches --
-    dict(launches, launch_of[R], tiles_of[launches], max_refs, img_of[launches], kc_of[launches])"""
+def _window_many_plan(fn, R, width):
+    """a packing plan of the test ABI (no device): fn(R, width, &launches, launch_of, tiles_of, &max_refs, img_of, kc_of) -> the dict"""
     R = int(R)
     n, mx = ctypes.c_int32(0), ctypes.c_int32(0)
     of, tiles, img, kc = (np.zeros(max(R, 1), dtype=np.int32) for _ in range(4))
-    B.check(B.load().muse_test_window_many_plan(R, int(L), ctypes.byref(n), B.i32ptr(of), B.i32ptr(tiles), ctypes.byref(mx),
-                                                B.i32ptr(img), B.i32ptr(kc)))
+    B.check(getattr(B.load(), fn)(R, int(width), ctypes.byref(n), B.i32ptr(of), B.i32ptr(tiles), ctypes.byref(mx), B.i32ptr(img),
+                                  B.i32ptr(kc)))
     k = int(n.value)
     return dict(launches=k, launch_of=of[:R].copy(), tiles_of=tiles[:k].copy(), max_refs=int(mx.value), img_of=img[:k].copy(),
                 kc_of=kc[:k].copy())
+
+
+def _plan_path(fn, *ints):
+    """a path plan of the test ABI (no device): fn(*ints, &path) -> path (a MUSE_IN_WINDOW_* / MUSE_SLIDE_IN_WINDOW_* value)"""
+    path = ctypes.c_int32(-1)
+    B.check(getattr(B.load(), fn)(*[int(v) for v in ints], ctypes.byref(path)))
+    return int(path.value)
+
+
+def window_many_plan(R, L):
+    """muse_test_window_many_plan (no device): how score_many_windowed cuts R references with window L into launches --
+    dict(launches, launch_of[R], tiles_of[launches], max_refs, img_of[launches], kc_of[launches])"""
+    return _window_many_plan("muse_test_window_many_plan", R, L)
 
 
 def window_rows_plan(M, N, num_cus):
@@ -995,25 +907,19 @@ def rows_lag_range_plan(M, N, num_cus, lag_lo, lag_hi):
 def in_window_plan(N, f32, max_lag):
     """muse_test_in_window_plan (no device): MUSE_IN_WINDOW_* -- the pass score_in_window takes for series of N samples
     (f32: float32 storage) and window max_lag"""
-    path = ctypes.c_int32(-1)
-    B.check(B.load().muse_test_in_window_plan(int(N), 1 if f32 else 0, int(max_lag), ctypes.byref(path)))
-    return int(path.value)
+    return _plan_path("muse_test_in_window_plan", N, bool(f32), max_lag)
 
 
 def lag_range_plan(N, f32, lag_lo, lag_hi):
     """muse_test_lag_range_plan (no device): MUSE_IN_WINDOW_* -- the pass score_in_lag_range takes for series of N samples
     (f32: float32 storage) and the lags lag_lo .. lag_hi"""
-    path = ctypes.c_int32(-1)
-    B.check(B.load().muse_test_lag_range_plan(int(N), 1 if f32 else 0, int(lag_lo), int(lag_hi), ctypes.byref(path)))
-    return int(path.value)
+    return _plan_path("muse_test_lag_range_plan", N, bool(f32), lag_lo, lag_hi)
 
 
 def slide_in_window_plan(N, f32, max_lag, k):
     """muse_test_slide_in_window_plan (no device): MUSE_SLIDE_IN_WINDOW_* -- how slide_score_in_window moves and scores series of N
     samples (f32: float32 storage) slid by k inside +-max_lag"""
-    path = ctypes.c_int32(-1)
-    B.check(B.load().muse_test_slide_in_window_plan(int(N), 1 if f32 else 0, int(max_lag), int(k), ctypes.byref(path)))
-    return int(path.value)
+    return _plan_path("muse_test_slide_in_window_plan", N, bool(f32), max_lag, k)
 
 
 def score_many_in_window(batches, max_lag):
@@ -1038,9 +944,7 @@ def run_many_in_window(batches, group_id=None, G=0, max_lag=10, top_n=20, thresh
 def many_in_window_plan(N, f32, max_lag, R):
     """muse_test_many_in_window_plan (no device): MUSE_IN_WINDOW_* -- the pass score_many_in_window takes for R references against
     series of N samples (f32: float32 storage) and window max_lag"""
-    path = ctypes.c_int32(-1)
-    B.check(B.load().muse_test_many_in_window_plan(int(N), 1 if f32 else 0, int(max_lag), int(R), ctypes.byref(path)))
-    return int(path.value)
+    return _plan_path("muse_test_many_in_window_plan", N, bool(f32), max_lag, R)
 
 
 def score_many_in_lag_range(batches, lag_lo, lag_hi):
@@ -1067,38 +971,25 @@ def run_many_in_lag_range(batches, lag_lo, lag_hi, group_id=None, G=0, top_n=20,
 def lag_band_plan(N, f32, lag_lo, lag_hi, sign=0):
     """muse_test_lag_band_plan (no device): MUSE_IN_WINDOW_* -- the pass score_in_lag_band takes for series of N samples inside the
     lags lag_lo .. lag_hi (a band that holds lag 0: signed_lag_range_plan)"""
-    path = ctypes.c_int32(0)
-    B.check(B.load().muse_test_lag_band_plan(int(N), 1 if f32 else 0, int(lag_lo), int(lag_hi), int(sign), ctypes.byref(path)))
-    return int(path.value)
+    return _plan_path("muse_test_lag_band_plan", N, bool(f32), lag_lo, lag_hi, sign)
 
 
 def signed_lag_range_plan(N, f32, lag_lo, lag_hi, sign):
     """muse_test_signed_lag_range_plan (no device): MUSE_IN_WINDOW_* -- the pass score_signed_in_lag_range takes for series of N
     samples (f32: float32 storage) inside the lags lag_lo .. lag_hi with the sign; sign = 0 is lag_range_plan"""
-    path = ctypes.c_int32(0)
-    B.check(B.load().muse_test_signed_lag_range_plan(int(N), 1 if f32 else 0, int(lag_lo), int(lag_hi), int(sign), ctypes.byref(path)))
-    return int(path.value)
+    return _plan_path("muse_test_signed_lag_range_plan", N, bool(f32), lag_lo, lag_hi, sign)
 
 
 def many_lag_range_plan(N, f32, lag_lo, lag_hi, R):
     """muse_test_many_lag_range_plan (no device): MUSE_IN_WINDOW_* -- the pass score_many_in_lag_range takes for R references
     against series of N samples (f32: float32 storage) and the lags lag_lo .. lag_hi"""
-    path = ctypes.c_int32(-1)
-    B.check(B.load().muse_test_many_lag_range_plan(int(N), 1 if f32 else 0, int(lag_lo), int(lag_hi), int(R), ctypes.byref(path)))
-    return int(path.value)
+    return _plan_path("muse_test_many_lag_range_plan", N, bool(f32), lag_lo, lag_hi, R)
 
 
 def window_many_plan_rows(R, W):
     """muse_test_window_many_plan_rows (no device): window_many_plan in the rows W of a reference's table (a window +-L: 2 L + 1,
     a lag range: its lags) -- the same dict"""
-    R = int(R)
-    n, mx = ctypes.c_int32(0), ctypes.c_int32(0)
-    of, tiles, img, kc = (np.zeros(max(R, 1), dtype=np.int32) for _ in range(4))
-    B.check(B.load().muse_test_window_many_plan_rows(R, int(W), ctypes.byref(n), B.i32ptr(of), B.i32ptr(tiles), ctypes.byref(mx),
-                                                     B.i32ptr(img), B.i32ptr(kc)))
-    k = int(n.value)
-    return dict(launches=k, launch_of=of[:R].copy(), tiles_of=tiles[:k].copy(), max_refs=int(mx.value), img_of=img[:k].copy(),
-                kc_of=kc[:k].copy())
+    return _window_many_plan("muse_test_window_many_plan_rows", R, W)
 
 
 def device_count():
@@ -1536,6 +1427,13 @@ def feed_group_winners(results, winners, state, labels_of):
     return fed
 
 
+def _feed_in_group_order(results, series, gid, idx, lag, score):
+    """A device selection (series indices, lags, scores) through Results.Update in group order, as the ordered drain feeds it
+    (muse_batch.go:124-128); gid: every series' group id."""
+    for k in np.argsort(gid[idx], kind="stable"):
+        results.Update(Score(series[int(idx[k])].Labels(), int(lag[k]), float(score[k])))
+
+
 class Batch:
     def __init__(self, ref, comp, results, cc, engine=None, engines=None):
         # muse_batch.go:24-28 (length check over the registry)
@@ -1594,10 +1492,7 @@ class Batch:
             idx, lag, score = self._run_sharded(gid, G)
         else:
             idx, lag, score, _ = self._batch().run(gid, G, r.MaxLag, r.TopN, r.Threshold, r.SignFilter, abs_scores=True)
-        # feed Results in group order, as the ordered drain does (muse_batch.go:124-128)
-        order = np.argsort(gid[idx], kind="stable")
-        for k in order:
-            r.Update(Score(series[int(idx[k])].Labels(), int(lag[k]), float(score[k])))
+        _feed_in_group_order(r, series, gid, idx, lag, score)
         return None
 
     def RunWindowed(self, groupByLabels):
@@ -1625,51 +1520,20 @@ class Batch:
         (FFT lengths 512 ... 4096).  One device.  Results is fed as Run feeds it: up to EXACT_FEED_MAX_GROUPS label groups ONE Score
         per group, in group order, through Results.Update (the device returns every group's winner, nothing filtered but NaN,
         which never passes); beyond, the device's TopN pre-selection in group order."""
-        comp = self.Comparison
-        labelValuesSet = comp.indexLabelValues(groupByLabels)
-        if not labelValuesSet:
-            return None
-        if self._engines:
-            raise MuseError(B.MUSE_ERR_UNSUPPORTED, "RunInWindow runs on one device")
         r = self.Results
-        if r.MaxLag < 0:
-            raise MuseError(B.MUSE_ERR_INVALID, "RunInWindow needs Results.MaxLag >= 0")
-        series = comp._series_list()
-        gid = comp._group_ids()
-        G = len(labelValuesSet)
-        if G <= EXACT_FEED_MAX_GROUPS:
-            idx, lag, score, _ = self._batch().run_in_window(r.MaxLag, gid, G, G, 0.0, SignFilter_ANY, abs_scores=True)
-        else:
-            idx, lag, score, _ = self._batch().run_in_window(r.MaxLag, gid, G, r.TopN, r.Threshold, r.SignFilter, abs_scores=True)
-        order = np.argsort(gid[idx], kind="stable")
-        for k in order:
-            r.Update(Score(series[int(idx[k])].Labels(), int(lag[k]), float(score[k])))
-        return None
+        return self._feed_in_window(
+            groupByLabels, "RunInWindow", lambda: r.MaxLag < 0 and "Results.MaxLag >= 0",
+            lambda db, *selection: db.run_in_window(r.MaxLag, *selection),
+            exact=(SignFilter_ANY, True), wide=(r.SignFilter, True))
 
     def RunInLagRange(self, groupByLabels, lagLo, lagHi):
         """RunInWindow for a one-sided or asymmetric window (muse_batch_run_in_lag_range): every series contributes its best match
         inside the lags lagLo .. lagHi, lagLo <= 0 <= lagHi (negative lags: the series trails the reference).  One device.  Results
         is fed exactly as RunInWindow feeds it, and Results.Update applies the Results' own filters unchanged."""
-        comp = self.Comparison
-        labelValuesSet = comp.indexLabelValues(groupByLabels)
-        if not labelValuesSet:
-            return None
-        if self._engines:
-            raise MuseError(B.MUSE_ERR_UNSUPPORTED, "RunInLagRange runs on one device")
-        r = self.Results
-        if lagLo > 0 or lagHi < 0:
-            raise MuseError(B.MUSE_ERR_INVALID, "RunInLagRange needs lagLo <= 0 <= lagHi")
-        series = comp._series_list()
-        gid = comp._group_ids()
-        G = len(labelValuesSet)
-        if G <= EXACT_FEED_MAX_GROUPS:
-            idx, lag, score, _ = self._batch().run_in_lag_range(lagLo, lagHi, gid, G, G, 0.0, SignFilter_ANY, abs_scores=True)
-        else:
-            idx, lag, score, _ = self._batch().run_in_lag_range(lagLo, lagHi, gid, G, r.TopN, r.Threshold, r.SignFilter, abs_scores=True)
-        order = np.argsort(gid[idx], kind="stable")
-        for k in order:
-            r.Update(Score(series[int(idx[k])].Labels(), int(lag[k]), float(score[k])))
-        return None
+        return self._feed_in_window(
+            groupByLabels, "RunInLagRange", lambda: (lagLo > 0 or lagHi < 0) and "lagLo <= 0 <= lagHi",
+            lambda db, *selection: db.run_in_lag_range(lagLo, lagHi, *selection),
+            exact=(SignFilter_ANY, True), wide=(self.Results.SignFilter, True))
 
     def RunSignedInLagRange(self, groupByLabels, lagLo, lagHi):
         """RunInLagRange with Results.SignFilter restricting the ARGMAX, not only filtering its answer
@@ -1680,27 +1544,11 @@ class Batch:
         (0, +0.0), which no sign filter passes), and Results.Update applies the Results' own filters unchanged.  Under a sign
         the Scores carry the SIGNED value, clamped to +-1 as Muse.Run's are (muse.go:72-76): Batch.Run reports magnitudes
         (muse_batch.go:74), which SignFilter_NEG never passes."""
-        comp = self.Comparison
-        labelValuesSet = comp.indexLabelValues(groupByLabels)
-        if not labelValuesSet:
-            return None
-        if self._engines:
-            raise MuseError(B.MUSE_ERR_UNSUPPORTED, "RunSignedInLagRange runs on one device")
-        r = self.Results
-        if lagLo > 0 or lagHi < 0:
-            raise MuseError(B.MUSE_ERR_INVALID, "RunSignedInLagRange needs lagLo <= 0 <= lagHi")
-        series = comp._series_list()
-        gid = comp._group_ids()
-        G = len(labelValuesSet)
-        mag = r.SignFilter == SignFilter_ANY
-        if G <= EXACT_FEED_MAX_GROUPS:
-            idx, lag, score, _ = self._batch().run_signed_in_lag_range(lagLo, lagHi, gid, G, G, 0.0, r.SignFilter, abs_scores=mag)
-        else:
-            idx, lag, score, _ = self._batch().run_signed_in_lag_range(lagLo, lagHi, gid, G, r.TopN, r.Threshold, r.SignFilter, abs_scores=mag)
-        order = np.argsort(gid[idx], kind="stable")
-        for k in order:
-            r.Update(Score(series[int(idx[k])].Labels(), int(lag[k]), float(score[k])))
-        return None
+        sign = self.Results.SignFilter
+        return self._feed_in_window(
+            groupByLabels, "RunSignedInLagRange", lambda: (lagLo > 0 or lagHi < 0) and "lagLo <= 0 <= lagHi",
+            lambda db, *selection: db.run_signed_in_lag_range(lagLo, lagHi, *selection),
+            exact=(sign, sign == SignFilter_ANY), wide=(sign, sign == SignFilter_ANY))
 
     def RunInLagBand(self, groupByLabels, lagLo, lagHi):
         """RunInLagRange for a lag band that need not hold lag 0 (muse_batch_run_in_lag_band): every series contributes its best
@@ -1708,41 +1556,47 @@ class Batch:
         RunInLagRange(0, k) reports lag 0 for every co-moving series.  A series with nothing in the band comes back as (0, +0.0).
         One device.  Results is fed exactly as RunInLagRange feeds it, and Results.Update applies the Results' own filters
         unchanged (its MaxLag included: set it to max(|lagLo|, |lagHi|) or wider to keep every lag of the band)."""
-        return self._run_in_lag_band(groupByLabels, lagLo, lagHi, False, "RunInLagBand")
+        # (the call's sign_filter is the argmax's sign too: beyond the exact feed the unsigned form pre-selects on the device WITHOUT a
+        # sign and leaves Results.SignFilter to Results.Update -- up to TopN of either sign reach it; RunInLagRange hands it down)
+        return self._feed_in_window(
+            groupByLabels, "RunInLagBand", lambda: lagLo > lagHi and "lagLo <= lagHi",
+            lambda db, *selection: db.run_in_lag_band(lagLo, lagHi, *selection),
+            exact=(SignFilter_ANY, True), wide=(SignFilter_ANY, True))
 
     def RunSignedInLagBand(self, groupByLabels, lagLo, lagHi):
         """RunInLagBand with Results.SignFilter restricting the ARGMAX (muse_batch_run_in_lag_band with the sign): under
         SignFilter_POS every series contributes its largest positive value inside the band, under SignFilter_NEG its most negative
         one; SignFilter_ANY is RunInLagBand.  Fed as RunSignedInLagRange feeds it: under a sign the Scores carry the signed
         value."""
-        return self._run_in_lag_band(groupByLabels, lagLo, lagHi, True, "RunSignedInLagBand")
+        sign = self.Results.SignFilter
+        return self._feed_in_window(
+            groupByLabels, "RunSignedInLagBand", lambda: lagLo > lagHi and "lagLo <= lagHi",
+            lambda db, *selection: db.run_in_lag_band(lagLo, lagHi, *selection),
+            exact=(sign, sign == SignFilter_ANY), wide=(sign, sign == SignFilter_ANY))
 
-    def _run_in_lag_band(self, groupByLabels, lagLo, lagHi, signed, who):
+    def _feed_in_window(self, groupByLabels, who, check, run, exact, wide):
+        """The one feed behind RunInWindow, RunInLagRange, RunSignedInLagRange, RunInLagBand and RunSignedInLagBand (feed_in_window in
+        muse.hpp).  who: the method's name for its refusals; check() -> what its arguments must satisfy when they do not;
+        run(device batch, group ids, G, top_n, threshold, sign_filter, abs_scores): its DeviceBatch call; exact / wide: the
+        (sign_filter, abs_scores) it asks for up to EXACT_FEED_MAX_GROUPS label groups / beyond."""
         comp = self.Comparison
         labelValuesSet = comp.indexLabelValues(groupByLabels)
         if not labelValuesSet:
             return None
         if self._engines:
             raise MuseError(B.MUSE_ERR_UNSUPPORTED, who + " runs on one device")
+        needs = check()
+        if needs:
+            raise MuseError(B.MUSE_ERR_INVALID, "%s needs %s" % (who, needs))
         r = self.Results
-        if lagLo > lagHi:
-            raise MuseError(B.MUSE_ERR_INVALID, who + " needs lagLo <= lagHi")
         series = comp._series_list()
         gid = comp._group_ids()
         G = len(labelValuesSet)
-        sign = r.SignFilter if signed else SignFilter_ANY
-        mag = sign == SignFilter_ANY
-        if G <= EXACT_FEED_MAX_GROUPS:
-            idx, lag, score, _ = self._batch().run_in_lag_band(lagLo, lagHi, gid, G, G, 0.0, sign, abs_scores=mag)
-        elif signed:
-            idx, lag, score, _ = self._batch().run_in_lag_band(lagLo, lagHi, gid, G, r.TopN, r.Threshold, sign, abs_scores=mag)
-        else:
-            # (the call's sign_filter is the argmax's sign too: the unsigned form pre-selects on the device without a sign and leaves
-            # Results.SignFilter to Results.Update -- up to TopN of either sign reach it)
-            idx, lag, score, _ = self._batch().run_in_lag_band(lagLo, lagHi, gid, G, r.TopN, r.Threshold, SignFilter_ANY, abs_scores=True)
-        order = np.argsort(gid[idx], kind="stable")
-        for k in order:
-            r.Update(Score(series[int(idx[k])].Labels(), int(lag[k]), float(score[k])))
+        if G <= EXACT_FEED_MAX_GROUPS:   # every group's winner, nothing filtered but NaN: Results.Update sees the reference's feed
+            idx, lag, score, _ = run(self._batch(), gid, G, G, 0.0, *exact)
+        else:                            # the device pre-selects TopN candidates
+            idx, lag, score, _ = run(self._batch(), gid, G, r.TopN, r.Threshold, *wide)
+        _feed_in_group_order(r, series, gid, idx, lag, score)
         return None
 
     def RunSigned(self, groupByLabels):
@@ -1865,9 +1719,7 @@ def _run_many_labels(batches, groupByLabels, each, run, sharded_ok, exact_feed):
     else:
         res = run(dbs, gid, G, r0.MaxLag, r0.TopN, r0.Threshold, r0.SignFilter, abs_scores=True)
     for b, (idx, lag, score, _) in zip(batches, res):
-        order = np.argsort(gid[idx], kind="stable")
-        for k in order:
-            b.Results.Update(Score(series[int(idx[k])].Labels(), int(lag[k]), float(score[k])))
+        _feed_in_group_order(b.Results, series, gid, idx, lag, score)
     return None
 
 
@@ -1925,18 +1777,26 @@ class Muse:
             raise
 
     def Run(self, compGraphs):                    # muse.go:46-92
+        return self._run(compGraphs, lambda: (), "run_rows", "run_group_rows")
+
+    def _run(self, compGraphs, window, run_rows, run_group_rows):
+        """The one run behind Run, RunWindowed and RunInLagRange (Muse::run in muse.hpp).  window() -> the lags the method scores inside,
+        as its DeviceBatch calls take them: (), (max_lag,) or (lag_lo, lag_hi); it raises the method's own refusal, which comes
+        behind the empty list and before the length check.  run_rows / run_group_rows: the names of the template's calls for host
+        rows / for rows that already live in one DeviceGroup (names: every refusal comes before the device side is touched)."""
         if len(compGraphs) == 0:
             return None
+        window = window()
         for s in compGraphs:                      # muse.go:68-70
             if s.Length() != self.refN:
                 raise MuseError(B.MUSE_ERR_LENGTH, "Encountered a comparison graph with differing length "
                                 "than the reference, %r" % (s.Labels(),))
         home = self._resident(compGraphs)
         if home is not None:      # every row already lives in one DeviceGroup on this engine: nothing crosses PCIe
-            win, state = self._template.run_group_rows(home[0], home[1], abs_scores=False)
+            win, state = getattr(self._template, run_group_rows)(home[0], home[1], *window, abs_scores=False)
         else:
             rows = np.stack([s.y for s in compGraphs])
-            win, state = self._template.run_rows(rows, abs_scores=False)      # one ABI call (muse_batch_run_rows)
+            win, state = getattr(self._template, run_rows)(rows, *window, abs_scores=False)      # one ABI call (muse_batch_run_rows*)
         if state == 1 and win["series"] >= 0:
             # the group's Score through the unchanged Update, which applies passed() as the reference does (results.go:55-72)
             self.Results.Update(Score(compGraphs[int(win["series"])].Labels(), int(win["lag"]), float(win["score"])))
@@ -1947,24 +1807,12 @@ class Muse:
         """Run with Results.MaxLag as a LAG WINDOW (muse_batch_run_rows_windowed / _run_group_rows_windowed): every series
         contributes its best match inside +-MaxLag, where Run takes its best match over all lags and Update then drops the group
         when that lies outside.  Same length check, same resident-row reuse, same Update as Run; Run itself never changes."""
-        if len(compGraphs) == 0:
-            return None
-        window = int(self.Results.MaxLag)
-        if window < 0 or window > B.MUSE_LAG_WINDOW_MAX:
-            raise MuseError(B.MUSE_ERR_UNSUPPORTED, "RunWindowed needs 0 <= Results.MaxLag <= %d" % B.MUSE_LAG_WINDOW_MAX)
-        for s in compGraphs:                      # muse.go:68-70
-            if s.Length() != self.refN:
-                raise MuseError(B.MUSE_ERR_LENGTH, "Encountered a comparison graph with differing length "
-                                "than the reference, %r" % (s.Labels(),))
-        home = self._resident(compGraphs)
-        if home is not None:
-            win, state = self._template.run_group_rows_windowed(home[0], home[1], window, abs_scores=False)
-        else:
-            rows = np.stack([s.y for s in compGraphs])
-            win, state = self._template.run_rows_windowed(rows, window, abs_scores=False)
-        if state == 1 and win["series"] >= 0:
-            self.Results.Update(Score(compGraphs[int(win["series"])].Labels(), int(win["lag"]), float(win["score"])))
-        return None
+        def window():
+            w = int(self.Results.MaxLag)
+            if w < 0 or w > B.MUSE_LAG_WINDOW_MAX:
+                raise MuseError(B.MUSE_ERR_UNSUPPORTED, "RunWindowed needs 0 <= Results.MaxLag <= %d" % B.MUSE_LAG_WINDOW_MAX)
+            return (w,)
+        return self._run(compGraphs, window, "run_rows_windowed", "run_group_rows_windowed")
 
     def RunInLagRange(self, compGraphs, lagLo, lagHi):
         """Run inside the lags lagLo .. lagHi, lagLo <= 0 <= lagHi (muse_batch_run_rows_in_lag_range / _run_group_rows_in_lag_range):
@@ -1972,24 +1820,12 @@ class Muse:
         of these series trails the reference by up to k samples?".  Same length check, same resident-row reuse, same Update as
         RunWindowed; Results is fed as Batch.RunInLagRange feeds it: the group's Score through Results.Update, which applies the
         Results' own filters unchanged.  Run itself never changes."""
-        if len(compGraphs) == 0:
-            return None
-        lagLo, lagHi = int(lagLo), int(lagHi)
-        if lagLo > 0 or lagHi < 0:
-            raise MuseError(B.MUSE_ERR_INVALID, "RunInLagRange needs lagLo <= 0 <= lagHi")
-        for s in compGraphs:                      # muse.go:68-70
-            if s.Length() != self.refN:
-                raise MuseError(B.MUSE_ERR_LENGTH, "Encountered a comparison graph with differing length "
-                                "than the reference, %r" % (s.Labels(),))
-        home = self._resident(compGraphs)
-        if home is not None:
-            win, state = self._template.run_group_rows_in_lag_range(home[0], home[1], lagLo, lagHi, abs_scores=False)
-        else:
-            rows = np.stack([s.y for s in compGraphs])
-            win, state = self._template.run_rows_in_lag_range(rows, lagLo, lagHi, abs_scores=False)
-        if state == 1 and win["series"] >= 0:
-            self.Results.Update(Score(compGraphs[int(win["series"])].Labels(), int(win["lag"]), float(win["score"])))
-        return None
+        def window():
+            lo, hi = int(lagLo), int(lagHi)
+            if lo > 0 or hi < 0:
+                raise MuseError(B.MUSE_ERR_INVALID, "RunInLagRange needs lagLo <= 0 <= lagHi")
+            return lo, hi
+        return self._run(compGraphs, window, "run_rows_in_lag_range", "run_group_rows_in_lag_range")
 
     def _resident(self, compGraphs):
         """(DeviceGroup, rows) when reuse is on and every series has a live home in ONE DeviceGroup on this engine"""
