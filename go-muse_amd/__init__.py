@@ -22,3 +22,6 @@ from .muse import (Batch, DefaultLabel, DeviceBatch, DeviceGroup, Engine, Group,
                    RunManyInLagRange, run_many_in_lag_range, score_many_in_lag_range, scores_many_in_lag_range, many_lag_range_plan,
                    window_many_plan_rows,
                    merge_group_records, merge_group_winners)
+from . import many_band  # noqa: F401
+from .many_band import (RunManyInLagBand, RunManySignedInLagBand, run_many_in_lag_band, score_many_in_lag_band,  # noqa: F401
+                        scores_many_in_lag_band, many_lag_band_plan)

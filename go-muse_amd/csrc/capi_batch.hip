@@ -816,6 +816,12 @@ extern "C" int muse_batch_kernel_name(muse_batch *b, char *name, int32_t cap)
     const ScoreOrigin &o = b->origin; // (the in-window and packed kinds: an argument of a call, not a setting the next pass takes)
     if (o.slide == MUSE_SLIDE_IN_WINDOW_FUSED) { // (muse_batch_slide_score_in_window's one kernel: plain or masked argmax)
         snprintf(k, sizeof(k), "xcorr_fused_n4096_fold<false, %s, %s, %s, true>", padded, f32, o.kind == ScoreOrigin::MASKED ? "true" : "false");
+    } else if (o.kind == ScoreOrigin::MASKED && o.variant == ScoreOrigin::MANY && (o.sign != 0 || o.window.band())) {
+        // (muse_batch_score_many_in_lag_band's one masked pass: n = 4096, and n = 512 ... 2048 on float64 rows)
+        if (b->n == 4096)
+            snprintf(k, sizeof(k), "xcorr_fused_n4096_fold_multi_band<%s, %s, %d, %s>", padded, f32, o.sign, o.window.band() ? "true" : "false");
+        else
+            snprintf(k, sizeof(k), "xcorr_fused_small_many_band<%d, %s, %d, %s>", b->logn, padded, o.sign, o.window.band() ? "true" : "false");
     } else if (o.kind == ScoreOrigin::MASKED && o.window.band()) { // (muse_batch_score_in_lag_band: the band builds, any sign)
         if (b->n == 4096)
             snprintf(k, sizeof(k), "xcorr_fused_n4096_%s_band<%s, %s, %d>", o.variant == KERNEL_R16_OCC3 ? "occ4" : "fold", padded, f32, o.sign);
@@ -845,6 +851,9 @@ extern "C" int muse_batch_kernel_name(muse_batch *b, char *name, int32_t cap)
     } else if (o.kind == ScoreOrigin::MFMA) { // (the direct product with the call's window, whatever the batch's own setting)
         snprintf(k, sizeof(k), "xcorr_window_mfma<%d, %s>", o.mfma_tiles(),
                  window_wide(b->g->rows, b->g->stride) ? "true" : "false");
+    } else if (o.kind == ScoreOrigin::PACKED && (o.sign != 0 || o.window.band())) { // (muse_batch_score_many_in_lag_band's packed launches)
+        snprintf(k, sizeof(k), "xcorr_window_many_signed_mfma<%d, %s, %d, %s>", o.tiles, window_wide(b->g->rows, b->g->stride) ? "true" : "false",
+                 o.sign, o.window.band() ? "true" : "false");
     } else if (o.kind == ScoreOrigin::PACKED) {
         snprintf(k, sizeof(k), "xcorr_window_many_mfma<%d, %s>", o.tiles, window_wide(b->g->rows, b->g->stride) ? "true" : "false");
     } else if (b->windowed()) {

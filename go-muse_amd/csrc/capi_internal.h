@@ -557,6 +557,10 @@ inline void set_window(muse::FusedParams &p, const LagRange &w)
 // capi_window.hip: a call's lags lag_lo .. lag_hi against the batch's own window, which must be off or equal, i.e. L with -L .. L the
 // call's (r: the batch's index in a list, -1: a single batch)
 int check_own_window(const muse_batch *b, int32_t lag_lo, int32_t lag_hi, int r = -1);
+// capi_window.hip, the band calls' own argument checks (a sign of -1 .. 1, lag_lo <= lag_hi) and the refusal of a band of which
+// nothing is left inside the lags of FFT length n: shared by muse_batch_score_in_lag_band and muse_batch_score_many_in_lag_band
+int check_band_args(int32_t lag_lo, int32_t lag_hi, int32_t sign);
+int fail_empty_band(int32_t lag_lo, int32_t lag_hi, int64_t n);
 // Results.MaxLag of a Run inside lag_lo .. lag_hi: max(-lag_lo, lag_hi), every lag of the range passes the lag filter
 inline int32_t range_max_lag(int32_t lag_lo, int32_t lag_hi)
 {
@@ -595,8 +599,9 @@ int check_batch_list(muse_batch *const *bs, int32_t R);
 enum ManyKind { MANY_NONE, MANY_SMALL, MANY_MULTI, MANY_LONG, MANY_REAL };
 ManyKind many_kind(muse_batch *const *bs, int32_t R);
 // ONE pass of the `kind` kernels over the rows for every batch of a checked list; mask != nullptr: the argmax masked to it (SMALL at
-// n <= 2048 and MULTI only)
-int score_many_pass(muse_batch *const *bs, int32_t R, ManyKind kind, const LagRange *mask);
+// n <= 2048 and MULTI only); sign (with a mask): +-1 = the signed mask; a band mask and a sign reach the redo launches too
+// (muse_batch_score_many_in_lag_band)
+int score_many_pass(muse_batch *const *bs, int32_t R, ManyKind kind, const LagRange *mask, int sign = 0);
 // every lag for a checked list: that one pass where a kernel family serves the list, batch_score(., each) batch after batch otherwise
 int score_many_every_lag(muse_batch *const *bs, int32_t R, const ScorePass &each);
 // batches of one group share N, and with it (muse_batch_create) the FFT length; a list that does not is scored reference by reference
@@ -608,8 +613,9 @@ inline bool one_length(muse_batch *const *bs, int32_t R)
     return same;
 }
 // capi_window_many.hip: the direct product inside w for a checked list of float64 batches of one length with time-domain references,
-// packed launches where the planner packs; alone: what names a reference that fills its launch alone
-int score_many_direct(muse_batch *const *bs, int32_t R, LagRange w, const ScoreOrigin &alone);
+// packed launches where the planner packs; alone: what names a reference that fills its launch alone; sign / a band w: the signed /
+// band scan (muse_batch_score_many_in_lag_band)
+int score_many_direct(muse_batch *const *bs, int32_t R, LagRange w, const ScoreOrigin &alone, int sign = 0);
 // the Run of every batch of a scored list: run_select, then emit into row r of the caller's arrays
 int run_many_select(muse_batch *const *bs, int32_t R, const int32_t *group_id, int32_t G, int32_t max_lag, int32_t top_n,
                     double threshold, int32_t sign_filter, int32_t abs_scores, bool prescreened, int64_t *out_series,

@@ -90,7 +90,7 @@ ManyKind many_kind(muse_batch *const *bs, int32_t R)
     return small_n ? MANY_SMALL : real_n ? MANY_REAL : long_n ? MANY_LONG : MANY_MULTI;
 }
 
-int score_many_pass(muse_batch *const *bs, int32_t R, ManyKind kind, const LagRange *mask)
+int score_many_pass(muse_batch *const *bs, int32_t R, ManyKind kind, const LagRange *mask, int sign)
 {
     muse_batch *b0 = bs[0];
     muse_ctx *ctx = b0->ctx;
@@ -138,8 +138,10 @@ int score_many_pass(muse_batch *const *bs, int32_t R, ManyKind kind, const LagRa
     p.c1_many = (const double *const *)(t + 3 * R);
     p.zscratch = ctx->zscratch.p; // (read at n = 16384 only)
     p.zslots = (int)(ctx->zscratch.cap / 4096);
-    if (mask) // (the two bounds as the caller clipped them)
+    if (mask) { // (the two bounds as the caller clipped them; a band: its one interval; the sign of muse_batch_score_many_in_lag_band)
         set_window(p, *mask);
+        p.win_sign = sign;
+    }
     HIP_TRY(b0->ovf_list.ensure(ctx, 2 * p.npairs, b0->stream()));
     p.ovf_count = b0->ovf_count;
     p.work_counter = b0->ovf_count + 1;
@@ -174,8 +176,10 @@ int score_many_pass(muse_batch *const *bs, int32_t R, ManyKind kind, const LagRa
         FusedParams q = base_params(bs[r]);
         q.pair_list = b0->ovf_list.p;
         q.pair_count = b0->ovf_count;
-        if (mask) // the redone pairs keep their window (the WIN build of the redo kernel)
+        if (mask) { // the redone pairs keep their window (the WIN build of the redo kernel), its sign and its band
             set_window(q, *mask);
+            q.win_sign = sign;
+        }
         if (long_n) { // (the four-step kernel that isolates and rescales first, as behind a single long-series pass)
             q.npairs = std::min<long long>(q.npairs, (long long)ctx->num_cus * STOCKHAM_GLOBAL_WGS_PER_CU);
             HIP_TRY(launch_fused(q, KERNEL_STOCKHAM, ctx->num_cus, ctx->stream));
@@ -192,6 +196,7 @@ int score_many_pass(muse_batch *const *bs, int32_t R, ManyKind kind, const LagRa
             b->last_path = MUSE_RUN_PATH_FP64;
             b->last_screened = false;
             b->origin = ScoreOrigin::in_window(MUSE_IN_WINDOW_MASKED, *mask, ScoreOrigin::MANY);
+            b->origin.sign = sign;
         }
     }
     return MUSE_OK;

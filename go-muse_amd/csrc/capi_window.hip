@@ -386,7 +386,7 @@ extern "C" int muse_batch_run_signed_in_lag_range(muse_batch *b, const int32_t *
 // holds lag 0 IS the signed range call; one that does not is a LagRange with lag 0 outside (capi_internal.h: band()), which
 // window_plan / signed_window_plan dispatch by its rows as they are -- never every lag -- and score_direct / batch_score send to the
 // band builds of the kernels (xcorr_window_band_mfma; the BAND builds of the masked transform kernels)
-static int check_band_args(int32_t lag_lo, int32_t lag_hi, int32_t sign)
+int check_band_args(int32_t lag_lo, int32_t lag_hi, int32_t sign)
 {
     if (sign != MUSE_SIGN_ANY && sign != MUSE_SIGN_POS && sign != MUSE_SIGN_NEG)
         return fail(MUSE_ERR_INVALID, "sign %d: one of MUSE_SIGN_ANY (0), MUSE_SIGN_POS (1), MUSE_SIGN_NEG (-1)", sign);
@@ -395,7 +395,7 @@ static int check_band_args(int32_t lag_lo, int32_t lag_hi, int32_t sign)
     return MUSE_OK;
 }
 
-static int fail_empty_band(int32_t lag_lo, int32_t lag_hi, int64_t n)
+int fail_empty_band(int32_t lag_lo, int32_t lag_hi, int64_t n)
 {
     return fail(MUSE_ERR_INVALID, "nothing of the lag band %d .. %d is left inside the lags %lld .. %lld of FFT length %lld", lag_lo, lag_hi,
                 -(long long)(n / 2 - 1), (long long)(n / 2), (long long)n);

@@ -74,8 +74,9 @@ extern "C" int muse_batch_score_many_windowed(muse_batch *const *bs, int32_t R, 
 }
 
 // The direct product inside w for a checked list of one length, in as few launches as the planner gives.  Each batch's tables are its
-// own, cached as score_direct caches them (window_tables): the packed and the single pass serve each other's tables.
-int score_many_direct(muse_batch *const *bs, int32_t R, LagRange w, const ScoreOrigin &alone)
+// own, cached as score_direct caches them (window_tables): the packed and the single pass serve each other's tables.  sign != 0 or a
+// band w: the signed / band scan (launch_window_many_signed; a reference alone: launch_window_signed / launch_window_band)
+int score_many_direct(muse_batch *const *bs, int32_t R, LagRange w, const ScoreOrigin &alone, int sign)
 {
     muse_batch *b0 = bs[0];
     muse_ctx *ctx = b0->ctx;
@@ -124,7 +125,7 @@ int score_many_direct(muse_batch *const *bs, int32_t R, LagRange w, const ScoreO
         while (r1 < R && launch_of[(size_t)r1] == launch_of[(size_t)r0])
             r1++;
         if (r1 - r0 == 1) { // a reference that fills its launch alone: the single-reference kernel
-            rc = score_direct(bs[r0], w, false);
+            rc = score_direct(bs[r0], w, false, sign);
             if (rc)
                 return rc;
         } else {
@@ -135,13 +136,17 @@ int score_many_direct(muse_batch *const *bs, int32_t R, LagRange w, const ScoreO
             p.pw = (const double *const *)(tab_dev + R + r0);
             p.mv = (double *const *)(tab_dev + 2 * R + r0);
             p.lag = (int *const *)(tab_dev + 3 * R + r0);
-            HIP_TRY(launch_window_many(p, st));
+            HIP_TRY(launch_window_many_signed(p, sign, st)); // (no sign, lag 0 inside: launch_window_many)
         }
         for (int r = r0; r < r1; r++) {
             bs[r]->scores_exact = true;
             bs[r]->last_path = MUSE_RUN_PATH_FP64;
             bs[r]->last_screened = false;
             bs[r]->origin = r1 - r0 > 1 ? ScoreOrigin::packed(tiles_of[(size_t)launch_of[(size_t)r0]]) : alone;
+            if (r1 - r0 > 1 && (sign != 0 || w.band())) { // (what names the packed signed / band kernel)
+                bs[r]->origin.window = w;
+                bs[r]->origin.sign = sign;
+            }
         }
         r0 = r1;
     }

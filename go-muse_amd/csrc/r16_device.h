@@ -148,6 +148,28 @@ __device__ __forceinline__ void mask_window_quot(double2 (&v)[16], const int bas
     }
 }
 
+// mask_window_quot with the sign and / or the band (muse_batch_score_many_in_lag_band; a function of its own, so that the one above
+// keeps its text): the same two quotients in the same two registers.  BAND: the window is the ONE index interval nl <= index <= lpos
+// (FusedParams::win_a / ::win_b), so register m is inside iff ceil((nl - base) / STEP) <= m <= floor((lpos - base) / STEP): the two
+// compares and'ed instead of or'ed.  SGN: mask_keeps unchanged -- per component one more compare against the literal 0.0.  No
+// register and no literal beyond those of the mask above.
+template <bool BITREV, int STEP, int SGN, bool BAND>
+__device__ __forceinline__ void mask_window_quot_band(double2 (&v)[16], const int base, const int lpos, const int nl)
+{
+    static_assert(STEP > 0 && (STEP & (STEP - 1)) == 0, "the quotients are shifts");
+    static_assert(SGN != 0 || BAND, "by magnitude inside a window that holds lag 0: mask_window_quot");
+    constexpr int SH = __builtin_ctz(STEP);
+    int a = (lpos - base) >> SH, b = (nl - base + STEP - 1) >> SH;
+    asm volatile("" : "+v"(a), "+v"(b));
+#pragma unroll
+    for (int m = 0; m < 16; m++) {
+        const int k = BITREV ? ((m & 1) << 3) | ((m & 2) << 1) | ((m & 4) >> 1) | ((m & 8) >> 3) : m;
+        const bool in = BAND ? (m <= a && m >= b) : (m <= a || m >= b);
+        v[k].x = mask_keeps<SGN>(in, v[k].x) ? v[k].x : 0.0;
+        v[k].y = mask_keeps<SGN>(in, v[k].y) ? v[k].y : 0.0;
+    }
+}
+
 // One LDS transpose in two half rounds through the 8 x 272 buffer (positions in
 // double2 units).  Layouts (same bank analysis as xcorr_kernels.hip):
 //   A: writer (b = hi, c = lo) output k1 -> 272*(k1&7) + t

@@ -304,6 +304,10 @@ int window_many_kc(int W, int refs);
 int window_many_plan(int R, int W, int *launch_of, int *tiles_of);
 // (every reference's table has the shape's origin and rows: origin + L <= 2 MUSE_LAG_WINDOW_MAX, Lneg <= origin)
 hipError_t launch_window_many(WindowManyParams p, hipStream_t stream);
+// ---- the packed pass under a sign or over a lag band (xcorr_window_many_band.hip; muse_batch_score_many_in_lag_band): the same
+// product, planner and launch sizes with the scan of launch_window_signed / launch_window_band (xcorr_window_many_signed_mfma).  A band
+// is the shape L = hi, Lneg = origin = -lo with one of L, Lneg negative; sign = 0 over a window that holds lag 0 is launch_window_many
+hipError_t launch_window_many_signed(WindowManyParams p, int sign, hipStream_t stream);
 hipError_t launch_direct(const double *x, int lenx, const double *y, int leny, int n, int normalize_x,
                          int normalize_y, double x_scale, double cc_scale, double *cc, int *lag, double *mv,
                          int *status, hipStream_t stream);

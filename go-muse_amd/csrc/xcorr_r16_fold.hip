@@ -171,7 +171,9 @@ constexpr int MULTI_WGS_PER_CU = 2;
 // TIMING: the phase-stamped build of tools/ablate/multi_phases.hip (FusedParams::dbg); the product kernel below is <.., false>.
 // WIN: masked argmax (muse_batch_score_many_in_window): every reference's values outside the ONE lag window p.win_lpos / p.win_lneg
 // are replaced by +0.0 right in front of its argmax (behind the PADDED correction), as in xcorr_fused_n4096_fold
-template <bool PADDED, bool F32, bool TIMING, bool WIN = false>
+// SGN / BAND (with WIN; muse_batch_score_many_in_lag_band): the sign and / or the one index interval p.win_a .. p.win_b in the mask
+// (mask_window_quot_band); 0 / false is the build above, its mask call unchanged
+template <bool PADDED, bool F32, bool TIMING, bool WIN = false, int SGN = 0, bool BAND = false>
 __device__ __forceinline__ void fold_multi_body(const FusedParams &p)
 {
     using namespace occ4;
@@ -249,7 +251,9 @@ __device__ __forceinline__ void fold_multi_body(const FusedParams &p)
         gdft16_nr_s4(v, g3[4], g3[5], g3[6], g3[7]);
         if (PADDED) // with reference r's table
             correct_padded<4>(v, uniform_ptr(p.c1_many[r]), t, st[8] * invN, st[9] * invN);
-        if (WIN) // cc index t + 256 m3 at v[BR16(m3)]
+        if constexpr (WIN && (SGN != 0 || BAND)) // cc index t + 256 m3 at v[BR16(m3)]
+            mask_window_quot_band<true, 256, SGN, BAND>(v, tl<true>(t), BAND ? p.win_b : p.win_lpos, BAND ? p.win_a : 4096 - p.win_lneg);
+        else if (WIN)
             mask_window_quot<true, 256>(v, tl<true>(t), p.win_lpos, 4096 - p.win_lneg);
         clk.template stamp<11>();
         wave_argmax_store(v, wave, lane, tr + 6 * wave);
@@ -345,6 +349,15 @@ __global__ __launch_bounds__(OCC_THREADS, MULTI_WGS_PER_CU) void xcorr_fused_n40
     fold_multi_body<PADDED, F32, false, WIN>(p);
 }
 
+// the WIN build with the signed and / or the band mask (muse_batch_score_many_in_lag_band; FusedParams::win_sign / ::win_band): one
+// sign and one window or band for every reference; a kernel of its own, so that xcorr_fused_n4096_fold_multi keeps its symbols
+template <bool PADDED, bool F32, int SGN, bool BAND>
+__global__ __launch_bounds__(OCC_THREADS, MULTI_WGS_PER_CU) void xcorr_fused_n4096_fold_multi_band(const FusedParams p)
+{
+    static_assert(SGN != 0 || BAND, "by magnitude inside a window that holds lag 0: xcorr_fused_n4096_fold_multi<PADDED, F32, true>");
+    fold_multi_body<PADDED, F32, false, true, SGN, BAND>(p);
+}
+
 // R >= 1 references, n == 4096 (N < 4096: p.c1_many); p.ovf_count and p.work_counter zeroed; a resident grid
 // (pairs are handed out dynamically)
 hipError_t launch_fused_multi(const FusedParams &p_in, int num_cus, hipStream_t stream)
@@ -354,8 +367,20 @@ hipError_t launch_fused_multi(const FusedParams &p_in, int num_cus, hipStream_t 
     if (!p.work_counter || p.R < 1 || !p.g2 || !p.g3a || !p.g3b || !p.xcp_many || !p.mv_many || !p.lag_many)
         return hipErrorInvalidValue;
     const dim3 g((unsigned)grid), b(OCC_THREADS);
-    if ((p.N < 4096 && !p.c1_many) || !window_bounds_ok(p) || p.win_sign || p.win_band) // (one window for every reference: muse_batch_score_many_in_window; no signed build, no band build)
+    if ((p.N < 4096 && !p.c1_many) || !window_bounds_ok(p)) // (one window for every reference: muse_batch_score_many_in_window)
         return hipErrorInvalidValue;
+    if (p.win_sign || p.win_band) { // one sign and one window or band for every reference (muse_batch_score_many_in_lag_band)
+        if (!p.win || p.win_sign < -1 || p.win_sign > 1)
+            return hipErrorInvalidValue;
+        with_bools([&](auto padded, auto f32, auto band) {
+            with_sign(p.win_sign, [&](auto sgn) {
+                if constexpr (decltype(sgn)::value != 0 || decltype(band)::value)
+                    hipLaunchKernelGGL((xcorr_fused_n4096_fold_multi_band<decltype(padded)::value, decltype(f32)::value, decltype(sgn)::value, decltype(band)::value>),
+                                       g, b, 0, stream, p);
+            });
+        }, p.N < 4096, p.rows32 != nullptr, p.win_band != 0);
+        return hipGetLastError();
+    }
     with_bools([&](auto padded, auto f32, auto win) {
         hipLaunchKernelGGL((xcorr_fused_n4096_fold_multi<decltype(padded)::value, decltype(f32)::value, decltype(win)::value>), g, b, 0, stream, p);
     }, p.N < 4096, p.rows32 != nullptr, p.win != 0);

@@ -82,6 +82,15 @@ __global__ __launch_bounds__((LOGN >= 11 ? (1 << LOGN) / 16 : 256), 4) void xcor
     constexpr bool MULTI = false, WIN = true, BAND = true;
 #include "xcorr_small_body.h"
 }
+// the MULTI + WIN build with the signed and / or the band mask (muse_batch_score_many_in_lag_band): R references in one pass, one
+// sign and one window or band for all of them; float64 rows, as every MULTI + WIN build (SGN = 0 without BAND is xcorr_fused_small's)
+template <int LOGN, bool PADDED, int SGN, bool BAND>
+__global__ __launch_bounds__((LOGN >= 11 ? (1 << LOGN) / 16 : 256), 2) void xcorr_fused_small_many_band(const FusedParams p)
+{
+    static_assert(SGN != 0 || BAND, "by magnitude inside a window that holds lag 0: xcorr_fused_small<LOGN, PADDED, true, false, true>");
+    constexpr bool MULTI = true, F32 = false, WIN = true;
+#include "xcorr_small_body.h"
+}
 
 // The batched two-sided xCorr (xcorr.go:102-153) on the same transforms: pair i = (x_i, y_i), each zero-padded
 // in front on its own (any Nx, Ny <= n).  With xr[j] = x[-j mod n] (the row read backwards: an address pattern) and
@@ -272,10 +281,10 @@ static hipError_t launch_small_n(const FusedParams &p, int num_cus, hipStream_t 
     const long long ngroups = (p.npairs + G - 1) / G;
     if (p.R > 1 && p.win && LOGN > 11)
         return hipErrorInvalidValue; // (the masked argmax is built for n = 512, 1024, 2048)
-    if (p.win_sign && (p.R > 1 || !p.win || (p.win_sign != 1 && p.win_sign != -1)))
-        return hipErrorInvalidValue; // (the signed mask: one reference, a window, a sign of +-1)
-    if (p.win_band && (p.R > 1 || !p.win || LOGN > 11 || !band_bounds_ok(p, 1 << LOGN)))
-        return hipErrorInvalidValue; // (the band mask: one reference, a window, one index interval on one side of lag 0)
+    if (p.win_sign && (!p.win || LOGN > 11 || (p.win_sign != 1 && p.win_sign != -1)))
+        return hipErrorInvalidValue; // (the signed mask: a window, a sign of +-1; R > 1: xcorr_fused_small_many_band)
+    if (p.win_band && (!p.win || LOGN > 11 || !band_bounds_ok(p, 1 << LOGN)))
+        return hipErrorInvalidValue; // (the band mask: a window, one index interval on one side of lag 0; R > 1: xcorr_fused_small_many_band)
     if (p.R > 1) { // one pass for R references: exactly the resident workgroups (n = 16384: each with its slice of the spectrum scratch)
         constexpr bool ZREG = LOGN <= 13;
         if (!p.xcp_many || !p.mv_many || !p.lag_many || (!ZREG && !p.zscratch))
@@ -287,6 +296,16 @@ static hipError_t launch_small_n(const FusedParams &p, int num_cus, hipStream_t 
             if (p.win) { // the masked argmax, one window for every reference (muse_batch_score_many_in_window)
                 if (p.pair_list || p.win_lpos < 0 || p.win_lneg < 0 || p.win_lpos > (1 << LOGN) / 2 || p.win_lneg > (1 << LOGN) / 2 - 1)
                     return hipErrorInvalidValue;
+                if (p.win_sign || p.win_band) { // one sign and one band for every reference (muse_batch_score_many_in_lag_band)
+                    with_bools([&](auto padded, auto band) {
+                        with_sign(p.win_sign, [&](auto sgn) {
+                            if constexpr (decltype(sgn)::value != 0 || decltype(band)::value)
+                                hipLaunchKernelGGL((xcorr_fused_small_many_band<LOGN, decltype(padded)::value, decltype(sgn)::value, decltype(band)::value>),
+                                                   dim3((unsigned)grid), dim3(TPB), 0, stream, p);
+                        });
+                    }, p.N < (1 << LOGN), p.win_band != 0);
+                    return hipGetLastError();
+                }
                 if (p.N < (1 << LOGN))
                     hipLaunchKernelGGL((xcorr_fused_small<LOGN, true, true, false, true>), dim3((unsigned)grid), dim3(TPB), 0, stream, p);
                 else

@@ -32,6 +32,8 @@ namespace muse {
 
 constexpr int WINM_STAGE = 3; // image samples per thread and reference in one batch of staging loads
 
+// (xcorr_window_many_band.hip holds a copy of this body with the signed / band scan, xcorr_window_many_signed_mfma, kept apart so that this
+// kernel keeps its symbols and its code: a fix to the staging, the k-loop or the scan's cut is made in both)
 template <int TILES, bool WIDE>
 __global__ __launch_bounds__(WIN_THREADS) void xcorr_window_many_mfma(const WindowManyParams p)
 {

@@ -1050,7 +1050,49 @@ func RunManyInLagRange(batches []*Batch, groupByLabels []string, lagLo, lagHi in
 		})
 }
 
-// runManyInLags is what RunManyInWindow and RunManyInLagRange share: the batches that qualify (otherwise each, batch after batch),
+// RunManyInLagBand is RunMany inside the lag band lagLo .. lagHi, which need not hold lag 0 (muse_batch_run_many_in_lag_band): every
+// batch receives what its own RunInLagBand gives -- the argmax by magnitude, the Results' own filters applied afterwards -- from
+// one pass over the rows.  One device.  Batches that do not qualify for RunMany are RunInLagBand one after the other.
+func RunManyInLagBand(batches []*Batch, groupByLabels []string, lagLo, lagHi int) error {
+	if lagLo > lagHi {
+		return fmt.Errorf("RunManyInLagBand: lagLo <= lagHi")
+	}
+	return runManyInLags(batches, groupByLabels, "RunManyInLagBand",
+		func(b *Batch) error { return b.RunInLagBand(groupByLabels, lagLo, lagHi) },
+		func() error { return nil },
+		func(hs **C.muse_batch, R, G, topN C.int32_t, gid *C.int32_t, threshold C.double, sign C.int32_t, idx *C.int64_t,
+			lag *C.int32_t, score *C.double, cnt *C.int32_t, mean *C.double) C.int {
+			return C.muse_batch_run_many_in_lag_band(hs, R, gid, G, C.int32_t(lagLo), C.int32_t(lagHi), topN, threshold, 0, 1, idx,
+				lag, score, cnt, mean)
+		})
+}
+
+// RunManySignedInLagBand is RunManyInLagBand with the shared Results.SignFilter restricting the ARGMAX: every batch receives what
+// its own RunSignedInLagBand gives; under a sign the Scores carry the signed value.  Batches that do not qualify are
+// RunSignedInLagBand one after the other, each under its own filter.
+func RunManySignedInLagBand(batches []*Batch, groupByLabels []string, lagLo, lagHi int) error {
+	if lagLo > lagHi {
+		return fmt.Errorf("RunManySignedInLagBand: lagLo <= lagHi")
+	}
+	if len(batches) == 0 {
+		return nil
+	}
+	filter := C.int32_t(batches[0].Results.SignFilter)
+	abs := C.int32_t(0)
+	if filter == 0 {
+		abs = 1
+	}
+	return runManyInLags(batches, groupByLabels, "RunManySignedInLagBand",
+		func(b *Batch) error { return b.RunSignedInLagBand(groupByLabels, lagLo, lagHi) },
+		func() error { return nil },
+		func(hs **C.muse_batch, R, G, topN C.int32_t, gid *C.int32_t, threshold C.double, sign C.int32_t, idx *C.int64_t,
+			lag *C.int32_t, score *C.double, cnt *C.int32_t, mean *C.double) C.int {
+			return C.muse_batch_run_many_in_lag_band(hs, R, gid, G, C.int32_t(lagLo), C.int32_t(lagHi), topN, threshold, filter, abs,
+				idx, lag, score, cnt, mean)
+		})
+}
+
+// runManyInLags is what RunManyInWindow, RunManyInLagRange and RunManyInLagBand share: the batches that qualify (otherwise each, batch after batch),
 // pre (the form's own refusal once they do), the label groups, the resident rows, the handles, the call (one of the library's
 // _run_many_in_ entry points) and the feed of every Results in group order.
 func runManyInLags(batches []*Batch, groupByLabels []string, name string, each func(*Batch) error, pre func() error,

@@ -1275,7 +1275,44 @@ public:
             });
     }
 
-    // what RunManyInWindow and RunManyInLagRange share: the batches that qualify (one Comparison, one engine, one device, the same
+    // RunMany inside the lag band lagLo .. lagHi, which need not hold lag 0 (muse_batch_run_many_in_lag_band): every batch receives
+    // what its own RunInLagBand gives -- the argmax by magnitude, the Results' own filters applied afterwards -- from one pass over
+    // the rows.  One device.  Batches that do not qualify for RunMany are RunInLagBand one by one.
+    static void RunManyInLagBand(const std::vector<std::shared_ptr<Batch>> &batches, const std::vector<std::string> &groupByLabels,
+                                 int lagLo, int lagHi)
+    {
+        if (lagLo > lagHi)
+            throw Error(MUSE_ERR_INVALID, "RunManyInLagBand: lagLo <= lagHi");
+        feed_many_in_window(
+            batches, groupByLabels, [&](Batch &b) { b.RunInLagBand(groupByLabels, lagLo, lagHi); }, [] {},
+            [&](muse_batch *const *hs, int32_t R, const int32_t *gid, int32_t G, int32_t top, double threshold, int32_t, int64_t *idx,
+                int32_t *lag, double *score, int32_t *cnt, double *mean) {
+                return muse_batch_run_many_in_lag_band(hs, R, gid, G, (int32_t)lagLo, (int32_t)lagHi, top, threshold, 0, 1, idx, lag, score,
+                                                       cnt, mean);
+            });
+    }
+
+    // RunManyInLagBand with the shared Results.SignFilter restricting the ARGMAX: every batch receives what its own
+    // RunSignedInLagBand gives; under a sign the Scores carry the signed value.  Batches that do not qualify are RunSignedInLagBand
+    // one by one, each under its own filter.
+    static void RunManySignedInLagBand(const std::vector<std::shared_ptr<Batch>> &batches, const std::vector<std::string> &groupByLabels,
+                                       int lagLo, int lagHi)
+    {
+        if (lagLo > lagHi)
+            throw Error(MUSE_ERR_INVALID, "RunManySignedInLagBand: lagLo <= lagHi");
+        if (batches.empty())
+            return;
+        const int32_t filter = (int32_t)batches[0]->Results_->Filter;
+        feed_many_in_window(
+            batches, groupByLabels, [&](Batch &b) { b.RunSignedInLagBand(groupByLabels, lagLo, lagHi); }, [] {},
+            [&](muse_batch *const *hs, int32_t R, const int32_t *gid, int32_t G, int32_t top, double threshold, int32_t, int64_t *idx,
+                int32_t *lag, double *score, int32_t *cnt, double *mean) {
+                return muse_batch_run_many_in_lag_band(hs, R, gid, G, (int32_t)lagLo, (int32_t)lagHi, top, threshold, filter,
+                                                       filter == 0 ? 1 : 0, idx, lag, score, cnt, mean);
+            });
+    }
+
+    // what RunManyInWindow, RunManyInLagRange and RunManyInLagBand share: the batches that qualify (one Comparison, one engine, one device, the same
     // Results settings; otherwise `each` batch by batch), `pre` (the form's own refusal once they do), the label groups, the call (one
     // of the library's _run_many_in_ entry points) and the feed of every Results in group order
     template <class Each, class Pre, class Call>

@@ -445,7 +445,7 @@ int muse_batch_run_in_lag_range(muse_batch *b, const int32_t *group_id, int32_t 
  * muse_batch_run_in_window), Results.MaxLag = max(-lag_lo, lag_hi).  A label group's maximum is then taken over its members' best
  * values OF THE SIGN: a group whose first-by-magnitude member has the wrong sign is no longer dropped whole.  sign_filter == 0 is
  * muse_batch_run_in_lag_range.
- * Limits: the many-references forms, the slide forms, the Muse.Run rows forms, the muse_batch_set_lag_window setting (a batch's own
+ * Limits: the slide forms, the Muse.Run rows forms, the muse_batch_set_lag_window setting (a batch's own
  * window is unsigned), the multi-device and dist.py layers; signed passes where the table above says MUSE_ERR_UNSUPPORTED (every
  * lag, more than 127 lags or float32 storage outside FFT lengths 512 ... 4096). */
 int muse_batch_score_signed_in_lag_range(muse_batch *b, int32_t lag_lo, int32_t lag_hi, int32_t sign);
@@ -481,7 +481,7 @@ int muse_batch_run_signed_in_lag_range(muse_batch *b, const int32_t *group_id, i
  * muse_batch_run_in_lag_band is that pass followed by Batch.Run's selection, outputs as muse_batch_run_in_lag_range, with
  * Results.MaxLag = max(|lag_lo|, |lag_hi|); sign_filter is both the argmax's sign and the selection's filter, as in
  * muse_batch_run_signed_in_lag_range; the selection's own argument checks come first.
- * Limits: the many-references form, the Muse.Run rows and panels forms, the slide forms, the muse_batch_set_lag_window setting, the
+ * Limits: the Muse.Run rows and panels forms, the slide forms, the muse_batch_set_lag_window setting, the
  * multi-device and dist.py layers; bands where the table above says MUSE_ERR_UNSUPPORTED (more than 127 lags or float32 storage
  * outside FFT lengths 512 ... 4096, series longer than 65536 samples). */
 int muse_batch_score_in_lag_band(muse_batch *b, int32_t lag_lo, int32_t lag_hi, int32_t sign);
@@ -725,12 +725,48 @@ int muse_batch_run_many_in_window(muse_batch *const *batches, int32_t R, const i
  * muse_batch_run_many_in_lag_range is that pass followed by Batch.Run's selection for every batch, outputs as muse_batch_run_many,
  * with Results.MaxLag = max(-lag_lo, lag_hi).  A sign_filter outside -1 .. 1 or a negative G with group_id is refused before anything
  * is scored.
- * Limits: one range per reference; ranges that exclude lag 0 (one reference: muse_batch_score_in_lag_band); the multi-device layer. */
+ * Limits: one range per reference; ranges that exclude lag 0 (muse_batch_score_many_in_lag_band below scores them); the multi-device
+ * layer. */
 int muse_batch_score_many_in_lag_range(muse_batch *const *batches, int32_t R, int32_t lag_lo, int32_t lag_hi);
 int muse_batch_run_many_in_lag_range(muse_batch *const *batches, int32_t R, const int32_t *group_id, int32_t G,
                                      int32_t lag_lo, int32_t lag_hi, int32_t top_n, double threshold, int32_t sign_filter,
                                      int32_t abs_scores, int64_t *out_series, int32_t *out_lag, double *out_score,
                                      int32_t *out_count, double *out_mean_abs);
+/* Many references INSIDE A LAG BAND OR UNDER A SIGN in one pass over the rows: per batch and series the (lag, mv) of
+ * muse_batch_score_in_lag_band(b, lag_lo, lag_hi, sign) -- its clipping, its ascending scan with strict '>', its key |cc| / cc / -cc
+ * and its outcomes: (0, +0.0) where nothing wins, (0, 0.0) for sigma == 0, (0, NaN) for a NaN / Inf series -- one band and one sign
+ * for every reference, no batch's own lag_window touched.  "What led each of my eight open alerts by 1 .. 15 samples", "what moved
+ * WITH each of them".  sign == MUSE_SIGN_ANY with lag_lo <= 0 <= lag_hi is by definition muse_batch_score_many_in_lag_range (and so,
+ * for lag_lo == -lag_hi, muse_batch_score_many_in_window), bit for bit on every path.  Otherwise, with W = hi - lo + 1 the lags of
+ * the clipped band:
+ *   float64 group, W <= 2 MUSE_LAG_WINDOW_MAX + 1, up to 65536 samples : the direct product with the signed / band scan.  Up to 48 lags
+ *                                                                      the references' W table rows are packed into the accumulator
+ *                                                                      tiles of one launch (xcorr_window_many_signed_mfma: eight
+ *                                                                      references at 1 .. 7 are 56 rows, four tiles), wherever the
+ *                                                                      band lies; wider bands, and batches that do not share one
+ *                                                                      length, take one launch per reference.  Per batch BIT FOR BIT
+ *                                                                      muse_batch_score_in_lag_band, whose cached tables it shares
+ *   FFT length 512 ... 4096 otherwise (every lag under a sign too), R >= 2, and muse_batch_score_many's own one-pass conditions (as at
+ *   muse_batch_score_many_in_window: either storage at 4096, float64 below) : ONE pass of the many-references transform kernels with every
+ *                                                                      reference's argmax masked to the band, the sign in the mask
+ *                                                                      (xcorr_fused_n4096_fold_multi_band, xcorr_fused_small_many_band);
+ *                                                                      listed pairs are redone with the band and the sign
+ *   the same lengths where those conditions do not hold              : muse_batch_score_in_lag_band(b, lag_lo, lag_hi, sign) batch after batch
+ *   anything else                                                    : MUSE_ERR_UNSUPPORTED, nothing changed
+ * Exact fp64, never screened, the group's spectrum cache neither read nor built.  A kernel variant forced by a test hook that has no
+ * masked build is refused (MUSE_ERR_UNSUPPORTED), never run unmasked.
+ *   MUSE_ERR_INVALID: the list checks of muse_batch_score_many; lag_lo > lag_hi; a sign outside -1 .. 1; a band that is empty after
+ *   clipping; a batch whose own window is on (unless the band is the symmetric range equal to it).  Everything is checked before
+ *   anything is enqueued: a refusal leaves every batch's scores and cached tables as they were.
+ * muse_batch_run_many_in_lag_band is that pass followed by Batch.Run's selection for every batch, outputs as muse_batch_run_many,
+ * with Results.MaxLag = max(|lag_lo|, |lag_hi|); sign_filter is both the argmax's sign and the selection's filter, as in
+ * muse_batch_run_in_lag_band; the selection's own argument checks come first.
+ * Limits: one band and one sign per list; the Muse.Run rows and slide forms; the multi-device and dist.py layers. */
+int muse_batch_score_many_in_lag_band(muse_batch *const *batches, int32_t R, int32_t lag_lo, int32_t lag_hi, int32_t sign);
+int muse_batch_run_many_in_lag_band(muse_batch *const *batches, int32_t R, const int32_t *group_id, int32_t G,
+                                    int32_t lag_lo, int32_t lag_hi, int32_t top_n, double threshold, int32_t sign_filter,
+                                    int32_t abs_scores, int64_t *out_series, int32_t *out_lag, double *out_score,
+                                    int32_t *out_count, double *out_mean_abs);
 int muse_batch_free(muse_batch *b);
 
 /* ------------------------------------------- single-pair entry points */

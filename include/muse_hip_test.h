@@ -185,6 +185,17 @@ int muse_test_many_in_window_plan(int32_t N, int32_t f32_storage, int32_t max_la
  * lag_lo == -lag_hi it is muse_test_many_in_window_plan(N, ., lag_hi, R).  MUSE_ERR_INVALID for N < 2, lag_lo > 0, lag_hi < 0, R < 1
  * or a NULL out pointer. */
 int muse_test_many_lag_range_plan(int32_t N, int32_t f32_storage, int32_t lag_lo, int32_t lag_hi, int32_t R, int32_t *path);
+/* muse_batch_score_many_in_lag_band's dispatch, a pure host function (no device needed): the pass that scores R >= 1 references
+ * against series of N >= 2 samples inside the lags lag_lo .. lag_hi (lag 0 inside or not) under sign -1 .. 1.  sign == 0 with lag 0
+ * inside: muse_test_many_lag_range_plan.  Otherwise, with the band clipped: *path = MUSE_IN_WINDOW_MFMA (float64, at most
+ * 2 MUSE_LAG_WINDOW_MAX + 1 lags, up to 65536 samples: the direct product with the signed / band scan, packed where the planner
+ * packs), _MASKED (ONE masked many-references pass: R >= 2 at FFT length 4096, or at 512 ... 2048 on float64 storage), _MASKED_EACH
+ * (R single masked passes, muse_batch_score_in_lag_band per batch: R == 1, float32 storage at 512 ... 2048; a forced kernel variant
+ * or a missing correction table turns _MASKED into it when the call runs) or _UNSUPPORTED; never _PLAIN (every lag under a sign is a
+ * masked pass).  For
+ * R == 1 it is muse_test_lag_band_plan with _MASKED_EACH for _MASKED.  MUSE_ERR_INVALID for N < 2, R < 1, lag_lo > lag_hi, a band
+ * that is empty after clipping, a sign outside -1 .. 1 or a NULL out pointer. */
+int muse_test_many_lag_band_plan(int32_t N, int32_t f32_storage, int32_t lag_lo, int32_t lag_hi, int32_t sign, int32_t R, int32_t *path);
 /* muse_batch_slide_score_in_window's dispatch, a pure host function (no device needed): how a group of series of N >= 2 samples
  * (f32_storage: a float32-storage group) is slid by 0 <= k <= N samples and scored inside +-max_lag >= 0 --
  *   _UNSUPPORTED : muse_test_in_window_plan says so (the call returns MUSE_ERR_UNSUPPORTED, nothing moves)
