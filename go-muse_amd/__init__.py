@@ -25,3 +25,6 @@ from .muse import (Batch, DefaultLabel, DeviceBatch, DeviceGroup, Engine, Group,
 from . import many_band  # noqa: F401
 from .many_band import (RunManyInLagBand, RunManySignedInLagBand, run_many_in_lag_band, score_many_in_lag_band,  # noqa: F401
                         scores_many_in_lag_band, many_lag_band_plan)
+from . import many_bands  # noqa: F401
+from .many_bands import (RunManyInLagBands, RunManySignedInLagBands, RunManySigned, run_many_in_lag_bands,  # noqa: F401
+                         score_many_in_lag_bands, scores_many_in_lag_bands, many_lag_bands_plan)

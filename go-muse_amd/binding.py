@@ -168,6 +168,10 @@ SIGNATURES = {
     "muse_batch_run_many_in_lag_band": (ctypes.c_int, [ctypes.POINTER(_vp), _i32, _i32p, _i32, _i32, _i32, _i32, _f64, _i32, _i32,
                                                        _i64p, _i32p, _dp, _i32p, _dp]),
     "muse_test_many_lag_band_plan": (ctypes.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, _i32p]),
+    "muse_batch_score_many_in_lag_bands": (ctypes.c_int, [ctypes.POINTER(_vp), _i32, _i32p, _i32p, _i32p]),
+    "muse_batch_run_many_in_lag_bands": (ctypes.c_int, [ctypes.POINTER(_vp), _i32, _i32p, _i32, _i32p, _i32p, _i32p, _dp, _i32p, _i32,
+                                                        _i32, _i64p, _i32p, _dp, _i32p, _dp]),
+    "muse_test_many_lag_bands_plan": (ctypes.c_int, [_i32, _i32, _i32, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p]),
     "muse_test_window_many_plan_rows": (ctypes.c_int, [_i32, _i32, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p]),
     "muse_batch_run_many": (ctypes.c_int, [ctypes.POINTER(_vp), _i32, _i32p, _i32, _i32, _i32, _f64, _i32, _i32,
                                            _i64p, _i32p, _dp, _i32p, _dp]),

@@ -851,6 +851,8 @@ extern "C" int muse_batch_kernel_name(muse_batch *b, char *name, int32_t cap)
     } else if (o.kind == ScoreOrigin::MFMA) { // (the direct product with the call's window, whatever the batch's own setting)
         snprintf(k, sizeof(k), "xcorr_window_mfma<%d, %s>", o.mfma_tiles(),
                  window_wide(b->g->rows, b->g->stride) ? "true" : "false");
+    } else if (o.kind == ScoreOrigin::PACKED_EACH) { // (muse_batch_score_many_in_lag_bands' mixed packed launches)
+        snprintf(k, sizeof(k), "xcorr_window_many_each_mfma<%d, %s>", o.tiles, window_wide(b->g->rows, b->g->stride) ? "true" : "false");
     } else if (o.kind == ScoreOrigin::PACKED && (o.sign != 0 || o.window.band())) { // (muse_batch_score_many_in_lag_band's packed launches)
         snprintf(k, sizeof(k), "xcorr_window_many_signed_mfma<%d, %s, %d, %s>", o.tiles, window_wide(b->g->rows, b->g->stride) ? "true" : "false",
                  o.sign, o.window.band() ? "true" : "false");

@@ -301,9 +301,20 @@ inline bool clip_lag_band(int64_t n, int32_t lag_lo, int32_t lag_hi, LagRange *w
     return true;
 }
 
+// lag_lo .. lag_hi clipped at FFT length n: the band where lag 0 is outside (false: nothing of it is left), the range otherwise
+inline bool clip_band_or_range(int64_t n, int32_t lag_lo, int32_t lag_hi, LagRange *w)
+{
+    if (lag_lo <= 0 && lag_hi >= 0) { // (clipping moves neither bound across lag 0)
+        *w = clip_lag_range(n, lag_lo, lag_hi);
+        return true;
+    }
+    return clip_lag_band(n, lag_lo, lag_hi, w);
+}
+
 // Which pass filled a batch's mv / lag.  The in-window kinds carry the MUSE_IN_WINDOW_* value (muse_hip_test.h) they report.
 struct ScoreOrigin {
     enum Kind : int32_t {
+        PACKED_EACH = -2, // a packed launch of muse_batch_score_many_in_lag_bands whose members differ in range, band or sign (`tiles` tiles)
         PACKED = -1, // a packed launch of muse_batch_score_many_windowed (capi_window_many.hip) of `tiles` accumulator tiles
         OWN = 0,     // the batch's own setting: choose_kernel, or its own lag window (what the next muse_batch_score takes too)
         PLAIN = MUSE_IN_WINDOW_PLAIN, MFMA = MUSE_IN_WINDOW_MFMA, MASKED = MUSE_IN_WINDOW_MASKED // a call's window (`window`)
@@ -316,6 +327,7 @@ struct ScoreOrigin {
     int32_t slide = 0;   // the MUSE_SLIDE_IN_WINDOW_* path if the pass was muse_batch_slide_score_in_window's and moved the rows, 0 otherwise
     int32_t sign = 0;    // MFMA / MASKED: +-1 if the pass was muse_batch_score_signed_in_lag_range's signed best match, 0 otherwise
     static ScoreOrigin packed(int32_t tiles) { return ScoreOrigin{PACKED, LagRange{0, 0, 0}, 0, tiles}; }
+    static ScoreOrigin packed_each(int32_t tiles) { return ScoreOrigin{PACKED_EACH, LagRange{0, 0, 0}, 0, tiles}; }
     static ScoreOrigin in_window(int32_t path, const LagRange &w, int32_t variant = 0) { return ScoreOrigin{(Kind)path, w, variant}; }
     int32_t in_window_path() const { return kind > OWN ? (int32_t)kind : 0; }
     int32_t mfma_tiles() const { return (window.rows() + 15) / 16; } // MFMA: the accumulator tiles of the direct product

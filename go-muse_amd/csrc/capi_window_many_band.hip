@@ -27,16 +27,6 @@ static int many_band_plan(int32_t N, bool f32, const LagRange &w, int sign, int3
     return R >= 2 && (muse_next_pow2((double)N) == 4096 || !f32) ? MUSE_IN_WINDOW_MASKED : MUSE_IN_WINDOW_MASKED_EACH;
 }
 
-// lag_lo .. lag_hi clipped at FFT length n: the band where lag 0 is outside (false: nothing of it is left), the range otherwise
-static bool clip_band_or_range(int64_t n, int32_t lag_lo, int32_t lag_hi, LagRange *w)
-{
-    if (lag_lo <= 0 && lag_hi >= 0) { // (clipping moves neither bound across lag 0)
-        *w = clip_lag_range(n, lag_lo, lag_hi);
-        return true;
-    }
-    return clip_lag_band(n, lag_lo, lag_hi, w);
-}
-
 extern "C" int muse_test_many_lag_band_plan(int32_t N, int32_t f32, int32_t lag_lo, int32_t lag_hi, int32_t sign, int32_t R, int32_t *path)
 {
     if (!path || N < 2 || R < 1)

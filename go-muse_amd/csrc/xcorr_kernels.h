@@ -308,6 +308,40 @@ hipError_t launch_window_many(WindowManyParams p, hipStream_t stream);
 // product, planner and launch sizes with the scan of launch_window_signed / launch_window_band (xcorr_window_many_signed_mfma).  A band
 // is the shape L = hi, Lneg = origin = -lo with one of L, Lneg negative; sign = 0 over a window that holds lag 0 is launch_window_many
 hipError_t launch_window_many_signed(WindowManyParams p, int sign, hipStream_t stream);
+// ---- the packed pass with a lag range, band and sign PER REFERENCE (xcorr_window_many_each.hip; muse_batch_score_many_in_lag_bands):
+// the same product, each reference's table under its own origin and row count, its scan and outcome chosen at run time from the six
+// builds of window_scan_pos / window_outcome (xcorr_window_many_each_mfma).  What is per reference is a descriptor in device memory
+struct WindowEachRef {
+    int L, Lneg, origin, W; // the reference's shape (WindowShape's; a band: one of L, Lneg negative); W = origin + L + 1 table rows
+    int sign, band;         // -1 / 0 / +1; 1: lag 0 is outside
+    int row0;               // its first row in the launch's packed A rows: the sum of the W in front of it
+    int img0;               // the LDS offset of its staged image (window_each_place)
+};
+struct WindowEachParams {
+    const double *rows;       // M x N row-major float64, row stride `stride` elements (WindowShape's)
+    long long M, stride;
+    int N;
+    double invN, invNm1;
+    int R;                    // references of this launch
+    const double *const *e;   // [R] each reference's WindowParams::e   (the four tables and the descriptors: device memory)
+    const double *const *pw;  // [R] each reference's WindowParams::pw
+    double *const *mv;        // [R] out: each reference's M signed values
+    int *const *lag;          // [R] out: each reference's M lags
+    const WindowEachRef *ref; // [R]
+    int total;                // packed rows: the sum of the W
+    int kc, buf, parts;       // chunk length, doubles of the image / tile region, scan parts per reference
+};
+// the planner (pure host functions).  window_each_place: img0[0 .. m) of m references with W[j] table rows at chunk length kc --
+// img0[0] = 0, img0[j + 1] the smallest offset >= img0[j] + kc + W[j] - 1 with img0[j + 1] - img0[j] = W[j] + 2 (mod 32); returns the
+// offset behind the last image, placed by the same rule (the launch's image doubles).  window_each_plan: R references, W[r] table rows
+// each (W[r] <= 0: not on the direct product, launch_of[r] = -1), cut into launches in list order: a reference of more than
+// WINM_PACK_MAX_ROWS rows has a launch to itself, the others join the open launch until one more would pass 16 WINM_MAX_TILES rows or,
+// at kc = 256, WINM_IMG_DOUBLES image doubles.  Launches are numbered by their first member.  Returns their number; tiles_of / kc_of
+// [launches <= R] (a reference alone in its launch: the single-reference kernel's tiles and WIN_KC), img0[R] (alone: 0)
+int window_each_place(const int *W, int m, int kc, int *img0);
+int window_each_plan(int R, const int *W, int *launch_of, int *tiles_of, int *kc_of, int *img0);
+// ref_host: the launch's descriptors as uploaded to p.ref (the launcher checks every one of them and sizes the launch from them)
+hipError_t launch_window_many_each(WindowEachParams p, const WindowEachRef *ref_host, hipStream_t stream);
 hipError_t launch_direct(const double *x, int lenx, const double *y, int leny, int n, int normalize_x,
                          int normalize_y, double x_scale, double cc_scale, double *cc, int *lag, double *mv,
                          int *status, hipStream_t stream);

@@ -1092,6 +1092,178 @@ func RunManySignedInLagBand(batches []*Batch, groupByLabels []string, lagLo, lag
 		})
 }
 
+// RunManyInLagBands is RunMany with a lag band PER BATCH (muse_batch_run_many_in_lag_bands): batch r receives what its own
+// RunInLagBand(groupByLabels, bands[r][0], bands[r][1]) gives -- the argmax by magnitude, its own Results' filters applied
+// afterwards -- from one pass over the rows.  The batches' Results may differ in every field.  One device.  Batches that do not
+// share the Comparison are RunInLagBand one after the other.
+func RunManyInLagBands(batches []*Batch, groupByLabels []string, bands [][2]int) error {
+	return runManyInBands(batches, groupByLabels, bands, "RunManyInLagBands", false)
+}
+
+// RunManySignedInLagBands is RunManyInLagBands with each batch's OWN Results.SignFilter restricting its argmax: batch r receives
+// what its own RunSignedInLagBand gives; under a sign the Scores carry the signed value.
+func RunManySignedInLagBands(batches []*Batch, groupByLabels []string, bands [][2]int) error {
+	return runManyInBands(batches, groupByLabels, bands, "RunManySignedInLagBands", true)
+}
+
+// RunManySigned is RunManySignedInLagBands with bands[r] = (-MaxLag_r, MaxLag_r): every batch receives what its own RunSigned
+// gives, under its own Results.MaxLag, TopN, Threshold and SignFilter, from one pass over the rows.
+func RunManySigned(batches []*Batch, groupByLabels []string) error {
+	bands := make([][2]int, len(batches))
+	for i, b := range batches {
+		if b.Results.MaxLag < 0 {
+			return fmt.Errorf("RunManySigned: MaxLag < 0")
+		}
+		bands[i] = [2]int{-b.Results.MaxLag, b.Results.MaxLag}
+	}
+	return runManyInBands(batches, groupByLabels, bands, "RunManySigned", true)
+}
+
+// runManyInBands is what the three share: the checks, the batches that share one Comparison (otherwise the single methods one
+// after the other), and every Results fed in group order what its own single method feeds it -- up to exactFeedMaxGroups label
+// groups every group's winner, beyond the device's pre-selection under the batch's OWN TopN and Threshold -- with the (sign,
+// abs_scores) that method hands its device call.  The C call takes one abs_scores: under signs the batches that report magnitudes
+// (SignFilterAny) and those that report signed values take one pass each.
+func runManyInBands(batches []*Batch, groupByLabels []string, bands [][2]int, name string, signed bool) error {
+	if len(batches) == 0 {
+		return nil
+	}
+	if len(bands) != len(batches) {
+		return fmt.Errorf("%s: one (lagLo, lagHi) per batch", name)
+	}
+	b0 := batches[0]
+	same := true
+	signs := make([]int, len(batches))
+	for i, b := range batches {
+		if bands[i][0] > bands[i][1] {
+			return fmt.Errorf("%s: lagLo <= lagHi", name)
+		}
+		if signed {
+			signs[i] = int(b.Results.SignFilter)
+		}
+		same = same && b.Comparison == b0.Comparison
+	}
+	if !same {
+		for i, b := range batches {
+			var err error
+			if signed {
+				err = b.RunSignedInLagBand(groupByLabels, bands[i][0], bands[i][1])
+			} else {
+				err = b.RunInLagBand(groupByLabels, bands[i][0], bands[i][1])
+			}
+			if err != nil {
+				return err
+			}
+		}
+		return nil
+	}
+	if es := shardEngines(); es != nil {
+		return fmt.Errorf("%s runs on one device", name)
+	}
+	labelValuesSet := b0.Comparison.indexLabelValues(groupByLabels)
+	if len(labelValuesSet) == 0 {
+		return nil
+	}
+	e, err := getEngine()
+	if err != nil {
+		return err
+	}
+	dg, err := b0.Comparison.residentRows(e)
+	if err != nil {
+		return err
+	}
+	pos := make(map[string]int, len(b0.Comparison.order))
+	for i, s := range b0.Comparison.order {
+		pos[s.UID()] = i
+	}
+	gid := make([]C.int32_t, len(b0.Comparison.order))
+	gi := 0
+	for _, lv := range labelValuesSet {
+		for _, uid := range b0.Comparison.index[lv.ID(lv.Keys())] {
+			gid[pos[uid]] = C.int32_t(gi)
+		}
+		gi++
+	}
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	G := len(labelValuesSet)
+	for pass := 0; pass < 2; pass++ { // the batches that report magnitudes, then those that report signed values
+		var of []int
+		for i := range batches {
+			if (signs[i] == 0) == (pass == 0) {
+				of = append(of, i)
+			}
+		}
+		R := len(of)
+		if R == 0 {
+			continue
+		}
+		// the handle array lives in C memory: cgo forbids passing Go memory that holds pointers
+		hs := (**C.muse_batch)(C.malloc(C.size_t(R) * C.size_t(unsafe.Sizeof((*C.muse_batch)(nil)))))
+		defer C.free(unsafe.Pointer(hs))
+		hv := batchView(hs, R)
+		lo := make([]C.int32_t, R)
+		hi := make([]C.int32_t, R)
+		topN := make([]C.int32_t, R)
+		sign := make([]C.int32_t, R)
+		threshold := make([]C.double, R)
+		stride := 1
+		for k, i := range of {
+			b := batches[i]
+			if b.batch == nil || b.batchGroup != dg {
+				if b.batch != nil {
+					C.muse_batch_free(b.batch)
+				}
+				st := C.muse_batch_create(e.ctx, dg, (*C.double)(unsafe.Pointer(&b.ref[0])), C.int32_t(len(b.ref)), &b.batch)
+				if err := hipError(st); err != nil {
+					return err
+				}
+				b.batchGroup = dg
+			}
+			// (as Run does: a window an earlier RunWindowed left on the handle goes; this pass takes its own as an argument)
+			if err := hipError(C.muse_batch_set_lag_window(b.batch, C.int32_t(b.window))); err != nil {
+				return err
+			}
+			hv[k] = b.batch
+			lo[k], hi[k], sign[k] = C.int32_t(bands[i][0]), C.int32_t(bands[i][1]), C.int32_t(signs[i])
+			topN[k], threshold[k] = C.int32_t(b.Results.TopN), C.double(b.Results.Threshold)
+			if G <= exactFeedMaxGroups {
+				topN[k], threshold[k] = C.int32_t(G), 0.0
+			}
+			if int(topN[k]) > stride {
+				stride = int(topN[k])
+			}
+		}
+		abs := C.int32_t(0)
+		if pass == 0 {
+			abs = 1
+		}
+		idx := make([]C.int64_t, R*stride)
+		lag := make([]C.int32_t, R*stride)
+		score := make([]C.double, R*stride)
+		cnt := make([]C.int32_t, R)
+		mean := make([]C.double, R)
+		st := C.muse_batch_run_many_in_lag_bands(hs, C.int32_t(R), &gid[0], C.int32_t(G), &lo[0], &hi[0], &topN[0], &threshold[0],
+			&sign[0], abs, C.int32_t(stride), &idx[0], &lag[0], &score[0], &cnt[0], &mean[0])
+		if err := hipError(st); err != nil {
+			return err
+		}
+		for k, i := range of {
+			b := batches[i]
+			o := k * stride
+			order := make([]int, int(cnt[k]))
+			for j := range order {
+				order[j] = j
+			}
+			sort.SliceStable(order, func(a, c int) bool { return gid[idx[o+order[a]]] < gid[idx[o+order[c]]] })
+			for _, j := range order {
+				b.Results.Update(Score{Labels: b.Comparison.order[idx[o+j]].Labels(), Lag: int(lag[o+j]), PercentScore: float64(score[o+j])})
+			}
+		}
+	}
+	return nil
+}
+
 // runManyInLags is what RunManyInWindow, RunManyInLagRange and RunManyInLagBand share: the batches that qualify (otherwise each, batch after batch),
 // pre (the form's own refusal once they do), the label groups, the resident rows, the handles, the call (one of the library's
 // _run_many_in_ entry points) and the feed of every Results in group order.

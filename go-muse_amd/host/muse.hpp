@@ -1312,6 +1312,115 @@ public:
             });
     }
 
+    // RunMany with a lag band PER BATCH (muse_batch_run_many_in_lag_bands): batch r receives what its own
+    // RunInLagBand(groupByLabels, bands[r].first, bands[r].second) gives -- the argmax by magnitude, its own Results' filters applied
+    // afterwards -- from one pass over the rows.  The batches' Results may differ in every field.  One device.  Batches that do not
+    // share the Comparison and the engine are RunInLagBand one by one.
+    static void RunManyInLagBands(const std::vector<std::shared_ptr<Batch>> &batches, const std::vector<std::string> &groupByLabels,
+                                  const std::vector<std::pair<int, int>> &bands)
+    {
+        feed_many_in_bands(batches, groupByLabels, bands, "RunManyInLagBands", false);
+    }
+
+    // RunManyInLagBands with each batch's OWN Results.SignFilter restricting its argmax: batch r receives what its own
+    // RunSignedInLagBand gives; under a sign the Scores carry the signed value.
+    static void RunManySignedInLagBands(const std::vector<std::shared_ptr<Batch>> &batches, const std::vector<std::string> &groupByLabels,
+                                        const std::vector<std::pair<int, int>> &bands)
+    {
+        feed_many_in_bands(batches, groupByLabels, bands, "RunManySignedInLagBands", true);
+    }
+
+    // RunManySignedInLagBands with bands[r] = (-MaxLag_r, MaxLag_r): every batch receives what its own RunSigned gives, under its own
+    // Results.MaxLag, TopN, Threshold and SignFilter, from one pass over the rows.
+    static void RunManySigned(const std::vector<std::shared_ptr<Batch>> &batches, const std::vector<std::string> &groupByLabels)
+    {
+        std::vector<std::pair<int, int>> bands;
+        for (auto &b : batches) {
+            if (b->Results_->MaxLag < 0)
+                throw Error(MUSE_ERR_INVALID, "RunManySigned: MaxLag < 0");
+            bands.emplace_back(-b->Results_->MaxLag, b->Results_->MaxLag);
+        }
+        feed_many_in_bands(batches, groupByLabels, bands, "RunManySigned", true);
+    }
+
+    // what the three share: the checks, the batches that share one Comparison and one engine on one device (otherwise the single
+    // methods one by one), and every Results fed in group order what its own single method (feed_in_window) feeds it -- up to
+    // EXACT_FEED_MAX_GROUPS label groups every group's winner, beyond the device's pre-selection under the batch's OWN TopN and
+    // Threshold -- with the (sign, abs_scores) that method hands its device call.  The C call takes one abs_scores: under signs the
+    // batches that report magnitudes (SignFilter_ANY) and those that report signed values take one pass each.
+    static void feed_many_in_bands(const std::vector<std::shared_ptr<Batch>> &batches, const std::vector<std::string> &groupByLabels,
+                                   const std::vector<std::pair<int, int>> &bands, const char *who, bool signed_)
+    {
+        if (batches.empty())
+            return;
+        if (bands.size() != batches.size())
+            throw Error(MUSE_ERR_INVALID, std::string(who) + ": one (lagLo, lagHi) per batch");
+        bool same = true;
+        std::vector<int32_t> signs;
+        for (size_t r = 0; r < batches.size(); r++) {
+            if (!batches[r]->engines_.empty())
+                throw Error(MUSE_ERR_UNSUPPORTED, std::string(who) + " runs on one device");
+            if (bands[r].first > bands[r].second)
+                throw Error(MUSE_ERR_INVALID, std::string(who) + ": lagLo <= lagHi");
+            signs.push_back(signed_ ? (int32_t)batches[r]->Results_->Filter : 0);
+            same &= batches[r]->Comparison == batches[0]->Comparison && batches[r]->eng_ == batches[0]->eng_;
+        }
+        if (!same) {
+            for (size_t r = 0; r < batches.size(); r++) {
+                if (signed_)
+                    batches[r]->RunSignedInLagBand(groupByLabels, bands[r].first, bands[r].second);
+                else
+                    batches[r]->RunInLagBand(groupByLabels, bands[r].first, bands[r].second);
+            }
+            return;
+        }
+        Batch &b0 = *batches[0];
+        std::vector<int32_t> gid;
+        auto lvs = b0.Comparison->indexLabelValues(groupByLabels, &gid);
+        if (lvs.empty())
+            return;
+        muse_group *dg = b0.Comparison->device(b0.eng_);
+        const bool exact = (int64_t)lvs.size() <= EXACT_FEED_MAX_GROUPS;
+        for (int magnitudes = 1; magnitudes >= 0; magnitudes--) {
+            std::vector<size_t> of;
+            std::vector<muse_batch *> hs;
+            std::vector<int32_t> lo, hi, top, sign;
+            std::vector<double> thr;
+            int32_t cap = 1;
+            for (size_t r = 0; r < batches.size(); r++) {
+                if ((signs[r] == 0) != (magnitudes == 1))
+                    continue;
+                batches[r]->ensure(dg);
+                of.push_back(r);
+                hs.push_back(batches[r]->batch_);
+                lo.push_back((int32_t)bands[r].first);
+                hi.push_back((int32_t)bands[r].second);
+                sign.push_back(signs[r]);
+                top.push_back(exact ? (int32_t)lvs.size() : batches[r]->Results_->TopN);
+                thr.push_back(exact ? 0.0 : batches[r]->Results_->Threshold);
+                cap = std::max(cap, top.back());
+            }
+            const int R = (int)hs.size();
+            if (R == 0)
+                continue;
+            std::vector<int64_t> idx((size_t)R * cap);
+            std::vector<int32_t> lag((size_t)R * cap), cnt((size_t)R);
+            std::vector<double> score((size_t)R * cap), mean((size_t)R);
+            check(muse_batch_run_many_in_lag_bands(hs.data(), R, gid.data(), (int32_t)lvs.size(), lo.data(), hi.data(), top.data(), thr.data(),
+                                                   sign.data(), magnitudes, cap, idx.data(), lag.data(), score.data(), cnt.data(),
+                                                   mean.data()));
+            for (int r = 0; r < R; r++) {
+                const size_t o = (size_t)r * cap;
+                std::vector<int> order(cnt[r]);
+                for (int i = 0; i < cnt[r]; i++)
+                    order[i] = i;
+                std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return gid[idx[o + a]] < gid[idx[o + b]]; });
+                for (int k : order)
+                    batches[of[r]]->Results_->Update(Score{b0.Comparison->series()[idx[o + k]]->Labels(), lag[o + k], score[o + k]});
+            }
+        }
+    }
+
     // what RunManyInWindow, RunManyInLagRange and RunManyInLagBand share: the batches that qualify (one Comparison, one engine, one device, the same
     // Results settings; otherwise `each` batch by batch), `pre` (the form's own refusal once they do), the label groups, the call (one
     // of the library's _run_many_in_ entry points) and the feed of every Results in group order

@@ -767,6 +767,41 @@ int muse_batch_run_many_in_lag_band(muse_batch *const *batches, int32_t R, const
                                     int32_t lag_lo, int32_t lag_hi, int32_t top_n, double threshold, int32_t sign_filter,
                                     int32_t abs_scores, int64_t *out_series, int32_t *out_lag, double *out_score,
                                     int32_t *out_count, double *out_mean_abs);
+/* Many references, EACH INSIDE ITS OWN LAG BAND AND UNDER ITS OWN SIGN, in one pass over the rows: batch r is left exactly as
+ * muse_batch_score_in_lag_band(batches[r], lag_lo[r], lag_hi[r], sign[r]) leaves it -- scores, lags, what muse_batch_kernel_name and
+ * muse_test_last_in_window_path report -- and no batch's own lag_window is touched.  "What led alert A by 1 .. 7 samples, what
+ * trailed alert B by up to 7, what moved against alert C inside +-3": (1, 7) / ANY, (-7, 0) / ANY, (-3, 3) / NEG, 15 + 8 + 7 table
+ * rows in two accumulator tiles of one launch.  sign == NULL: MUSE_SIGN_ANY for every reference.
+ *   the whole list shares one (lag_lo, lag_hi, sign)    : muse_batch_score_many_in_lag_band, bit for bit and kernel for kernel
+ *   batches of one length, the references the single dispatch sends to the direct product (float64 group, at most
+ *   2 MUSE_LAG_WINDOW_MAX + 1 lags after clipping, up to 65536 samples) : cut into launches in list order -- a reference of more than
+ *                                                         48 lags has a launch to itself; the others join the open launch until one
+ *                                                         more would pass 128 packed table rows or the launch's staged images their
+ *                                                         LDS budget.  A launch whose members differ: xcorr_window_many_each_mfma,
+ *                                                         every reference's shape, sign and image offset in a descriptor table in
+ *                                                         device memory; one whose members share range and sign: the uniform packed
+ *                                                         kernel of muse_batch_score_many_in_lag_band; a reference alone in its launch:
+ *                                                         the single-reference kernel, named as the single call names it.  Per batch
+ *                                                         BIT FOR BIT muse_batch_score_in_lag_band, whose cached tables it shares
+ *   every other reference (more lags, float32 storage, every lag under a sign), and lists of mixed length : its own single pass, behind
+ *                                                         the packed launches
+ * Exact fp64, never screened, asynchronous; results land in each batch's own buffers.
+ *   MUSE_ERR_INVALID: the list checks of muse_batch_score_many; NULL lag_lo / lag_hi; at any index lag_lo > lag_hi, a sign outside
+ *   -1 .. 1, a band that is empty after clipping, a batch whose own window is on (unless the band is the symmetric range equal to it).
+ *   MUSE_ERR_UNSUPPORTED: what the single call refuses for a reference that is not on the direct product.  Everything is checked
+ *   before anything is enqueued: a refusal leaves every batch's scores and cached tables as they were.
+ * muse_batch_run_many_in_lag_bands is that pass followed by Batch.Run's selection for every batch: batch r with Results.MaxLag =
+ * max(|lag_lo[r]|, |lag_hi[r]|), top_n[r], threshold[r] and sign_filter[r], which is both the argmax's sign and the selection's filter,
+ * as in muse_batch_run_in_lag_band (NULL: MUSE_SIGN_ANY).  Row r of out_series / out_lag / out_score starts at out_stride * r;
+ * out_stride < top_n[r] at any index, NULL top_n / threshold: MUSE_ERR_INVALID.  The selection's own argument checks come first.
+ * Limits: the masked many-references transform kernels take one mask per pass (those references take their single passes); the list is
+ * packed in the order given; the Muse.Run rows, panels and slide forms; the multi-device and dist.py layers. */
+int muse_batch_score_many_in_lag_bands(muse_batch *const *batches, int32_t R, const int32_t *lag_lo, const int32_t *lag_hi,
+                                       const int32_t *sign);
+int muse_batch_run_many_in_lag_bands(muse_batch *const *batches, int32_t R, const int32_t *group_id, int32_t G,
+                                     const int32_t *lag_lo, const int32_t *lag_hi, const int32_t *top_n, const double *threshold,
+                                     const int32_t *sign_filter, int32_t abs_scores, int32_t out_stride, int64_t *out_series,
+                                     int32_t *out_lag, double *out_score, int32_t *out_count, double *out_mean_abs);
 int muse_batch_free(muse_batch *b);
 
 /* ------------------------------------------- single-pair entry points */

@@ -196,6 +196,17 @@ int muse_test_many_lag_range_plan(int32_t N, int32_t f32_storage, int32_t lag_lo
  * R == 1 it is muse_test_lag_band_plan with _MASKED_EACH for _MASKED.  MUSE_ERR_INVALID for N < 2, R < 1, lag_lo > lag_hi, a band
  * that is empty after clipping, a sign outside -1 .. 1 or a NULL out pointer. */
 int muse_test_many_lag_band_plan(int32_t N, int32_t f32_storage, int32_t lag_lo, int32_t lag_hi, int32_t sign, int32_t R, int32_t *path);
+/* muse_batch_score_many_in_lag_bands' planner for a list that does NOT share one (lag_lo, lag_hi, sign), a pure host function (no
+ * device needed): R >= 1 references against series of N >= 2 samples, reference r inside lag_lo[r] .. lag_hi[r] under sign[r] (NULL:
+ * MUSE_SIGN_ANY).  path[r] = the MUSE_IN_WINDOW_* value of the single dispatch (muse_test_lag_band_plan).  The references with
+ * path[r] == MUSE_IN_WINDOW_MFMA are cut into *launches launches, numbered by their first member: launch_of[r] (-1 for every other
+ * reference), tiles_of[l] and kc_of[l] per launch (a reference alone in its launch: the single-reference kernel's tiles and chunk of
+ * 1024), img0[r] the LDS offset of the reference's staged image inside its launch (0 for a reference alone and for launch_of[r] == -1).
+ * launch_of, path and img0 hold R entries, tiles_of and kc_of up to R.  MUSE_ERR_INVALID for N < 2, R < 1, a NULL array, and at any
+ * index lag_lo > lag_hi, a sign outside -1 .. 1 or a band that is empty after clipping. */
+int muse_test_many_lag_bands_plan(int32_t N, int32_t f32_storage, int32_t R, const int32_t *lag_lo, const int32_t *lag_hi,
+                                  const int32_t *sign, int32_t *path, int32_t *launch_of, int32_t *launches, int32_t *tiles_of,
+                                  int32_t *kc_of, int32_t *img0);
 /* muse_batch_slide_score_in_window's dispatch, a pure host function (no device needed): how a group of series of N >= 2 samples
  * (f32_storage: a float32-storage group) is slid by 0 <= k <= N samples and scored inside +-max_lag >= 0 --
  *   _UNSUPPORTED : muse_test_in_window_plan says so (the call returns MUSE_ERR_UNSUPPORTED, nothing moves)
