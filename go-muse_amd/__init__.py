@@ -28,3 +28,5 @@ from .many_band import (RunManyInLagBand, RunManySignedInLagBand, run_many_in_la
 from . import many_bands  # noqa: F401
 from .many_bands import (RunManyInLagBands, RunManySignedInLagBands, RunManySigned, run_many_in_lag_bands,  # noqa: F401
                          score_many_in_lag_bands, scores_many_in_lag_bands, many_lag_bands_plan)
+# (the package attribute lag_profile is the module's row-level function of that name)
+from .lag_profile import LagProfiles, lag_profile, lag_profile_into, lag_profile_plan  # noqa: F401

@@ -172,6 +172,9 @@ SIGNATURES = {
     "muse_batch_run_many_in_lag_bands": (ctypes.c_int, [ctypes.POINTER(_vp), _i32, _i32p, _i32, _i32p, _i32p, _i32p, _dp, _i32p, _i32,
                                                         _i32, _i64p, _i32p, _dp, _i32p, _dp]),
     "muse_test_many_lag_bands_plan": (ctypes.c_int, [_i32, _i32, _i32, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p]),
+    "muse_batch_lag_profile": (ctypes.c_int, [_vp, _i64p, _i64, _i32, _i32, _dp, _i64]),
+    "muse_batch_lag_profile_device": (ctypes.c_int, [_vp, _i64p, _i64, _i32, _i32, _vp, _i64]),
+    "muse_test_lag_profile_plan": (ctypes.c_int, [_i32, _i32, _i32, _i32p, _i32p, _i32p, _i32]),
     "muse_test_window_many_plan_rows": (ctypes.c_int, [_i32, _i32, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p]),
     "muse_batch_run_many": (ctypes.c_int, [ctypes.POINTER(_vp), _i32, _i32p, _i32, _i32, _i32, _f64, _i32, _i32,
                                            _i64p, _i32p, _dp, _i32p, _dp]),

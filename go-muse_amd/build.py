@@ -13,7 +13,7 @@ ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIBDIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIBDIR, "libmuse_hip.so")
-SOURCES = ["xcorr_kernels.hip", "xcorr_r16_fold.hip", "xcorr_r16_cached.hip", "xcorr_r16_occ4.hip", "xcorr_stockham.hip", "xcorr_two_sided.hip", "xcorr_small.hip", "xcorr_long.hip", "xcorr_real.hip", "xcorr_huge.hip", "xcorr_r16_screen.hip", "xcorr_screen_stk.hip", "reduce_kernels.hip", "diag_kernels.hip", "capi_context.hip", "capi_group.hip", "capi_batch.hip", "capi_run.hip", "capi_rows.hip", "capi_screen.hip", "capi_many.hip", "capi_huge.hip", "capi_xcorr.hip", "row_gather.hip", "row_slide.hip", "xcorr_window.hip", "xcorr_window_band.hip", "capi_window.hip", "xcorr_window_many.hip", "capi_window_many.hip", "capi_window_many_in.hip", "xcorr_window_many_band.hip", "capi_window_many_band.hip", "xcorr_window_many_each.hip", "capi_window_many_each.hip", "xcorr_window_split.hip", "xcorr_window_slide.hip", "xcorr_window_panels.hip"]
+SOURCES = ["xcorr_kernels.hip", "xcorr_r16_fold.hip", "xcorr_r16_cached.hip", "xcorr_r16_occ4.hip", "xcorr_stockham.hip", "xcorr_two_sided.hip", "xcorr_small.hip", "xcorr_long.hip", "xcorr_real.hip", "xcorr_huge.hip", "xcorr_r16_screen.hip", "xcorr_screen_stk.hip", "reduce_kernels.hip", "diag_kernels.hip", "capi_context.hip", "capi_group.hip", "capi_batch.hip", "capi_run.hip", "capi_rows.hip", "capi_screen.hip", "capi_many.hip", "capi_huge.hip", "capi_xcorr.hip", "row_gather.hip", "row_slide.hip", "xcorr_window.hip", "xcorr_window_band.hip", "xcorr_window_profile.hip", "capi_window.hip", "capi_profile.hip", "xcorr_window_many.hip", "capi_window_many.hip", "capi_window_many_in.hip", "xcorr_window_many_band.hip", "capi_window_many_band.hip", "xcorr_window_many_each.hip", "capi_window_many_each.hip", "xcorr_window_split.hip", "xcorr_window_slide.hip", "xcorr_window_panels.hip"]
 HEADERS = [os.path.join(CSRC, "xcorr_kernels.h"), os.path.join(CSRC, "xcorr_huge.h"), os.path.join(CSRC, "fft_device.h"), os.path.join(CSRC, "r16_device.h"), os.path.join(CSRC, "fold_device.h"), os.path.join(CSRC, "foldk_device.h"), os.path.join(CSRC, "n4096_pair_device.h"), os.path.join(CSRC, "long_device.h"), os.path.join(CSRC, "stk_device.h"), os.path.join(CSRC, "small_device.h"), os.path.join(CSRC, "xcorr_small_body.h"), os.path.join(CSRC, "two_device.h"), os.path.join(CSRC, "window_device.h"), os.path.join(CSRC, "capi_internal.h"), os.path.join(ROOT, "include", "muse_hip.h"), os.path.join(ROOT, "include", "muse_hip_test.h")]
 
 
@@ -95,6 +95,7 @@ ROWS_LAG_RANGE_TEST = os.path.join(LIBDIR, "muse_rows_lag_range_test")
 SIGNED_LAG_RANGE_TEST = os.path.join(LIBDIR, "muse_signed_lag_range_test")
 LAG_BAND_TEST = os.path.join(LIBDIR, "muse_lag_band_test")
 MANY_LAG_BAND_TEST = os.path.join(LIBDIR, "muse_many_lag_band_test")
+LAG_PROFILE_TEST = os.path.join(LIBDIR, "muse_lag_profile_test")
 
 
 def build_host_test(force=False):
@@ -170,3 +171,8 @@ def build_lag_band_test(force=False):
 def build_many_lag_band_test(force=False):
     """The host mirror's many-references lag-band program (tests/test_gpu_many_lag_band.py)."""
     return _build_host_program("muse_many_lag_band_test", "-O1", force)
+
+
+def build_lag_profile_test(force=False):
+    """The host mirror's lag-profile program (tests/test_gpu_lag_profile.py)."""
+    return _build_host_program("muse_lag_profile_test", "-O1", force)

@@ -945,6 +945,13 @@ extern "C" int muse_batch_free(muse_batch *b)
     b->est_save.release(c);
     b->win_e.release(c);
     b->win_pw.release(c);
+    b->prof_e.release(c);
+    b->prof_pw.release(c);
+    b->prof_out.release(c);
+    b->prof_idx_host.release(c);
+    b->prof_idx.release(c);
+    if (b->prof_copied)
+        (void)hipEventDestroy(b->prof_copied);
     muse_group *g = b->g;
     muse_ctx *ctx = b->ctx;
     delete b;

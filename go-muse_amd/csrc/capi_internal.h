@@ -415,6 +415,13 @@ struct muse_batch {
     int32_t win_key = -1;
     PoolBuf<double> win_e, win_pw;
     bool windowed() const { return lag_window >= 0; }
+    // lag profiles (muse_batch_lag_profile, capi_profile.hip): the tables of the launch in flight (a sibling of win_e / win_pw with
+    // no key: win_key and what it names stay as the scoring calls left them), the host form's staging rows, and the series list --
+    // a pinned image and its device copy, the image reused once `prof_copied` has passed
+    PoolBuf<double> prof_e, prof_pw, prof_out;
+    HostBuf<long long> prof_idx_host;
+    PoolBuf<long long> prof_idx;
+    hipEvent_t prof_copied = nullptr;
     // which pass filled mv / lag (muse_batch_kernel_name names it, muse_test_last_in_window_path reports it): every scoring pass
     // assigns a whole value, a selection and a refused call leave it alone
     ScoreOrigin origin;

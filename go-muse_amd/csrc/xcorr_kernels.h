@@ -236,6 +236,25 @@ hipError_t launch_window_signed(const WindowParams &p, int sign, hipStream_t str
 hipError_t launch_window_tables_at(const double *xs, int N, int n, int origin, int W, double *e, long long e_len, double *pw, hipStream_t stream);
 hipError_t launch_window_tables_band(const double *xs, int N, int n, int lo, int W, double *e, long long e_len, double *pw, hipStream_t stream);
 hipError_t launch_window_band(const WindowParams &p, int sign, hipStream_t stream);
+// ---- the lag profile (xcorr_window_profile.hip; muse_batch_lag_profile): the band's product with the scan replaced by a write-out,
+// out[k * out_stride + v] = cc at lag lo + v of output row k, v = 0 .. W - 1 <= 2 MUSE_LAG_WINDOW_MAX (tables: launch_window_tables_at
+// with the origin -lo, lag 0 inside or not); columns W .. out_stride - 1 are never written.  series == nullptr: output row k is row k
+// of `rows`; otherwise row series[k] (M entries in device memory, each inside the rows, any order, duplicates allowed)
+struct WindowProfileParams {
+    const double *rows;      // row-major float64, row stride `stride` elements
+    long long M, stride;     // M output rows
+    int N, W;
+    double invN, invNm1;
+    const double *e;         // WindowParams::e / ::pw of the table
+    const double *pw;
+    const long long *series; // [M] or nullptr
+    double *out;
+    long long out_stride;    // >= W
+};
+hipError_t launch_window_profile(const WindowProfileParams &p, hipStream_t stream);
+// the planner (pure host function): lags lo .. hi in consecutive launches of up to 2 MUSE_LAG_WINDOW_MAX + 1 table rows; returns the
+// launch count and fills lo_of / rows_of (each launch's first lag and its rows) up to cap entries
+int window_profile_plan(int lo, int hi, int *lo_of, int *rows_of, int cap);
 // ---- the same while the rows slide (xcorr_window_slide.hip; muse_batch_slide_score_windowed): xcorr_window_mfma over the NEW rows
 // -- old row[k .. N) followed by tails[r * k + 0 .. k), a dense M x k device buffer, 16-byte aligned -- which are stored in place on
 // the way: one read and one write of the rows instead of launch_row_slide's pair plus launch_window's read, the same bits as the two.

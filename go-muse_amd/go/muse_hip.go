@@ -600,6 +600,70 @@ func (b *Batch) RunSignedInLagBand(groupByLabels []string, lagLo, lagHi int) err
 	return b.feedInWindow(groupByLabels, true, lagLo, lagHi, true, true)
 }
 
+// LagProfile returns the correlation itself at every lag of lagLo .. lagHi (muse_batch_lag_profile), where every Run returns its
+// argmax alone: row k of the result, lagHi - lagLo + 1 values, is cc[(lagLo + v) mod n] of series rows[k] of the Comparison group
+// (rows == nil: every series in order) -- raw values, +0.0 for a series with sigma == 0, NaN for one that holds NaN or Inf; bit for
+// bit what RunInLagBand / RunInLagRange scan at that lag on the direct product.  Lags inside -(n / 2 - 1) .. n / 2, not clipped;
+// float64 groups of up to 65536 samples.  One device.  The batch's scores and its window stay as they were.
+func (b *Batch) LagProfile(lagLo, lagHi int, rows []int64) ([][]float64, error) {
+	if lagLo > lagHi {
+		return nil, fmt.Errorf("LagProfile: lagLo <= lagHi")
+	}
+	if es := shardEngines(); es != nil {
+		return nil, fmt.Errorf("LagProfile runs on one device")
+	}
+	e, err := getEngine()
+	if err != nil {
+		return nil, err
+	}
+	dg, err := b.Comparison.residentRows(e)
+	if err != nil {
+		return nil, err
+	}
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	if b.batch == nil || b.batchGroup != dg {
+		if b.batch != nil {
+			C.muse_batch_free(b.batch)
+		}
+		st := C.muse_batch_create_like(b.template, dg, &b.batch)
+		if err := hipError(st); err != nil {
+			return nil, err
+		}
+		b.batchGroup = dg
+	}
+	W := lagHi - lagLo + 1
+	K := len(b.Comparison.order)
+	var list *C.int64_t
+	var idx []C.int64_t
+	if rows != nil {
+		K = len(rows)
+		idx = make([]C.int64_t, K+1) // (a list of no entries is still a list: a non-nil pointer)
+		for i, r := range rows {
+			idx[i] = C.int64_t(r)
+		}
+		list = &idx[0]
+	}
+	flat := make([]C.double, K*W+1)
+	listed := C.int64_t(0)
+	if rows != nil {
+		listed = C.int64_t(K)
+	}
+	st := C.muse_batch_lag_profile(b.batch, list, listed, C.int32_t(lagLo), C.int32_t(lagHi), &flat[0], C.int64_t(W))
+	runtime.KeepAlive(idx)
+	if err := hipError(st); err != nil {
+		return nil, err
+	}
+	out := make([][]float64, K)
+	for k := range out {
+		out[k] = make([]float64, W)
+		for v := range out[k] {
+			out[k][v] = float64(flat[k*W+v])
+		}
+	}
+	return out, nil
+}
+
 // RunSigned is RunSignedInLagRange(-MaxLag, MaxLag): RunInWindow with Results.SignFilter restricting the argmax.
 func (b *Batch) RunSigned(groupByLabels []string) error {
 	if b.Results.MaxLag < 0 {

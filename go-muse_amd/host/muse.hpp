@@ -1181,6 +1181,66 @@ public:
         });
     }
 
+    // Lag profiles (muse_batch_lag_profile): the correlation itself at every lag of lagLo .. lagHi, where every Run returns its argmax
+    // alone.  Row level: row k of the result, lagHi - lagLo + 1 doubles, is cc[(lagLo + v) mod n] of series rows[k] of the Comparison
+    // group (rows empty and all == true: every series in order) -- raw values, +0.0 for a series with sigma == 0, NaN for one that
+    // holds NaN or Inf; bit for bit what RunInLagBand / RunInLagRange scan at that lag on the direct product.  Lags inside
+    // -(n / 2 - 1) .. n / 2, not clipped; float64 groups of up to 65536 samples.  One device.  The batch's scores stay as they were.
+    std::vector<double> LagProfile(int lagLo, int lagHi, const std::vector<int64_t> &rows = {}, bool all = true)
+    {
+        if (!engines_.empty())
+            throw Error(MUSE_ERR_UNSUPPORTED, "LagProfile runs on one device: this batch is sharded over several engines");
+        if (lagLo > lagHi)
+            throw Error(MUSE_ERR_INVALID, "LagProfile: lagLo <= lagHi");
+        muse_group *dg = Comparison->device(eng_);
+        ensure(dg);
+        const bool listed = !rows.empty() || !all;
+        const int64_t W = (int64_t)lagHi - lagLo + 1;
+        const int64_t K = listed ? (int64_t)rows.size() : (int64_t)Comparison->series().size();
+        std::vector<double> out((size_t)(K * W));
+        static const int64_t none = 0; // (a list of no entries is still a list: a non-NULL pointer)
+        check(muse_batch_lag_profile(batch_, listed ? (rows.empty() ? &none : rows.data()) : nullptr, listed ? K : 0, (int32_t)lagLo,
+                                     (int32_t)lagHi, out.data(), W));
+        return out;
+    }
+
+    // Label level: the curve behind every Score of `scores` (what Results.Fetch() returned) -- the lag profile of the first series of
+    // the Comparison group that carries the Score's Labels, as (Score, lags lagLo .. lagHi, cc).  A Score whose Labels are not in the
+    // group is an Error.
+    struct Profile {
+        Score score;
+        std::vector<int> lags;
+        std::vector<double> cc;
+    };
+    std::vector<Profile> LagProfiles(int lagLo, int lagHi, const Scores &scores)
+    {
+        if (!engines_.empty())
+            throw Error(MUSE_ERR_UNSUPPORTED, "LagProfiles runs on one device: this batch is sharded over several engines");
+        std::map<std::string, int64_t> row_of;
+        const auto &series = Comparison->series();
+        for (size_t i = 0; i < series.size(); i++)
+            row_of.emplace(series[i]->Labels()->ID(), (int64_t)i);
+        std::vector<int64_t> rows;
+        for (const Score &s : scores) {
+            const auto at = s.Labels ? row_of.find(s.Labels->ID()) : row_of.end();
+            if (at == row_of.end())
+                throw Error(MUSE_ERR_INVALID, "LagProfiles: no series of the comparison group carries " + (s.Labels ? s.Labels->ID() : "no labels"));
+            rows.push_back(at->second);
+        }
+        std::vector<Profile> out;
+        if (rows.empty())
+            return out;
+        const std::vector<double> cc = LagProfile(lagLo, lagHi, rows, false);
+        const size_t W = (size_t)((int64_t)lagHi - lagLo + 1);
+        for (size_t k = 0; k < scores.size(); k++) {
+            Profile p{scores[k], std::vector<int>(W), std::vector<double>(cc.begin() + (ptrdiff_t)(k * W), cc.begin() + (ptrdiff_t)((k + 1) * W))};
+            for (size_t v = 0; v < W; v++)
+                p.lags[v] = lagLo + (int)v;
+            out.push_back(std::move(p));
+        }
+        return out;
+    }
+
     // RunSignedInLagRange(-MaxLag, MaxLag): RunInWindow with Results.SignFilter restricting the argmax
     void RunSigned(const std::vector<std::string> &groupByLabels)
     {

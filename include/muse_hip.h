@@ -802,6 +802,32 @@ int muse_batch_run_many_in_lag_bands(muse_batch *const *batches, int32_t R, cons
                                      const int32_t *lag_lo, const int32_t *lag_hi, const int32_t *top_n, const double *threshold,
                                      const int32_t *sign_filter, int32_t abs_scores, int32_t out_stride, int64_t *out_series,
                                      int32_t *out_lag, double *out_score, int32_t *out_count, double *out_mean_abs);
+/* LAG PROFILES: the correlation itself, not its argmax.  For output row k, out[k * out_stride + v] = cc[(lag_lo + v) mod n],
+ * v = 0 .. W - 1, W = lag_hi - lag_lo + 1: the slice xCorrWithX computes for that series against the batch's reference (xcorr.go:160-197),
+ * n the FFT length.  series == NULL: every series of the group in order (K must be 0 or M); otherwise K host indices in 0 .. M - 1, any
+ * order, duplicates allowed, output row k belonging to series[k].  The values are raw -- no clamp to +-1, no sign filter, no
+ * threshold; a series with sigma == 0 gives a row of +0.0 and one that holds NaN or Inf a row of NaN (the rules of every lag-window
+ * pass).  Columns W .. out_stride - 1 are never written.
+ *   The pass is the direct product of muse_batch_score_in_lag_band with its scan replaced by a write-out (xcorr_window_profile.hip):
+ *   the value at a lag is BIT FOR BIT the one the band, range and signed passes scan at that lag on the direct product, whatever band
+ *   it was asked in.  More than 2 MUSE_LAG_WINDOW_MAX + 1 lags: consecutive launches of up to that many, each one read of the rows
+ *   writing its own columns (muse_test_lag_profile_plan).  The tables of a launch are built into buffers of the call's own (a sibling
+ *   of the cached window tables): the batch's score buffers, what names their pass, its own lag window, its cached window tables with
+ *   their key and the spectrum cache are left as they were.
+ *   muse_batch_lag_profile writes host memory and returns when the data is there.  It stages through a grow-on-demand device buffer
+ *   in chunks of rows: at most MUSE_LAG_PROFILE_STAGE_BYTES of device memory however many rows are asked for.
+ *   muse_batch_lag_profile_device writes caller-owned device memory of the batch's context (a torch tensor's data_ptr()); it is
+ *   enqueued on the batch's stream like a score pass and does not wait.
+ *   MUSE_ERR_INVALID: a NULL batch or output; lag_lo > lag_hi; a lag outside -(n / 2 - 1) .. n / 2 (the band calls clip, this one
+ *   does not: clipping would change which column is which lag); out_stride < W; K < 0, series == NULL with K neither 0 nor M, an
+ *   index outside 0 .. M - 1.  MUSE_ERR_UNSUPPORTED: a float32-storage group, series longer than 65536 samples, a batch without its
+ *   time-domain reference (where the direct product is refused everywhere).  Everything is checked before anything is enqueued or
+ *   written.  K == 0 with a list, or an empty group: MUSE_OK, nothing written. */
+#define MUSE_LAG_PROFILE_STAGE_BYTES (64LL << 20)
+int muse_batch_lag_profile(muse_batch *b, const int64_t *series, int64_t K, int32_t lag_lo, int32_t lag_hi, double *out,
+                           int64_t out_stride);
+int muse_batch_lag_profile_device(muse_batch *b, const int64_t *series, int64_t K, int32_t lag_lo, int32_t lag_hi, double *dev_out,
+                                  int64_t out_stride);
 int muse_batch_free(muse_batch *b);
 
 /* ------------------------------------------- single-pair entry points */

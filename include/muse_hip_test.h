@@ -227,6 +227,13 @@ int muse_test_slide_in_window_force(muse_ctx *ctx, int32_t mode);
 /* The path (MUSE_SLIDE_IN_WINDOW_*) the batch's last scoring pass took if it was a muse_batch_slide_score_in_window / _slide_run_in_window /
  * _slide_run that moved rows; 0 after any other scoring pass (k = 0 included). */
 int muse_test_last_slide_path(muse_batch *b, int32_t *path);
+/* muse_batch_lag_profile's planner and its lag checks, a pure host function (no device needed): the lags lag_lo .. lag_hi of series of
+ * N >= 2 samples in *launches consecutive launches of up to 2 MUSE_LAG_WINDOW_MAX + 1 table rows -- lo_of[j] the first lag of launch
+ * j, rows_of[j] its table rows; the first min(*launches, cap) entries are filled (NULL arrays with cap == 0: the count alone).
+ * MUSE_ERR_INVALID for N < 2, lag_lo > lag_hi, a lag outside -(n / 2 - 1) .. n / 2 at the FFT length n of N, cap < 0 or a NULL
+ * out pointer; MUSE_ERR_UNSUPPORTED for N > 65536: the entry points' own checks. */
+int muse_test_lag_profile_plan(int32_t N, int32_t lag_lo, int32_t lag_hi, int32_t *launches, int32_t *lo_of, int32_t *rows_of,
+                               int32_t cap);
 
 #ifdef __cplusplus
 }
